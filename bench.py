@@ -14,11 +14,18 @@ Workload per rank:
 A step = one xyws_decode_stream call over the whole batch (boundaries found on
 the device, every payload unmasked in place). XOR is an involution and headers
 are never modified, so consecutive steps re-mask/unmask the same batch; the
-parity check after the timed region compares the device digest with the
+parity check after the timed region (--full) compares the device digest with the
 reference digest for that parity of step count (tests/golden/configs.json).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1|c4]
-                       [--mode fused|serial] [--no-cpu] [--host-path] [--copies C] [--dry-run]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                       [--config c3|c2|c1|c4] [--mode fused|serial] [--no-cpu] [--host-path]
+                       [--copies C] [--dry-run]
+A plain run builds the batch, settles and warms up, times the K steps and
+prints the result line. --full adds what takes runs of its own after the timed
+region: the parity check against the reference digests, the CPU baseline
+(--no-cpu leaves it out) and the in-run copy ceiling (--no-ceiling leaves it
+out). --dump-outputs DIR writes what the last timed step returned to its caller
+as DIR/<name>.npy (dump_outputs below).
 --gpus N without a launcher starts N ranks (torch.distributed.run, one process
 per GPU) as a child process and passes their output through.
 """
@@ -381,6 +388,66 @@ def pmc_traffic(config, mode):
     return rec["hbm_bytes_per_launch"], f"profiles/pmc_traffic.json {config}:{mode} ({rec.get('profile', '?')})"
 
 
+DUMP_SAMPLE = 4 << 20  # bytes sampled from an output larger than that (16 MiB as float32)
+DUMP_SEED = 0x5EED0D0A
+
+
+def dump_sample(torch, t, limit=DUMP_SAMPLE):
+    """A device byte tensor as a float32 host array: whole when it has at most
+    `limit` bytes, else the bytes at `limit` fixed positions (sorted draws of a
+    generator seeded with DUMP_SEED and the length, so the same positions in
+    every run and every build)."""
+    import numpy as np
+    n = t.numel()
+    if n > limit:
+        idx = np.sort(np.random.default_rng([DUMP_SEED, n]).integers(0, n, size=limit, dtype=np.int64))
+        parts = []
+        for lo in range(0, n, 1 << 30):  # gathered per 1 GiB slice: indices stay below 2^31
+            a, b = np.searchsorted(idx, [lo, lo + (1 << 30)])
+            parts.append(t[lo:lo + (1 << 30)][torch.from_numpy(idx[a:b] - lo).to(t.device)])
+        t = torch.cat(parts)
+    return t.cpu().numpy().astype(np.float32)
+
+
+def dump_outputs(torch, T, dec, out_dir, buf, ndecodes, frames_t, n_t, suffix=""):
+    """--dump-outputs: what the last timed step handed its caller, as
+    DIR/<name>.npy (float32 / float64, about 40 MB at most):
+      batch            the batch that step decoded in place, as it left it (a
+                       fixed seeded sample of its bytes when larger than 4 MiB)
+      batch_digest     the 64-bit digest of the whole of it (xyws_tools_digest),
+                       as four 16-bit limbs, least significant first
+      decode_count     how many decodes that batch has had: odd, its payloads
+                       are unmasked; even, masked again (XOR is an involution)
+      batch_unmasked   the same sample with the payloads unmasked: `batch`
+                       itself at an odd count, else after one more decode
+                       (which the returned count includes)
+      frames, nframes  with --frames: the frame table (sampled like the batch)
+                       and the count that step returned
+    The batch is generated from the config's seed, so two runs with the same
+    arguments dump the same arrays. Returns the batch's decode count."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+    torch.cuda.synchronize()
+    save("batch", dump_sample(torch, buf))
+    d = device_digest(torch, T, buf)
+    save("batch_digest", np.array([(d >> (16 * i)) & 0xFFFF for i in range(4)], dtype=np.float64))
+    save("decode_count", np.array([ndecodes], dtype=np.float64))
+    if frames_t is not None:
+        nf = int(n_t.item())
+        save("nframes", np.array([nf], dtype=np.float64))
+        save("frames", dump_sample(torch, frames_t[: max(0, min(nf, frames_t.numel() // 32)) * 32], DUMP_SAMPLE // 2))
+    if ndecodes % 2 == 0:
+        dec.decode(buf, cap=0, count=False, carry=False)
+        ndecodes += 1
+        torch.cuda.synchronize()
+    save("batch_unmasked", dump_sample(torch, buf))
+    return ndecodes
+
+
 # --op: the §8(f) callers on the decoded batch (tests/golden/gen_ops_golden.py
 # holds the same parameters and writes the expected digests)
 OP_PARAMS = {"enc_flags": 0x11, "cls_max_payload": 1 << 20, "cls_policy": 0x1, "rs_opts": 0x1}
@@ -582,8 +649,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--mode", default="fused", choices=["fused", "serial"])
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-ceiling", action="store_true", help="skip the in-run copy-ceiling measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check parity against the reference digests, time the CPU "
+                         "baseline and measure the in-run copy ceiling (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ceiling", action="store_true",
+                    help="with --full: skip the in-run copy-ceiling measurement")
     ap.add_argument("--host-path", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--copies", type=int, default=0,
@@ -713,6 +786,11 @@ def main():
                        2: "runs (k_stream_runs, 512-thread workgroups, 64 KiB segments)",
                        3: "lattice (k_stream_lattice)"}.get(int(pol[4]) & 3)
 
+    if args.dump_outputs and args.steps > 0:  # the batch of the last timed step (and its frame table)
+        k = (settle + args.warmup + args.steps - 1) % ncopies
+        uses[k] = dump_outputs(torch, T, dec, args.dump_outputs, part(bufs[k]), uses[k], frames_t, n_t,
+                               suffix=f"_rank{rank}" if world > 1 else "")
+
     if args.stats and rank == 0:  # two extra decodes of copy 0 (keeps its parity)
         names = ["runs", "runs_without_entry", "bad_boundaries", "repairs", "cuts", "spins", "dense_passes",
                  "frames", "scan_segments", "scan_survivors", "scan_undecided", "cyc_scan_filter",
@@ -736,17 +814,17 @@ def main():
                 st[k.replace("cyc_", "us_per_run_")] = round(st.pop(k) / nrun / 2100.0, 3)
         print(json.dumps({"stats": st}), flush=True)
 
-    # parity after the timed region: every copy against the reference digest
-    # for the parity of its decode count (XOR is an involution)
-    if bounds is not None:  # the other ranks' ranges, as often (mod 2) as this one's
+    # --full: parity after the timed region: every copy against the reference
+    # digest for the parity of its decode count (XOR is an involution)
+    if args.full and bounds is not None:  # the other ranks' ranges, as often (mod 2) as this one's
         for b, u in zip(bufs, uses):
             for r in range(world):
                 if r != rank and u % 2:
                     dec.decode(part(b, r), cap=0, count=False, carry=False)
         torch.cuda.synchronize()
-    dev_err = dec.ctx.last_device_error()
     parity = None
-    if golden is not None:
+    if args.full and golden is not None:
+        dev_err = dec.ctx.last_device_error()
         parity = dev_err == 0
         for b, u in zip(bufs, uses):
             parity = parity and device_digest(torch, T, b) == (golden["out_digest"] if u % 2 else golden["in_digest"])
@@ -762,17 +840,18 @@ def main():
     value = args.steps * total_payload / elapsed / GIB
     algo_bytes = info["algo_bytes"] + (32 * info["nframes"] if args.frames else 0)  # + the descriptors
     achieved = algo_bytes / (avg_ms * 1e-3) / 1e9
-    parity_all = all_ranks(dist, torch, parity, "cpu") if dist else parity
+    parity_all = all_ranks(dist, torch, parity, "cpu") if dist and args.full else parity
 
     cpu = None
     host_rate = None
-    if rank == 0 and world == 1 and (not args.no_cpu or args.host_path):
+    want_cpu = args.full and not args.no_cpu
+    if rank == 0 and world == 1 and (want_cpu or args.host_path):
         # both legs take the masked input batch: decode copy 0 once more if it is unmasked
         if uses[0] % 2:
             dec.decode(bufs[0], cap=0, count=False, carry=False)
             uses[0] += 1
             torch.cuda.synchronize()
-        if not args.no_cpu:
+        if want_cpu:
             cpu = cpu_baseline(torch, bufs[0], info, args.cpu_budget)
         if args.host_path and info["nframes"] and args.config != "c4" and golden is not None:
             host_rate = host_path_rate(torch, ws, T, info, bufs[0], golden)
@@ -780,7 +859,7 @@ def main():
 
     traffic, traffic_src = pmc_traffic(args.config, args.mode + ("+frames" if args.frames else ""))
     ceiling = None
-    if rank == 0 and not args.no_ceiling:
+    if rank == 0 and args.full and not args.no_ceiling:
         ceiling = copy_ceiling(torch, ws, bufs[0])
         ceiling["frac_vs_unmask"] = round(achieved / ceiling["unmask_inplace_gbs"], 4)
         ceiling["frac_vs_d2d_copy"] = round(achieved / ceiling["d2d_copy_gbs"], 4)
@@ -794,6 +873,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "settle_calls": settle,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong" if one else "weak",

@@ -6,7 +6,7 @@
 # gpurun_out/${TAG}_*; copy the summaries worth keeping into profiles/.
 #   tests   pytest -m gpu
 #   smoke   __graft_entry__.smoke()
-#   bench   bench.py lines for CFGS (default c3 c2 c1 c4; c3 with the CPU baseline and copy ceiling)
+#   bench   bench.py --full lines for CFGS (default c3 c2 c1 c4: parity and CPU baseline; c3 also with the copy ceiling)
 #   prof    rocprofv3 --kernel-trace --stats per config + steady-state summary (trace_summary.py)
 #   pmc     FETCH_SIZE and WRITE_SIZE passes per config (separate runs; pmc_summary.py folds them)
 #   ops     the §8(f) callers on c1-c4 (encode, classify, reassemble)
@@ -27,8 +27,8 @@ has tests && step tests 900 python -u -m pytest tests -m gpu -x -q --timeout 120
 has smoke && step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 if has bench; then
   for c in $CFGS; do
-    if [ "$c" = c3 ]; then step bench_$c 400 python bench.py --config $c $BENCH
-    else step bench_$c 300 python bench.py --config $c --no-ceiling $BENCH; fi
+    if [ "$c" = c3 ]; then step bench_$c 400 python bench.py --config $c --full $BENCH
+    else step bench_$c 300 python bench.py --config $c --full --no-ceiling $BENCH; fi
   done
 fi
 if has prof; then

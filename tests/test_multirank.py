@@ -88,7 +88,7 @@ def test_bench_shard_one_batch_dry_run(cfg, world):
     over the generator's table: every rank computes the same plan, the ranges
     tile the batch, start at frames, are balanced within one frame and carry
     the batch's whole payload. (The cut decoding to the unsplit bytes:
-    tests/test_shard.py with the oracle; on the GPU, bench.py's parity.)"""
+    tests/test_shard.py with the oracle; on the GPU, the parity of bench.py --full.)"""
     import subprocess
     import numpy as np
     sys.path.insert(0, ROOT)
