@@ -225,12 +225,25 @@ typedef struct xyws_iov {
  * pieces, at most XYWS_IOV_MAX, any lengths and alignments, 0-length pieces
  * allowed) are ONE stream, decoded as if concatenated; every piece is
  * unmasked in place. Descriptor offsets count bytes across the pieces in
- * order (piece k starts at the sum of the earlier pieces' lengths). Three
- * launches whatever niov (gather into the stream's staging buffer, one
- * decode, scatter back); the staging buffer grows to the largest total seen
- * (XYWS_ERR_CAPACITY under capture before it has, or before
- * xyws_ctx_reserve_iov reserved it). XYWS_OPT_SERIAL_SCAN is refused
- * (XYWS_ERR_INVALID). */
+ * order (piece k starts at the sum of the earlier pieces' lengths). The
+ * call takes one of three paths:
+ *  - single piece: one non-empty piece is decoded as xyws_decode_stream
+ *    decodes that buffer;
+ *  - pieces in place: several non-empty pieces, no descriptors asked for
+ *    (dev_frames null or cap 0), and every non-empty piece at least 64 MiB
+ *    when the stream's previous call found frames of one size, else at least
+ *    256 MiB: one decode per piece where it lies, the carry chained from
+ *    piece to piece on the device;
+ *  - staged: everything else. Three launches whatever niov (gather into the
+ *    stream's staging buffer, one decode, scatter back); the staging buffer
+ *    grows to the largest total seen (XYWS_ERR_CAPACITY under capture before
+ *    it has, or before xyws_ctx_reserve_iov reserved it).
+ * Every path sizes and reserves all the scratch the call needs before it
+ * queues any work: an error other than XYWS_ERR_HIP means that nothing was
+ * queued and the caller's buffers are untouched, so the call may be repeated.
+ * (The options XYWS_OPT_IOV_PIECES and XYWS_OPT_IOV_STAGE that force the
+ * second or third path are internal, for tests and measurements.)
+ * XYWS_OPT_SERIAL_SCAN is refused (XYWS_ERR_INVALID). */
 int xyws_decode_stream_iov(xyws_ctx* ctx, const xyws_iov* iov, uint32_t niov,
                            const xyws_carry* dev_carry_in, xyws_carry* dev_carry_out,
                            xyws_frame* dev_frames, uint64_t cap, uint64_t* dev_nframes,

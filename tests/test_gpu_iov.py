@@ -109,6 +109,65 @@ def test_equal_frames_take_the_lattice_decoder(ws, oracle):
         c = decode_seq(ws, oracle, dec, pieces_of(src, rng, 9), c, rng)
 
 
+OPT_LATTICE = 0x400  # xyws_stream.h: the lattice decoder first
+
+
+@pytest.mark.parametrize("npieces", [5, 17])
+@pytest.mark.parametrize("odd_frame", [False, True])
+def test_equal_frames_in_place(ws, oracle, npieces, odd_frame):
+    """The stream of test_equal_frames_take_the_lattice_decoder decoded in
+    place piece by piece: with the lattice forced, and with one 700-byte frame
+    in a middle piece (the lattice decoder hands over to the run decoder
+    inside that piece; the stream is fresh, so the lattice goes first)."""
+    rng = streams.SplitMix(11)
+    frames = [streams.frame(rng, 0x82, 500) for _ in range(3000)]
+    seq = pieces_of(b"".join(frames), rng, npieces)
+    if odd_frame:
+        # the first frame that starts in the middle piece: the bytes before it,
+        # and so the piece it starts in, stay as they are
+        mid = len(seq) // 2
+        at = sum(len(p) for p in seq[:mid])
+        assert 0 < mid < len(seq) - 1 and len(seq[mid]) > 2 * len(frames[0])
+        k = -(-at // len(frames[0]))
+        frames[k] = streams.frame(rng, 0x82, 700)
+        src = b"".join(frames)
+        cuts = [sum(len(p) for p in seq[:i]) for i in range(len(seq))] + [len(src)]
+        seq = [src[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+    dec = ws.frame_decoder(opts=OPT_IOV_PIECES | (0 if odd_frame else OPT_LATTICE))
+    c = decode_seq(ws, oracle, dec, seq, None, rng, desc=False)
+    decode_seq(ws, oracle, dec, seq, c, rng, desc=False)  # (the stream goes on: the count carries over)
+
+
+def test_nothing_is_queued_when_a_later_piece_does_not_fit(ws):
+    """Pieces in place under graph capture with scratch reserved for 64 KiB:
+    the first piece (32 KiB) fits, the second (8 MiB) does not. The call is
+    refused with XYWS_ERR_CAPACITY before anything is queued: replaying the
+    captured graph leaves both pieces masked (a first piece already queued
+    would be unmasked by the replay, and once more by the caller's retry)."""
+    from xynet_amd._lib import XywsError
+    rng = streams.SplitMix(0x51EC)
+    src = b"".join(streams.frame(rng, 0x82, 500) for _ in range((32768 + (8 << 20)) // 508 + 1))
+    seq = [src[:32768], src[32768:32768 + (8 << 20)]]
+    ctx = ws.Context(0)
+    ctx.reserve(65536, 0)
+    ctx.reserve_iov(len(src))
+    dec = ws.frame_decoder(ctx=ctx, opts=OPT_IOV_PIECES)
+    views = [torch.frombuffer(bytearray(b), dtype=torch.uint8).cuda() for b in seq]
+    s = torch.cuda.Stream()
+    g = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    with torch.cuda.graph(g, stream=s):
+        with pytest.raises(XywsError) as e:
+            dec.decode_iov(views, cap=0, carry=False)
+    assert e.value.code == -4  # XYWS_ERR_CAPACITY
+    torch.cuda.synchronize()
+    g.replay()
+    torch.cuda.synchronize()
+    for v, b in zip(views, seq):
+        assert host(v) == b
+    ctx.close()
+
+
 def test_piece_limit(ws, oracle):
     src = streams.case_bytes("random_frames_50")
     rng = streams.SplitMix(3)

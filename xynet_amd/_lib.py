@@ -147,6 +147,11 @@ def load():
     L.xyws_debug_lattice.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     L.xyws_debug_records.restype = C.c_int64
     L.xyws_debug_records.argtypes = [vp, vp, C.POINTER(C.c_uint64), u64]
+    # (no HIP call: the decode's host-side plan, tests/test_plan.py)
+    L.xyws_debug_plan.restype = i32
+    L.xyws_debug_plan.argtypes = [i32, C.POINTER(u64), u64, u64, u64, u32, C.POINTER(u64)]
+    L.xyws_debug_plan_reserve.restype = i32
+    L.xyws_debug_plan_reserve.argtypes = [i32, u64, u64, C.POINTER(u64)]
     L.xyws_decode_stream.restype = i32
     L.xyws_decode_stream.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u32, vp]
     L.xyws_decode_stream_iov.restype = i32

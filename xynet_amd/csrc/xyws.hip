@@ -451,14 +451,11 @@ int xyws_ctx_reserve(xyws_ctx* ctx, uint64_t max_batch_bytes, uint64_t max_frame
     // every slot; the per-frame tables in the slots bound to a stream now and
     // in one spare, so that a stream first used inside graph capture finds
     // them (the others get them when a stream binds them: acquire_slot)
-    int rc = stream_scratch_reserve(&sl.ss, ctx->reserve_bytes);
-    if (rc) return rc;
-    const bool take = sl.bound || spare;
+    const bool take = (sl.bound || spare) && ctx->reserve_frames;
     if (!sl.bound) spare = false;
-    if (ctx->reserve_frames && take) {
-      if ((rc = ensure_table(&sl, ctx->reserve_frames, false))) return rc;
-      if ((rc = stream_scratch_reserve_frames(&sl.ss, ctx->reserve_bytes, ctx->reserve_frames))) return rc;
-    }
+    if (const int rc = stream_scratch_reserve(&sl.ss, ctx->reserve_bytes, take ? ctx->reserve_frames : 0)) return rc;
+    if (take)
+      if (const int rc = ensure_table(&sl, ctx->reserve_frames, false)) return rc;
   }
   return XYWS_OK;
 }
@@ -554,6 +551,35 @@ int xyws_debug_policy(xyws_ctx* ctx, void* stream, uint64_t* out) {
   return XYWS_ERR_INVALID;
 }
 
+// Internal (tests, no HIP call): the plan of a stream decode of bytes
+// [lo, hi) on a device of ncu compute units after a call that left the policy
+// words pol (null: no pinned words), with descriptors for cap frames (0:
+// none). out: XYWS_PLAN_WORDS words {geometry (run_geom), segment bytes,
+// threads, nruns, rbytes, nflat, want_lat, lnseg, lattice grid, lattice
+// segment bytes (2), pfs, dense0, bigscan, rcap, needs: runs, descriptor
+// region bytes, lattice segments}.
+#define XYWS_PLAN_WORDS 18
+int xyws_debug_plan(int ncu, const uint64_t pol[5], uint64_t lo, uint64_t hi, uint64_t cap, uint32_t opts,
+                    uint64_t* out) {
+  if (!out || ncu <= 0 || hi < lo) return XYWS_ERR_INVALID;
+  const policy_view pv = pol ? policy_view{true, pol[0], pol[2], pol[3]} : policy_view{};
+  const decode_plan p = plan_decode(ncu, pv, lo, hi, cap, opts);
+  const uint64_t w[XYWS_PLAN_WORDS] = {p.geom, p.seg, p.threads, p.nruns, p.rbytes, p.nflat, p.want_lat, p.lnseg,
+                                       p.lgrid, p.lseg[0], p.lseg[1], p.pfs, p.dense0, p.bigscan, p.rcap,
+                                       p.need.runs, p.need.fmem_bytes, p.need.lat_segs};
+  memcpy(out, w, sizeof w);
+  return XYWS_OK;
+}
+
+// Internal (tests, no HIP call): what xyws_ctx_reserve(max_batch_bytes,
+// max_frames) reserves on such a device. out: the three needs, as above.
+int xyws_debug_plan_reserve(int ncu, uint64_t max_batch_bytes, uint64_t max_frames, uint64_t* out) {
+  if (!out || ncu <= 0) return XYWS_ERR_INVALID;
+  const scratch_need n = plan_reserve(ncu, max_batch_bytes, max_frames);
+  out[0] = n.runs; out[1] = n.fmem_bytes; out[2] = n.lat_segs;
+  return XYWS_OK;
+}
+
 // xyws_unmask with ctx->mu held: the claim counter is the stream's scratch
 // slot's when the stream has one bound or a free slot to bind (eager launches
 // only); a captured launch, or a stream finding every slot bound to others,
@@ -577,17 +603,15 @@ static int unmask_locked(xyws_ctx* ctx, void* dev, uint64_t len, const uint8_t k
   } else {
     ncu = (uint32_t)ctx->slot[0].ss.ncu;
   }
-  const uintptr_t addr = reinterpret_cast<uintptr_t>(dev);
-  uint8_t* base = reinterpret_cast<uint8_t*>(addr & ~(uintptr_t)15);
-  const uint64_t lo = addr & 15, hi = lo + len;
+  const range16 r = span16(dev, len);
   const uint32_t k = (uint32_t)key[0] | ((uint32_t)key[1] << 8) | ((uint32_t)key[2] << 16) |
                      ((uint32_t)key[3] << 24);
   // aligned_key(k, lo, phase) on the host: rotation by (phase - lo) mod 4
-  const uint32_t c = (uint32_t)(phase - lo) & 3u;
+  const uint32_t c = (uint32_t)(phase - r.lo) & 3u;
   const uint32_t kw = c ? ((k >> (8u * c)) | (k << (32u - 8u * c))) : k;
-  const uint64_t chunks = ((hi + 15) >> 4) - (lo >> 4);
+  const uint64_t chunks = ((r.hi + 15) >> 4) - (r.lo >> 4);
   const uint32_t grid = grid_for(chunks, UNMASK_NT * UNMASK_U, ncu * UNMASK_WPC);
-  hipLaunchKernelGGL(k_unmask_range, dim3(grid), dim3(UNMASK_NT), 0, s, base, lo, hi, kw, ctr);
+  hipLaunchKernelGGL(k_unmask_range, dim3(grid), dim3(UNMASK_NT), 0, s, r.base, r.lo, r.hi, kw, ctr);
   return hip_err(hipGetLastError());
 }
 
@@ -665,9 +689,7 @@ int xyws_decode_indexed(xyws_ctx* ctx, void* dev_buf, uint64_t len, const uint64
   int rc = acquire_slot(ctx, s, cap, &sl);
   if (rc) return rc;
   if ((rc = ensure_table(sl, n, cap))) return rc;
-  const uintptr_t addr = reinterpret_cast<uintptr_t>(dev_buf);
-  uint8_t* base = reinterpret_cast<uint8_t*>(addr & ~(uintptr_t)15);
-  const uint64_t lo = addr & 15, hi = lo + len;
+  const auto [base, lo, hi] = span16(dev_buf, len);
   frame_table t = table_of(sl);
   hipLaunchKernelGGL(k_parse_indexed, dim3(grid_for(n, 256, 1u << 30)), dim3(256), 0, s, base, lo, hi,
                      dev_starts, n, t, dev_frames);
@@ -689,9 +711,7 @@ int xyws_decode_stream(xyws_ctx* ctx, void* dev_buf, uint64_t len, const xyws_ca
   std::lock_guard<std::mutex> lk(ctx->mu);
   device_guard g(ctx->device);
   if (!g.ok) return XYWS_ERR_HIP;
-  const uintptr_t addr = reinterpret_cast<uintptr_t>(dev_buf);
-  uint8_t* base = reinterpret_cast<uint8_t*>(addr & ~(uintptr_t)15);
-  const uint64_t lo = addr & 15, hi = lo + len;
+  const auto [base, lo, hi] = span16(dev_buf, len);
   hipStream_t s = (hipStream_t)stream;
   const bool capt = capturing(s);
   scratch_slot* sl = nullptr;
@@ -721,11 +741,15 @@ int xyws_decode_stream(xyws_ctx* ctx, void* dev_buf, uint64_t len, const xyws_ca
 
 // ---------------------------------------------------------------------------
 // xyws_decode_stream_iov: a recv's buffer sequence (buffer.h:94-110, filled by
-// recv_all.h:99-121) decoded as one stream — the pieces gathered into the
-// slot's staging buffer by one launch, one fused decode there, the bytes
-// scattered back by one launch: three launches whatever the piece count (one
-// decode per piece would cost a decode's fixed latency each). The piece
-// table travels in the kernel arguments.
+// recv_all.h:99-121) decoded as one stream: a single non-empty piece as that
+// buffer's decode; several large pieces without descriptors in place, one
+// decode each (below); otherwise staged: the pieces gathered into the slot's
+// staging buffer by one launch, one fused decode there, the bytes scattered
+// back by one launch (three launches whatever the piece count: a decode per
+// small piece would cost its fixed latency each; the piece table travels in
+// the kernel arguments). Every path plans its decodes and reserves their
+// scratch before it queues anything: an error other than XYWS_ERR_HIP leaves
+// the buffers untouched.
 struct iov_args {
   uint8_t* base[XYWS_IOV_MAX];
   uint64_t len[XYWS_IOV_MAX];
@@ -843,18 +867,29 @@ int xyws_decode_stream_iov(xyws_ctx* ctx, const xyws_iov* iov, uint32_t niov, co
     // which is the sequence's: every piece before it is empty)
     for (uint32_t k = 0; k < niov; k++)
       if (iov[k].len) {
-        const uintptr_t addr = reinterpret_cast<uintptr_t>(iov[k].base);
-        return stream_decode_fused(&sl->ss, reinterpret_cast<uint8_t*>(addr & ~(uintptr_t)15), addr & 15,
-                                   (addr & 15) + iov[k].len, dev_carry_in, dev_carry_out, dev_frames, cap,
+        const range16 r = span16(iov[k].base, iov[k].len);
+        return stream_decode_fused(&sl->ss, r.base, r.lo, r.hi, dev_carry_in, dev_carry_out, dev_frames, cap,
                                    dev_nframes, opts, s);
       }
   }
-  const volatile uint64_t* pol = sl->ss.pol_h;  // (the stream's previous call: equal frames?)
-  const bool equal = pol && pol[3] && pol[2] == pol[3];
+  // one snapshot for the piece threshold and every piece's plan (policy_view)
+  const policy_view pv = policy_snapshot(&sl->ss);
+  const bool equal = pv.fsmax && pv.fsmin == pv.fsmax;
   const uint64_t pmin = equal ? IOV_PIECE_MIN_EQUAL : IOV_PIECE_MIN_MIXED;
   const bool pieces = nz > 1 && !desc && !(opts & XYWS_OPT_IOV_STAGE) &&
                       ((opts & XYWS_OPT_IOV_PIECES) || minlen >= pmin);
   if (pieces) {
+    // every piece's plan and the largest of their needs first (a piece
+    // refused after earlier ones were queued would leave those unmasked in
+    // the caller's buffers, and a retry would mask them again)
+    decode_plan plan[XYWS_IOV_MAX];
+    scratch_need need = {};
+    for (uint32_t k = 0; k < niov; k++) {
+      const range16 r = span16(iov[k].base, iov[k].len);
+      plan[k] = plan_decode(sl->ss.ncu, pv, r.lo, r.hi, 0, opts);
+      need_max(&need, plan[k].need);
+    }
+    if ((rc = reserve_for(&sl->ss, need, capt))) return rc;
     // scratch: [0, 64) the carry between pieces, [64, 72) the frame count of
     // the stream before the call (the count is the difference at the end)
     if ((rc = ensure_iov(sl, 128, capt))) return rc;
@@ -871,11 +906,8 @@ int xyws_decode_stream_iov(xyws_ctx* ctx, const xyws_iov* iov, uint32_t niov, co
       if (!iov[k].len) continue;
       const bool lastp = ++j == nz;
       xyws_carry* cout = lastp ? last_out : mid;
-      const uintptr_t addr = reinterpret_cast<uintptr_t>(iov[k].base);
-      uint8_t* b = reinterpret_cast<uint8_t*>(addr & ~(uintptr_t)15);
-      const uint64_t lo = addr & 15;
-      if ((rc = stream_decode_fused(&sl->ss, b, lo, lo + iov[k].len, cin, cout, nullptr, 0, nullptr, opts, s)))
-        return rc;
+      uint8_t* b = span16(iov[k].base, iov[k].len).base;
+      if ((rc = launch_plan(&sl->ss, plan[k], b, cin, cout, nullptr, 0, nullptr, s))) return rc;
       cin = cout;
     }
     if (dev_nframes) {
@@ -884,6 +916,8 @@ int xyws_decode_stream_iov(xyws_ctx* ctx, const xyws_iov* iov, uint32_t niov, co
     }
     return XYWS_OK;
   }
+  const decode_plan pl = plan_decode(sl->ss.ncu, pv, 0, total, dev_frames ? cap : 0, opts);
+  if ((rc = reserve_for(&sl->ss, pl.need, capt))) return rc;
   if ((rc = ensure_iov(sl, total + 16, capt))) return rc;
   uint8_t* stage = static_cast<uint8_t*>(sl->iov_mem);
   const dim3 grid((uint32_t)grid_for(longest / 16 + 2, 256, 1024), niov ? niov : 1);
@@ -891,9 +925,7 @@ int xyws_decode_stream_iov(xyws_ctx* ctx, const xyws_iov* iov, uint32_t niov, co
     hipLaunchKernelGGL(k_iov_copy, grid, dim3(256), 0, s, A, stage, 1);
     if ((rc = hip_err(hipGetLastError()))) return rc;
   }
-  if ((rc = stream_decode_fused(&sl->ss, stage, 0, total, dev_carry_in, dev_carry_out, dev_frames, cap,
-                                dev_nframes, opts, s)))
-    return rc;
+  if ((rc = launch_plan(&sl->ss, pl, stage, dev_carry_in, dev_carry_out, dev_frames, cap, dev_nframes, s))) return rc;
   if (niov && total && !(opts & XYWS_OPT_PARSE_ONLY)) {
     hipLaunchKernelGGL(k_iov_copy, grid, dim3(256), 0, s, A, stage, 0);
     if ((rc = hip_err(hipGetLastError()))) return rc;

@@ -92,6 +92,17 @@ inline bool capturing(hipStream_t s) {
   return cs != hipStreamCaptureStatusNone;
 }
 
+// A device range as the kernels address it: bytes [lo, hi) from the
+// 16-byte-aligned address at or below its start.
+struct range16 {
+  uint8_t* base;
+  uint64_t lo, hi;
+};
+inline range16 span16(const void* p, uint64_t len) {
+  const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
+  return range16{reinterpret_cast<uint8_t*>(addr & ~(uintptr_t)15), addr & 15, (addr & 15) + len};
+}
+
 inline int ensure_table(scratch_slot* sl, uint64_t n, bool capture) {
   if (n <= sl->tab_cap && sl->tab_mem) return XYWS_OK;
   if (capture) return XYWS_ERR_CAPACITY;
@@ -167,7 +178,7 @@ inline int acquire_slot(xyws_ctx* ctx, hipStream_t stream, bool capture, scratch
     // xyws_ctx_reserve's per-frame tables go to the slots streams bind (not
     // to all XYWS_SLOTS up front: tens of GB for 2^26 frames)
     if (const int rc = ensure_table(pick, ctx->reserve_frames, false)) return rc;
-    if (const int rc = stream_scratch_reserve_frames(&pick->ss, ctx->reserve_bytes, ctx->reserve_frames)) return rc;
+    if (const int rc = stream_scratch_reserve(&pick->ss, ctx->reserve_bytes, ctx->reserve_frames)) return rc;
   }
   pick->bound = true;
   pick->stream = stream;

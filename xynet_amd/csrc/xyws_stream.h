@@ -8,7 +8,6 @@
 // device error word.
 struct stream_scratch {
   void* mem;            // device allocation
-  uint64_t bytes;
   uint64_t max_runs;    // runs the allocation covers
   int ncu;              // compute units of the context's device (runs per launch)
   void* fmem;           // frame-start lists for descriptor emission (grown with the caller's cap)
@@ -25,8 +24,9 @@ struct stream_scratch {
 
 void stream_scratch_init(stream_scratch* s, int device);
 void stream_scratch_free(stream_scratch* s);
-int stream_scratch_reserve(stream_scratch* s, uint64_t max_batch_bytes);
-int stream_scratch_reserve_frames(stream_scratch* s, uint64_t max_batch_bytes, uint64_t max_frames);
+// xyws_ctx_reserve: everything a decode of up to max_batch_bytes needs, and
+// with max_frames its descriptor regions for that many frames (0: none)
+int stream_scratch_reserve(stream_scratch* s, uint64_t max_batch_bytes, uint64_t max_frames);
 // sticky device error word of this scratch (bit 1: an inter-workgroup wait
 // timed out, bit 2: a run record was not written by its call); clear: reset
 // it after reading (the device must be idle)
@@ -85,6 +85,69 @@ int stream_scratch_unmask_counter(stream_scratch* s, bool capturing, uint32_t** 
                                     // the checks and the XOR (its data path and control alone)
 #define XYWS_OPT_REDIRECT 0x2000u    // (set by stream_decode_fused only) the run decoder after the lattice decoder:
                                      // it reads the lattice's redirect record first
+
+// The stream decode's host side in three steps: plan_decode (pure: what the
+// call will run and what scratch it needs), reserve_for (the only step that
+// allocates, and the only one that fails with anything but XYWS_ERR_HIP),
+// launch_plan (queues the kernels). A caller that queues several decodes
+// (xyws_decode_stream_iov's pieces) plans them all and reserves their
+// largest needs before it queues the first.
+
+// The stream's previous call as the pinned policy words showed it at one
+// moment: one snapshot per public call, every choice of the call from it. The
+// device writes the words when a call finishes, so a snapshot may show any
+// earlier call of the stream; it steers speed only (which decoder, which
+// geometry, which entry scans go first), never the decode's result: every
+// choice can be forced by an option, and the forced-option parity tests
+// (tests/test_gpu_modes.py, test_gpu_lattice.py) hold each forced choice to
+// the same bytes, descriptors and carry.
+struct policy_view {
+  bool present;    // the pinned words exist (else the run decoder serves every call)
+  uint64_t epoch;  // != 0: a call has finished on this stream
+  uint64_t fsmin, fsmax;  // smallest, largest last-frame size of that call's runs
+};
+policy_view policy_snapshot(const stream_scratch* s);
+
+// What a decode needs of the three scratch areas (0: nothing).
+struct scratch_need {
+  uint64_t runs;        // run scratch, in runs
+  uint64_t fmem_bytes;  // descriptor regions
+  uint64_t lat_segs;    // lattice scratch, in segments
+};
+inline void need_max(scratch_need* a, const scratch_need& b) {
+  if (b.runs > a->runs) a->runs = b.runs;
+  if (b.fmem_bytes > a->fmem_bytes) a->fmem_bytes = b.fmem_bytes;
+  if (b.lat_segs > a->lat_segs) a->lat_segs = b.lat_segs;
+}
+
+enum run_geom : uint32_t { GEOM_SMALL, GEOM_MID, GEOM_WG512, GEOM_PROD };
+struct decode_plan {
+  uint64_t lo, hi;     // the batch: bytes [lo, hi) from a 16-byte-aligned base
+  uint32_t opts;       // (without XYWS_OPT_REDIRECT)
+  run_geom geom;       // the run decoder's geometry, its segment bytes and threads
+  uint32_t seg, threads;
+  uint64_t nruns, rbytes;  // nruns == 0: an empty batch (k_stream_empty, no scratch)
+  uint32_t nflat;
+  bool want_lat;       // the lattice decoder first: lnseg segments of lseg[0] bytes, lgrid
+  uint64_t lnseg;      // workgroups; the kernel takes lseg[0] or lseg[1] by the first frame
+  uint32_t lgrid, lseg[2];
+  uint64_t pfs;        // the run decoder's hints from the previous call (run_params)
+  uint32_t dense0, bigscan;
+  uint64_t rcap;       // entries per descriptor region (0: no descriptors)
+  scratch_need need;
+};
+decode_plan plan_decode(int ncu, const policy_view& pv, uint64_t lo, uint64_t hi, uint64_t cap_if_frames,
+                        uint32_t opts);
+// The largest needs of any plan of a batch of up to max_batch_bytes with up to
+// max_frames descriptors in the production geometries (the small-segment test
+// mode grows lazily).
+scratch_need plan_reserve(int ncu, uint64_t max_batch_bytes, uint64_t max_frames);
+// capturing: XYWS_ERR_CAPACITY where an area would have to grow.
+int reserve_for(stream_scratch* s, const scratch_need& need, bool capturing);
+// After reserve_for(s, pl.need): fails with XYWS_ERR_HIP only.
+int launch_plan(const stream_scratch* s, const decode_plan& pl, uint8_t* base, const xyws_carry* cin,
+                xyws_carry* cout, xyws_frame* frames, uint64_t cap, uint64_t* nframes, hipStream_t stream);
+// plan_decode, reserve_for, launch_plan
 int stream_decode_fused(stream_scratch* s, uint8_t* base, uint64_t lo, uint64_t hi,
                         const xyws_carry* cin, xyws_carry* cout, xyws_frame* frames, uint64_t cap,
                         uint64_t* nframes, uint32_t opts, hipStream_t stream);

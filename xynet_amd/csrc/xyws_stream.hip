@@ -55,6 +55,7 @@
 #include <cstring>
 #include <mutex>
 #include <cstdlib>
+#include <initializer_list>
 
 #include "xyws_stream.h"
 #include "xyws_device.h"
@@ -2900,29 +2901,38 @@ constexpr uint64_t HEAD_BYTES = 1024;  // u32 [0] ticket, [1] error, [2..3] tota
 
 // hipFuncSetAttribute applies to the current device: once per (device,
 // geometry), under a lock (one process may drive several devices from several
-// threads).
-template <class G>
-int set_lds_attr() {
-  static std::mutex mu;
-  static bool done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return XYWS_ERR_HIP;
-  std::lock_guard<std::mutex> lk(mu);
-  if (done[dev]) return XYWS_OK;
-  const int lds = (int)sizeof(lds_t<G>);
-  if (hipFuncSetAttribute((const void*)k_stream_runs<G>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-      hipSuccess)
-    return XYWS_ERR_HIP;
-  done[dev] = true;
-  return XYWS_OK;
-}
+// threads). One lds_once per kernel.
+struct lds_once {
+  std::mutex mu;
+  bool done[64] = {};
+  int set(const void* kernel, size_t lds) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return XYWS_ERR_HIP;
+    std::lock_guard<std::mutex> lk(mu);
+    if (done[dev]) return XYWS_OK;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return XYWS_ERR_HIP;
+    done[dev] = true;
+    return XYWS_OK;
+  }
+};
 
 template <class G>
 int launch_runs(const run_params& P, hipStream_t stream) {
+  static lds_once once;
   const size_t lds = sizeof(lds_t<G>);
-  if (const int rc = set_lds_attr<G>()) return rc;
+  if (const int rc = once.set((const void*)k_stream_runs<G>, lds)) return rc;
   hipLaunchKernelGGL(k_stream_runs<G>, dim3(P.nruns), dim3(G::NT), lds, stream, P);
   if (P.frames && P.cap) hipLaunchKernelGGL(k_stream_emit, dim3(P.nflat), dim3(256), 0, stream, P);
+  return hipGetLastError() == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
+}
+
+template <class GA, class GB>
+int launch_lattice(const run_params& P, uint32_t grid, hipStream_t stream) {
+  static lds_once once;
+  using LL = lat_lds<llay<GA, GB>>;
+  if (const int rc = once.set((const void*)k_stream_lattice<GA, GB>, sizeof(LL))) return rc;
+  hipLaunchKernelGGL((k_stream_lattice<GA, GB>), dim3(grid), dim3(GB::NT), sizeof(LL), stream, P);
   return hipGetLastError() == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
 }
 
@@ -2930,7 +2940,6 @@ int launch_runs(const run_params& P, hipStream_t stream) {
 
 void stream_scratch_init(stream_scratch* s, int device) {
   s->mem = nullptr;
-  s->bytes = 0;
   s->max_runs = 0;
   s->fmem = nullptr;
   s->fbytes = 0;
@@ -2965,32 +2974,12 @@ void stream_scratch_free(stream_scratch* s) {
   if (s->mem) (void)hipFree(s->mem);
   if (s->fmem) (void)hipFree(s->fmem);
   s->mem = nullptr;
-  s->bytes = 0;
   s->max_runs = 0;
   s->fmem = nullptr;
   s->fbytes = 0;
 }
 
-// Frame-start lists for descriptor emission: one region per flat item of
-// twice the caller's capacity spread over the runs + 1024 (a region that
-// overflows switches the call to the chain re-walk). Grown on demand, not
-// under graph capture (xyws_ctx_reserve).
-static uint64_t region_entries(uint64_t cap, uint64_t nruns) { return 2 * ((cap + nruns - 1) / nruns) + 1024; }
-static int fmem_grow(stream_scratch* s, uint64_t bytes, bool capturing) {
-  if (s->fmem && bytes <= s->fbytes) return XYWS_OK;
-  if (capturing) return XYWS_ERR_CAPACITY;
-  void* m = nullptr;
-  if (hipMalloc(&m, bytes) != hipSuccess) return XYWS_ERR_NOMEM;
-  if (s->fmem) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->fmem);
-  }
-  s->fmem = m;
-  s->fbytes = bytes;
-  return XYWS_OK;
-}
-
-// Scratch layout for up to `runs` runs (2 * runs flat indices):
+// Run scratch layout for up to `runs` runs (2 * runs flat indices):
 //   head | entry granules (16 B per flat index) | split words (16 B per run) |
 //   progress words (8 B per run) | records (R_WORDS x 8 B per flat index)
 // Everything up to the records is zeroed at allocation (epoch 0: stale).
@@ -3001,85 +2990,50 @@ static uint64_t records_off(uint64_t runs) {
   return HEAD_BYTES + granules_bytes(runs) + split_bytes(runs) + prog_bytes(runs);
 }
 
-static int scratch_grow(stream_scratch* s, uint64_t runs) {
-  if (s->mem && runs <= s->max_runs) return XYWS_OK;
-  const uint64_t want = runs < 64 ? 64 : runs;
-  const uint64_t bytes = records_off(want) + 2 * want * R_WORDS * 8;
-  void* m = nullptr;
-  if (hipMalloc(&m, bytes) != hipSuccess) return XYWS_ERR_NOMEM;
-  if (s->mem) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->mem);
-  }
-  s->mem = m;
-  s->bytes = bytes;
-  s->max_runs = want;
-  return xyws_internal::zero_now(m, records_off(want)) == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
-}
-
-// Lattice decoder scratch for up to `segs` segments: LW_STAT words of
-// scratch and one result word per segment, all zeroed at allocation (epoch 0:
-// no result of any call).
-static uint64_t lat_max_grid(const stream_scratch* s) {
-  const uint64_t g = (uint64_t)s->ncu;  // (one workgroup per CU)
-  return g > 64 ? g : 64;
-}
-static int lat_grow(stream_scratch* s, uint64_t segs, bool capturing) {
-  if (s->lmem && segs <= s->lmax_segs) return XYWS_OK;
+// One scratch area grown to hold `want` units in `bytes` bytes, the first
+// `zero` of them zeroed before any kernel can read them. Never under graph
+// capture (xyws_ctx_reserve). The old allocation is freed once the device is
+// idle: a call in flight may still use it.
+static int grow_area(void** mem, uint64_t* have, uint64_t want, uint64_t bytes, uint64_t zero, bool capturing) {
+  if (*mem && want <= *have) return XYWS_OK;
   if (capturing) return XYWS_ERR_CAPACITY;
-  const uint64_t want = segs < 64 ? 64 : segs;
-  // (statuses, group counts, LW_BRK replicas, one list per workgroup)
-  const uint64_t bytes = 8 * (lat_sl_off(want) + lat_max_grid(s) * LAT_LSW);
   void* m = nullptr;
   if (hipMalloc(&m, bytes) != hipSuccess) return XYWS_ERR_NOMEM;
-  if (s->lmem) {
+  if (*mem) {
     (void)hipDeviceSynchronize();
-    (void)hipFree(s->lmem);
+    (void)hipFree(*mem);
   }
-  s->lmem = m;
-  s->lmax_segs = want;
-  return xyws_internal::zero_now(m, bytes) == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
+  *mem = m;
+  *have = want;
+  return !zero || xyws_internal::zero_now(m, zero) == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
 }
 
-int stream_scratch_unmask_counter(stream_scratch* s, bool capturing, uint32_t** out) {
-  if (const int rc = lat_grow(s, 1, capturing)) return rc;
-  *out = reinterpret_cast<uint32_t*>(static_cast<uint64_t*>(s->lmem) + LW_UNMASK);
+int reserve_for(stream_scratch* s, const scratch_need& need, bool capturing) {
+  if (need.runs) {
+    const uint64_t want = need.runs < 64 ? 64 : need.runs;
+    const uint64_t bytes = records_off(want) + 2 * want * R_WORDS * 8;
+    if (const int rc = grow_area(&s->mem, &s->max_runs, want, bytes, records_off(want), capturing)) return rc;
+  }
+  // Frame-start lists for descriptor emission: one region per flat item.
+  if (need.fmem_bytes)
+    if (const int rc = grow_area(&s->fmem, &s->fbytes, need.fmem_bytes, need.fmem_bytes, 0, capturing)) return rc;
+  // Lattice decoder scratch: LW_STAT words of scratch, one result word per
+  // segment, group counts, LW_BRK replicas and one list per workgroup (one
+  // workgroup per CU, 64 in the small-segment test mode), all zeroed at
+  // allocation (epoch 0: no result of any call).
+  if (need.lat_segs) {
+    const uint64_t want = need.lat_segs < 64 ? 64 : need.lat_segs;
+    const uint64_t maxg = s->ncu > 64 ? (uint64_t)s->ncu : 64;
+    const uint64_t bytes = 8 * (lat_sl_off(want) + maxg * LAT_LSW);
+    if (const int rc = grow_area(&s->lmem, &s->lmax_segs, want, bytes, bytes, capturing)) return rc;
+  }
   return XYWS_OK;
 }
 
-// The most runs any production geometry launches: four per CU (G_MID, the
-// echo-sized batches), capped at MAX_RUNS.
-static uint64_t max_prod_runs(const stream_scratch* s) {
-  const uint64_t r = (uint64_t)s->ncu * 4;
-  return r < MAX_RUNS ? r : MAX_RUNS;
-}
-
-int stream_scratch_reserve_frames(stream_scratch* s, uint64_t max_batch_bytes, uint64_t max_frames) {
-  // the descriptor regions total 8 * 2R * (2 * cap / R + 1024 + 4) bytes:
-  // largest at the most runs a production geometry launches
-  const uint64_t runs = max_prod_runs(s);
-  (void)max_batch_bytes;
-  const uint64_t nflat = 2 * runs;
-  // (any smaller run count gives regions whose total is no larger, up to the
-  // rounding of cap / runs: + 4 entries per item)
-  return fmem_grow(s, 8 * nflat * (region_entries(max_frames, runs) + 4), false);
-}
-
-int stream_scratch_reserve(stream_scratch* s, uint64_t max_batch_bytes) {
-  // the production geometries (stream_decode_fused): one run per segment up
-  // to their run count (1, 2 or 4 per CU on 128, 64 or 16 KiB segments); the
-  // small-segment test mode grows scratch lazily
-  uint64_t runs = 0;
-  const uint64_t segs[3] = {G_PROD::SEG, G_PROD2::SEG, G_MID::SEG}, per_cu[3] = {1, 2, 4};
-  for (int g = 0; g < 3; g++) {
-    const uint64_t nseg = (max_batch_bytes + 15 + segs[g] - 1) / segs[g];
-    const uint64_t r = (uint64_t)s->ncu * per_cu[g], maxr = r < MAX_RUNS ? r : MAX_RUNS;
-    const uint64_t n = nseg < maxr ? nseg : maxr;
-    if (n > runs) runs = n;
-  }
-  if (const int rc = scratch_grow(s, runs)) return rc;
-  // the lattice decoder's (production geometries: the 75 KiB segments have the most)
-  return lat_grow(s, (max_batch_bytes + 15 + G_LAT5::SEG - 1) / G_LAT5::SEG, false);
+int stream_scratch_unmask_counter(stream_scratch* s, bool capturing, uint32_t** out) {
+  if (const int rc = reserve_for(s, scratch_need{0, 0, 1}, capturing)) return rc;
+  *out = reinterpret_cast<uint32_t*>(static_cast<uint64_t*>(s->lmem) + LW_UNMASK);
+  return XYWS_OK;
 }
 
 int stream_scratch_stats(stream_scratch* s, uint64_t out[XYWS_NSTATS]) {
@@ -3119,7 +3073,13 @@ uint32_t stream_scratch_error(stream_scratch* s, bool clear) {
   return v[1];
 }
 
-// The run decoder's geometry, by the same statistics: regular frames under
+// The only reader of the pinned policy words on the decode path.
+policy_view policy_snapshot(const stream_scratch* s) {
+  if (!s->pol_h) return policy_view{false, 0, 0, 0};
+  return policy_view{true, s->pol_h[0], s->pol_h[2], s->pol_h[3]};
+}
+
+// The run decoder's geometry, by the previous call's statistics: regular frames under
 // WG512_MAX_FRAME take two 512-thread workgroups per CU on 64 KiB segments
 // (while one workgroup chases its segment, the other's stores drain: c2's
 // 264-byte frames 0.247 -> 0.181 ms, same box), the rest one 1024-thread
@@ -3135,18 +3095,14 @@ constexpr uint64_t WG512_MAX_FRAME = 2048;
 // of the 512-thread geometry (a run's latency is the call's: 4 MiB of 0-1000 B
 // frames with descriptors 80.6 -> 65.7 us, 1 MiB 81.9 -> 57.4; 8 KiB segments
 // 78.9 / 53.6; at 16 MiB the 512-thread geometry stays faster, 94 vs 125).
-static bool mid_preferred(const stream_scratch* s, uint64_t len) {
-  if (!s->pol_h) return false;
-  const uint64_t fsmin = s->pol_h[2], fsmax = s->pol_h[3];
-  return fsmax && fsmax < WG512_MAX_FRAME && fsmin != fsmax && len <= (uint64_t)s->ncu * 32768;
+static bool mid_preferred(int ncu, const policy_view& pv, uint64_t len) {
+  return pv.fsmax && pv.fsmax < WG512_MAX_FRAME && pv.fsmin != pv.fsmax && len <= (uint64_t)ncu * 32768;
 }
 constexpr uint64_t DENSE0_MAX_FRAME = 2048;
 constexpr uint64_t BIGSCAN_MIN_FRAME = 16384;
-static bool wg512_preferred(const stream_scratch* s, uint64_t len) {
-  if (!s->pol_h) return false;
-  const uint64_t fsmin = s->pol_h[2], fsmax = s->pol_h[3];
-  const bool small_batch = len < (uint64_t)s->ncu * G_PROD::SEG;
-  return fsmax && fsmax < WG512_MAX_FRAME && (fsmin == fsmax || small_batch);
+static bool wg512_preferred(int ncu, const policy_view& pv, uint64_t len) {
+  const bool small_batch = len < (uint64_t)ncu * G_PROD::SEG;
+  return pv.fsmax && pv.fsmax < WG512_MAX_FRAME && (pv.fsmin == pv.fsmax || small_batch);
 }
 
 // The lattice decoder (xyws_lattice.h) goes first when the previous call on
@@ -3156,155 +3112,164 @@ static bool wg512_preferred(const stream_scratch* s, uint64_t len) {
 // stream (XYWS_OPT_REDIRECT) and decodes what it left: nothing (it exits at
 // once), the batch from the first frame off the lattice, or all of it. Its
 // miss costs its loads of the batch's first segments.
-static bool lattice_preferred(const stream_scratch* s) {
-  if (!s->pol_h) return false;
-  const uint64_t fsmin = s->pol_h[2], fsmax = s->pol_h[3];
-  if (!s->pol_h[0]) return true;  // (no call has finished on this stream)
-  return fsmax && fsmin == fsmax && fsmin >= LAT_FMIN;
+static bool lattice_preferred(const policy_view& pv) {
+  if (!pv.present) return false;
+  if (!pv.epoch) return true;  // (no call has finished on this stream)
+  return pv.fsmax && pv.fsmin == pv.fsmax && pv.fsmin >= LAT_FMIN;
 }
 
-template <class GA, class GB>
-int launch_lattice(const run_params& P, uint32_t grid, hipStream_t stream) {
-  static std::mutex mu;
-  static bool done[64] = {};
-  using LL = lat_lds<llay<GA, GB>>;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return XYWS_ERR_HIP;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done[dev]) {
-      if (hipFuncSetAttribute((const void*)k_stream_lattice<GA, GB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)sizeof(LL)) != hipSuccess)
-        return XYWS_ERR_HIP;
-      done[dev] = true;
-    }
+decode_plan plan_decode(int ncu, const policy_view& pv, uint64_t lo, uint64_t hi, uint64_t cap_if_frames,
+                        uint32_t opts) {
+  decode_plan p = {};
+  p.lo = lo; p.hi = hi;
+  opts &= ~XYWS_OPT_REDIRECT;  // (set by launch_plan only)
+  p.opts = opts;
+  if (hi == lo) return p;
+  const bool small = (opts & XYWS_OPT_SMALL_SEG) != 0;
+  constexpr uint32_t RUN_MODES = XYWS_OPT_PARSE_ONLY | XYWS_OPT_WG512 | XYWS_OPT_DIAG | XYWS_OPT_TEST_GIVEUP |
+                                 XYWS_OPT_STEAL | XYWS_OPT_TEST_STEAL | XYWS_OPT_RUNS | XYWS_OPT_NO_LATTICE |
+                                 XYWS_OPT_RUNS_NOWAIT | XYWS_OPT_WG1024 | XYWS_OPT_NO_LATENTRY;
+  p.want_lat = !(opts & (RUN_MODES | XYWS_OPT_NO_LATDEC)) &&
+               ((opts & XYWS_OPT_LATTICE) || (!small && lattice_preferred(pv)));
+  const bool mid = !small && !(opts & (XYWS_OPT_WG512 | XYWS_OPT_WG1024)) &&
+                   ((opts & XYWS_OPT_WG256) || mid_preferred(ncu, pv, hi - lo));
+  const bool wg512 = !small && !mid && !(opts & XYWS_OPT_WG1024) &&
+                     ((opts & XYWS_OPT_WG512) || wg512_preferred(ncu, pv, hi - lo));
+  uint64_t per_cu;  // workgroups a CU holds at once
+  if (small) p.geom = GEOM_SMALL, p.seg = G_SMALL::SEG, p.threads = G_SMALL::NT, per_cu = 0;
+  else if (mid) p.geom = GEOM_MID, p.seg = G_MID::SEG, p.threads = G_MID::NT, per_cu = 4;
+  else if (wg512) p.geom = GEOM_WG512, p.seg = G_PROD2::SEG, p.threads = G_PROD2::NT, per_cu = 2;
+  else p.geom = GEOM_PROD, p.seg = G_PROD::SEG, p.threads = G_PROD::NT, per_cu = 1;
+  // Runs get equal byte ranges (multiples of 16, one segment at least): every
+  // workgroup streams the same number of bytes, and a run whose chain crosses
+  // into the next range loads only the bytes below the successor's W there.
+  const uint64_t nseg = (hi + p.seg - 1) / p.seg;
+  const uint64_t r = small ? nseg : (uint64_t)ncu * per_cu;
+  const uint64_t maxr = r < MAX_RUNS ? r : MAX_RUNS;
+  p.rbytes = nseg <= maxr ? p.seg : ((hi + maxr - 1) / maxr + 15) & ~15ull;
+  p.nruns = (hi + p.rbytes - 1) / p.rbytes;
+  p.nflat = 2 * (uint32_t)p.nruns;
+  p.need.runs = p.nruns;
+  // the lattice entry (find_entry): the previous call's frames all F bytes
+  // long, several per segment
+  if (!(opts & XYWS_OPT_NO_LATENTRY) && pv.fsmax && pv.fsmin == pv.fsmax && pv.fsmax <= p.seg / 4) p.pfs = pv.fsmax;
+  // small frames of mixed sizes last call (every run's last frame under
+  // DENSE0_MAX_FRAME, not all one size): the dense pass from each run's first
+  // segment (echo-sized batches of 0-1000 B frames: one segment per run)
+  if (!(opts & XYWS_OPT_NO_DENSE0) && pv.fsmax && pv.fsmin != pv.fsmax && pv.fsmax < DENSE0_MAX_FRAME) p.dense0 = 1;
+  // large frames of mixed sizes last call (some last frame of BIGSCAN_MIN_FRAME
+  // or more: config 4): the entry scans filter a whole segment in one pass (a
+  // range start usually lies inside a large frame: the first 16 KiB hold no
+  // entry, and their own round of checks cost 3.6 us per scanned segment, c4)
+  p.bigscan = (opts & XYWS_OPT_BIGSCAN) ? 1u : 0u;
+  if (!(opts & XYWS_OPT_NO_BIGSCAN) && pv.fsmax && pv.fsmin != pv.fsmax && pv.fsmax >= BIGSCAN_MIN_FRAME)
+    p.bigscan = 1;
+  if (cap_if_frames) {
+    // Descriptor regions: one per flat item, of twice the caller's capacity
+    // spread over the runs + 1024 entries (a region that overflows switches
+    // the call to the chain re-walk). The need is their total with cap /
+    // nruns not rounded up, and one entry pair per region for the rounding:
+    // 8 * (4 * cap + 2052 * nruns) grows with cap and with nruns (the exact
+    // total does not: 1024 frames over 1023 runs take more than over 1024),
+    // so that a reserve for the most runs and frames covers every smaller call.
+    p.rcap = 2 * ((cap_if_frames + p.nruns - 1) / p.nruns) + 1024;
+    p.need.fmem_bytes = 8 * (4 * cap_if_frames + 2052 * p.nruns);
   }
-  hipLaunchKernelGGL((k_stream_lattice<GA, GB>), dim3(grid), dim3(GB::NT), sizeof(LL), stream, P);
-  return hipGetLastError() == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
+  if (p.want_lat) {
+    // Its segment geometry (75 KiB for frames of LAT5_MIN_FRAME and more, else
+    // 120 KiB), the first-segment gate and its bail-out after an irregular
+    // call are decided in the kernel (the batch's first frame, the device
+    // policy word HW_DPOL); the grid covers the smaller segments.
+    p.lseg[0] = small ? G_LAT_SMALL::SEG : G_LAT5::SEG;
+    p.lseg[1] = small ? G_LAT_SMALL::SEG : G_LAT::SEG;
+    p.lnseg = (hi + p.lseg[0] - 1) / p.lseg[0];
+    const uint64_t maxg = small ? 64 : (uint64_t)ncu;
+    p.lgrid = (uint32_t)(p.lnseg < maxg ? p.lnseg : maxg);
+    p.need.lat_segs = p.lnseg;
+  }
+  return p;
+}
+
+scratch_need plan_reserve(int ncu, uint64_t max_batch_bytes, uint64_t max_frames) {
+  // every geometry the choice can take, forced, on the largest batch at the
+  // largest misalignment: a plan's needs grow with its batch (one run per
+  // segment up to the geometry's run count, then that count: with segments of
+  // 16 * (MAX_RUNS - 1) bytes or more, rounding the runs up to 16 bytes never
+  // saves a run)
+  static_assert(G_MID::SEG >= 16 * (MAX_RUNS - 1), "the run count grows with the batch");
+  scratch_need need = {};
+  for (const uint32_t force : {XYWS_OPT_WG1024, XYWS_OPT_WG512, XYWS_OPT_WG256, XYWS_OPT_LATTICE})
+    need_max(&need, plan_decode(ncu, policy_view{}, 0, max_batch_bytes + 15, max_frames, force).need);
+  return need;
+}
+
+int stream_scratch_reserve(stream_scratch* s, uint64_t max_batch_bytes, uint64_t max_frames) {
+  return reserve_for(s, plan_reserve(s->ncu, max_batch_bytes, max_frames), false);
+}
+
+int launch_plan(const stream_scratch* s, const decode_plan& pl, uint8_t* base, const xyws_carry* cin,
+                xyws_carry* cout, xyws_frame* frames, uint64_t cap, uint64_t* nframes, hipStream_t stream) {
+  if (!pl.nruns) {
+    hipLaunchKernelGGL(k_stream_empty, dim3(1), dim3(64), 0, stream, cin, cout, nframes);
+    return hipGetLastError() == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
+  }
+  uint8_t* m = static_cast<uint8_t*>(s->mem);
+  run_params P;
+  P.base = base; P.lo = pl.lo; P.hi = pl.hi; P.rbytes = pl.rbytes;
+  P.nruns = (uint32_t)pl.nruns;
+  P.cout = cout; P.frames = frames; P.cap = cap; P.nframes = nframes;
+  P.head = reinterpret_cast<uint32_t*>(m);
+  P.nflat = pl.nflat;
+  P.flags = reinterpret_cast<uint64_t*>(m + HEAD_BYTES);
+  P.split = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->max_runs));
+  P.prog = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->max_runs) + split_bytes(s->max_runs));
+  P.rec = reinterpret_cast<uint64_t*>(m + records_off(s->max_runs));
+  P.opts = pl.opts;
+  // The ticket is zero here (zeroed at allocation, reset by finish_call
+  // after every call); granules, split and progress words carry the epoch of
+  // the call that wrote them; the error word [1] is sticky until read back.
+  // Run 0 snapshots the incoming carry into scratch.
+  if ((pl.opts & XYWS_OPT_STATS) && hipMemsetAsync(m + 128, 0, 8 * XYWS_NSTATS, stream) != hipSuccess)
+    return XYWS_ERR_HIP;
+  P.cin_user = cin;
+  P.cin = reinterpret_cast<xyws_carry*>(m + 64);
+  P.fst = pl.rcap ? static_cast<uint64_t*>(s->fmem) : nullptr;
+  P.rcap = pl.rcap;
+  P.pol = s->pol_d;
+  P.lat = static_cast<uint64_t*>(s->lmem);  // (nullable: the device policy word's second copy)
+  P.segb = pl.seg;
+  P.tbias = 0;
+  P.obias = 0;
+  P.nseg = 0;
+  P.pfs = pl.pfs;
+  P.dense0 = pl.dense0;
+  P.bigscan = pl.bigscan;
+  const bool small = pl.geom == GEOM_SMALL;
+  if (pl.want_lat) {
+    // the lattice decoder first; the run decoder after it reads its redirect
+    // record
+    run_params PL = P;
+    PL.opts &= ~XYWS_OPT_LAT_NOGATE;
+    PL.lgrp = PL.lat + LW_STAT + s->lmax_segs;
+    PL.lbrk = PL.lat + lat_rep_off(s->lmax_segs);
+    PL.lsl = PL.lat + lat_sl_off(s->lmax_segs);
+    PL.nseg = pl.lnseg;  // (the kernel counts the segments of the geometry it takes)
+    const int rc = small ? launch_lattice<G_LAT_SMALL, G_LAT_SMALL>(PL, pl.lgrid, stream)
+                         : launch_lattice<G_LAT5, G_LAT>(PL, pl.lgrid, stream);
+    if (rc) return rc;
+    P.opts |= XYWS_OPT_REDIRECT;
+    if (pl.opts & XYWS_OPT_LATX_ONLY) return XYWS_OK;  // (timing experiment: the lattice kernel alone)
+  }
+  return small                  ? launch_runs<G_SMALL>(P, stream)
+         : pl.geom == GEOM_MID   ? launch_runs<G_MID>(P, stream)
+         : pl.geom == GEOM_WG512 ? launch_runs<G_PROD2>(P, stream)
+                                 : launch_runs<G_PROD>(P, stream);
 }
 
 int stream_decode_fused(stream_scratch* s, uint8_t* base, uint64_t lo, uint64_t hi,
                         const xyws_carry* cin, xyws_carry* cout, xyws_frame* frames, uint64_t cap,
                         uint64_t* nframes, uint32_t opts, hipStream_t stream) {
-  opts &= ~XYWS_OPT_REDIRECT;  // (set here only)
-  if (hi == lo) {
-    hipLaunchKernelGGL(k_stream_empty, dim3(1), dim3(64), 0, stream, cin, cout, nframes);
-    return hipGetLastError() == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
-  }
-  const bool small = (opts & XYWS_OPT_SMALL_SEG) != 0;
-  constexpr uint32_t RUN_MODES = XYWS_OPT_PARSE_ONLY | XYWS_OPT_WG512 | XYWS_OPT_DIAG | XYWS_OPT_TEST_GIVEUP |
-                                 XYWS_OPT_STEAL | XYWS_OPT_TEST_STEAL | XYWS_OPT_RUNS | XYWS_OPT_NO_LATTICE |
-                                 XYWS_OPT_RUNS_NOWAIT | XYWS_OPT_WG1024 | XYWS_OPT_NO_LATENTRY;
-  const bool want_lat = !(opts & (RUN_MODES | XYWS_OPT_NO_LATDEC)) &&
-                        ((opts & XYWS_OPT_LATTICE) || (!small && lattice_preferred(s)));
-  const bool mid = !small && !(opts & (XYWS_OPT_WG512 | XYWS_OPT_WG1024)) &&
-                   ((opts & XYWS_OPT_WG256) || mid_preferred(s, hi - lo));
-  const bool wg512 = !small && !mid && !(opts & XYWS_OPT_WG1024) && ((opts & XYWS_OPT_WG512) || wg512_preferred(s, hi - lo));
-  const uint64_t seg = small ? G_SMALL::SEG : mid ? G_MID::SEG : wg512 ? G_PROD2::SEG : G_PROD::SEG;
-  // Runs get equal byte ranges (multiples of 16, one segment at least): every
-  // workgroup streams the same number of bytes, and a run whose chain crosses
-  // into the next range loads only the bytes below the successor's W there.
-  const uint64_t nseg = (hi + seg - 1) / seg;
-  uint64_t nruns, rbytes;
-  const uint64_t r = small ? nseg : (uint64_t)s->ncu * (mid ? 4u : wg512 ? 2u : 1u);
-  const uint64_t maxr = r < MAX_RUNS ? r : MAX_RUNS;
-  if (nseg <= maxr) {
-    rbytes = seg;
-  } else {
-    rbytes = ((hi + maxr - 1) / maxr + 15) & ~15ull;
-  }
-  nruns = (hi + rbytes - 1) / rbytes;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(stream, &cs);
-  if (nruns > s->max_runs || !s->mem) {
-    if (cs != hipStreamCaptureStatusNone) return XYWS_ERR_CAPACITY;
-    const int rc = scratch_grow(s, nruns);
-    if (rc) return rc;
-  }
-  uint8_t* m = static_cast<uint8_t*>(s->mem);
-  run_params P;
-  P.base = base; P.lo = lo; P.hi = hi; P.rbytes = rbytes;
-  P.nruns = (uint32_t)nruns;
-  P.cout = cout; P.frames = frames; P.cap = cap; P.nframes = nframes;
-  P.head = reinterpret_cast<uint32_t*>(m);
-  P.nflat = 2 * P.nruns;
-  P.flags = reinterpret_cast<uint64_t*>(m + HEAD_BYTES);
-  P.split = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->max_runs));
-  P.prog = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->max_runs) + split_bytes(s->max_runs));
-  P.rec = reinterpret_cast<uint64_t*>(m + records_off(s->max_runs));
-  P.opts = opts;
-  // The ticket is zero here (zeroed at allocation, reset by finish_call
-  // after every call); granules, split and progress words carry the epoch of
-  // the call that wrote them; the error word [1] is sticky until read back.
-  // Run 0 snapshots the incoming carry into scratch.
-  if ((opts & XYWS_OPT_STATS) && hipMemsetAsync(m + 128, 0, 8 * XYWS_NSTATS, stream) != hipSuccess) return XYWS_ERR_HIP;
-  P.cin_user = cin;
-  P.cin = reinterpret_cast<xyws_carry*>(m + 64);
-  P.fst = nullptr; P.rcap = 0;
-  P.pol = s->pol_d;
-  P.lat = static_cast<uint64_t*>(s->lmem);  // (nullable: the device policy word's second copy)
-  P.segb = (uint32_t)seg;
-  P.tbias = 0;
-  P.obias = 0;
-  P.nseg = 0;
-  // the lattice entry (find_entry): the previous call's frames all F bytes
-  // long, several per segment
-  P.pfs = 0;
-  P.dense0 = 0;
-  if (s->pol_h && !(opts & XYWS_OPT_NO_LATENTRY)) {
-    const uint64_t fsmin = s->pol_h[2], fsmax = s->pol_h[3];
-    if (fsmax && fsmin == fsmax && fsmax <= seg / 4) P.pfs = fsmax;
-  }
-  // small frames of mixed sizes last call (every run's last frame under
-  // DENSE0_MAX_FRAME, not all one size): the dense pass from each run's first
-  // segment (echo-sized batches of 0-1000 B frames: one segment per run)
-  if (s->pol_h && !(opts & XYWS_OPT_NO_DENSE0)) {
-    const uint64_t fsmin = s->pol_h[2], fsmax = s->pol_h[3];
-    if (fsmax && fsmin != fsmax && fsmax < DENSE0_MAX_FRAME) P.dense0 = 1;
-  }
-  // large frames of mixed sizes last call (some last frame of BIGSCAN_MIN_FRAME
-  // or more: config 4): the entry scans filter a whole segment in one pass (a
-  // range start usually lies inside a large frame: the first 16 KiB hold no
-  // entry, and their own round of checks cost 3.6 us per scanned segment, c4)
-  P.bigscan = (opts & XYWS_OPT_BIGSCAN) ? 1u : 0u;
-  if (s->pol_h && !(opts & XYWS_OPT_NO_BIGSCAN)) {
-    const uint64_t fsmin = s->pol_h[2], fsmax = s->pol_h[3];
-    if (fsmax && fsmin != fsmax && fsmax >= BIGSCAN_MIN_FRAME) P.bigscan = 1;
-  }
-  if (frames && cap) {
-    const uint64_t rc_n = region_entries(cap, nruns);
-    const int rc = fmem_grow(s, 8 * (uint64_t)P.nflat * rc_n, cs != hipStreamCaptureStatusNone);
-    if (rc) return rc;
-    P.fst = static_cast<uint64_t*>(s->fmem);
-    P.rcap = rc_n;
-  }
-  if (want_lat) {
-    // the lattice decoder first; the run decoder after it reads its redirect
-    // record. Its segment geometry (75 KiB for frames of LAT5_MIN_FRAME and
-    // more, else 120 KiB), the first-segment gate and its bail-out after an
-    // irregular call are decided in the kernel (the batch's first frame, the
-    // device policy word HW_DPOL); the grid covers the smaller segments.
-    const uint64_t lseg = small ? G_LAT_SMALL::SEG : G_LAT5::SEG;
-    const uint64_t lnseg = (hi + lseg - 1) / lseg;
-    if (const int rc = lat_grow(s, lnseg, cs != hipStreamCaptureStatusNone)) return rc;
-    run_params PL = P;
-    PL.opts &= ~XYWS_OPT_LAT_NOGATE;
-    PL.lat = static_cast<uint64_t*>(s->lmem);
-    PL.lgrp = PL.lat + LW_STAT + s->lmax_segs;
-    PL.lbrk = PL.lat + lat_rep_off(s->lmax_segs);
-    PL.lsl = PL.lat + lat_sl_off(s->lmax_segs);
-    PL.nseg = lnseg;  // (the kernel counts the segments of the geometry it takes)
-    const uint64_t maxg = small ? 64 : (uint64_t)s->ncu;
-    const uint32_t grid = (uint32_t)(lnseg < maxg ? lnseg : maxg);
-    const int rc = small ? launch_lattice<G_LAT_SMALL, G_LAT_SMALL>(PL, grid, stream)
-                         : launch_lattice<G_LAT5, G_LAT>(PL, grid, stream);
-    if (rc) return rc;
-    P.lat = PL.lat;
-    P.opts |= XYWS_OPT_REDIRECT;
-    if (opts & XYWS_OPT_LATX_ONLY) return XYWS_OK;  // (timing experiment: the lattice kernel alone)
-  }
-  return small ? launch_runs<G_SMALL>(P, stream)
-         : mid   ? launch_runs<G_MID>(P, stream)
-         : wg512 ? launch_runs<G_PROD2>(P, stream)
-                 : launch_runs<G_PROD>(P, stream);
+  const decode_plan pl = plan_decode(s->ncu, policy_snapshot(s), lo, hi, frames ? cap : 0, opts);
+  if (const int rc = reserve_for(s, pl.need, xyws_internal::capturing(stream))) return rc;
+  return launch_plan(s, pl, base, cin, cout, frames, cap, nframes, stream);
 }

@@ -263,8 +263,9 @@ class frame_decoder:
 
     def decode_iov(self, bufs, cap=0, count=True, carry=True):
         """Decode a buffer sequence (device uint8 tensors, one recv's pieces)
-        as ONE stream, every piece in place (xyws_decode_stream_iov: three
-        launches whatever the piece count). Descriptor offsets count bytes
+        as ONE stream, every piece in place (xyws_decode_stream_iov: a single
+        piece or few large ones where they lie, else gathered, decoded and
+        scattered back in three launches). Descriptor offsets count bytes
         across the pieces in order."""
         import torch
         ts = [_dev_u8(b) for b in bufs]
