@@ -149,12 +149,14 @@ int xyws_ctx_destroy(xyws_ctx* ctx);
  * nothing and can be captured into a hipGraph. The per-frame tables go to the
  * streams already used on the context and to one spare: the first stream new
  * to the context may be captured at once; a second new stream needs one
- * uncaptured call first (or XYWS_ERR_CAPACITY). Calls on larger batches grow
- * scratch lazily. */
+ * uncaptured call first (or XYWS_ERR_CAPACITY). A stream that gets them gets
+ * whatever this call and xyws_ctx_reserve_iov have reserved so far, whichever
+ * call it is. Calls on larger batches grow scratch lazily. */
 int xyws_ctx_reserve(xyws_ctx* ctx, uint64_t max_batch_bytes, uint64_t max_frames);
 /* The staging buffer of xyws_decode_stream_iov for sequences of up to
  * `max_total_bytes` in all, in the slots of the streams already used on the
- * context and in one spare (as xyws_ctx_reserve's per-frame tables): with
+ * context and in one spare (the same streams, by the same rule, as
+ * xyws_ctx_reserve's per-frame tables): with
  * xyws_ctx_reserve(ctx, max_total_bytes, ...) before it, an iov decode that
  * fits allocates nothing and can be captured into a hipGraph. */
 int xyws_ctx_reserve_iov(xyws_ctx* ctx, uint64_t max_total_bytes);

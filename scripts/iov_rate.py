@@ -47,16 +47,16 @@ def main():
         return e0.elapsed_time(e1) / reps
 
     from xynet_amd import _lib  # noqa: F401
-    dec.opts = 0x20000000  # XYWS_OPT_IOV_STAGE: gather, decode, scatter
+    dec.opts = _lib.OPT_IOV_STAGE  # gather, decode, scatter
     ms_stage = timed(lambda: dec.decode_iov(pieces, cap=0, count=False, carry=False))
-    dec.opts = 0x10000000  # XYWS_OPT_IOV_PIECES: the pieces in place, carry chained
+    dec.opts = _lib.OPT_IOV_PIECES  # the pieces in place, carry chained
     ms_iov = timed(lambda: dec.decode_iov(pieces, cap=0, count=False, carry=False))
     dec.opts = 0
     ms_one = timed(lambda: dec.decode(buf, cap=0, count=False, carry=False))
     # (4 + reps calls each: an even count when reps is even) one more iov call
     # (in pieces): unmasked
     assert (4 + reps) % 2 == 0
-    dec.opts = 0x10000000
+    dec.opts = _lib.OPT_IOV_PIECES
     r = dec.decode_iov(pieces, cap=0, count=True, carry=False)
     whole = torch.cat(pieces)
     ok = dev_digest(whole) == c["out_digest"] and r.nframes == c["decoded_frames"]

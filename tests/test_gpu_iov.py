@@ -16,6 +16,7 @@ import pytest
 
 import streams
 from test_gpu_parity import carry_list, dev_bytes, frames_list, host, torch
+from xynet_amd._lib import OPT_IOV_PIECES, OPT_LATTICE
 
 pytestmark = pytest.mark.gpu
 
@@ -34,9 +35,6 @@ def pieces_of(src, rng, n):
     if n > 2:
         cuts.insert(1, cuts[1])
     return [src[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
-
-
-OPT_IOV_PIECES = 0x10000000  # xyws_stream.h: the pieces in place one by one (no descriptors)
 
 
 def decode_seq(ws, oracle, dec, seq, carry_in, rng, desc=True):
@@ -107,9 +105,6 @@ def test_equal_frames_take_the_lattice_decoder(ws, oracle):
     c = None
     for _ in range(3):  # (one stream: the frame count carries on)
         c = decode_seq(ws, oracle, dec, pieces_of(src, rng, 9), c, rng)
-
-
-OPT_LATTICE = 0x400  # xyws_stream.h: the lattice decoder first
 
 
 @pytest.mark.parametrize("npieces", [5, 17])
@@ -210,5 +205,41 @@ def test_captured_after_reserve_iov(ws, oracle):
         torch.cuda.synchronize()
         got = b"".join(v.cpu().numpy().tobytes() for v in views)
         assert got == host.tobytes(), rep
+        assert r.nframes == on, rep
+    ctx.close()
+
+
+def test_a_slot_that_gets_a_reserve_gets_all_of_them(ws, oracle):
+    """reserve, an eager decode on stream A (it binds the spare slot), then
+    reserve_iov: the new spare slot gets the per-frame reserve with its
+    staging buffer, so a staged decode with descriptors captured on a stream
+    B new to the context allocates nothing."""
+    src = streams.case_bytes("random_frames_200")
+    rng = streams.SplitMix(0x10F)
+    seq = pieces_of(src, rng, 7)
+    want = np.frombuffer(src, np.uint8).copy()
+    ofr, _, on = oracle.decode_stream(want)
+    ctx = ws.Context(0)
+    ctx.reserve(len(src) + 64, 4096)
+    dec = ws.frame_decoder(ctx=ctx)
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    with torch.cuda.stream(a):
+        buf = torch.frombuffer(bytearray(src), dtype=torch.uint8).cuda()
+        assert dec.decode(buf, cap=on + 2, carry=False).nframes == on
+    ctx.reserve_iov(len(src) + 64)
+    views = [torch.frombuffer(bytearray(p if p else b"\0"), dtype=torch.uint8).cuda()[: len(p)] for p in seq]
+    origs = [v.clone() for v in views]
+    g = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    with torch.cuda.graph(g, stream=b):
+        r = dec.decode_iov(views, cap=on + 2, carry=False)
+    torch.cuda.synchronize()
+    for rep in range(3):
+        for v, o in zip(views, origs):
+            v.copy_(o)
+        g.replay()
+        torch.cuda.synchronize()
+        assert b"".join(host(v) for v in views) == want.tobytes(), rep
+        assert frames_list(r.frames(), True) == frames_list(ofr, True), rep
         assert r.nframes == on, rep
     ctx.close()

@@ -24,13 +24,10 @@ import pytest
 import streams
 from test_gpu_parity import carry_list, dev_bytes, frames_list, host, torch
 from test_gpu_choice import _policy
+from xynet_amd._lib import OPT_LATTICE, OPT_SMALL_SEG as OPT_SMALL, OPT_TEST_LATDUMP, OPT_TEST_LATSPEC
 
 pytestmark = pytest.mark.gpu
 
-OPT_LATTICE = 0x400
-OPT_SMALL = 0x200
-OPT_TEST_LATSPEC = 0x10  # every store speculative: a broken lattice is undone by the end-of-work check
-OPT_TEST_LATDUMP = 0x20  # no workgroup undoes its own stores at its end: every list goes to the finisher
 MODES = {"lat": {"opts": OPT_LATTICE}, "lat1k": {"opts": OPT_LATTICE | OPT_SMALL},
          "lat_blind": {"opts": OPT_LATTICE | OPT_TEST_LATSPEC},
          "lat1k_blind": {"opts": OPT_LATTICE | OPT_SMALL | OPT_TEST_LATSPEC},

@@ -20,11 +20,9 @@ import pytest
 from conftest import load_golden
 import streams
 from test_gpu_parity import carry_list, dev_bytes, frames_list, host, torch
+from xynet_amd._lib import OPT_UNMASKED_HINT
 
 pytestmark = pytest.mark.gpu
-
-OPT_UNMASKED_HINT = 0x2   # include/xyws.h
-
 
 @pytest.fixture(scope="module")
 def ws():

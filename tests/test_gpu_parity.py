@@ -12,20 +12,13 @@ import pytest
 
 from conftest import load_golden
 import streams
+from xynet_amd._lib import (OPT_BIGSCAN, OPT_LATTICE, OPT_NO_LATDEC, OPT_STEAL, OPT_TEST_GIVEUP, OPT_TEST_STEAL,
+                            OPT_UNMASKED_HINT, OPT_WG256, OPT_WG512)
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-OPT_TEST_GIVEUP = 0x100000  # xyws_stream.h: odd runs give up on their successor (finish bridges them)
-OPT_STEAL = 0x400000        # work stealing (off by default)
-OPT_TEST_STEAL = 0x800000   # every fourth run starts late; pieces of 1 segment and up are taken
-OPT_UNMASKED_HINT = 0x2     # include/xyws.h: speculate on server->client framing (wrong for these streams)
-OPT_WG512 = 0x40000         # two 512-thread workgroups per CU, 64 KiB segments
-OPT_WG256 = 0x8             # four 256-thread workgroups per CU, 16 KiB segments
-OPT_NO_LATDEC = 0x800       # the run decoder itself (equal frames would take the lattice decoder)
-OPT_LATTICE = 0x400         # the lattice decoder first whatever the previous call found (the bench's decoder)
-OPT_BIGSCAN = 0x4000000     # entry scans: one filter pass per segment, whatever the previous call found
 MODES = {"fused": {}, "serial": {"serial": True}, "runs1k": {"small_segments": True},
          "lat": {"opts": OPT_LATTICE},
          "bigscan": {"opts": OPT_BIGSCAN | OPT_NO_LATDEC}, "runs1k_bigscan": {"small_segments": True, "opts": OPT_BIGSCAN},

@@ -21,7 +21,7 @@ THREADS = {SMALL: 64, MID: 256, WG512: 512, PROD: 1024}
 PER_CU = {MID: 4, WG512: 2, PROD: 1}
 MAX_RUNS = 1024
 LSEG5, LSEG = 76800, 122880  # the lattice decoder's 75 KiB / 120 KiB segments
-OPT_PARSE_ONLY, OPT_WG256 = 0x1, 0x8
+OPT_PARSE_ONLY, OPT_WG256 = L.OPT_PARSE_ONLY, L.OPT_WG256
 FIELDS = ("geom", "seg", "threads", "nruns", "rbytes", "nflat", "want_lat", "lnseg", "lgrid", "lseg0", "lseg1",
           "pfs", "dense0", "bigscan", "rcap", "need_runs", "need_fmem", "need_lat")
 

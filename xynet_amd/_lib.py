@@ -16,22 +16,41 @@ XYWS_OK = 0
 XYWS_ERR_DEVICE = -5
 NSTATS = 48  # XYWS_NSTATS (xyws_stream.h)
 R_WORDS = 32  # u64 words per run record (xyws_stream.hip)
-# internal decode options (xyws_stream.h; not part of include/xyws.h)
+# Every XYWS_OPT_* bit under its header's name, by value: the only Python list
+# (tests/test_opts.py holds it to the headers). include/xyws.h:
+OPT_PARSE_ONLY = 0x1
+OPT_UNMASKED_HINT = 0x2
+OPT_SERIAL_SCAN = 0x4
+# internal (xynet_amd/csrc/xyws_stream.h, where each is described):
+OPT_WG256 = 0x8
+OPT_TEST_LATSPEC = 0x10
+OPT_TEST_LATDUMP = 0x20
+OPT_LATX_NOWORK = 0x40
+OPT_LATX_ONLY = 0x80
 OPT_STATS = 0x100
 OPT_SMALL_SEG = 0x200
+OPT_LATTICE = 0x400
+OPT_NO_LATDEC = 0x800
+OPT_NO_DENSE0 = 0x1000
+OPT_REDIRECT = 0x2000
+OPT_NO_LATENTRY = 0x4000
+OPT_WG1024 = 0x8000
+OPT_RUNS_NOWAIT = 0x10000
+OPT_NO_STORE = 0x20000
 OPT_WG512 = 0x40000
-OPT_NO_LATENTRY = 0x4000   # run decoder experiment: no lattice entry
-OPT_WG1024 = 0x8000        # the run decoder's default geometry, whatever the geometry choice would take
+OPT_DIAG = 0x80000
 OPT_TEST_GIVEUP = 0x100000
+OPT_NO_LATTICE = 0x200000
 OPT_STEAL = 0x400000
 OPT_TEST_STEAL = 0x800000
-OPT_RUNS = 0x80000000      # the run decoder whatever the decoder choice would take
-OPT_LATTICE = 0x400        # the lattice decoder first (the run decoder after it takes what it leaves)
-OPT_NO_LATDEC = 0x800      # never the lattice decoder
-OPT_BIGSCAN = 0x4000000    # tests: the entry scans' one-pass filter whatever the previous call found
-OPT_NO_BIGSCAN = 0x40000000  # the entry scans' window-0 pass whatever the previous call found
-OPT_TEST_LATSPEC = 0x10    # tests (lattice decoder): every store speculative (undone at the end of the work)
-OPT_TEST_LATDUMP = 0x20    # tests (lattice decoder): every speculative-store list undone by the finisher
+OPT_LAT_NOGATE = 0x1000000
+OPT_LAT_GATE = 0x2000000
+OPT_BIGSCAN = 0x4000000
+OPT_LATX_NOCHK = 0x8000000
+OPT_IOV_PIECES = 0x10000000
+OPT_IOV_STAGE = 0x20000000
+OPT_NO_BIGSCAN = 0x40000000
+OPT_RUNS = 0x80000000
 # debug stats indices (xyws_stream.hip)
 ST_RUNS, ST_NONE, ST_BAD, ST_REPAIR, ST_CUT, ST_SPIN, ST_SEGS, ST_FRAMES = range(8)
 ST_GIVEUP, ST_BRIDGE, ST_STEAL_REQ, ST_STEAL_ACC, ST_STEAL_SEGS = 32, 33, 34, 35, 36

@@ -27,10 +27,6 @@
 #include "xyws_stream.h"
 #include "xyws_ctx.h"
 
-#ifndef XYWS_HAVE_FUSED
-#define XYWS_HAVE_FUSED 1
-#endif
-
 #define UNMASK_TILE 16384u
 #define UNMASK_THREADS 256u
 #define UNMASK_LDS_FRAMES 512u
@@ -359,6 +355,13 @@ __global__ void __launch_bounds__(UNMASK_THREADS) k_unmask_tiles(uint8_t* __rest
 // ===========================================================================
 using namespace xyws_internal;
 
+// The payloads a frame table lists, unmasked in place (indexed + serial modes).
+static int unmask_table(uint8_t* base, uint64_t lo, uint64_t hi, const frame_table& t, hipStream_t s) {
+  const uint64_t tiles = (hi - (lo & ~(uint64_t)(UNMASK_TILE - 1)) + UNMASK_TILE - 1) / UNMASK_TILE;
+  hipLaunchKernelGGL(k_unmask_tiles, dim3(grid_for(tiles, 1, 4096)), dim3(UNMASK_THREADS), 0, s, base, lo, hi, t);
+  return hip_err(hipGetLastError());
+}
+
 extern "C" {
 
 int xyws_abi_version(void) { return XYWS_ABI_VERSION; }
@@ -386,25 +389,7 @@ int xyws_ctx_create(int device, xyws_ctx** out) {
   if (!g.ok) return XYWS_ERR_HIP;
   xyws_ctx* c = new xyws_ctx();
   c->device = device;
-  c->err = nullptr;
-  c->reserve_bytes = 0;
-  c->reserve_frames = 0;
-  c->reserve_iov = 0;
-  c->stage = nullptr;
-  c->stage_cap = 0;
-  for (auto& st : c->arena_stream) st = nullptr;
-  c->arena_rr = 0;
-  for (auto& sl : c->slot) {
-    sl.bound = false;
-    sl.stream = nullptr;
-    sl.tab_mem = nullptr;
-    sl.aux_mem = nullptr;
-    sl.aux_cap = 0;
-    sl.iov_mem = nullptr;
-    sl.iov_cap = 0;
-    sl.tab_cap = 0;
-    stream_scratch_init(&sl.ss, device);
-  }
+  for (auto& sl : c->slot) stream_scratch_init(&sl.ss, device);
   if (hipMalloc(&c->err, 64) != hipSuccess) {
     delete c;
     return XYWS_ERR_NOMEM;
@@ -424,13 +409,13 @@ int xyws_ctx_destroy(xyws_ctx* ctx) {
     device_guard g(ctx->device);
     (void)hipDeviceSynchronize();
     for (auto& sl : ctx->slot) {
-      if (sl.tab_mem) (void)hipFree(sl.tab_mem);
-      if (sl.aux_mem) (void)hipFree(sl.aux_mem);
-      if (sl.iov_mem) (void)hipFree(sl.iov_mem);
+      sl.tab.release();
+      sl.aux.release();
+      sl.iov.release();
       stream_scratch_free(&sl.ss);
     }
     if (ctx->err) (void)hipFree(ctx->err);
-    if (ctx->stage) (void)hipFree(ctx->stage);
+    ctx->stage.release();
     for (auto st : ctx->arena_stream)
       if (st) (void)hipStreamDestroy(st);
   }
@@ -445,19 +430,11 @@ int xyws_ctx_reserve(xyws_ctx* ctx, uint64_t max_batch_bytes, uint64_t max_frame
   if (!g.ok) return XYWS_ERR_HIP;
   if (max_batch_bytes > ctx->reserve_bytes) ctx->reserve_bytes = max_batch_bytes;
   if (max_frames > ctx->reserve_frames) ctx->reserve_frames = max_frames;
-  bool spare = true;  // the first unbound slot: the one the next new stream binds (acquire_slot)
-  for (auto& sl : ctx->slot) {
-    // the stream decoder's scratch (small: ~160 B per 128 KiB segment) in
-    // every slot; the per-frame tables in the slots bound to a stream now and
-    // in one spare, so that a stream first used inside graph capture finds
-    // them (the others get them when a stream binds them: acquire_slot)
-    const bool take = (sl.bound || spare) && ctx->reserve_frames;
-    if (!sl.bound) spare = false;
-    if (const int rc = stream_scratch_reserve(&sl.ss, ctx->reserve_bytes, take ? ctx->reserve_frames : 0)) return rc;
-    if (take)
-      if (const int rc = ensure_table(&sl, ctx->reserve_frames, false)) return rc;
-  }
-  return XYWS_OK;
+  // the stream decoder's scratch (small: ~160 B per 128 KiB segment) in every
+  // slot; everything per frame by the one rule
+  for (auto& sl : ctx->slot)
+    if (const int rc = stream_scratch_reserve(&sl.ss, ctx->reserve_bytes, 0)) return rc;
+  return reserve_bound_and_spare(ctx);
 }
 
 int xyws_ctx_reserve_iov(xyws_ctx* ctx, uint64_t max_total_bytes) {
@@ -467,17 +444,7 @@ int xyws_ctx_reserve_iov(xyws_ctx* ctx, uint64_t max_total_bytes) {
   if (!g.ok) return XYWS_ERR_HIP;
   const uint64_t bytes = max_total_bytes + 16;  // (xyws_decode_stream_iov's staging: total + 16)
   if (bytes > ctx->reserve_iov) ctx->reserve_iov = bytes;
-  // the slots bound to a stream now and one spare (the one the next new
-  // stream binds), as xyws_ctx_reserve's per-frame tables; the others get
-  // theirs when a stream binds them (acquire_slot)
-  bool spare = true;
-  for (auto& sl : ctx->slot) {
-    const bool take = sl.bound || spare;
-    if (!sl.bound) spare = false;
-    if (take)
-      if (const int rc = ensure_iov(&sl, ctx->reserve_iov, false)) return rc;
-  }
-  return XYWS_OK;
+  return reserve_bound_and_spare(ctx);
 }
 
 int xyws_ctx_last_device_error(xyws_ctx* ctx, uint32_t* out) {
@@ -500,9 +467,8 @@ int xyws_debug_stats(xyws_ctx* ctx, void* stream, uint64_t* out) {
   if (!ctx || !out) return XYWS_ERR_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   device_guard g(ctx->device);
-  for (auto& sl : ctx->slot)
-    if (sl.bound && sl.stream == (hipStream_t)stream) return stream_scratch_stats(&sl.ss, out);
-  return XYWS_ERR_INVALID;
+  scratch_slot* sl = find_slot(ctx, (hipStream_t)stream);
+  return sl ? stream_scratch_stats(&sl->ss, out) : XYWS_ERR_INVALID;
 }
 
 // Internal: the run records of the last fused stream decode on `stream`, at
@@ -512,9 +478,8 @@ int64_t xyws_debug_records(xyws_ctx* ctx, void* stream, uint64_t* out, uint64_t 
   if (!ctx || !out) return XYWS_ERR_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   device_guard g(ctx->device);
-  for (auto& sl : ctx->slot)
-    if (sl.bound && sl.stream == (hipStream_t)stream) return stream_scratch_records(&sl.ss, out, max_runs);
-  return XYWS_ERR_INVALID;
+  scratch_slot* sl = find_slot(ctx, (hipStream_t)stream);
+  return sl ? stream_scratch_records(&sl->ss, out, max_runs) : XYWS_ERR_INVALID;
 }
 
 // Internal: the lattice decoder's device-side choice on `stream`: {the device
@@ -528,9 +493,8 @@ int xyws_debug_lattice(xyws_ctx* ctx, void* stream, uint64_t* out) {
   if (!ctx || !out) return XYWS_ERR_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   device_guard g(ctx->device);
-  for (auto& sl : ctx->slot)
-    if (sl.bound && sl.stream == (hipStream_t)stream) return stream_scratch_lattice(&sl.ss, out);
-  return XYWS_ERR_INVALID;
+  scratch_slot* sl = find_slot(ctx, (hipStream_t)stream);
+  return sl ? stream_scratch_lattice(&sl->ss, out) : XYWS_ERR_INVALID;
 }
 
 // Internal: the decoder-choice words the last fused stream decode on `stream`
@@ -542,13 +506,10 @@ int xyws_debug_policy(xyws_ctx* ctx, void* stream, uint64_t* out) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   device_guard g(ctx->device);
   if (hipDeviceSynchronize() != hipSuccess) return XYWS_ERR_HIP;
-  for (auto& sl : ctx->slot)
-    if (sl.bound && sl.stream == (hipStream_t)stream) {
-      if (!sl.ss.pol_h) return XYWS_ERR_INVALID;
-      for (int i = 0; i < 5; i++) out[i] = sl.ss.pol_h[i];
-      return XYWS_OK;
-    }
-  return XYWS_ERR_INVALID;
+  scratch_slot* sl = find_slot(ctx, (hipStream_t)stream);
+  if (!sl || !sl->ss.pol_h) return XYWS_ERR_INVALID;
+  for (int i = 0; i < 5; i++) out[i] = sl->ss.pol_h[i];
+  return XYWS_OK;
 }
 
 // Internal (tests, no HIP call): the plan of a stream decode of bytes
@@ -591,8 +552,8 @@ static int unmask_locked(xyws_ctx* ctx, void* dev, uint64_t len, const uint8_t k
   uint32_t ncu = 256;
   if (!capturing(s)) {
     scratch_slot* sl = nullptr;
-    bool avail = false;
-    for (auto& x : ctx->slot) avail = avail || !x.bound || x.stream == s;
+    bool avail = find_slot(ctx, s) != nullptr;
+    for (auto& x : ctx->slot) avail = avail || !x.bound;
     if (avail) {
       if (const int rc = acquire_slot(ctx, s, false, &sl)) return rc;
       if (const int rc = stream_scratch_unmask_counter(&sl->ss, false, &ctr)) return rc;
@@ -658,21 +619,14 @@ int xyws_mask_bytes(xyws_ctx* ctx, void* data, uint64_t len, const uint8_t key[4
     return hip_err(hipStreamSynchronize(s));
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
-  if (ctx->stage_cap < len) {
-    if (ctx->stage) {
-      (void)hipStreamSynchronize(s);
-      (void)hipFree(ctx->stage);
-      ctx->stage = nullptr;
-      ctx->stage_cap = 0;
-    }
-    const uint64_t cap = len < 4096 ? 4096 : len;
-    if (hipMalloc(&ctx->stage, cap) != hipSuccess) return XYWS_ERR_NOMEM;
-    ctx->stage_cap = cap;
-  }
+  // the common rule (a failed allocation keeps the old stage; the device, not
+  // the stream alone, is idle before the old one is freed): the stage grows
+  // rarely and this call is synchronous anyway, so the wider wait costs nothing
+  if (const int rc = ensure_bytes(&ctx->stage, len, STAGE_MIN_BYTES, false)) return rc;
   // the stage keeps the bytes' 16-byte phase, so the kernel sees the same lanes
-  if (hipMemcpyAsync(ctx->stage, data, len, hipMemcpyHostToDevice, s) != hipSuccess) return XYWS_ERR_HIP;
-  if (const int rc = unmask_locked(ctx, ctx->stage, len, key, phase, s)) return rc;
-  if (hipMemcpyAsync(data, ctx->stage, len, hipMemcpyDeviceToHost, s) != hipSuccess) return XYWS_ERR_HIP;
+  if (hipMemcpyAsync(ctx->stage.mem, data, len, hipMemcpyHostToDevice, s) != hipSuccess) return XYWS_ERR_HIP;
+  if (const int rc = unmask_locked(ctx, ctx->stage.mem, len, key, phase, s)) return rc;
+  if (hipMemcpyAsync(data, ctx->stage.mem, len, hipMemcpyDeviceToHost, s) != hipSuccess) return XYWS_ERR_HIP;
   return hip_err(hipStreamSynchronize(s));
 }
 
@@ -680,27 +634,15 @@ int xyws_decode_indexed(xyws_ctx* ctx, void* dev_buf, uint64_t len, const uint64
                         uint64_t n, xyws_frame* dev_frames, uint32_t opts, void* stream) {
   if (!ctx || (!dev_buf && len) || (!dev_starts && n)) return XYWS_ERR_INVALID;
   if (!n) return XYWS_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  device_guard g(ctx->device);
-  if (!g.ok) return XYWS_ERR_HIP;
-  hipStream_t s = (hipStream_t)stream;
-  const bool cap = capturing(s);
-  scratch_slot* sl = nullptr;
-  int rc = acquire_slot(ctx, s, cap, &sl);
-  if (rc) return rc;
-  if ((rc = ensure_table(sl, n, cap))) return rc;
+  call_scope c(ctx, stream);
+  if (c.rc) return c.rc;
+  if (const int rc = ensure_table(c.sl, n, c.capt)) return rc;
   const auto [base, lo, hi] = span16(dev_buf, len);
-  frame_table t = table_of(sl);
-  hipLaunchKernelGGL(k_parse_indexed, dim3(grid_for(n, 256, 1u << 30)), dim3(256), 0, s, base, lo, hi,
+  frame_table t = table_of(c.sl);
+  hipLaunchKernelGGL(k_parse_indexed, dim3(grid_for(n, 256, 1u << 30)), dim3(256), 0, c.s, base, lo, hi,
                      dev_starts, n, t, dev_frames);
-  if ((rc = hip_err(hipGetLastError()))) return rc;
-  if (!(opts & XYWS_OPT_PARSE_ONLY) && len) {
-    const uint64_t tiles = (hi - (lo & ~(uint64_t)(UNMASK_TILE - 1)) + UNMASK_TILE - 1) / UNMASK_TILE;
-    hipLaunchKernelGGL(k_unmask_tiles, dim3(grid_for(tiles, 1, 4096)), dim3(UNMASK_THREADS), 0, s,
-                       base, lo, hi, t);
-    if ((rc = hip_err(hipGetLastError()))) return rc;
-  }
-  return XYWS_OK;
+  if (const int rc = hip_err(hipGetLastError())) return rc;
+  return !(opts & XYWS_OPT_PARSE_ONLY) && len ? unmask_table(base, lo, hi, t, c.s) : XYWS_OK;
 }
 
 int xyws_decode_stream(xyws_ctx* ctx, void* dev_buf, uint64_t len, const xyws_carry* dev_carry_in,
@@ -708,32 +650,22 @@ int xyws_decode_stream(xyws_ctx* ctx, void* dev_buf, uint64_t len, const xyws_ca
                        uint64_t* dev_nframes, uint32_t opts, void* stream) {
   if (!ctx || (!dev_buf && len)) return XYWS_ERR_INVALID;
   if (len >= (1ull << 46) - 64) return XYWS_ERR_INVALID;  // (entry granules hold 46-bit positions)
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  device_guard g(ctx->device);
-  if (!g.ok) return XYWS_ERR_HIP;
+  call_scope c(ctx, stream);
+  if (c.rc) return c.rc;
   const auto [base, lo, hi] = span16(dev_buf, len);
-  hipStream_t s = (hipStream_t)stream;
-  const bool capt = capturing(s);
-  scratch_slot* sl = nullptr;
-  int rc = acquire_slot(ctx, s, capt, &sl);
-  if (rc) return rc;
-  if ((opts & XYWS_OPT_SERIAL_SCAN) || !XYWS_HAVE_FUSED) {
+  hipStream_t s = c.s;
+  scratch_slot* sl = c.sl;
+  if (opts & XYWS_OPT_SERIAL_SCAN) {
     // worst case is a 2-byte unmasked frame every 2 bytes; the debug path caps
     // its table at 2^24 frames and flags the device error word beyond that.
     uint64_t want = len / 2 + 2;
     if (want > (1ull << 24)) want = 1ull << 24;
-    if ((rc = ensure_table(sl, want, capt))) return rc;
+    if (const int rc = ensure_table(sl, want, c.capt)) return rc;
     frame_table t = table_of(sl);
     hipLaunchKernelGGL(k_stream_serial, dim3(1), dim3(64), 0, s, base, lo, hi, dev_carry_in,
-                       dev_carry_out, t, sl->tab_cap, dev_frames, cap, dev_nframes, ctx->err);
-    if ((rc = hip_err(hipGetLastError()))) return rc;
-    if (!(opts & XYWS_OPT_PARSE_ONLY) && len) {
-      const uint64_t tiles = (hi - (lo & ~(uint64_t)(UNMASK_TILE - 1)) + UNMASK_TILE - 1) / UNMASK_TILE;
-      hipLaunchKernelGGL(k_unmask_tiles, dim3(grid_for(tiles, 1, 4096)), dim3(UNMASK_THREADS), 0, s,
-                         base, lo, hi, t);
-      if ((rc = hip_err(hipGetLastError()))) return rc;
-    }
-    return XYWS_OK;
+                       dev_carry_out, t, sl->tab.units, dev_frames, cap, dev_nframes, ctx->err);
+    if (const int rc = hip_err(hipGetLastError())) return rc;
+    return !(opts & XYWS_OPT_PARSE_ONLY) && len ? unmask_table(base, lo, hi, t, s) : XYWS_OK;
   }
   return stream_decode_fused(&sl->ss, base, lo, hi, dev_carry_in, dev_carry_out, dev_frames, cap,
                              dev_nframes, opts, s);
@@ -824,7 +756,7 @@ int xyws_decode_stream_iov(xyws_ctx* ctx, const xyws_iov* iov, uint32_t niov, co
                            xyws_carry* dev_carry_out, xyws_frame* dev_frames, uint64_t cap,
                            uint64_t* dev_nframes, uint32_t opts, void* stream) {
   if (!ctx || (!iov && niov) || niov > XYWS_IOV_MAX) return XYWS_ERR_INVALID;
-  if ((opts & XYWS_OPT_SERIAL_SCAN) || !XYWS_HAVE_FUSED) return XYWS_ERR_INVALID;  // (the fused path only)
+  if (opts & XYWS_OPT_SERIAL_SCAN) return XYWS_ERR_INVALID;  // (the fused path only)
   iov_args A;
   uint64_t total = 0, longest = 0;
   constexpr uint64_t LIMIT = (1ull << 46) - 64;
@@ -837,14 +769,12 @@ int xyws_decode_stream_iov(xyws_ctx* ctx, const xyws_iov* iov, uint32_t niov, co
     total += iov[k].len;
     if (iov[k].len > longest) longest = iov[k].len;
   }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  device_guard g(ctx->device);
-  if (!g.ok) return XYWS_ERR_HIP;
-  hipStream_t s = (hipStream_t)stream;
-  const bool capt = capturing(s);
-  scratch_slot* sl = nullptr;
-  int rc = acquire_slot(ctx, s, capt, &sl);
+  call_scope c(ctx, stream);
+  int rc = c.rc;
   if (rc) return rc;
+  hipStream_t s = c.s;
+  const bool capt = c.capt;
+  scratch_slot* sl = c.sl;
   // Pieces in place: each piece decoded where it lies as the next batch of the
   // stream, the carry chained from piece to piece on the device (a frame or
   // header cut by a piece's end continues in the next, as across any two
@@ -893,8 +823,8 @@ int xyws_decode_stream_iov(xyws_ctx* ctx, const xyws_iov* iov, uint32_t niov, co
     // scratch: [0, 64) the carry between pieces, [64, 72) the frame count of
     // the stream before the call (the count is the difference at the end)
     if ((rc = ensure_iov(sl, 128, capt))) return rc;
-    xyws_carry* mid = static_cast<xyws_carry*>(sl->iov_mem);
-    uint64_t* base_cnt = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(sl->iov_mem) + 64);
+    xyws_carry* mid = static_cast<xyws_carry*>(sl->iov.mem);
+    uint64_t* base_cnt = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(sl->iov.mem) + 64);
     xyws_carry* last_out = dev_carry_out ? dev_carry_out : mid;
     if (dev_nframes) {
       hipLaunchKernelGGL(k_iov_count, dim3(1), dim3(64), 0, s, dev_carry_in, base_cnt, (uint64_t*)nullptr);
@@ -919,7 +849,7 @@ int xyws_decode_stream_iov(xyws_ctx* ctx, const xyws_iov* iov, uint32_t niov, co
   const decode_plan pl = plan_decode(sl->ss.ncu, pv, 0, total, dev_frames ? cap : 0, opts);
   if ((rc = reserve_for(&sl->ss, pl.need, capt))) return rc;
   if ((rc = ensure_iov(sl, total + 16, capt))) return rc;
-  uint8_t* stage = static_cast<uint8_t*>(sl->iov_mem);
+  uint8_t* stage = static_cast<uint8_t*>(sl->iov.mem);
   const dim3 grid((uint32_t)grid_for(longest / 16 + 2, 256, 1024), niov ? niov : 1);
   if (niov && total) {
     hipLaunchKernelGGL(k_iov_copy, grid, dim3(256), 0, s, A, stage, 1);

@@ -1,11 +1,16 @@
 // xyws_ctx.h — internal: the C-ABI context (per-stream device scratch slots)
-// shared by the entry points in xyws.hip and xyws_frames.hip.
+// shared by the entry points in xyws.hip and xyws_frames.hip. Each host-side
+// rule is stated once here: how a buffer grows (dev_area, xyws_host.h), which
+// slot a stream has (find_slot, acquire_slot), what a reserve gives a slot
+// (reserve_slot) and which slots get it (reserve_bound_and_spare), and how an
+// entry point begins (call_scope).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
 
 #include "xyws.h"
+#include "xyws_host.h"
 #include "xyws_stream.h"
 
 // ---------------------------------------------------------------------------
@@ -28,136 +33,102 @@ struct frame_table {
 // synchronized (every slot idle) and the bindings start over.
 #define XYWS_SLOTS 16
 
+// Every buffer is a dev_area and grows by its one rule; these floors are the
+// smallest allocation of each.
+constexpr uint64_t TAB_MIN_ENTRIES = 1024, IOV_MIN_BYTES = 1u << 20, AUX_MIN_BYTES = 65536, STAGE_MIN_BYTES = 4096;
+
 struct scratch_slot {
-  bool bound;
-  hipStream_t stream;
-  // frame table scratch (indexed + serial modes)
-  void* tab_mem;
-  uint64_t tab_cap;
-  stream_scratch ss;  // fused stream decoder scratch (xyws_stream.hip)
-  // frame-list kernels' scratch (xyws_frames.hip): block sums, message tables
-  void* aux_mem;
-  uint64_t aux_cap;
-  // xyws_decode_stream_iov: the pieces of one buffer sequence, gathered
-  void* iov_mem;
-  uint64_t iov_cap;
+  bool bound = false;
+  hipStream_t stream = nullptr;
+  xyws_internal::dev_area tab;  // frame table scratch (indexed + serial modes; units: entries)
+  stream_scratch ss;            // fused stream decoder scratch (xyws_stream.hip)
+  xyws_internal::dev_area aux;  // frame-list kernels' scratch (xyws_frames.hip): block sums, message tables
+  xyws_internal::dev_area iov;  // xyws_decode_stream_iov: the pieces of one buffer sequence, gathered
 };
 
+#define XYWS_ARENA_STREAMS 8
 struct xyws_ctx {
-  int device;
+  int device = 0;
   std::mutex mu;
-  uint32_t* err;  // device error word (serial / indexed modes)
-  uint64_t reserve_bytes, reserve_frames;  // applied to every slot
-  uint64_t reserve_iov;                     // xyws_ctx_reserve_iov: the iov staging buffer of bound slots
-  void* stage;          // xyws_mask_bytes: device copy of host bytes (under mu)
-  uint64_t stage_cap;
+  uint32_t* err = nullptr;  // device error word (serial / indexed modes)
+  // xyws_ctx_reserve, xyws_ctx_reserve_iov: the largest asked for so far.
+  // reserve_slot applies all three to a slot
+  uint64_t reserve_bytes = 0, reserve_frames = 0, reserve_iov = 0;
+  xyws_internal::dev_area stage;  // xyws_mask_bytes: device copy of host bytes (under mu)
   scratch_slot slot[XYWS_SLOTS];
   // recv arenas share a few streams of the context (arena k: stream k mod
   // XYWS_ARENA_STREAMS), so that any number of connections bind at most that
   // many scratch slots (created on first use, destroyed with the context)
-  hipStream_t arena_stream[8];
-  uint32_t arena_rr;
+  hipStream_t arena_stream[XYWS_ARENA_STREAMS] = {};
+  uint32_t arena_rr = 0;
 };
-#define XYWS_ARENA_STREAMS 8
 
 namespace xyws_internal {
 
-struct device_guard {
-  int prev = -1;
-  bool ok = false;
-  explicit device_guard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~device_guard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-inline int hip_err(hipError_t e) { return e == hipSuccess ? XYWS_OK : XYWS_ERR_HIP; }
-
-// Zero device memory and wait until it is zero: hipMemset on device memory may
-// return before the memset ran (it goes to the null stream, which does not
-// order the caller's non-blocking streams); a kernel on such a stream would
-// otherwise read the allocation's old contents (scratch tickets, epochs).
-inline hipError_t zero_now(void* p, size_t n) {
-  hipError_t e = hipMemset(p, 0, n);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  return e;
-}
-
-inline bool capturing(hipStream_t s) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &cs);
-  return cs != hipStreamCaptureStatusNone;
-}
-
-// A device range as the kernels address it: bytes [lo, hi) from the
-// 16-byte-aligned address at or below its start.
-struct range16 {
-  uint8_t* base;
-  uint64_t lo, hi;
-};
-inline range16 span16(const void* p, uint64_t len) {
-  const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
-  return range16{reinterpret_cast<uint8_t*>(addr & ~(uintptr_t)15), addr & 15, (addr & 15) + len};
-}
-
 inline int ensure_table(scratch_slot* sl, uint64_t n, bool capture) {
-  if (n <= sl->tab_cap && sl->tab_mem) return XYWS_OK;
-  if (capture) return XYWS_ERR_CAPACITY;
-  uint64_t cap = n < 1024 ? 1024 : n;
-  void* mem = nullptr;
-  size_t bytes = cap * (8 + 8 + 8 + 4) + 64;
-  if (hipMalloc(&mem, bytes) != hipSuccess) return XYWS_ERR_NOMEM;
-  if (sl->tab_mem) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(sl->tab_mem);
-  }
-  sl->tab_mem = mem;
-  sl->tab_cap = cap;
-  return XYWS_OK;
+  const uint64_t cap = n < TAB_MIN_ENTRIES ? TAB_MIN_ENTRIES : n;
+  return sl->tab.grow(cap, cap * (8 + 8 + 8 + 4) + 64, 0, capture);
 }
 
 inline frame_table table_of(scratch_slot* sl) {
   frame_table t;
-  char* m = static_cast<char*>(sl->tab_mem);
+  char* m = static_cast<char*>(sl->tab.mem);
   t.start = reinterpret_cast<uint64_t*>(m);
-  t.ps = t.start + sl->tab_cap;
-  t.pe = t.ps + sl->tab_cap;
-  t.count = t.pe + sl->tab_cap;
+  t.ps = t.start + sl->tab.units;
+  t.pe = t.ps + sl->tab.units;
+  t.count = t.pe + sl->tab.units;
   t.kw = reinterpret_cast<uint32_t*>(t.count + 8);
   return t;
 }
 
-inline int grid_for(uint64_t items, uint32_t per_block, uint32_t cap) {
-  uint64_t g = (items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
+// An area counted in bytes, of at least `bytes` and its floor (ctx->mu held).
+inline int ensure_bytes(dev_area* a, uint64_t bytes, uint64_t floor, bool capture) {
+  const uint64_t cap = bytes < floor ? floor : bytes;
+  return a->grow(cap, cap, 0, capture);
+}
+inline int ensure_iov(scratch_slot* sl, uint64_t bytes, bool capture) {
+  return ensure_bytes(&sl->iov, bytes, IOV_MIN_BYTES, capture);
+}
+inline int ensure_aux(scratch_slot* sl, uint64_t bytes, bool capture) {
+  return ensure_bytes(&sl->aux, bytes, AUX_MIN_BYTES, capture);
 }
 
-// The iov staging buffer of at least `bytes` (ctx->mu held).
-inline int ensure_iov(scratch_slot* sl, uint64_t bytes, bool capture) {
-  if (bytes <= sl->iov_cap && sl->iov_mem) return XYWS_OK;
-  if (capture) return XYWS_ERR_CAPACITY;
-  uint64_t cap = bytes < (1u << 20) ? (1u << 20) : bytes;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, cap) != hipSuccess) return XYWS_ERR_NOMEM;
-  if (sl->iov_mem) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(sl->iov_mem);
+// The slot bound to `stream`, or null (ctx->mu held).
+inline scratch_slot* find_slot(xyws_ctx* ctx, hipStream_t stream) {
+  for (auto& sl : ctx->slot)
+    if (sl.bound && sl.stream == stream) return &sl;
+  return nullptr;
+}
+
+// Everything the context has recorded (xyws_ctx_reserve, xyws_ctx_reserve_iov)
+// applied to one slot: whatever call brings a slot its reserve, it brings all.
+inline int reserve_slot(xyws_ctx* ctx, scratch_slot* sl) {
+  if (ctx->reserve_iov)
+    if (const int rc = ensure_iov(sl, ctx->reserve_iov, false)) return rc;
+  if (ctx->reserve_frames)
+    if (const int rc = ensure_table(sl, ctx->reserve_frames, false)) return rc;
+  if (!ctx->reserve_bytes && !ctx->reserve_frames) return XYWS_OK;
+  return stream_scratch_reserve(&sl->ss, ctx->reserve_bytes, ctx->reserve_frames);
+}
+
+// reserve_slot for the slots bound to a stream now and one spare, the first
+// unbound one: the one the next new stream binds, so that a stream first used
+// inside graph capture finds its reserve. Not all XYWS_SLOTS up front: the
+// per-frame tables are tens of GB for 2^26 frames; the others get theirs when
+// a stream binds them (acquire_slot).
+inline int reserve_bound_and_spare(xyws_ctx* ctx) {
+  bool spare = true;
+  for (auto& sl : ctx->slot) {
+    if (sl.bound || spare)
+      if (const int rc = reserve_slot(ctx, &sl)) return rc;
+    if (!sl.bound) spare = false;
   }
-  sl->iov_mem = mem;
-  sl->iov_cap = cap;
   return XYWS_OK;
 }
 
 // The slot of `stream` (ctx->mu held).
 inline int acquire_slot(xyws_ctx* ctx, hipStream_t stream, bool capture, scratch_slot** out) {
-  scratch_slot* pick = nullptr;
-  for (auto& sl : ctx->slot)
-    if (sl.bound && sl.stream == stream) { pick = &sl; break; }
+  scratch_slot* pick = find_slot(ctx, stream);
   if (!pick) {
     bool any_free = false;
     for (auto& sl : ctx->slot) any_free = any_free || !sl.bound;
@@ -169,16 +140,8 @@ inline int acquire_slot(xyws_ctx* ctx, hipStream_t stream, bool capture, scratch
     }
     for (auto& sl : ctx->slot)
       if (!sl.bound) { pick = &sl; break; }
-  }
-  if (!pick->bound && ctx->reserve_iov && !capture) {
-    // (xyws_ctx_reserve_iov's staging buffer, as the per-frame tables below)
-    if (const int rc = ensure_iov(pick, ctx->reserve_iov, false)) return rc;
-  }
-  if (!pick->bound && ctx->reserve_frames && !capture) {
-    // xyws_ctx_reserve's per-frame tables go to the slots streams bind (not
-    // to all XYWS_SLOTS up front: tens of GB for 2^26 frames)
-    if (const int rc = ensure_table(pick, ctx->reserve_frames, false)) return rc;
-    if (const int rc = stream_scratch_reserve(&pick->ss, ctx->reserve_bytes, ctx->reserve_frames)) return rc;
+    if (!capture)
+      if (const int rc = reserve_slot(ctx, pick)) return rc;
   }
   pick->bound = true;
   pick->stream = stream;
@@ -186,21 +149,22 @@ inline int acquire_slot(xyws_ctx* ctx, hipStream_t stream, bool capture, scratch
   return XYWS_OK;
 }
 
-
-// Frame-list kernels' scratch of at least `bytes` (ctx->mu held).
-inline int ensure_aux(scratch_slot* sl, uint64_t bytes, bool capture) {
-  if (bytes <= sl->aux_cap && sl->aux_mem) return XYWS_OK;
-  if (capture) return XYWS_ERR_CAPACITY;
-  uint64_t cap = bytes < 65536 ? 65536 : bytes;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, cap) != hipSuccess) return XYWS_ERR_NOMEM;
-  if (sl->aux_mem) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(sl->aux_mem);
+// The prologue of an entry point that queues work on a stream with a scratch
+// slot: ctx->mu held and the context's device current for the scope's life,
+// the stream, whether it is capturing, its slot. rc != XYWS_OK: return it.
+struct call_scope {
+  std::lock_guard<std::mutex> lk;
+  device_guard g;
+  hipStream_t s;
+  bool capt = false;
+  scratch_slot* sl = nullptr;
+  int rc;
+  call_scope(xyws_ctx* ctx, void* stream)
+      : lk(ctx->mu), g(ctx->device), s((hipStream_t)stream), rc(g.ok ? XYWS_OK : XYWS_ERR_HIP) {
+    if (rc) return;
+    capt = capturing(s);
+    rc = acquire_slot(ctx, s, capt, &sl);
   }
-  sl->aux_mem = mem;
-  sl->aux_cap = cap;
-  return XYWS_OK;
-}
+};
 
 }  // namespace xyws_internal

@@ -1121,6 +1121,34 @@ __global__ void __launch_bounds__(FT) k_utf8(const uint8_t* out, uint64_t out_lo
 
 __global__ void k_put(uint64_t* p, uint64_t v) { *p = v; }
 
+// The gather's parameters for reassembly; encode adds its flags, options and keys.
+gparams gather_params(uint32_t mode, const void* src, uint64_t src_len, const xyws_frame* frames,
+                      const uint64_t* off, uint64_t n, const uint64_t* dev_n, void* out, uint64_t out_cap,
+                      uint32_t* err) {
+  const range16 rs = xyws_internal::span16(src, src_len), ro = xyws_internal::span16(out, out_cap);
+  gparams G;
+  G.src = rs.base; G.src_lo = rs.lo; G.src_len = src_len;
+  G.frames = frames; G.off = off; G.n = n; G.dev_n = dev_n;
+  G.mode = mode; G.flags = 0; G.enc_opts = 0; G.keys = nullptr;
+  G.out = ro.base; G.out_lo = ro.lo; G.out_cap = out_cap;
+  G.err = err;
+  return G;
+}
+
+// Gather tiles of the output (bytes from the aligned base, and one to spare).
+uint64_t gather_tiles(const void* out, uint64_t out_cap) {
+  return (xyws_internal::span16(out, out_cap).hi + GTILE - 1) / GTILE + 1;
+}
+
+// The items' bytes into the output: the tile map (ntiles = gather_tiles), then the gather.
+int launch_gather(const gparams& G, uint64_t* tmap, uint64_t ntiles, hipStream_t s) {
+  if (!G.n || !G.out_cap) return XYWS_OK;
+  const uint64_t tiles = (G.out_lo + G.out_cap + GTILE - 1) / GTILE;
+  hipLaunchKernelGGL(k_tile_map, dim3((G.n + FT - 1) / FT), dim3(FT), 0, s, G, tmap, ntiles);
+  hipLaunchKernelGGL(k_gather, dim3(grid_for(tiles, 1, 8192)), dim3(FT), 0, s, G, (const uint64_t*)tmap, ntiles);
+  return hip_err(hipGetLastError());
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1145,52 +1173,26 @@ int xyws_encode_frames(xyws_ctx* ctx, const void* dev_src, uint64_t src_len, con
                        void* dev_out, uint64_t out_cap, uint64_t* dev_offsets, uint64_t* dev_out_len,
                        void* stream) {
   if (!ctx || (!dev_frames && n) || (!dev_src && src_len) || (!dev_out && out_cap)) return XYWS_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  device_guard gd(ctx->device);
-  if (!gd.ok) return XYWS_ERR_HIP;
-  hipStream_t s = (hipStream_t)stream;
-  const bool capt = capturing(s);
-  scratch_slot* sl = nullptr;
-  int rc = acquire_slot(ctx, s, capt, &sl);
-  if (rc) return rc;
+  call_scope c(ctx, stream);
+  if (c.rc) return c.rc;
+  hipStream_t s = c.s;
   // scratch: offsets (n + 1, unless the caller's), block partials, total
   const uint64_t nb = (n + SB - 1) / SB + 1;
-  const uint64_t oa0 = reinterpret_cast<uintptr_t>(dev_out) & 15;
-  const uint64_t ntiles = (oa0 + out_cap + GTILE - 1) / GTILE + 1;
-  if ((rc = ensure_aux(sl, 8 * ((dev_offsets ? 0 : n + 1) + nb + 2 + ntiles), capt))) return rc;
-  uint64_t* aux = static_cast<uint64_t*>(sl->aux_mem);
+  const uint64_t ntiles = gather_tiles(dev_out, out_cap);
+  if (const int rc = ensure_aux(c.sl, 8 * ((dev_offsets ? 0 : n + 1) + nb + 2 + ntiles), c.capt)) return rc;
+  uint64_t* aux = static_cast<uint64_t*>(c.sl->aux.mem);
   uint64_t* off = dev_offsets ? dev_offsets : aux;
   uint64_t* part = dev_offsets ? aux : aux + n + 1;
   uint64_t* total = part + nb;
   uint64_t* tmap = total + 2;
-  const uintptr_t oa = reinterpret_cast<uintptr_t>(dev_out);
-  const uintptr_t sa = reinterpret_cast<uintptr_t>(dev_src);
-  gparams G;
-  G.src = reinterpret_cast<const uint8_t*>(sa & ~(uintptr_t)15);
-  G.src_lo = sa & 15;
-  G.src_len = src_len;
-  G.frames = dev_frames;
-  G.off = off;
-  G.n = n;
-  G.dev_n = dev_n;
-  G.mode = G_ENC;
+  gparams G = gather_params(G_ENC, dev_src, src_len, dev_frames, off, n, dev_n, dev_out, out_cap, ctx->err);
   G.flags = flags;
   G.enc_opts = enc_opts;
   G.keys = dev_keys;
-  G.out = reinterpret_cast<uint8_t*>(oa & ~(uintptr_t)15);
-  G.out_lo = oa & 15;
-  G.out_cap = out_cap;
-  G.err = ctx->err;
   // (the sizes made in the scan's first pass; the total also into dev_out_len)
-  if ((rc = scan<op_sum, false, true>(off, n, part, total, dev_out_len, gen_enc{G, dev_verdicts, action_mask}, s)))
+  if (const int rc = scan<op_sum, false, true>(off, n, part, total, dev_out_len, gen_enc{G, dev_verdicts, action_mask}, s))
     return rc;
-  if (n && out_cap) {
-    const uint64_t tiles = (G.out_lo + out_cap + GTILE - 1) / GTILE;
-    hipLaunchKernelGGL(k_tile_map, dim3((n + FT - 1) / FT), dim3(FT), 0, s, G, tmap, ntiles);
-    hipLaunchKernelGGL(k_gather, dim3(grid_for(tiles, 1, 8192)), dim3(FT), 0, s, G, (const uint64_t*)tmap, ntiles);
-    if ((rc = hip_err(hipGetLastError()))) return rc;
-  }
-  return XYWS_OK;
+  return launch_gather(G, tmap, ntiles, s);
 }
 
 int xyws_classify_frames(xyws_ctx* ctx, const void* dev_src, uint64_t src_len, const xyws_frame* dev_frames,
@@ -1216,21 +1218,18 @@ int xyws_reassemble(xyws_ctx* ctx, const void* dev_src, uint64_t src_len, const 
                     xyws_message* dev_msgs, uint64_t msg_cap, uint64_t* dev_nmsgs, void* stream) {
   if (!ctx || (!dev_frames && n) || (!dev_src && src_len) || (!dev_out && out_cap) || (!dev_msgs && msg_cap))
     return XYWS_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  device_guard gd(ctx->device);
-  if (!gd.ok) return XYWS_ERR_HIP;
-  hipStream_t s = (hipStream_t)stream;
-  const bool capt = capturing(s);
-  scratch_slot* sl = nullptr;
-  int rc = acquire_slot(ctx, s, capt, &sl);
+  call_scope c(ctx, stream);
+  int rc = c.rc;
   if (rc) return rc;
+  hipStream_t s = c.s;
   // scratch: a, b, st/rank, sz/off, cnt/cntoff, orphan flags/prefix (n + 1
   // each), block partials, totals
   const uint64_t w = n + 1, nb = (n + SB - 1) / SB + 1;
-  const uint64_t ntiles = ((reinterpret_cast<uintptr_t>(dev_out) & 15) + out_cap + GTILE - 1) / GTILE + 1;
-  const uint64_t utiles = ((reinterpret_cast<uintptr_t>(dev_out) & 15) + out_cap + UT - 1) / UT + 1;
-  if ((rc = ensure_aux(sl, 8 * (7 * w + 3 * nb + 4 + ntiles + utiles), capt))) return rc;
-  uint64_t* A = static_cast<uint64_t*>(sl->aux_mem);
+  const range16 ro = xyws_internal::span16(dev_out, out_cap);
+  const uint64_t ntiles = gather_tiles(dev_out, out_cap);
+  const uint64_t utiles = (ro.hi + UT - 1) / UT + 1;
+  if ((rc = ensure_aux(c.sl, 8 * (7 * w + 3 * nb + 4 + ntiles + utiles), c.capt))) return rc;
+  uint64_t* A = static_cast<uint64_t*>(c.sl->aux.mem);
   uint64_t *a = A, *b = A + w, *st = A + 2 * w, *off = A + 3 * w, *cnt = A + 4 * w, *orph = A + 5 * w;
   uint64_t* starts = A + 6 * w;   // every message's first frame
   uint64_t* part = A + 7 * w;     // 3 * nb: one slice per scan of a group
@@ -1258,33 +1257,10 @@ int xyws_reassemble(xyws_ctx* ctx, const void* dev_src, uint64_t src_len, const 
   hipLaunchKernelGGL(k_rs_msgs, gn, dim3(FT), 0, s, dev_frames, dev_n, n, (const uint64_t*)(tot + 1),
                      (const uint64_t*)off,
                      (const uint64_t*)cnt, (const uint64_t*)b, (const uint64_t*)starts, (const uint64_t*)orph,
-                     out_cap, dev_msgs, msg_cap, dev_nmsgs, ctx->err, utf8 ? umap : nullptr, utiles,
-                     (uint64_t)(reinterpret_cast<uintptr_t>(dev_out) & 15));
+                     out_cap, dev_msgs, msg_cap, dev_nmsgs, ctx->err, utf8 ? umap : nullptr, utiles, ro.lo);
   if ((rc = hip_err(hipGetLastError()))) return rc;
-  const uintptr_t oa = reinterpret_cast<uintptr_t>(dev_out);
-  const uintptr_t sa = reinterpret_cast<uintptr_t>(dev_src);
-  gparams G;
-  G.src = reinterpret_cast<const uint8_t*>(sa & ~(uintptr_t)15);
-  G.src_lo = sa & 15;
-  G.src_len = src_len;
-  G.frames = dev_frames;
-  G.off = off;
-  G.n = n;
-  G.dev_n = dev_n;
-  G.mode = G_REASM;
-  G.flags = 0;
-  G.enc_opts = 0;
-  G.keys = nullptr;
-  G.out = reinterpret_cast<uint8_t*>(oa & ~(uintptr_t)15);
-  G.out_lo = oa & 15;
-  G.out_cap = out_cap;
-  G.err = ctx->err;
-  if (n && out_cap) {
-    const uint64_t tiles = (G.out_lo + out_cap + GTILE - 1) / GTILE;
-    hipLaunchKernelGGL(k_tile_map, dim3((n + FT - 1) / FT), dim3(FT), 0, s, G, tmap, ntiles);
-    hipLaunchKernelGGL(k_gather, dim3(grid_for(tiles, 1, 8192)), dim3(FT), 0, s, G, (const uint64_t*)tmap, ntiles);
-    if ((rc = hip_err(hipGetLastError()))) return rc;
-  }
+  const gparams G = gather_params(G_REASM, dev_src, src_len, dev_frames, off, n, dev_n, dev_out, out_cap, ctx->err);
+  if ((rc = launch_gather(G, tmap, ntiles, s))) return rc;
   if (utf8) {
     // (the UTF-8 tile map: k_rs_msgs)
     hipLaunchKernelGGL(k_utf8, dim3(grid_for(utiles, 1, 4096)), dim3(FT), 0, s, (const uint8_t*)G.out, G.out_lo,

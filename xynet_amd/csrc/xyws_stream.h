@@ -3,23 +3,23 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "xyws.h"
+#include "xyws_host.h"
 
 // Scratch owned by a context: one record + one flag per run, a ticket and a
-// device error word.
+// device error word. Its three areas grow in reserve_for alone, from floors
+// of SCRATCH_MIN_RUNS runs and SCRATCH_MIN_SEGS lattice segments.
+constexpr uint64_t SCRATCH_MIN_RUNS = 64, SCRATCH_MIN_SEGS = 64;
 struct stream_scratch {
-  void* mem;            // device allocation
-  uint64_t max_runs;    // runs the allocation covers
-  int ncu;              // compute units of the context's device (runs per launch)
-  void* fmem;           // frame-start lists for descriptor emission (grown with the caller's cap)
-  uint64_t fbytes;
+  xyws_internal::dev_area runs;  // run scratch (units: runs)
+  int ncu = 256;                 // compute units of the context's device (runs per launch)
+  xyws_internal::dev_area desc;  // frame-start lists for descriptor emission (units: bytes, the caller's cap)
   // decoder choice: pinned host words the finisher of every call writes
   // ({epoch, batch bytes, smallest, largest last-frame size, decoder}) and
   // their device address; null when the pinned allocation failed (then the
   // run decoder serves every call)
-  volatile uint64_t* pol_h;
-  uint64_t* pol_d;
-  void* lmem;           // lattice decoder: scratch words + one result word per segment
-  uint64_t lmax_segs;
+  volatile uint64_t* pol_h = nullptr;
+  uint64_t* pol_d = nullptr;
+  xyws_internal::dev_area lat;   // lattice decoder: scratch words + one result word per segment (units: segments)
 };
 
 void stream_scratch_init(stream_scratch* s, int device);
@@ -44,11 +44,23 @@ int stream_scratch_lattice(stream_scratch* s, uint64_t out[5]);
 int stream_scratch_unmask_counter(stream_scratch* s, bool capturing, uint32_t** out);
 
 // Internal decode options (not part of include/xyws.h):
+#define XYWS_OPT_WG256 0x8u  // the run decoder in four 256-thread workgroups per CU on 16 KiB segments
+#define XYWS_OPT_TEST_LATSPEC 0x10u  // tests (lattice decoder): every store speculative (no first-segment gate, no
+                                     // failing-point filter): a broken lattice is undone by the end-of-work check
+#define XYWS_OPT_TEST_LATDUMP 0x20u  // tests (lattice decoder): a workgroup never undoes its own speculative
+                                    // stores at its end: every list goes to the finisher
+#define XYWS_OPT_LATX_NOWORK 0x40u  // timing experiment only (wrong bytes): the lattice decoder's data waves skip
+                                    // the checks and the XOR (its data path and control alone)
+#define XYWS_OPT_LATX_ONLY 0x80u  // timing experiment only (wrong bytes after a redirect): no run decoder after the lattice
 #define XYWS_OPT_STATS 0x100u      // count speculation/repair events (xyws_debug_stats)
 #define XYWS_OPT_SMALL_SEG 0x200u  // 1 KiB segments, one per run: exercises run-boundary
                                    // speculation and repair on small test inputs
+#define XYWS_OPT_LATTICE 0x400u      // the lattice decoder first, whatever the decoder choice would take
+#define XYWS_OPT_NO_LATDEC 0x800u    // never the lattice decoder
 #define XYWS_OPT_NO_DENSE0 0x1000u  // experiment (run decoder): the stride pass first in every run's first
                                    // segment even after a call of small mixed-size frames (no dense0 hint)
+#define XYWS_OPT_REDIRECT 0x2000u    // (set by stream_decode_fused only) the run decoder after the lattice decoder:
+                                     // it reads the lattice's redirect record first
 #define XYWS_OPT_NO_LATENTRY 0x4000u // experiment (run decoder): no lattice entry (find_entry scans every run)
 #define XYWS_OPT_WG1024 0x8000u    // the run decoder in its default geometry (one 1024-thread workgroup per CU),
                                    // whatever the geometry choice (wg512_preferred) would take
@@ -66,25 +78,13 @@ int stream_scratch_unmask_counter(stream_scratch* s, bool capturing, uint32_t** 
                                         // first-segment gate: the previous call on the stream was the lattice's
 #define XYWS_OPT_LAT_GATE 0x2000000u    // experiment (lattice decoder): the first-segment gate whatever the
                                         // previous call found
+#define XYWS_OPT_BIGSCAN 0x4000000u  // tests (entry scans): one filter pass per segment, whatever the previous
+                                     // call found
 #define XYWS_OPT_LATX_NOCHK 0x8000000u  // experiment (lattice decoder): no check of lattice points 1 and 2 up front
 #define XYWS_OPT_IOV_PIECES 0x10000000u  // xyws_decode_stream_iov: the pieces in place one by one (no descriptors)
 #define XYWS_OPT_IOV_STAGE 0x20000000u   // xyws_decode_stream_iov: gather, decode, scatter whatever the pieces
-#define XYWS_OPT_BIGSCAN 0x4000000u  // tests (entry scans): one filter pass per segment, whatever the previous
-                                     // call found
 #define XYWS_OPT_NO_BIGSCAN 0x40000000u // experiment (entry scans): the window-0 pass whatever the previous call found
 #define XYWS_OPT_RUNS 0x80000000u     // the run decoder, whatever the decoder choice would take
-#define XYWS_OPT_LATTICE 0x400u      // the lattice decoder first, whatever the decoder choice would take
-#define XYWS_OPT_NO_LATDEC 0x800u    // never the lattice decoder
-#define XYWS_OPT_TEST_LATSPEC 0x10u  // tests (lattice decoder): every store speculative (no first-segment gate, no
-                                     // failing-point filter): a broken lattice is undone by the end-of-work check
-#define XYWS_OPT_WG256 0x8u  // the run decoder in four 256-thread workgroups per CU on 16 KiB segments
-#define XYWS_OPT_LATX_ONLY 0x80u  // timing experiment only (wrong bytes after a redirect): no run decoder after the lattice
-#define XYWS_OPT_TEST_LATDUMP 0x20u  // tests (lattice decoder): a workgroup never undoes its own speculative
-                                    // stores at its end: every list goes to the finisher
-#define XYWS_OPT_LATX_NOWORK 0x40u  // timing experiment only (wrong bytes): the lattice decoder's data waves skip
-                                    // the checks and the XOR (its data path and control alone)
-#define XYWS_OPT_REDIRECT 0x2000u    // (set by stream_decode_fused only) the run decoder after the lattice decoder:
-                                     // it reads the lattice's redirect record first
 
 // The stream decode's host side in three steps: plan_decode (pure: what the
 // call will run and what scratch it needs), reserve_for (the only step that

@@ -59,7 +59,6 @@
 
 #include "xyws_stream.h"
 #include "xyws_device.h"
-#include "xyws_ctx.h"  // (zero_now)
 
 namespace {
 
@@ -2939,15 +2938,6 @@ int launch_lattice(const run_params& P, uint32_t grid, hipStream_t stream) {
 }  // namespace
 
 void stream_scratch_init(stream_scratch* s, int device) {
-  s->mem = nullptr;
-  s->max_runs = 0;
-  s->fmem = nullptr;
-  s->fbytes = 0;
-  s->ncu = 256;
-  s->pol_h = nullptr;
-  s->pol_d = nullptr;
-  s->lmem = nullptr;
-  s->lmax_segs = 0;
   void* ph = nullptr;
   if (hipHostMalloc(&ph, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
     void* pd = nullptr;
@@ -2968,15 +2958,9 @@ void stream_scratch_free(stream_scratch* s) {
   if (s->pol_h) (void)hipHostFree(const_cast<uint64_t*>(s->pol_h));
   s->pol_h = nullptr;
   s->pol_d = nullptr;
-  if (s->lmem) (void)hipFree(s->lmem);
-  s->lmem = nullptr;
-  s->lmax_segs = 0;
-  if (s->mem) (void)hipFree(s->mem);
-  if (s->fmem) (void)hipFree(s->fmem);
-  s->mem = nullptr;
-  s->max_runs = 0;
-  s->fmem = nullptr;
-  s->fbytes = 0;
+  s->lat.release();
+  s->runs.release();
+  s->desc.release();
 }
 
 // Run scratch layout for up to `runs` runs (2 * runs flat indices):
@@ -2990,86 +2974,68 @@ static uint64_t records_off(uint64_t runs) {
   return HEAD_BYTES + granules_bytes(runs) + split_bytes(runs) + prog_bytes(runs);
 }
 
-// One scratch area grown to hold `want` units in `bytes` bytes, the first
-// `zero` of them zeroed before any kernel can read them. Never under graph
-// capture (xyws_ctx_reserve). The old allocation is freed once the device is
-// idle: a call in flight may still use it.
-static int grow_area(void** mem, uint64_t* have, uint64_t want, uint64_t bytes, uint64_t zero, bool capturing) {
-  if (*mem && want <= *have) return XYWS_OK;
-  if (capturing) return XYWS_ERR_CAPACITY;
-  void* m = nullptr;
-  if (hipMalloc(&m, bytes) != hipSuccess) return XYWS_ERR_NOMEM;
-  if (*mem) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(*mem);
-  }
-  *mem = m;
-  *have = want;
-  return !zero || xyws_internal::zero_now(m, zero) == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
-}
-
 int reserve_for(stream_scratch* s, const scratch_need& need, bool capturing) {
   if (need.runs) {
-    const uint64_t want = need.runs < 64 ? 64 : need.runs;
+    const uint64_t want = need.runs < SCRATCH_MIN_RUNS ? SCRATCH_MIN_RUNS : need.runs;
     const uint64_t bytes = records_off(want) + 2 * want * R_WORDS * 8;
-    if (const int rc = grow_area(&s->mem, &s->max_runs, want, bytes, records_off(want), capturing)) return rc;
+    if (const int rc = s->runs.grow(want, bytes, records_off(want), capturing)) return rc;
   }
   // Frame-start lists for descriptor emission: one region per flat item.
   if (need.fmem_bytes)
-    if (const int rc = grow_area(&s->fmem, &s->fbytes, need.fmem_bytes, need.fmem_bytes, 0, capturing)) return rc;
+    if (const int rc = s->desc.grow(need.fmem_bytes, need.fmem_bytes, 0, capturing)) return rc;
   // Lattice decoder scratch: LW_STAT words of scratch, one result word per
   // segment, group counts, LW_BRK replicas and one list per workgroup (one
   // workgroup per CU, 64 in the small-segment test mode), all zeroed at
   // allocation (epoch 0: no result of any call).
   if (need.lat_segs) {
-    const uint64_t want = need.lat_segs < 64 ? 64 : need.lat_segs;
+    const uint64_t want = need.lat_segs < SCRATCH_MIN_SEGS ? SCRATCH_MIN_SEGS : need.lat_segs;
     const uint64_t maxg = s->ncu > 64 ? (uint64_t)s->ncu : 64;
     const uint64_t bytes = 8 * (lat_sl_off(want) + maxg * LAT_LSW);
-    if (const int rc = grow_area(&s->lmem, &s->lmax_segs, want, bytes, bytes, capturing)) return rc;
+    if (const int rc = s->lat.grow(want, bytes, bytes, capturing)) return rc;
   }
   return XYWS_OK;
 }
 
 int stream_scratch_unmask_counter(stream_scratch* s, bool capturing, uint32_t** out) {
   if (const int rc = reserve_for(s, scratch_need{0, 0, 1}, capturing)) return rc;
-  *out = reinterpret_cast<uint32_t*>(static_cast<uint64_t*>(s->lmem) + LW_UNMASK);
+  *out = reinterpret_cast<uint32_t*>(static_cast<uint64_t*>(s->lat.mem) + LW_UNMASK);
   return XYWS_OK;
 }
 
 int stream_scratch_stats(stream_scratch* s, uint64_t out[XYWS_NSTATS]) {
-  if (!s->mem) return XYWS_ERR_INVALID;
+  if (!s->runs.mem) return XYWS_ERR_INVALID;
   if (hipDeviceSynchronize() != hipSuccess) return XYWS_ERR_HIP;
-  return hipMemcpy(out, static_cast<uint8_t*>(s->mem) + 128, 8 * XYWS_NSTATS, hipMemcpyDeviceToHost) == hipSuccess
+  return hipMemcpy(out, static_cast<uint8_t*>(s->runs.mem) + 128, 8 * XYWS_NSTATS, hipMemcpyDeviceToHost) == hipSuccess
              ? XYWS_OK : XYWS_ERR_HIP;
 }
 
 int stream_scratch_lattice(stream_scratch* s, uint64_t out[5]) {
   for (int i = 0; i < 5; i++) out[i] = 0;
   if (hipDeviceSynchronize() != hipSuccess) return XYWS_ERR_HIP;
-  if (s->mem && hipMemcpy(out, static_cast<uint8_t*>(s->mem) + 8 * HW_DPOL, 8, hipMemcpyDeviceToHost) != hipSuccess)
+  if (s->runs.mem && hipMemcpy(out, static_cast<uint8_t*>(s->runs.mem) + 8 * HW_DPOL, 8, hipMemcpyDeviceToHost) != hipSuccess)
     return XYWS_ERR_HIP;
-  if (s->lmem) {
+  if (s->lat.mem) {
     const uint32_t w[4] = {LW_NBAIL_POL, LW_NBAIL_HYP, LW_NLOOP_A, LW_NLOOP_B};
     for (int i = 0; i < 4; i++)
-      if (hipMemcpy(out + 1 + i, static_cast<uint64_t*>(s->lmem) + w[i], 8, hipMemcpyDeviceToHost) != hipSuccess)
+      if (hipMemcpy(out + 1 + i, static_cast<uint64_t*>(s->lat.mem) + w[i], 8, hipMemcpyDeviceToHost) != hipSuccess)
         return XYWS_ERR_HIP;
   }
   return XYWS_OK;
 }
 
 int64_t stream_scratch_records(stream_scratch* s, uint64_t* out, uint64_t max_recs) {
-  if (!s->mem) return XYWS_ERR_INVALID;
+  if (!s->runs.mem) return XYWS_ERR_INVALID;
   if (hipDeviceSynchronize() != hipSuccess) return XYWS_ERR_HIP;
-  const uint64_t n = max_recs < 2 * s->max_runs ? max_recs : 2 * s->max_runs;
-  const uint8_t* rec = static_cast<const uint8_t*>(s->mem) + records_off(s->max_runs);
+  const uint64_t n = max_recs < 2 * s->runs.units ? max_recs : 2 * s->runs.units;
+  const uint8_t* rec = static_cast<const uint8_t*>(s->runs.mem) + records_off(s->runs.units);
   return hipMemcpy(out, rec, n * R_WORDS * 8, hipMemcpyDeviceToHost) == hipSuccess ? (int64_t)n : XYWS_ERR_HIP;
 }
 
 uint32_t stream_scratch_error(stream_scratch* s, bool clear) {
-  if (!s->mem) return 0;
+  if (!s->runs.mem) return 0;
   uint32_t v[2] = {0, 0};
-  if (hipMemcpy(v, s->mem, 8, hipMemcpyDeviceToHost) != hipSuccess) return 0xFFFFFFFFu;
-  if (clear && v[1] && xyws_internal::zero_now(static_cast<uint8_t*>(s->mem) + 4, 4) != hipSuccess) return 0xFFFFFFFFu;
+  if (hipMemcpy(v, s->runs.mem, 8, hipMemcpyDeviceToHost) != hipSuccess) return 0xFFFFFFFFu;
+  if (clear && v[1] && xyws_internal::zero_now(static_cast<uint8_t*>(s->runs.mem) + 4, 4) != hipSuccess) return 0xFFFFFFFFu;
   return v[1];
 }
 
@@ -3213,7 +3179,7 @@ int launch_plan(const stream_scratch* s, const decode_plan& pl, uint8_t* base, c
     hipLaunchKernelGGL(k_stream_empty, dim3(1), dim3(64), 0, stream, cin, cout, nframes);
     return hipGetLastError() == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
   }
-  uint8_t* m = static_cast<uint8_t*>(s->mem);
+  uint8_t* m = static_cast<uint8_t*>(s->runs.mem);
   run_params P;
   P.base = base; P.lo = pl.lo; P.hi = pl.hi; P.rbytes = pl.rbytes;
   P.nruns = (uint32_t)pl.nruns;
@@ -3221,9 +3187,9 @@ int launch_plan(const stream_scratch* s, const decode_plan& pl, uint8_t* base, c
   P.head = reinterpret_cast<uint32_t*>(m);
   P.nflat = pl.nflat;
   P.flags = reinterpret_cast<uint64_t*>(m + HEAD_BYTES);
-  P.split = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->max_runs));
-  P.prog = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->max_runs) + split_bytes(s->max_runs));
-  P.rec = reinterpret_cast<uint64_t*>(m + records_off(s->max_runs));
+  P.split = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->runs.units));
+  P.prog = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->runs.units) + split_bytes(s->runs.units));
+  P.rec = reinterpret_cast<uint64_t*>(m + records_off(s->runs.units));
   P.opts = pl.opts;
   // The ticket is zero here (zeroed at allocation, reset by finish_call
   // after every call); granules, split and progress words carry the epoch of
@@ -3233,10 +3199,10 @@ int launch_plan(const stream_scratch* s, const decode_plan& pl, uint8_t* base, c
     return XYWS_ERR_HIP;
   P.cin_user = cin;
   P.cin = reinterpret_cast<xyws_carry*>(m + 64);
-  P.fst = pl.rcap ? static_cast<uint64_t*>(s->fmem) : nullptr;
+  P.fst = pl.rcap ? static_cast<uint64_t*>(s->desc.mem) : nullptr;
   P.rcap = pl.rcap;
   P.pol = s->pol_d;
-  P.lat = static_cast<uint64_t*>(s->lmem);  // (nullable: the device policy word's second copy)
+  P.lat = static_cast<uint64_t*>(s->lat.mem);  // (nullable: the device policy word's second copy)
   P.segb = pl.seg;
   P.tbias = 0;
   P.obias = 0;
@@ -3250,9 +3216,9 @@ int launch_plan(const stream_scratch* s, const decode_plan& pl, uint8_t* base, c
     // record
     run_params PL = P;
     PL.opts &= ~XYWS_OPT_LAT_NOGATE;
-    PL.lgrp = PL.lat + LW_STAT + s->lmax_segs;
-    PL.lbrk = PL.lat + lat_rep_off(s->lmax_segs);
-    PL.lsl = PL.lat + lat_sl_off(s->lmax_segs);
+    PL.lgrp = PL.lat + LW_STAT + s->lat.units;
+    PL.lbrk = PL.lat + lat_rep_off(s->lat.units);
+    PL.lsl = PL.lat + lat_sl_off(s->lat.units);
     PL.nseg = pl.lnseg;  // (the kernel counts the segments of the geometry it takes)
     const int rc = small ? launch_lattice<G_LAT_SMALL, G_LAT_SMALL>(PL, pl.lgrid, stream)
                          : launch_lattice<G_LAT5, G_LAT>(PL, pl.lgrid, stream);

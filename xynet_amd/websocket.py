@@ -237,7 +237,8 @@ class frame_decoder:
         self.ctx = ctx if ctx is not None else context(device)
         self.device = torch.device("cuda", self.ctx.device)
         self.carry_t = torch.zeros(64, dtype=torch.uint8, device=self.device)
-        self.opts = (4 if serial else 0) | (1 if parse_only else 0) | (0x200 if small_segments else 0) | opts
+        self.opts = ((_lib.OPT_SERIAL_SCAN if serial else 0) | (_lib.OPT_PARSE_ONLY if parse_only else 0) |
+                     (_lib.OPT_SMALL_SEG if small_segments else 0) | opts)
 
     def reset(self):
         self.carry_t.zero_()
