@@ -160,8 +160,9 @@ int xyws_ctx_reserve(xyws_ctx* ctx, uint64_t max_batch_bytes, uint64_t max_frame
  * xyws_ctx_reserve(ctx, max_total_bytes, ...) before it, an iov decode that
  * fits allocates nothing and can be captured into a hipGraph. */
 int xyws_ctx_reserve_iov(xyws_ctx* ctx, uint64_t max_total_bytes);
-/* Device-side error word of the last completed call (0 = none). Synchronizes
- * the context's device. */
+/* Device-side error word of the last completed call (0 = none; its bits are
+ * the DERR_* of xynet_amd/csrc/xyws_stream.h). Synchronizes the context's
+ * device. */
 int xyws_ctx_last_device_error(xyws_ctx* ctx, uint32_t* out);
 
 /* ---- hot path ------------------------------------------------------------ */
@@ -299,7 +300,8 @@ uint64_t xyws_header_build(uint8_t flags, const uint8_t* key, uint64_t len, uint
  * frames get a reply (others: none). dev_offsets (nullable) receives n_eff+1
  * reply offsets; *dev_out_len (nullable) the total reply bytes. Bytes past
  * out_cap are not written (compare *dev_out_len with out_cap); payload bytes
- * past src_len read as zero and set bit 0x100 of the device error word. */
+ * past src_len read as zero and set DERR_SRC_OOB (0x100) in the device error
+ * word. */
 #define XYWS_ENC_FRAME_OPCODE 0x1u
 typedef struct xyws_verdict xyws_verdict;
 int xyws_encode_frames(xyws_ctx* ctx, const void* dev_src, uint64_t src_len,
@@ -347,7 +349,7 @@ int xyws_classify_frames(xyws_ctx* ctx, const void* dev_src, uint64_t src_len,
  * XYWS_REASM_UTF8 every text message is validated (RFC 3629: no overlongs,
  * surrogates or code points above U+10FFFF). A continuation outside a
  * message is dropped and reported with XYWS_MSG_ORPHANS on the next message
- * (bit 0x200 of the device error word if none follows). */
+ * (DERR_ORPHANS (0x200) in the device error word if none follows). */
 #define XYWS_REASM_UTF8 0x1u
 #define XYWS_MSG_COMPLETE   0x1u /* the FIN fragment is in this batch */
 #define XYWS_MSG_UTF8_BAD   0x2u /* text message: invalid UTF-8 (a sequence cut by the end of an

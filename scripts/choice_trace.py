@@ -33,10 +33,10 @@ def main():
         dec.decode(buf, cap=0, count=False, carry=False)
         e1.record(s)
         torch.cuda.synchronize()
-        pol = (C.c_uint64 * 5)()
+        pol = (C.c_uint64 * _lib.POL_WORDS)()
         dec.ctx.L.xyws_debug_policy(dec.ctx.h, C.c_void_p(s.cuda_stream), pol)
-        out.append({"config": cfg, "ms": round(e0.elapsed_time(e1), 4), "decoder": int(pol[4]),
-                    "fsmin": int(pol[2]), "fsmax": int(pol[3])})
+        out.append({"config": cfg, "ms": round(e0.elapsed_time(e1), 4), "decoder": int(pol[_lib.POL_DECODER]),
+                    "fsmin": int(pol[_lib.POL_FSMIN]), "fsmax": int(pol[_lib.POL_FSMAX])})
     print(json.dumps(out), flush=True)
 
 

@@ -11,9 +11,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-NAMES = {16: "ctrl_A_claim_entry0", 17: "ctrl_C_publish_gate", 18: "ctrl_after_D_advance_and_wait_A",
-         19: "data_fill", 20: "data_wait_B", 21: "data_table", 22: "data_wait_C", 23: "data_mask_xor_lds",
-         24: "data_wait_D", 25: "data_store", 26: "data_wait_A", 28: "ctrl_C_wait_vmcnt"}
+NAMES = {"LT_C_A": "ctrl_A_claim_entry0", "LT_C_C": "ctrl_C_publish_gate",
+         "LT_C_ADV": "ctrl_after_D_advance_and_wait_A", "LT_D_FILL": "data_fill", "LT_D_WB": "data_wait_B",
+         "LT_D_TAB": "data_table", "LT_D_WC": "data_wait_C", "LT_D_MASK": "data_mask_xor_lds",
+         "LT_D_WD": "data_wait_D", "LT_D_ST": "data_store", "LT_D_WA": "data_wait_A", "LT_GATE": "ctrl_C_wait_vmcnt"}
 
 
 def main():
@@ -41,14 +42,15 @@ def main():
     torch.cuda.synchronize()
     out = (C.c_uint64 * _lib.NSTATS)()
     dec.ctx.L.xyws_debug_stats(dec.ctx.h, C.c_void_p(s.cuda_stream), out)
-    pol = (C.c_uint64 * 5)()
+    pol = (C.c_uint64 * _lib.POL_WORDS)()
     dec.ctx.L.xyws_debug_policy(dec.ctx.h, C.c_void_p(s.cuda_stream), pol)
-    segs = max(1, out[27])
+    nseg = int(out[_lib.LT_SEGS])
+    segs = max(1, nseg)
     res = {"config": cfg, "xopts": hex(xopts), "ms_call_with_stats": round(e0.elapsed_time(e1), 4),
-           "segments": int(out[27]), "policy": list(pol), "segments_per_workgroup": round(int(out[27]) / 512, 1)}
+           "segments": nseg, "policy": list(pol), "segments_per_workgroup": round(nseg / 512, 1)}
     for k, n in NAMES.items():
-        res["us_per_segment_" + n] = round(out[k] / segs / 2100.0, 3)
-    res["us_gate_wait_per_workgroup"] = round(out[29] / max(1, int(sys.argv[3]) if len(sys.argv) > 3 else 256) / 2100.0, 3)
+        res["us_per_segment_" + n] = round(out[getattr(_lib, k)] / segs / 2100.0, 3)
+    res["us_gate_wait_per_workgroup"] = round(out[_lib.LT_END] / max(1, int(sys.argv[3]) if len(sys.argv) > 3 else 256) / 2100.0, 3)
     print(json.dumps(res), flush=True)
 
 

@@ -35,8 +35,7 @@ def main():
     nrec = 2048
     out = (C.c_uint64 * (nrec * _lib.R_WORDS))()
     n = dec.ctx.L.xyws_debug_records(dec.ctx.h, C.c_void_p(s.cuda_stream), out, nrec)
-    W = _lib.R_WORDS
-    R_H, R_T0, R_T1, R_T2 = 0, 25, 26, 27
+    W, R_H, R_T0, R_T1, R_T2 = _lib.R_WORDS, _lib.R_H, _lib.R_T0, _lib.R_T1, _lib.R_T2
     NONE = (1 << 64) - 1
     runs = []
     for f in range(0, n, 2):

@@ -38,22 +38,27 @@ e.record()
 torch.cuda.synchronize()
 us = s.elapsed_time(e) / 20 * 1e3
 stream = torch.cuda.current_stream()
-names = ["runs", "runs_without_entry", "bad_boundaries", "repairs", "cuts", "spins", "dense_passes",
-         "frames", "scan_segments", "scan_survivors", "scan_undecided", "cyc_scan_filter",
-         "cyc_scan_check", "cyc_scan_resolve", "cyc_dense_entry", "cyc_dense_chase", "cyc_prologue", "cyc_main",
-         "cyc_wait", "cyc_fill", "cyc_chase_sync", "cyc_xor", "cyc_tail", "cyc_prefetch_issue", "cyc_chase_pass",
-         "cyc_pro_fill", "cyc_pro_scan", "cyc_pro_publish", "dense_no_entry", "dense_chase_fail",
-         "dense_mismatch", "dense_overflow", "giveups", "bridges", "steal_requests", "steals",
-         "stolen_segments", "cyc_dense_validate", "cyc_rows", "cyc_serial_chase", "p_lattice", "x41", "x42",
-         "x43", "x44", "x45", "cyc_stride_pass"]
+names = {"ST_RUNS": "runs", "ST_NONE": "runs_without_entry", "ST_BAD": "bad_boundaries", "ST_REPAIR": "repairs",
+         "ST_CUT": "cuts", "ST_SPIN": "spins", "ST_SEGS": "dense_passes", "ST_FRAMES": "frames",
+         "ST_P_WIN": "scan_segments", "ST_P_CAND": "scan_survivors", "ST_P_UND": "scan_undecided",
+         "ST_P_TCOMP": "cyc_scan_filter", "ST_P_TCHECK": "cyc_scan_check", "ST_P_TRES": "cyc_scan_resolve",
+         "ST_D_TENT": "cyc_dense_entry", "ST_D_TCHASE": "cyc_dense_chase", "ST_T_PRO": "cyc_prologue",
+         "ST_T_MAIN": "cyc_main", "ST_T_WAIT": "cyc_wait", "ST_T_FILL": "cyc_fill", "ST_T_CHASE": "cyc_chase_sync",
+         "ST_T_XOR": "cyc_xor", "ST_T_TAIL": "cyc_tail", "ST_T_PF": "cyc_prefetch_issue", "ST_T_CP": "cyc_chase_pass",
+         "ST_P_FILL": "cyc_pro_fill", "ST_P_SCAN": "cyc_pro_scan", "ST_P_PUB": "cyc_pro_publish",
+         "ST_D_NOENT": "dense_no_entry", "ST_D_CHASE": "dense_chase_fail", "ST_D_MISMATCH": "dense_mismatch",
+         "ST_D_OVF": "dense_overflow", "ST_GIVEUP": "giveups", "ST_BRIDGE": "bridges", "ST_STEAL_REQ": "steal_requests",
+         "ST_STEAL_ACC": "steals", "ST_STEAL_SEGS": "stolen_segments", "ST_D_TVAL": "cyc_dense_validate",
+         "ST_T_ROWS": "cyc_rows", "ST_T_SER": "cyc_serial_chase", "ST_P_LATTICE": "p_lattice", "ST_X_W0": "x41",
+         "ST_X_BITS": "x42", "ST_X_SURV": "x43", "ST_T_STRIDE": "cyc_stride_pass"}
 out = (C.c_uint64 * _lib.NSTATS)()
 for _ in range(2):
     dec.opts = xo | _lib.OPT_STATS
     dec.decode(dev, cap=cap, carry=False)
     dec.ctx.L.xyws_debug_stats(dec.ctx.h, C.c_void_p(stream.cuda_stream), out)
-pol = (C.c_uint64 * 5)()
+pol = (C.c_uint64 * _lib.POL_WORDS)()
 dec.ctx.L.xyws_debug_policy(dec.ctx.h, C.c_void_p(stream.cuda_stream), pol)
-st = dict(zip(names, list(out)))
+st = {label: int(out[getattr(_lib, slot)]) for slot, label in names.items()}
 nrun = max(1, st["runs"])
 for k in list(st):
     if k.startswith("cyc_"):

@@ -1,4 +1,4 @@
-"""The decoder choice of xyws_decode_stream (stream_decode_fused), through the
+"""The decoder choice of xyws_decode_stream (plan_decode), through the
 C-ABI: which decoder serves a call follows what the previous call on the same
 stream found (the policy words its finisher publishes), and every call's bytes,
 count and carry are the reference's whichever decoder ran
@@ -9,6 +9,7 @@ import ctypes as C
 import pytest
 
 from test_gpu_parity import dev_digest, tools_batch
+from xynet_amd._lib import DEC_LATTICE, DEC_RUNS, DEC_RUNS512, POL_DECODER, POL_FSMAX, POL_FSMIN, POL_WORDS
 
 pytestmark = pytest.mark.gpu
 
@@ -23,8 +24,11 @@ def ws():
     return websocket
 
 
+RUN_DECODER = (DEC_RUNS, DEC_RUNS512)
+
+
 def _policy(dec):
-    out = (C.c_uint64 * 5)()
+    out = (C.c_uint64 * POL_WORDS)()
     stream = torch.cuda.current_stream()
     assert dec.ctx.L.xyws_debug_policy(dec.ctx.h, C.c_void_p(stream.cuda_stream), out) == 0
     return list(out)
@@ -42,10 +46,10 @@ def _lat_counters(dec):
 
 
 def test_decoder_choice_follows_the_frames(ws):
-    """The decoder choice (stream_decode_fused): the lattice decoder first when
-    the previous call on the stream found frames of one size (>= 128 B, policy
-    word 4 = 3), the run decoder otherwise (0, or
-    2 in 512-thread workgroups after regular frames under 2 KiB). An irregular
+    """The decoder choice (plan_decode): the lattice decoder first when the
+    previous call on the stream found frames of one size (>= 128 B, POL_DECODER
+    = DEC_LATTICE), the run decoder otherwise (DEC_RUNS, or DEC_RUNS512 in
+    512-thread workgroups after regular frames under 2 KiB). An irregular
     batch after regular ones goes to the lattice decoder, which checks lattice
     points 1 and 2 before anything else and hands the whole batch to the run
     decoder: its time stays that of the run decoder alone (the decoder-choice
@@ -85,28 +89,28 @@ def test_decoder_choice_follows_the_frames(ws):
         assert dev_digest(buf) == (c["out_digest"] if (k + 1) % 2 else c["in_digest"]), (name, k)
         assert dec.ctx.last_device_error() == 0
         p = _policy(dec)
-        used.append(p[4])
+        used.append(p[POL_DECODER])
         pols.append(p)
         lats.append(_lat_counters(dec))
     # c3: regular 64 KiB frames (65 550 B with the header): the lattice decoder
-    assert pols[1][2] == pols[1][3] == 65550
-    assert used[1] == 3 and used[2] == 3
+    assert pols[1][POL_FSMIN] == pols[1][POL_FSMAX] == 65550
+    assert used[1] == DEC_LATTICE and used[2] == DEC_LATTICE
     # the first c4 call after c3 goes to the lattice decoder, which hands the
     # whole batch to the run decoder at once: the run decoder's statistics...
-    assert used[3] in (0, 2) and pols[3][2] < pols[3][3]
+    assert used[3] in RUN_DECODER and pols[3][POL_FSMIN] < pols[3][POL_FSMAX]
     # ...after the lattice kernel's prologue handed it over at lattice point 1
     # (its checks, not its segment loop: nothing loaded past the first frames)
     assert lats[3][2] == lats[2][2] + 1 and lats[3][3:] == lats[2][3:], (lats[2], lats[3])
     # ...and the run decoder's time (c4 on the run decoder alone: calls 4, 5;
     # the best of the three c4-after-c3 calls 3, 13, 15 against the best alone)
-    assert used[4] in (0, 2) and used[5] in (0, 2)
-    assert used[13] in (0, 2) and used[15] in (0, 2)
+    assert used[4] in RUN_DECODER and used[5] in RUN_DECODER
+    assert used[13] in RUN_DECODER and used[15] in RUN_DECODER
     assert min(ms[3], ms[13], ms[15]) <= 1.05 * min(ms[4], ms[5]) + 0.02, ms
     # after c4's mixed sizes: the run decoder
-    assert used[6] in (0, 2) and used[7] in (0, 2), used
+    assert used[6] in RUN_DECODER and used[7] in RUN_DECODER, used
     # c2 after c4: the run decoder, then the lattice
-    assert used[8] in (0, 2) and pols[8][2] == pols[8][3] == 264 and used[9] == 3
-    assert used[10] in (0, 2)                      # XYWS_OPT_RUNS forces the run decoder
+    assert used[8] in RUN_DECODER and pols[8][POL_FSMIN] == pols[8][POL_FSMAX] == 264 and used[9] == DEC_LATTICE
+    assert used[10] in RUN_DECODER                 # XYWS_OPT_RUNS forces the run decoder
     # c3's first frame is 64 KiB: every lattice call runs 75 KiB segments
     assert lats[2][3] - lats[0][3] == 2 and lats[2][4] == lats[0][4], lats
     # c2's 264-byte frames: 120 KiB segments
@@ -142,4 +146,4 @@ def test_decoder_choice_for_calls_in_flight(ws):
     assert dev_digest(c4) == k4["out_digest"]
     assert l1[3] - l0[3] == 2 and l1[4] == l0[4], (l0, l1)   # c3: the loops ran, 75 KiB segments
     assert l1[2] - l0[2] == 1, (l0, l1)                      # one lattice attempt on c4
-    assert (l1[0] >> 48) & 0x7F in (0, 2) and l1[0] & ((1 << 48) - 1) == 0  # the run decoder, mixed sizes
+    assert (l1[0] >> 48) & 0x7F in RUN_DECODER and l1[0] & ((1 << 48) - 1) == 0  # the run decoder, mixed sizes

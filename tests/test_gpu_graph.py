@@ -121,9 +121,10 @@ def test_decode_captured_after_mid_geometry_calls():
             r = dec.decode(buf, cap=on + 2, carry=False)
             assert r.nframes == on
     torch.cuda.synchronize()
-    pol = (__import__("ctypes").c_uint64 * 5)()
+    from xynet_amd._lib import POL_FSMAX, POL_FSMIN, POL_WORDS
+    pol = (__import__("ctypes").c_uint64 * POL_WORDS)()
     assert ctx.L.xyws_debug_policy(ctx.h, __import__("ctypes").c_void_p(s.cuda_stream), pol) == 0
-    assert pol[3] < 2048 and pol[2] != pol[3], list(pol)
+    assert pol[POL_FSMAX] < 2048 and pol[POL_FSMIN] != pol[POL_FSMAX], list(pol)
     g = torch.cuda.CUDAGraph()
     buf.copy_(orig)
     torch.cuda.synchronize()

@@ -24,7 +24,7 @@ import pytest
 import streams
 from test_gpu_parity import carry_list, dev_bytes, frames_list, host, torch
 from test_gpu_choice import _policy
-from xynet_amd._lib import OPT_LATTICE, OPT_SMALL_SEG as OPT_SMALL, OPT_TEST_LATDUMP, OPT_TEST_LATSPEC
+from xynet_amd._lib import DEC_LATTICE, POL_DECODER, OPT_LATTICE, OPT_SMALL_SEG as OPT_SMALL, OPT_TEST_LATDUMP, OPT_TEST_LATSPEC
 
 pytestmark = pytest.mark.gpu
 
@@ -188,7 +188,7 @@ def test_speculation_list_overflow_hands_over(ws, oracle, change_at):
     regular batch above 32 MiB reaches it: 40 MiB, with and without a size
     change near its end. Bytes, count, the whole descriptor table and the
     carry against the oracle; the lattice did not finish the call (the run
-    decoder took the tail: policy word 4 != 3)."""
+    decoder took the tail: POL_DECODER != DEC_LATTICE)."""
     from test_gpu_parity import decoder_policy
     src, n = _big_regular(0x5A17 + (change_at or 0), 4096, 40 << 20, change_at)
     ob = src.copy()
@@ -201,7 +201,7 @@ def test_speculation_list_overflow_hands_over(ws, oracle, change_at):
     assert oracle.digest(t.cpu().numpy()) == oracle.digest(ob)
     assert oracle.frames_digest(r.frames_t[: on * 32].cpu().numpy()) == oracle.frames_digest(oraw)
     assert carry_list(dec.carry()) == carry_list(ocarry)
-    assert decoder_policy(dec)[4] != 3, decoder_policy(dec)
+    assert decoder_policy(dec)[POL_DECODER] != DEC_LATTICE, decoder_policy(dec)
 
 
 def test_lattice_then_irregular_then_lattice(ws, oracle):
@@ -209,7 +209,7 @@ def test_lattice_then_irregular_then_lattice(ws, oracle):
     an irregular one after them is redirected at its first size change, the
     next irregular one takes the run decoder, and a regular one after that
     the run decoder once more (the choice follows the previous call), then the
-    lattice again (policy word 4: 3 = lattice)."""
+    lattice again (POL_DECODER: DEC_LATTICE)."""
     dec = ws.frame_decoder()
     reg = regular(1, 4096, 500)
     irr = streams.case_bytes("random_frames_300")
@@ -222,5 +222,6 @@ def test_lattice_then_irregular_then_lattice(ws, oracle):
         assert r.nframes == on
         assert host(view) == ob.tobytes()
         assert frames_list(r.frames(), True) == frames_list(ofr, True)
-        used.append(_policy(dec)[4])
-    assert used[1] == 3 and used[3] != 3 and used[4] != 3 and used[5] == 3  # (call 0 follows the stream's past)
+        used.append(_policy(dec)[POL_DECODER])
+    assert (used[1] == DEC_LATTICE and used[3] != DEC_LATTICE and used[4] != DEC_LATTICE and
+            used[5] == DEC_LATTICE)  # (call 0 follows the stream's past)

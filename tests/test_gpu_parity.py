@@ -12,7 +12,7 @@ import pytest
 
 from conftest import load_golden
 import streams
-from xynet_amd._lib import (OPT_BIGSCAN, OPT_LATTICE, OPT_NO_LATDEC, OPT_STEAL, OPT_TEST_GIVEUP, OPT_TEST_STEAL,
+from xynet_amd._lib import (DEC_LATTICE, POL_DECODER, POL_WORDS, OPT_BIGSCAN, OPT_LATTICE, OPT_NO_LATDEC, OPT_STEAL, OPT_TEST_GIVEUP, OPT_TEST_STEAL,
                             OPT_UNMASKED_HINT, OPT_WG256, OPT_WG512)
 
 pytestmark = pytest.mark.gpu
@@ -441,17 +441,17 @@ def test_config_batches(ws, oracle, name, mode):
     assert frames_digest(oracle, r, n) == c["frames_digest"]
     assert dec.ctx.last_device_error() == 0
     if mode == "lat":
-        # the lattice held over the whole batch (policy word 4 = 3) on the
+        # the lattice held over the whole batch (POL_DECODER = DEC_LATTICE) on the
         # regular configs; c4 is handed to the run decoder at frame 1
-        assert (decoder_policy(dec)[4] == 3) == (name != "c4_mixed"), decoder_policy(dec)
+        assert (decoder_policy(dec)[POL_DECODER] == DEC_LATTICE) == (name != "c4_mixed"), decoder_policy(dec)
     del buf, r
     torch.cuda.empty_cache()
 
 
 def decoder_policy(dec):
-    """The policy words of the last call on the current stream (xyws_debug_policy):
-    [epoch, batch bytes, smallest and largest last-frame size, decoder]."""
-    out = (C.c_uint64 * 5)()
+    """The policy words of the last call on the current stream (xyws_debug_policy:
+    _lib.POL_* index them)."""
+    out = (C.c_uint64 * POL_WORDS)()
     stream = torch.cuda.current_stream()
     assert dec.ctx.L.xyws_debug_policy(dec.ctx.h, C.c_void_p(stream.cuda_stream), out) == 0
     return list(out)
@@ -476,7 +476,7 @@ def test_config_batches_bench_path(ws, name):
     assert carry_list(dec.carry()) == c["carry"]
     assert dec.ctx.last_device_error() == 0
     # the lattice decoder on the regular configs, the run decoder on c4
-    assert (decoder_policy(dec)[4] == 3) == (name != "c4_mixed"), decoder_policy(dec)
+    assert (decoder_policy(dec)[POL_DECODER] == DEC_LATTICE) == (name != "c4_mixed"), decoder_policy(dec)
     del buf, r
     torch.cuda.empty_cache()
 

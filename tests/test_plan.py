@@ -25,19 +25,28 @@ OPT_PARSE_ONLY, OPT_WG256 = L.OPT_PARSE_ONLY, L.OPT_WG256
 FIELDS = ("geom", "seg", "threads", "nruns", "rbytes", "nflat", "want_lat", "lnseg", "lgrid", "lseg0", "lseg1",
           "pfs", "dense0", "bigscan", "rcap", "need_runs", "need_fmem", "need_lat")
 
-# the policy words {epoch, batch bytes, smallest, largest last-frame size, decoder} a call leaves
-FRESH = [0, 0, 0, 0, 0]                  # no call has finished on the stream
-EQUAL_264 = [7, 1 << 28, 264, 264, 3]
-EQUAL_127 = [7, 1 << 20, 127, 127, 2]
-MIXED_1000 = [3, 4 << 20, 2, 1006, 0]    # 0-1000 B payloads
-MIXED_1M = [3, 128 << 20, 100, 1 << 20, 0]
+
+
+def policy(epoch, nbytes, fsmin, fsmax, decoder):
+    """The policy words a call leaves (L.POL_*)."""
+    words = [0] * L.POL_WORDS
+    words[L.POL_EPOCH], words[L.POL_BYTES], words[L.POL_FSMIN], words[L.POL_FSMAX] = epoch, nbytes, fsmin, fsmax
+    words[L.POL_DECODER] = decoder
+    return words
+
+
+FRESH = policy(0, 0, 0, 0, 0)            # no call has finished on the stream
+EQUAL_264 = policy(7, 1 << 28, 264, 264, L.DEC_LATTICE)
+EQUAL_127 = policy(7, 1 << 20, 127, 127, L.DEC_RUNS512)
+MIXED_1000 = policy(3, 4 << 20, 2, 1006, L.DEC_RUNS)    # 0-1000 B payloads
+MIXED_1M = policy(3, 128 << 20, 100, 1 << 20, L.DEC_RUNS)
 POLICIES = [None, FRESH, EQUAL_264, EQUAL_127, MIXED_1000, MIXED_1M]
 
 
 def plan(pol, lo, hi, cap=0, opts=0, ncu=NCU):
     lib = L.load()
     out = (C.c_uint64 * len(FIELDS))()
-    words = (C.c_uint64 * 5)(*pol) if pol is not None else None
+    words = (C.c_uint64 * L.POL_WORDS)(*pol) if pol is not None else None
     assert lib.xyws_debug_plan(ncu, words, lo, hi, cap, opts, out) == 0
     return dict(zip(FIELDS, out))
 

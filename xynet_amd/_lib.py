@@ -14,8 +14,6 @@ HEADER = os.path.join(ROOT, "include", "xyws.h")
 
 XYWS_OK = 0
 XYWS_ERR_DEVICE = -5
-NSTATS = 48  # XYWS_NSTATS (xyws_stream.h)
-R_WORDS = 32  # u64 words per run record (xyws_stream.hip)
 # Every XYWS_OPT_* bit under its header's name, by value: the only Python list
 # (tests/test_opts.py holds it to the headers). include/xyws.h:
 OPT_PARSE_ONLY = 0x1
@@ -51,10 +49,33 @@ OPT_IOV_PIECES = 0x10000000
 OPT_IOV_STAGE = 0x20000000
 OPT_NO_BIGSCAN = 0x40000000
 OPT_RUNS = 0x80000000
-# debug stats indices (xyws_stream.hip)
-ST_RUNS, ST_NONE, ST_BAD, ST_REPAIR, ST_CUT, ST_SPIN, ST_SEGS, ST_FRAMES = range(8)
+# The scratch layout section of xynet_amd/csrc/xyws_stream.h (where each is
+# described), under the header's names, by value: tests/test_layout.py holds
+# every one to the header. Debug stats slots (xyws_debug_stats: NSTATS words),
+# the run decoder's:
+NSTATS = 48  # XYWS_NSTATS
+ST_RUNS, ST_NONE, ST_BAD, ST_REPAIR, ST_CUT, ST_SPIN, ST_SEGS, ST_FRAMES = 0, 1, 2, 3, 4, 5, 6, 7
+ST_P_WIN, ST_P_CAND, ST_P_UND, ST_P_TCOMP, ST_P_TCHECK, ST_P_TRES = 8, 9, 10, 11, 12, 13
+ST_D_TENT, ST_D_TCHASE = 14, 15
+ST_T_PRO, ST_T_MAIN, ST_T_WAIT, ST_T_FILL, ST_T_CHASE, ST_T_XOR = 16, 17, 18, 19, 20, 21
+ST_T_TAIL, ST_T_PF, ST_T_CP = 22, 23, 24
+ST_P_FILL, ST_P_SCAN, ST_P_PUB, ST_D_NOENT, ST_D_CHASE, ST_D_MISMATCH, ST_D_OVF = 25, 26, 27, 28, 29, 30, 31
 ST_GIVEUP, ST_BRIDGE, ST_STEAL_REQ, ST_STEAL_ACC, ST_STEAL_SEGS = 32, 33, 34, 35, 36
-ST_P_LATTICE = 40  # run decoder: runs whose entry the lattice gave (find_entry)
+ST_D_TVAL, ST_T_ROWS, ST_T_SER = 37, 38, 39
+ST_P_LATTICE, ST_X_W0, ST_X_BITS, ST_X_SURV, ST_T_STRIDE = 40, 41, 42, 43, 46
+# ...and the lattice decoder's (it shares slots 16..29 with the run decoder's timing slots)
+LT_C_A, LT_C_C, LT_C_ADV, LT_D_FILL, LT_D_WB, LT_D_TAB, LT_D_WC = 16, 17, 18, 19, 20, 21, 22
+LT_D_MASK, LT_D_WD, LT_D_ST, LT_D_WA, LT_SEGS, LT_GATE, LT_END = 23, 24, 25, 26, 27, 28, 29
+# run record words (xyws_debug_records: R_WORDS u64 per flat index)
+R_WORDS = 32
+R_H, R_W, R_S0, R_HEAD, R_OKW, R_HN, R_WN, R_CNT, R_TAIL, R_FIRST, R_F0 = 0, 1, 2, 7, 8, 9, 10, 11, 12, 13, 14
+R_EFROM, R_ECNT, R_EORD, R_ECARRY, R_EP = 20, 21, 22, 23, 24
+R_T0, R_T1, R_T2, R_SPLIT, R_XCC, R_NREC = 25, 26, 27, 28, 29, 30
+# pinned policy words (xyws_debug_policy, xyws_debug_plan: POL_WORDS u64) and the decoder codes in POL_DECODER
+POL_EPOCH, POL_BYTES, POL_FSMIN, POL_FSMAX, POL_DECODER, POL_WORDS = 0, 1, 2, 3, 4, 5
+DEC_RUNS, DEC_RUNS512, DEC_LATTICE = 0, 2, 3
+# device error bits (xyws_ctx_last_device_error)
+DERR_TABLE, DERR_TIMEOUT, DERR_STALE, DERR_TAG, DERR_SRC_OOB, DERR_ORPHANS = 0x1, 0x2, 0x4, 0x8, 0x100, 0x200
 ERRORS = {-1: "invalid argument", -2: "HIP runtime error", -3: "device allocation failed",
           -4: "scratch capacity exceeded", -5: "device-side error", -6: "not complete yet"}
 

@@ -250,7 +250,7 @@ __global__ void k_stream_serial(const uint8_t* __restrict__ base, uint64_t lo, u
       c.key[0] = (uint8_t)h.key; c.key[1] = (uint8_t)(h.key >> 8);
       c.key[2] = (uint8_t)(h.key >> 16); c.key[3] = (uint8_t)(h.key >> 24);
     }
-    if (nt >= tab_cap) { atomicOr(err, 1u); break; }
+    if (nt >= tab_cap) { atomicOr(err, DERR_TABLE); break; }
     tab.start[nt] = pos; tab.ps[nt] = ps; tab.pe[nt] = pe; tab.kw[nt] = aligned_key(h.key, ps, 0);
     nt++;
     if (frames && nf < cap) {
@@ -461,7 +461,7 @@ int xyws_ctx_last_device_error(xyws_ctx* ctx, uint32_t* out) {
 }
 
 // Internal (not part of include/xyws.h): resolution counters of the last fused
-// stream decode run with XYWS_OPT_STATS (0x100) on `stream`. Synchronizes the
+// stream decode run with XYWS_OPT_STATS on `stream`. Synchronizes the
 // device. out: XYWS_NSTATS words.
 int xyws_debug_stats(xyws_ctx* ctx, void* stream, uint64_t* out) {
   if (!ctx || !out) return XYWS_ERR_INVALID;
@@ -498,9 +498,8 @@ int xyws_debug_lattice(xyws_ctx* ctx, void* stream, uint64_t* out) {
 }
 
 // Internal: the decoder-choice words the last fused stream decode on `stream`
-// published ({epoch, batch bytes, smallest, largest last-frame size, decoder:
-// 0 or 2 the run decoder (2: 512-thread workgroups), 3 the lattice
-// decoder}). Synchronizes the device.
+// published (POL_WORDS words POL_*, the decoder a DEC_* code: xyws_stream.h).
+// Synchronizes the device.
 int xyws_debug_policy(xyws_ctx* ctx, void* stream, uint64_t* out) {
   if (!ctx || !out) return XYWS_ERR_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -508,7 +507,7 @@ int xyws_debug_policy(xyws_ctx* ctx, void* stream, uint64_t* out) {
   if (hipDeviceSynchronize() != hipSuccess) return XYWS_ERR_HIP;
   scratch_slot* sl = find_slot(ctx, (hipStream_t)stream);
   if (!sl || !sl->ss.pol_h) return XYWS_ERR_INVALID;
-  for (int i = 0; i < 5; i++) out[i] = sl->ss.pol_h[i];
+  for (int i = 0; i < POL_WORDS; i++) out[i] = sl->ss.pol_h[i];
   return XYWS_OK;
 }
 
@@ -520,10 +519,10 @@ int xyws_debug_policy(xyws_ctx* ctx, void* stream, uint64_t* out) {
 // segment bytes (2), pfs, dense0, bigscan, rcap, needs: runs, descriptor
 // region bytes, lattice segments}.
 #define XYWS_PLAN_WORDS 18
-int xyws_debug_plan(int ncu, const uint64_t pol[5], uint64_t lo, uint64_t hi, uint64_t cap, uint32_t opts,
+int xyws_debug_plan(int ncu, const uint64_t pol[POL_WORDS], uint64_t lo, uint64_t hi, uint64_t cap, uint32_t opts,
                     uint64_t* out) {
   if (!out || ncu <= 0 || hi < lo) return XYWS_ERR_INVALID;
-  const policy_view pv = pol ? policy_view{true, pol[0], pol[2], pol[3]} : policy_view{};
+  const policy_view pv = pol ? policy_view{true, pol[POL_EPOCH], pol[POL_FSMIN], pol[POL_FSMAX]} : policy_view{};
   const decode_plan p = plan_decode(ncu, pv, lo, hi, cap, opts);
   const uint64_t w[XYWS_PLAN_WORDS] = {p.geom, p.seg, p.threads, p.nruns, p.rbytes, p.nflat, p.want_lat, p.lnseg,
                                        p.lgrid, p.lseg[0], p.lseg[1], p.pfs, p.dense0, p.bigscan, p.rcap,

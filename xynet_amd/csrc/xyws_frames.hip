@@ -312,7 +312,7 @@ XYWS_DEV gitem item_of(const gparams& G, uint64_t i) {
 
 XYWS_DEV uint8_t src_byte(const gparams& G, uint64_t p) {
   if (p < G.src_len) return G.src[G.src_lo + p];
-  atomicOr(G.err, 0x100u);
+  atomicOr(G.err, DERR_SRC_OOB);
   return 0;
 }
 
@@ -678,7 +678,7 @@ __global__ void __launch_bounds__(FT) k_gather(gparams G, const uint64_t* __rest
           w |= (v ^ kw) & m;
         }
       }
-      if (oob) atomicOr(G.err, 0x100u);
+      if (oob) atomicOr(G.err, DERR_SRC_OOB);
       if (a >= o0 && a + 16 <= o1) {
         __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(G.out + a));
       } else {
@@ -809,7 +809,7 @@ constexpr uint32_t UT = 65536;  // UTF-8 tile: bytes of out[] (k_utf8)
 
 // each record from the offsets of its start and the next start (starts[]:
 // every message's first frame, k_rs_sizes); continuations after the last
-// message's FIN with no message after them set bit 0x200 of the device error
+// message's FIN with no message after them set DERR_ORPHANS in the device error
 // word. With umap, also the UTF-8 tile map: umap[t] = the message holding
 // the first byte of UTF-8 tile t (UT bytes of out[]), written by the lanes of
 // the messages whose bytes start a tile (a 1 MiB message spans 16), so that a
@@ -827,7 +827,7 @@ __global__ void __launch_bounds__(FT) k_rs_msgs(const xyws_frame* frames, const 
   if (m == 0) {
     if (dev_nmsgs) *dev_nmsgs = nm;
     const uint64_t before = nm ? orph_rank[starts[nm - 1]] : 0;
-    if (orph_rank[ne] > before) atomicOr(err, 0x200u);
+    if (orph_rank[ne] > before) atomicOr(err, DERR_ORPHANS);
   }
   if (m >= nm || m >= msg_cap) return;
   const uint64_t s = starts[m];

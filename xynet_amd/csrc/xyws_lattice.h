@@ -60,24 +60,7 @@
 
 constexpr uint64_t LAT_FMIN = 128;          // smaller frames: the run decoder (its dense pass)
 constexpr uint64_t LAT_FMAX = 1ull << 40;   // (lattice arithmetic stays well inside 64 bits)
-// lattice scratch (u64 words, zeroed at allocation)
-enum {
-  LW_CNT = 0,      // u32 [0] claim counter, u32 [1] done count (reset by the finisher)
-  LW_BRK = 2,      // ~(earliest failing lattice index) of this call, 0 = none (reset by the finisher)
-  LW_UNMASK = 3,   // xyws_unmask's claim counter pair (u32 claims, u32 done; reset by its last workgroup)
-  LW_W = 4,        // the decided prefix: every segment below it has published its result (reset by the finisher)
-  LW_LOOPS = 5,    // workgroups whose segment loop has ended (reset by the finisher)
-  // one 16-byte granule, loaded by the prologue in one round trip:
-  LW_DPOL = 6,     // the device policy word of the previous call in the stream (dpol_publish)
-  LW_EPOCH = 7,    // completed calls (a call runs with E = this + 1)
-  LW_REDIR = 8,    // redirect record for the run decoder: [0] state, [1] p, [2] frames before p
-  LW_NBAIL_POL = 12,  // calls handed whole to the run decoder on the device policy word (cumulative)
-  LW_NBAIL_HYP = 13,  // calls handed whole to the run decoder by the prologue's checks (cumulative)
-  LW_NLOOP_A = 14,    // calls whose segment loops ran in the large-frame geometry (cumulative)
-  LW_NLOOP_B = 15,    // ... in the default geometry (cumulative)
-  LW_RCARRY = 16,  // the carry the run decoder starts from at p (8 words)
-  LW_STAT = 32     // per segment: (E << 2) | LS_*
-};
+// (lattice scratch words LW_*: xyws_stream.h; LW_STAT results:)
 enum { LS_AGG = 1, LS_BRK = 3 };
 constexpr uint32_t LAT_SLIST = 512;            // speculative stores a workgroup records (lat_undo's list)
 constexpr uint32_t LAT_NOCLAIM = 0x7FFFFFFFu;  // (no claim: the next segment after it is none)
@@ -105,7 +88,6 @@ using G_LAT_SMALL = lgeom<64, 1024>;  // tests: 1 KiB segments, many segment bou
 // The LDS layout of a kernel holding the loops of geometries GA and GB: the
 // larger segment and table (the scalar words first: the prologue writes them
 // before it knows which loop runs).
-static_assert(LW_DPOL == LW_DPOL_WORD && LW_EPOCH == LW_DPOL + 1 && LW_DPOL % 2 == 0, "one 16-byte granule");
 
 template <class GA, class GB>
 struct llay {
@@ -191,12 +173,12 @@ XYWS_DEV uint64_t lat_advance(const run_params& P, uint64_t E, uint32_t lane) {
   return w1;
 }
 // Wait (wave 0) until every segment up to s has decided; bounded (device
-// error bit 2). Every segment at or below s was claimed by a running
+// error bit DERR_TIMEOUT). Every segment at or below s was claimed by a running
 // workgroup and decides on its own bytes, so the wait ends.
 XYWS_DEV void lat_wait_decided(const run_params& P, uint64_t E, uint64_t s, uint32_t lane) {
   for (uint32_t it = 0; lat_advance(P, E, lane) <= s; it++) {
     if (it >= (1u << 20)) {
-      if (lane == 0) atomicOr(P.head + 1, 2u);
+      if (lane == 0) atomicOr(head_error(P), DERR_TIMEOUT);
       return;
     }
     __builtin_amdgcn_s_sleep(8);  // (polls at the coherence point: spaced)
@@ -334,7 +316,7 @@ XYWS_DEV bool lat_redirect(run_params& P) {
   P.base += pal;
   P.lo = p - pal;
   P.hi -= pal;
-  // runs over the rest, cut as stream_decode_fused cuts a batch, with the
+  // runs over the rest, cut as plan_decode cuts a batch, with the
   // launched run count as the cap
   const uint64_t seg = P.segb, nseg = (P.hi + seg - 1) / seg, maxr = P.nruns;
   P.rbytes = nseg <= maxr ? seg : ((P.hi + maxr - 1) / maxr + 15) & ~15ull;
@@ -433,29 +415,26 @@ XYWS_DEV uint32_t lat_ctrl_load(const run_params& P, uint64_t s, uint64_t SEGB, 
 // region (one loop holding both spilled the prefetch in round 3's sweep decoder).
 enum { LR_ALL = 0, LR_CTRL = 1, LR_DATA = 2 };
 // stats mode (XYWS_OPT_STATS): shader clocks summed over workgroups, per phase,
-// for the control lane (tid 0) and one data lane (tid 64) — the debug stats
-// words from 16 on (the run decoder's timing slots; it does not run in a call
-// the lattice finished)
-enum { LT_C_A = 16, LT_C_C, LT_C_ADV, LT_D_FILL, LT_D_WB, LT_D_TAB, LT_D_WC, LT_D_MASK, LT_D_WD, LT_D_ST, LT_D_WA,
-       LT_SEGS, LT_GATE, LT_END };
+// for the control lane (tid 0) and one data lane (tid 64), in the LT_* stats
+// slots (xyws_stream.h: LCLK_NSLOTS from LCLK_SLOT0 on)
 struct lat_clock {
   bool on;
-  uint64_t t, acc[16];
+  uint64_t t, acc[LCLK_NSLOTS];
   XYWS_DEV void start(bool o) {
     on = o;
-    for (int i = 0; i < 16; i++) acc[i] = 0;
+    for (int i = 0; i < LCLK_NSLOTS; i++) acc[i] = 0;
     t = on ? __builtin_amdgcn_s_memtime() : 0;
   }
   XYWS_DEV void mark(int slot) {
     if (!on) return;
     const uint64_t n = __builtin_amdgcn_s_memtime();
-    acc[slot - 16] += n - t;
+    acc[slot - LCLK_SLOT0] += n - t;
     t = n;
   }
   XYWS_DEV void flush(const run_params& P) {
     if (!on) return;
-    for (int i = 0; i < 16; i++)
-      if (acc[i]) stat_add(P, 16 + i, acc[i]);
+    for (int i = 0; i < LCLK_NSLOTS; i++)
+      if (acc[i]) stat_add(P, LCLK_SLOT0 + i, acc[i]);
   }
 };
 template <class G, int ROLE, class LL>
@@ -743,7 +722,7 @@ XYWS_DEV void lat_loop(const run_params& P, LL& L, uint32_t tid0, uint32_t ahead
     }
     it++;
     // the control wave raises the decided prefix while the data waves store
-    if (clk.on && cl) clk.acc[LT_SEGS - 16]++;
+    if (clk.on && cl) clk.acc[LT_SEGS - LCLK_SLOT0]++;
     cur = nxt;
   }
   clk.mark(cl ? LT_C_ADV : LT_D_ST);

@@ -87,21 +87,13 @@ constexpr int AUX_NT = 2;             // buffer cache policy: nontemporal (the s
 // ms, c1 0.1106 -> 0.1090 against nt alone, same box; sc1 alone 0.6564,
 // plain 0.7198 (profiles/r05y_store_policy_ab.txt); the run decoder measured
 // 0.5126 vs 0.5015 ms on c4 with them (r05z vs r05x) and keeps nt
-#ifndef XYWS_EXP_AUX_ST
-#define XYWS_EXP_AUX_ST 2
-#endif
-constexpr int AUX_ST = XYWS_EXP_AUX_ST;
+constexpr int AUX_ST = 2;
 constexpr int AUX_ST_STREAM = 18;
 constexpr uint64_t PLEN_SPEC_MAX = 1ull << 46;
 constexpr uint32_t MAX_RUNS = 1024;
 // work stealing: a run is asked for its tail when it has at least this many
 // segments left after the current one; the piece is at least this long
-#ifndef XYWS_STEAL_MIN_LEFT
-#define XYWS_STEAL_MIN_LEFT 8
-#endif
-#ifndef XYWS_STEAL_MIN_PIECE
-#define XYWS_STEAL_MIN_PIECE 3
-#endif
+constexpr uint64_t STEAL_MIN_LEFT = 8, STEAL_MIN_PIECE = 3;
 
 
 // chase-state bits
@@ -150,20 +142,7 @@ struct walk_t {
   uint32_t ok, tmo, ecarry, act;
 };
 
-// run record: R_WORDS x u64
-enum {
-  R_H = 0, R_W, R_S0, R_HEAD = R_S0 + 5,            // prologue: entry, write start, state, head frames
-  R_OK = 8, R_HN, R_WN, R_CNT, R_TAIL, R_FIRST,     // results (R_OK: ok | tmo << 1 | succ << 32)
-  R_F0 = 14,                                        // final state (5 words)
-  R_EFROM = 20, R_ECNT, R_EORD, R_ECARRY,           // emission plan (finish_call)
-  R_EP = 24,                                        // epoch of the call that wrote the results
-  R_T0, R_T1, R_T2,                                 // stats mode: s_memrealtime at start, after the prologue, at the end
-  R_SPLIT,                                          // own runs: the split segment a thief took the rest from (NONE: none)
-  R_XCC,                                            // stats mode: the XCD (XCC_ID) the run's workgroup ran on
-  R_NREC,                                           // descriptors requested: frame starts in the item's region
-  R_WORDS = 32
-};
-// R_OK bits
+// R_OKW bits (run records: R_*, xyws_stream.h)
 constexpr uint64_t OK_BIT = 1, TMO_BIT = 2;  // chain landed on the successor; successor wait timed out
 
 // Entry granules, 16 bytes per run, each written by ONE 16-byte sc1 store and
@@ -184,22 +163,6 @@ XYWS_DEV uint64_t flag_claimed(uint64_t E) { return E << 1; }
 XYWS_DEV uint64_t flag_published(uint64_t E) { return (E << 1) | 1u; }
 constexpr uint64_t G_NONE = (1ull << 46) - 1;
 XYWS_DEV uint64_t granule_tag(uint64_t E) { return (E & 0x1FFFull) << 51; }
-constexpr uint32_t HEAD_EPOCH = 4;   // u32 index of the u64 epoch word in head[]
-// End-of-call words (u64 indices in head[], bytes 512..576), zeroed at
-// allocation and reset by the workgroup that finishes the call: workgroups
-// done, hand-overs that need the repair walk, frames of all items, and the
-// final chain state of the item whose chain reached the batch end.
-constexpr uint32_t HW_DONE = 64, HW_BAD = 65, HW_TOTAL = 66, HW_FINAL = 67;
-// descriptor emission: non-zero when the frame-start lists cannot be used (a
-// region overflowed, or a repaired hand-over changed the plan) and
-// k_stream_emit re-walks the chains instead
-constexpr uint32_t HW_EMIT_SLOW = 73;
-// ...copied by finish_call for k_stream_emit (and reset there)
-constexpr uint32_t HW_EMIT_FLAG = 74;
-// decoder choice (stream_decode_fused): the largest and (complemented) the
-// smallest size of the last frame of every run / segment exit of the call,
-// published by the finisher into the context's host-visible policy slot
-constexpr uint32_t HW_FSMAX = 75, HW_FSMIN = 76;
 
 XYWS_DEV void granule_store(uint64_t* g, uint64_t a, uint64_t b) {
   const u32x4 v = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
@@ -257,8 +220,7 @@ struct run_params {
   uint64_t* nframes;
   uint64_t* rec;          // R_WORDS per flat index
   uint64_t* flags;        // per flat index: entry granule (2 x u64, see flag_claimed)
-  uint32_t* head;         // [0] ticket, [1] error word, [2..3] u64 total, [4..5] u64 epoch;
-                          // [16..32) carry snapshot; stats at [32..)
+  uint32_t* head;         // the run scratch head (HEAD_*, HW_*: xyws_stream.h; the accessors below)
   uint32_t opts;
   // descriptors requested: the starts of the frames each item (run or piece)
   // finds, in chain order, in its own region of rcap entries (fst + item *
@@ -335,17 +297,18 @@ XYWS_DEV uint64_t st_load(const uint64_t* p) {
   return __hip_atomic_load(const_cast<uint64_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 XYWS_DEV bool stats_on(const run_params& P) { return (P.opts & XYWS_OPT_STATS) != 0; }
-enum { ST_RUNS = 0, ST_NONE, ST_BAD, ST_REPAIR, ST_CUT, ST_SPIN, ST_SEGS, ST_FRAMES,
-       ST_P_WIN, ST_P_CAND, ST_P_UND, ST_P_TCOMP, ST_P_TCHECK, ST_P_TRES, ST_D_TENT, ST_D_TCHASE,
-       ST_T_PRO = 16, ST_T_MAIN, ST_T_WAIT, ST_T_FILL, ST_T_CHASE, ST_T_XOR, ST_T_TAIL, ST_T_PF, ST_T_CP,
-       ST_P_FILL, ST_P_SCAN, ST_P_PUB, ST_D_NOENT, ST_D_CHASE, ST_D_MISMATCH, ST_D_OVF,
-       ST_GIVEUP = 32, ST_BRIDGE, ST_STEAL_REQ, ST_STEAL_ACC, ST_STEAL_SEGS, ST_D_TVAL, ST_T_ROWS, ST_T_SER,
-       ST_X_W0 = 41, ST_X_BITS = 42, ST_X_SURV = 43,  // entry scan (lane 0): window 0 to its check; the
-                            // rest's candidate bits (from the segment's start); its survivors loop
-       ST_T_STRIDE = 46,    // the run decoder's stride-pass time
-       ST_P_LATTICE = 40 }; // runs whose entry the lattice gave
+// The run scratch head (byte offsets HEAD_*, HW_*: xyws_stream.h).
+XYWS_DEV uint32_t* head_ticket(const run_params& P) { return P.head + HEAD_TICKET / 4; }
+XYWS_DEV uint32_t* head_error(const run_params& P) { return P.head + HEAD_ERROR / 4; }
+XYWS_DEV uint64_t* head_word(const run_params& P, uint32_t off) {  // HEAD_TOTAL, HEAD_EPOCH, an HW_* word
+  return reinterpret_cast<uint64_t*>(P.head + off / 4);
+}
+XYWS_DEV uint32_t* head_done(const run_params& P) { return P.head + HW_DONE / 4; }
+XYWS_DEV unsigned long long* head_stats(const run_params& P) {
+  return reinterpret_cast<unsigned long long*>(P.head + HEAD_STATS / 4);
+}
 XYWS_DEV void stat_add(const run_params& P, uint32_t i, uint64_t v) {
-  if (stats_on(P)) atomicAdd(reinterpret_cast<unsigned long long*>(P.head + 32) + i, (unsigned long long)v);
+  if (stats_on(P)) atomicAdd(head_stats(P) + i, (unsigned long long)v);
 }
 
 // The size of the frame a chain state last completed (H + P), for the
@@ -353,10 +316,9 @@ XYWS_DEV void stat_add(const run_params& P, uint32_t i, uint64_t v) {
 XYWS_DEV uint64_t last_frame_size(const cstate& S);
 // Lane 0 of a run or segment: fold a last-frame size into the call's min/max.
 XYWS_DEV void fs_note(const run_params& P, uint64_t fsmin, uint64_t fsmax) {
-  uint64_t* hw = reinterpret_cast<uint64_t*>(P.head);
   if (!fsmax) return;
-  __hip_atomic_fetch_max(hw + HW_FSMAX, fsmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_fetch_max(hw + HW_FSMIN, ~fsmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_fetch_max(head_word(P, HW_FSMAX), fsmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_fetch_max(head_word(P, HW_FSMIN), ~fsmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // The device-resident copy of the decoder-choice words, written by the
 // workgroup finishing a call: bit 63 a call has finished, bits 48..55 its
@@ -367,30 +329,31 @@ XYWS_DEV void fs_note(const run_params& P, uint64_t fsmin, uint64_t fsmax) {
 // with its epoch, so its first-segment gate and its bail-out after an
 // irregular call follow the previous call in the stream, not the host's view
 // of the pinned words (which lags by the calls in flight).
-enum : uint64_t { DEC_RUNS = 0, DEC_RUNS512 = 2, DEC_LATTICE = 3 };
-constexpr uint32_t HW_DPOL = 77;
-constexpr uint32_t LW_DPOL_WORD = 6;  // (= LW_DPOL, xyws_lattice.h)
 XYWS_DEV void dpol_publish(const run_params& P, uint64_t F, uint64_t decoder) {
   const uint64_t f = F < (1ull << 48) ? F : 0;
   const uint64_t v = (1ull << 63) | (decoder << 48) | f;
-  st_store(reinterpret_cast<uint64_t*>(P.head) + HW_DPOL, v);
-  if (P.lat) st_store(P.lat + LW_DPOL_WORD, v);
+  st_store(head_word(P, HW_DPOL), v);
+  if (P.lat) st_store(P.lat + LW_DPOL, v);
 }
 // The finisher (lane 0): the call's frame-size range into the host-visible
-// policy slot {epoch, batch bytes, smallest, largest last-frame size, decoder}
-// (and its device copy) and the words reset for the next call. Host memory:
-// system-scope stores.
+// policy slot (the POL_* words, the epoch last, and their device copy) and
+// the words reset for the next call. Host memory: system-scope stores.
 XYWS_DEV void pol_publish(const run_params& P, uint64_t E, uint64_t decoder) {
-  uint64_t* hw = reinterpret_cast<uint64_t*>(P.head);
-  const uint64_t mx = st_load(hw + HW_FSMAX), mn = ~st_load(hw + HW_FSMIN);
-  st_store(hw + HW_FSMAX, 0);
-  st_store(hw + HW_FSMIN, 0);
+  const uint64_t mx = st_load(head_word(P, HW_FSMAX)), mn = ~st_load(head_word(P, HW_FSMIN));
+  st_store(head_word(P, HW_FSMAX), 0);
+  st_store(head_word(P, HW_FSMIN), 0);
   dpol_publish(P, mx && mn == mx ? mx : 0, decoder);
   if (!P.pol) return;
-  const uint64_t v[5] = {E, P.hi - P.lo, mx ? mn : 0, mx, decoder};
+  uint64_t v[POL_WORDS];
+  v[POL_EPOCH] = E;
+  v[POL_BYTES] = P.hi - P.lo;
+  v[POL_FSMIN] = mx ? mn : 0;
+  v[POL_FSMAX] = mx;
+  v[POL_DECODER] = decoder;
 #pragma unroll
-  for (int i = 1; i < 5; i++) __hip_atomic_store(P.pol + i, v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(P.pol, v[0], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  for (int i = 0; i < POL_WORDS; i++)
+    if (i != POL_EPOCH) __hip_atomic_store(P.pol + i, v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(P.pol + POL_EPOCH, v[POL_EPOCH], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 XYWS_DEV uint32_t clamp_rel(uint64_t x, uint64_t ss) {
@@ -730,7 +693,7 @@ XYWS_DEV bool parse_rel(const lds_t<G>& L, uint32_t x, uint32_t& hl, uint32_t& p
 // appended to the item's region. An overflow switches the emission to the
 // chain re-walk.
 XYWS_DEV void flag_emit_slow(const run_params& P) {
-  __hip_atomic_fetch_or(reinterpret_cast<uint64_t*>(P.head) + HW_EMIT_SLOW, 1ull, __ATOMIC_RELAXED,
+  __hip_atomic_fetch_or(head_word(P, HW_EMIT_SLOW), 1ull, __ATOMIC_RELAXED,
                         __HIP_MEMORY_SCOPE_AGENT);
 }
 template <class G>
@@ -1342,7 +1305,7 @@ XYWS_DEV bool wait_published(const run_params& P, uint32_t j, uint64_t E, uint64
   }
   if (it) stat_add(P, ST_SPIN, it);
   if (a != want) {
-    atomicOr(P.head + 1, 2u);
+    atomicOr(head_error(P), DERR_TIMEOUT);
     return false;
   }
   return true;
@@ -1377,7 +1340,7 @@ XYWS_DEV uint32_t lookup_successor(const run_params& P, lds_t<G>& L, uint64_t& h
       const bool test = (P.opts & XYWS_OPT_TEST_GIVEUP) && ((self >> 1) & 1u) && !(self & 1);
       if (test || (a >> 1) < E || (a != flag_published(E) && !wait_published(P, (uint32_t)j, E, a, b)) ||
           (b & (0x1FFFull << 51)) != granule_tag(E)) {
-        if (a == flag_published(E) && (b & (0x1FFFull << 51)) != granule_tag(E)) atomicOr(P.head + 1, 8u);
+        if (a == flag_published(E) && (b & (0x1FFFull << 51)) != granule_tag(E)) atomicOr(head_error(P), DERR_TAG);
         succ = j;
         return LK_GIVEUP;
       }
@@ -1429,7 +1392,7 @@ XYWS_DEV void answer_split(const run_params& P, lds_t<G>& L, uint64_t ss, uint64
   const uint64_t i = (ss - L.rs) / G::SEG, nseg = (rend - L.rs + G::SEG - 1) / G::SEG;
   const uint64_t m = nseg > i ? nseg - i : 0;
   const uint64_t e = i + 2 + (m > 3 ? (m - 3) / 2 : 0);
-  const uint64_t minp = (P.opts & XYWS_OPT_TEST_STEAL) ? 1 : XYWS_STEAL_MIN_PIECE;
+  const uint64_t minp = (P.opts & XYWS_OPT_TEST_STEAL) ? 1 : STEAL_MIN_PIECE;
   if (!L.known && e + minp <= nseg && e < (1u << 22)) {
     L.split_e = e;
     L.rng_end = L.rs + e * G::SEG;
@@ -2149,7 +2112,7 @@ XYWS_DEV void prologue(const run_params& P, lds_t<G>& L, seg_io<G>& io, uint32_t
 // assembled in 64-bit words (no byte array: nothing goes to scratch).
 XYWS_DEV void write_outputs(const run_params& P, const xyws_carry* cin, uint64_t total, const cstate& o) {
   if (P.nframes) *P.nframes = total + P.tbias;  // (tbias: frames the lattice decoder decoded before a redirect)
-  __hip_atomic_store(reinterpret_cast<uint64_t*>(P.head + 2), total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(head_word(P, HEAD_TOTAL), total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (!P.cout) return;
   const uint64_t lo = P.lo, hi = P.hi;
   uint64_t pr = 0, ph = 0, key = 0, hl = 0, h0 = 0, h1 = 0;  // h0/h1: header bytes 0..7 / 8..13
@@ -2233,7 +2196,7 @@ XYWS_DEV void finish_fast(const run_params& P, lds_t<G>& L, uint32_t tid) {
   auto load_rec = [&](uint32_t r, rec_t& x) {
     const uint64_t* rec = P.rec + (uint64_t)r * R_WORDS;
     x.cw = st_load(rec + R_CNT);
-    x.okw = st_load(rec + R_OK);
+    x.okw = st_load(rec + R_OKW);
     x.ep = st_load(rec + R_EP);
     x.hn = st_load(rec + R_HN);
     x.fs = get_state(rec + R_F0);
@@ -2243,7 +2206,7 @@ XYWS_DEV void finish_fast(const run_params& P, lds_t<G>& L, uint32_t tid) {
   // interleaved, each would wait for the ones before it)
   uint64_t c[9];
   if (tid == 0) {
-    c[8] = st_load(reinterpret_cast<const uint64_t*>(P.head + HEAD_EPOCH));
+    c[8] = st_load(head_word(P, HEAD_EPOCH));
 #pragma unroll
     for (int i = 0; i < 8; i++) c[i] = st_load(reinterpret_cast<const uint64_t*>(P.cin) + i);
   }
@@ -2315,7 +2278,7 @@ XYWS_DEV void finish_fast(const run_params& P, lds_t<G>& L, uint32_t tid) {
   }
   // a record not written by this call: a run did not complete (reported; the
   // outputs of this call are invalid)
-  if (__syncthreads_or(stale) && tid == 0) atomicOr(P.head + 1, 4u);
+  if (__syncthreads_or(stale) && tid == 0) atomicOr(head_error(P), DERR_STALE);
   const bool any_bad = __syncthreads_or(bad);
   if (tid == 0) L.aux1 = 0;
   __syncthreads();
@@ -2360,7 +2323,7 @@ XYWS_DEV void decode_range(const run_params& P, lds_t<G>& L, seg_io<G>& io, uint
     }
     uint64_t* rec = P.rec + L.self * R_WORDS;
     const bool ok = !L.tmo && (L.succ >= P.nflat || (L.past && L.ok));
-    st_store(rec + R_OK, (ok ? OK_BIT : 0) | (L.tmo ? TMO_BIT : 0) | ((uint64_t)L.succ << 32));
+    st_store(rec + R_OKW, (ok ? OK_BIT : 0) | (L.tmo ? TMO_BIT : 0) | ((uint64_t)L.succ << 32));
     st_store(rec + R_HN, L.hn);
     st_store(rec + R_WN, L.Wn);
     st_store(rec + R_CNT, L.cnt);
@@ -2371,10 +2334,9 @@ XYWS_DEV void decode_range(const run_params& P, lds_t<G>& L, seg_io<G>& io, uint
     if (P.fst) st_store(rec + R_NREC, L.nrec);
     // what the workgroup finishing the call needs when every hand-over is
     // good: the frame total and the final state (the item without successor)
-    uint64_t* hw = reinterpret_cast<uint64_t*>(P.head);
-    if (!ok) __hip_atomic_fetch_or(hw + HW_BAD, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (L.cnt) __hip_atomic_fetch_add(hw + HW_TOTAL, L.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (ok && L.succ >= P.nflat) put_state(hw + HW_FINAL, L.S);
+    if (!ok) __hip_atomic_fetch_or(head_word(P, HW_BAD), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (L.cnt) __hip_atomic_fetch_add(head_word(P, HW_TOTAL), L.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (ok && L.succ >= P.nflat) put_state(head_word(P, HW_FINAL), L.S);
     if (L.cnt) {
       const uint64_t fs = last_frame_size(L.S);
       fs_note(P, fs, fs);
@@ -2395,7 +2357,7 @@ XYWS_DEV void decode_range(const run_params& P, lds_t<G>& L, seg_io<G>& io, uint
 template <class G>
 XYWS_DEV uint32_t steal_piece(const run_params& P, lds_t<G>& L, uint32_t tid) {
   const uint64_t E = L.E;
-  const uint64_t min_left = (P.opts & XYWS_OPT_TEST_STEAL) ? 3 : XYWS_STEAL_MIN_LEFT;
+  const uint64_t min_left = (P.opts & XYWS_OPT_TEST_STEAL) ? 3 : STEAL_MIN_LEFT;
   for (uint32_t attempt = 0; attempt < 2 * P.nruns; attempt++) {
     if (tid == 0) L.aux0 = 0;
     __syncthreads();
@@ -2432,7 +2394,7 @@ XYWS_DEV uint32_t steal_piece(const run_params& P, lds_t<G>& L, uint32_t tid) {
           L.act = 1;
           L.aux1 = split_seg(w);
         } else if (split_is(w, E, SP_REQ)) {
-          atomicOr(P.head + 1, 2u);  // (bounded wait timed out: reported, the run is left alone)
+          atomicOr(head_error(P), DERR_TIMEOUT);  // (bounded wait timed out: reported, the run is left alone)
         }
       }
     }
@@ -2458,8 +2420,8 @@ __global__ void __launch_bounds__(G::NT, G::WPE) k_stream_runs(run_params P0) {
   if (!lat_redirect(P)) return;
   const uint32_t tid0 = threadIdx.x, tid = tid0;
   if (tid == 0) {
-    L.ticket = atomicAdd(P.head, 1u);
-    L.E = st_load(reinterpret_cast<const uint64_t*>(P.head + HEAD_EPOCH)) + 1;
+    L.ticket = atomicAdd(head_ticket(P), 1u);
+    L.E = st_load(head_word(P, HEAD_EPOCH)) + 1;
   }
   __syncthreads();
   const uint32_t run = uniform32(L.ticket);
@@ -2588,7 +2550,7 @@ __global__ void __launch_bounds__(G::NT, G::WPE) k_stream_runs(run_params P0) {
   if (tid0 == 0) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the flag must not overtake the write-back)
-    const uint32_t last = atomicAdd(P.head + 2 * HW_DONE, 1u) + 1 == P.nruns ? 1u : 0u;
+    const uint32_t last = atomicAdd(head_done(P), 1u) + 1 == P.nruns ? 1u : 0u;
     if (last) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2612,7 +2574,7 @@ XYWS_DEV uint64_t next_visible(const run_params& P, uint64_t r) {
 // is the one its chain landed on.
 XYWS_DEV void load_piece(const run_params& P, walk_t& w, uint64_t r) {
   const uint64_t* rec = P.rec + r * R_WORDS;
-  const uint64_t okw = st_load(rec + R_OK);
+  const uint64_t okw = st_load(rec + R_OKW);
   w.r = r;
   w.efrom = st_load(rec + R_H);
   w.ecarry = r == 0 ? 1u : 0u;
@@ -2692,7 +2654,7 @@ XYWS_DEV void finish_walk(const run_params& P, lds_t<G>& L, uint32_t tid) {
           stat_add(P, ST_REPAIR, 1);
           w.act = 2;
           const uint64_t* rs = P.rec + w.succ * R_WORDS;
-          chain_start(L, get_state(rs + R_S0), st_load(rs + R_HN), st_load(rs + R_WN), st_load(rs + R_OK) >> 32);
+          chain_start(L, get_state(rs + R_S0), st_load(rs + R_HN), st_load(rs + R_WN), st_load(rs + R_OKW) >> 32);
         }
       }
     }
@@ -2741,7 +2703,7 @@ XYWS_DEV void finish_walk(const run_params& P, lds_t<G>& L, uint32_t tid) {
     __syncthreads();
     if (tid == 0) {
       walk_t& w = L.wk;
-      const uint64_t ws = st_load(rs + R_OK);
+      const uint64_t ws = st_load(rs + R_OKW);
       w.efrom = w.first != NONE ? w.first : w.F.X;
       w.cnt = w.tail + L.cnt;
       w.r = sj;
@@ -2774,9 +2736,8 @@ XYWS_DEV void finish_walk(const run_params& P, lds_t<G>& L, uint32_t tid) {
 // ISA, and the private segment is ~190 B, in the prologue and this path)
 template <class G>
 __device__ __attribute__((always_inline)) inline void finish_call(run_params P, lds_t<G>& L, uint32_t tid) {
-  uint64_t* hw = reinterpret_cast<uint64_t*>(P.head);
   if (tid == 0) {
-    const uint64_t bad = st_load(hw + HW_BAD);
+    const uint64_t bad = st_load(head_word(P, HW_BAD));
     L.act = (bad || (P.frames && P.cap)) ? 1u : 0u;
   }
   __syncthreads();
@@ -2791,8 +2752,8 @@ __device__ __attribute__((always_inline)) inline void finish_call(run_params P, 
     uint64_t c[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) c[i] = st_load(reinterpret_cast<const uint64_t*>(P.cin) + i);
-    const uint64_t total = st_load(hw + HW_TOTAL);
-    const cstate S = get_state(hw + HW_FINAL);
+    const uint64_t total = st_load(head_word(P, HW_TOTAL));
+    const cstate S = get_state(head_word(P, HW_FINAL));
 #pragma unroll
     for (int i = 0; i < 8; i++) reinterpret_cast<uint64_t*>(&L.cinc)[i] = c[i];
     write_outputs(P, &L.cinc, total, S);
@@ -2801,17 +2762,17 @@ __device__ __attribute__((always_inline)) inline void finish_call(run_params P, 
     if (P.fst) {
       // the frame-start lists stand unless they overflowed or a repair changed
       // the plan (k_stream_emit then re-walks the chains)
-      st_store(hw + HW_EMIT_FLAG, (walked || st_load(hw + HW_EMIT_SLOW)) ? 1u : 0u);
-      st_store(hw + HW_EMIT_SLOW, 0);
+      st_store(head_word(P, HW_EMIT_FLAG), (walked || st_load(head_word(P, HW_EMIT_SLOW))) ? 1u : 0u);
+      st_store(head_word(P, HW_EMIT_SLOW), 0);
     }
     pol_publish(P, L.E, G::NT == 512 ? DEC_RUNS512 : DEC_RUNS);
-    st_store(hw + HW_BAD, 0);
-    st_store(hw + HW_TOTAL, 0);
-    st_store(hw + HW_DONE, 0);
+    st_store(head_word(P, HW_BAD), 0);
+    st_store(head_word(P, HW_TOTAL), 0);
+    st_store(head_word(P, HW_DONE), 0);
     // the ticket starts the next call at zero; the epoch word advances (this
     // call's entry granules read as stale from now on)
-    __hip_atomic_store(P.head, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    st_store(reinterpret_cast<uint64_t*>(P.head + HEAD_EPOCH), L.E);
+    __hip_atomic_store(head_ticket(P), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    st_store(head_word(P, HEAD_EPOCH), L.E);
   }
 }
 
@@ -2845,7 +2806,7 @@ __global__ void __launch_bounds__(256) k_stream_emit(run_params P0) {
   if (n == 0 || ord >= P.cap) return;
   const uint64_t end = ord + n < P.cap ? ord + n : P.cap;
   const bool ecarry = st_load(rec + R_ECARRY) != 0;
-  const bool slow = st_load(reinterpret_cast<const uint64_t*>(P.head) + HW_EMIT_FLAG) != 0;
+  const bool slow = st_load(head_word(P, HW_EMIT_FLAG)) != 0;
   uint64_t o = ord, X = st_load(rec + R_EFROM);
   if (ecarry) {  // run 0: the carried-header frame comes first
     X = P.lo;
@@ -2895,9 +2856,6 @@ __global__ void k_stream_empty(const xyws_carry* cin, xyws_carry* cout, uint64_t
 
 #include "xyws_lattice.h"
 
-constexpr uint64_t HEAD_BYTES = 1024;  // u32 [0] ticket, [1] error, [2..3] total, [4..5] epoch; bytes [64..128) carry,
-                                       // [128..512) stats, [512..576) end-of-call words (HW_*)
-
 // hipFuncSetAttribute applies to the current device: once per (device,
 // geometry), under a lock (one process may drive several devices from several
 // threads). One lds_once per kernel.
@@ -2939,6 +2897,7 @@ int launch_lattice(const run_params& P, uint32_t grid, hipStream_t stream) {
 
 void stream_scratch_init(stream_scratch* s, int device) {
   void* ph = nullptr;
+  static_assert(8 * POL_WORDS <= 64, "the pinned policy words");
   if (hipHostMalloc(&ph, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
     void* pd = nullptr;
     memset(ph, 0, 64);
@@ -2963,22 +2922,11 @@ void stream_scratch_free(stream_scratch* s) {
   s->desc.release();
 }
 
-// Run scratch layout for up to `runs` runs (2 * runs flat indices):
-//   head | entry granules (16 B per flat index) | split words (16 B per run) |
-//   progress words (8 B per run) | records (R_WORDS x 8 B per flat index)
-// Everything up to the records is zeroed at allocation (epoch 0: stale).
-static uint64_t granules_bytes(uint64_t runs) { return (32 * runs + 255) & ~255ull; }
-static uint64_t split_bytes(uint64_t runs) { return (16 * runs + 255) & ~255ull; }
-static uint64_t prog_bytes(uint64_t runs) { return (8 * runs + 255) & ~255ull; }
-static uint64_t records_off(uint64_t runs) {
-  return HEAD_BYTES + granules_bytes(runs) + split_bytes(runs) + prog_bytes(runs);
-}
-
 int reserve_for(stream_scratch* s, const scratch_need& need, bool capturing) {
   if (need.runs) {
     const uint64_t want = need.runs < SCRATCH_MIN_RUNS ? SCRATCH_MIN_RUNS : need.runs;
-    const uint64_t bytes = records_off(want) + 2 * want * R_WORDS * 8;
-    if (const int rc = s->runs.grow(want, bytes, records_off(want), capturing)) return rc;
+    const run_layout l = run_layout_of(want);
+    if (const int rc = s->runs.grow(want, l.total, l.zeroed, capturing)) return rc;
   }
   // Frame-start lists for descriptor emission: one region per flat item.
   if (need.fmem_bytes)
@@ -3005,14 +2953,14 @@ int stream_scratch_unmask_counter(stream_scratch* s, bool capturing, uint32_t** 
 int stream_scratch_stats(stream_scratch* s, uint64_t out[XYWS_NSTATS]) {
   if (!s->runs.mem) return XYWS_ERR_INVALID;
   if (hipDeviceSynchronize() != hipSuccess) return XYWS_ERR_HIP;
-  return hipMemcpy(out, static_cast<uint8_t*>(s->runs.mem) + 128, 8 * XYWS_NSTATS, hipMemcpyDeviceToHost) == hipSuccess
+  return hipMemcpy(out, static_cast<uint8_t*>(s->runs.mem) + HEAD_STATS, 8 * XYWS_NSTATS, hipMemcpyDeviceToHost) == hipSuccess
              ? XYWS_OK : XYWS_ERR_HIP;
 }
 
 int stream_scratch_lattice(stream_scratch* s, uint64_t out[5]) {
   for (int i = 0; i < 5; i++) out[i] = 0;
   if (hipDeviceSynchronize() != hipSuccess) return XYWS_ERR_HIP;
-  if (s->runs.mem && hipMemcpy(out, static_cast<uint8_t*>(s->runs.mem) + 8 * HW_DPOL, 8, hipMemcpyDeviceToHost) != hipSuccess)
+  if (s->runs.mem && hipMemcpy(out, static_cast<uint8_t*>(s->runs.mem) + HW_DPOL, 8, hipMemcpyDeviceToHost) != hipSuccess)
     return XYWS_ERR_HIP;
   if (s->lat.mem) {
     const uint32_t w[4] = {LW_NBAIL_POL, LW_NBAIL_HYP, LW_NLOOP_A, LW_NLOOP_B};
@@ -3027,22 +2975,23 @@ int64_t stream_scratch_records(stream_scratch* s, uint64_t* out, uint64_t max_re
   if (!s->runs.mem) return XYWS_ERR_INVALID;
   if (hipDeviceSynchronize() != hipSuccess) return XYWS_ERR_HIP;
   const uint64_t n = max_recs < 2 * s->runs.units ? max_recs : 2 * s->runs.units;
-  const uint8_t* rec = static_cast<const uint8_t*>(s->runs.mem) + records_off(s->runs.units);
+  const uint8_t* rec = static_cast<const uint8_t*>(s->runs.mem) + run_layout_of(s->runs.units).records;
   return hipMemcpy(out, rec, n * R_WORDS * 8, hipMemcpyDeviceToHost) == hipSuccess ? (int64_t)n : XYWS_ERR_HIP;
 }
 
 uint32_t stream_scratch_error(stream_scratch* s, bool clear) {
   if (!s->runs.mem) return 0;
-  uint32_t v[2] = {0, 0};
-  if (hipMemcpy(v, s->runs.mem, 8, hipMemcpyDeviceToHost) != hipSuccess) return 0xFFFFFFFFu;
-  if (clear && v[1] && xyws_internal::zero_now(static_cast<uint8_t*>(s->runs.mem) + 4, 4) != hipSuccess) return 0xFFFFFFFFu;
-  return v[1];
+  uint8_t* err = static_cast<uint8_t*>(s->runs.mem) + HEAD_ERROR;
+  uint32_t v = 0;
+  if (hipMemcpy(&v, err, 4, hipMemcpyDeviceToHost) != hipSuccess) return 0xFFFFFFFFu;
+  if (clear && v && xyws_internal::zero_now(err, 4) != hipSuccess) return 0xFFFFFFFFu;
+  return v;
 }
 
 // The only reader of the pinned policy words on the decode path.
 policy_view policy_snapshot(const stream_scratch* s) {
   if (!s->pol_h) return policy_view{false, 0, 0, 0};
-  return policy_view{true, s->pol_h[0], s->pol_h[2], s->pol_h[3]};
+  return policy_view{true, s->pol_h[POL_EPOCH], s->pol_h[POL_FSMIN], s->pol_h[POL_FSMAX]};
 }
 
 // The run decoder's geometry, by the previous call's statistics: regular frames under
@@ -3180,25 +3129,26 @@ int launch_plan(const stream_scratch* s, const decode_plan& pl, uint8_t* base, c
     return hipGetLastError() == hipSuccess ? XYWS_OK : XYWS_ERR_HIP;
   }
   uint8_t* m = static_cast<uint8_t*>(s->runs.mem);
+  const run_layout l = run_layout_of(s->runs.units);
   run_params P;
   P.base = base; P.lo = pl.lo; P.hi = pl.hi; P.rbytes = pl.rbytes;
   P.nruns = (uint32_t)pl.nruns;
   P.cout = cout; P.frames = frames; P.cap = cap; P.nframes = nframes;
   P.head = reinterpret_cast<uint32_t*>(m);
   P.nflat = pl.nflat;
-  P.flags = reinterpret_cast<uint64_t*>(m + HEAD_BYTES);
-  P.split = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->runs.units));
-  P.prog = reinterpret_cast<uint64_t*>(m + HEAD_BYTES + granules_bytes(s->runs.units) + split_bytes(s->runs.units));
-  P.rec = reinterpret_cast<uint64_t*>(m + records_off(s->runs.units));
+  P.flags = reinterpret_cast<uint64_t*>(m + l.granules);
+  P.split = reinterpret_cast<uint64_t*>(m + l.split);
+  P.prog = reinterpret_cast<uint64_t*>(m + l.prog);
+  P.rec = reinterpret_cast<uint64_t*>(m + l.records);
   P.opts = pl.opts;
   // The ticket is zero here (zeroed at allocation, reset by finish_call
   // after every call); granules, split and progress words carry the epoch of
-  // the call that wrote them; the error word [1] is sticky until read back.
+  // the call that wrote them; the error word is sticky until read back.
   // Run 0 snapshots the incoming carry into scratch.
-  if ((pl.opts & XYWS_OPT_STATS) && hipMemsetAsync(m + 128, 0, 8 * XYWS_NSTATS, stream) != hipSuccess)
+  if ((pl.opts & XYWS_OPT_STATS) && hipMemsetAsync(m + HEAD_STATS, 0, 8 * XYWS_NSTATS, stream) != hipSuccess)
     return XYWS_ERR_HIP;
   P.cin_user = cin;
-  P.cin = reinterpret_cast<xyws_carry*>(m + 64);
+  P.cin = reinterpret_cast<xyws_carry*>(m + HEAD_CARRY);
   P.fst = pl.rcap ? static_cast<uint64_t*>(s->desc.mem) : nullptr;
   P.rcap = pl.rcap;
   P.pol = s->pol_d;
