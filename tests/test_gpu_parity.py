@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+import history
 import streams
 from xynet_amd._lib import (DEC_LATTICE, POL_DECODER, POL_WORDS, OPT_BIGSCAN, OPT_LATTICE, OPT_NO_LATDEC, OPT_STEAL, OPT_TEST_GIVEUP, OPT_TEST_STEAL,
                             OPT_UNMASKED_HINT, OPT_WG256, OPT_WG512)
@@ -181,22 +182,7 @@ def test_dense_frames_with_header_like_payloads(ws, oracle, fake, mode):
     and the sequential repair of the dense pass runs (the one-pass entry
     scans: chains of fake headers carried from segment to segment). GPU vs
     oracle: bytes, count, descriptors."""
-    rng = streams.SplitMix(0xDE5E + fake)
-    out = bytearray()
-    while len(out) < (3 << 20):
-        plen = 120 + rng.below(400)
-        key = rng.bytes(4)
-        if fake == 0:
-            wire = rng.bytes(plen)
-        else:
-            # fake 7-byte frames (FIN binary, masked, 1-byte payload) or, for
-            # fake == 2, fake 126-form frames that jump within the segment
-            unit = (bytes([0x82, 0x81]) + rng.bytes(5)) if fake == 1 else \
-                (bytes([0x82, 0xFE, 0x00, 0x40]) + rng.bytes(4) + rng.bytes(64))
-            off = rng.below(len(unit))
-            wire = (rng.bytes(off) + unit * (plen // len(unit) + 2))[:plen]
-        out += streams.header(0x82, plen, key, None) + wire
-    src = bytes(out)
+    src = history.header_like_dense(fake)
     view, _ = dev_bytes(src)
     dec = ws.frame_decoder(**MODES[mode])
     ob = np.frombuffer(src, np.uint8).copy()
@@ -219,38 +205,7 @@ def test_stride_pass_adversarial(ws, oracle, mode, kind):
     every few frames, 126/127-form lengths and 2^31+ lengths in a run,
     and runs crossing segment ends / the batch end. GPU vs oracle: bytes,
     count, descriptors, carry."""
-    rng = streams.SplitMix(0x57D1 + len(kind))
-    out = bytearray()
-    target = 3 << 20 if mode in ("fused", "bigscan") else 200000
-    while len(out) < target:
-        if kind == "stride_fakes":
-            plen = 100 + rng.below(300)
-            # the payload: valid headers of frames of exactly `size` bytes at every
-            # offset d, d + size, ... from a random d (fake starts on a shifted lattice)
-            fake = streams.header(0x82, plen, rng.bytes(4), None)
-            size = len(fake) + plen
-            d = 1 + rng.below(size - 1)
-            body = bytearray(rng.bytes(plen))
-            for o in range(d % size, plen - len(fake), size):
-                body[o:o + len(fake)] = fake
-            for _ in range(1 + rng.below(40)):
-                out += streams.header(0x82, plen, rng.bytes(4), None) + bytes(body)
-        elif kind == "size_changes":
-            plen = rng.below(600)
-            for _ in range(1 + rng.below(6)):
-                out += streams.frame(rng, 0x82, plen)
-        elif kind == "long_lengths":
-            for _ in range(1 + rng.below(20)):
-                out += streams.frame(rng, 0x81, 126 + rng.below(2))  # 126 form at the 7-bit edge
-            out += streams.frame(rng, 0x82, 65536 + rng.below(3))    # 127 form
-            if rng.below(8) == 0:
-                out += streams.header(0x82, (1 << 31) + rng.below(5), rng.bytes(4), None)  # runs past the end
-                break
-        else:  # equal frames whose headers straddle 1 KiB and 128 KiB boundaries
-            plen = 1024 - 8 - rng.below(24)
-            for _ in range(1 + rng.below(200)):
-                out += streams.frame(rng, 0x82, plen)
-    src = bytes(out)
+    src = history.adversarial_stream(kind, 3 << 20 if mode in ("fused", "bigscan") else 200000)
     for cut in (len(src), len(src) - 5, len(src) - 1000):
         piece = src[:cut]
         view, _ = dev_bytes(piece)
