@@ -258,6 +258,55 @@ class Oracle:
         nm = self.L.oracle_reassemble(_ptr(src), src.size, fr, n, opts, _ptr(out), cap, msgs, cap_m)
         return out, [msgs[i] for i in range(nm)]
 
+    # --- the same three C functions on numpy arrays (tables of 10^5 frames:
+    # no per-element ctypes copies). table: uint8, n * 32 bytes (xyws_frame).
+    @staticmethod
+    def _table(table):
+        t = np.ascontiguousarray(table, dtype=np.uint8).reshape(-1)
+        assert t.size % 32 == 0
+        return t, t.size // 32
+
+    def encode_frames_raw(self, src: np.ndarray, table, flags, enc_opts=0, keys=None, verdicts=None,
+                          action_mask=0, out_cap=None):
+        """(reply bytes uint8[min(cap, total)], offsets uint64[n + 1], total).
+        keys: uint8[4 n] or None; verdicts: uint8[8 n] (xyws_verdict) or None."""
+        t, n = self._table(table)
+        kb = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint8)
+        vd = None if verdicts is None else np.ascontiguousarray(verdicts, dtype=np.uint8)
+        assert kb is None or kb.size >= 4 * n
+        assert vd is None or vd.size >= 8 * n
+        offs = np.zeros(n + 1, np.uint64)
+        total = self.L.oracle_encode_frames(_ptr(src), src.size, _ptr(t), n, flags, enc_opts, _ptr(kb), _ptr(vd),
+                                            action_mask, None, 0, _ptr(offs))
+        cap = total if out_cap is None else out_cap
+        out = np.zeros(max(cap, 1), np.uint8)
+        self.L.oracle_encode_frames(_ptr(src), src.size, _ptr(t), n, flags, enc_opts, _ptr(kb), _ptr(vd),
+                                    action_mask, _ptr(out), cap, _ptr(offs))
+        return out[:min(cap, total)], offs, total
+
+    def classify_raw(self, src: np.ndarray, table, max_payload, policy):
+        """(verdict records uint8[8 n], first close)."""
+        t, n = self._table(table)
+        out = np.zeros(8 * max(n, 1), np.uint8)
+        first = C.c_uint64()
+        self.L.oracle_classify(_ptr(src), src.size, _ptr(t), n, max_payload, policy, _ptr(out), C.byref(first))
+        return out[:8 * n], first.value
+
+    def reassemble_raw(self, src: np.ndarray, table, opts, out_cap=None, msg_cap=None):
+        """(gathered bytes uint8[cap], message records uint8[40 min(nm, msg_cap)],
+        message count). out_cap defaults to the data frames' payload bytes,
+        msg_cap to n."""
+        t, n = self._table(table)
+        if out_cap is None:
+            rec = t.reshape(n, 32)
+            data = (rec[:, 28] & 0x0F) <= 2
+            out_cap = int(rec[:, 16:24].copy().view(np.uint64).reshape(-1)[data].sum())
+        mcap = n if msg_cap is None else msg_cap
+        msgs = np.zeros(40 * max(mcap, 1), np.uint8)
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        nm = self.L.oracle_reassemble(_ptr(src), src.size, _ptr(t), n, opts, _ptr(out), out_cap, _ptr(msgs), mcap)
+        return out[:out_cap], msgs[:40 * min(nm, mcap)], nm
+
     def fill_uniform(self, nframes, plen, b0, seed) -> np.ndarray:
         H = 2 + (0 if plen < 126 else (2 if plen <= 0xFFFF else 8)) + 4
         buf = np.empty(nframes * (H + plen), np.uint8)

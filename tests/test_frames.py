@@ -13,6 +13,15 @@ builder is pinned by the reference's own header bytes (frame_header.json
 builds, tests/test_oracle.py); its UTF-8 check by Python's codec (below); the
 close policy restates websocket.h:81-108 (no reference test covers it:
 parity there is unpinned beyond that restatement).
+
+The streams here come frame by frame from msg_streams.py and stay below
+every size at which xyws_frames.hip changes path (one scan block, a few
+items per gather tile, a few dozen messages per UTF-8 tile). Those sizes
+(more than one scan block and more than FT of them, every gather route up to
+the per-byte path, UTF-8 tiles past UMS messages, long valid text, a
+misaligned output, dev_n, n = 0, the first close across blocks, a small call
+after a large one) are tested in tests/test_frames_scale.py on tables built by
+tests/op_tables.py.
 """
 import codecs
 import ctypes as C

@@ -397,13 +397,20 @@ def encode_frames(src, frames_t, n, flags, dev_n=None, enc_opts=0, keys=None, ve
     return out, olen
 
 
-def classify_frames(src, frames_t, n, max_payload, policy=0, dev_n=None):
+def classify_frames(src, frames_t, n, max_payload, policy=0, dev_n=None, verdicts=None):
     """websocket_check_parser_result per frame (xyws_classify_frames): returns
-    (verdicts tensor (n*8 bytes), first-close tensor)."""
+    (verdicts tensor (n*8 bytes), first-close tensor). verdicts: the caller's
+    device uint8 tensor for the records (n*8 bytes at least) instead of a
+    fresh zeroed one."""
     import torch
     t = _dev_u8(src)
     ctx = context(t.device.index)
-    verd = torch.zeros(max(n, 1) * 8, dtype=torch.uint8, device=t.device)
+    if verdicts is None:
+        verd = torch.zeros(max(n, 1) * 8, dtype=torch.uint8, device=t.device)
+    else:
+        verd = _dev_u8(verdicts)
+        if verd.numel() < n * 8:
+            raise XywsError(-1, "verdicts tensor smaller than n records")
     first = torch.zeros(1, dtype=torch.int64, device=t.device)
     check(ctx.L.xyws_classify_frames(ctx.h, C.c_void_p(t.data_ptr()), t.numel(), _opt_ptr(frames_t), n,
                                      _opt_ptr(dev_n), max_payload, policy, C.c_void_p(verd.data_ptr()),
@@ -411,16 +418,30 @@ def classify_frames(src, frames_t, n, max_payload, policy=0, dev_n=None):
     return verd, first
 
 
-def reassemble(src, frames_t, n, opts=0, out_cap=None, msg_cap=None, dev_n=None):
+def reassemble(src, frames_t, n, opts=0, out_cap=None, msg_cap=None, dev_n=None, out=None, msgs=None):
     """FIN=0 chains gathered into messages (xyws_reassemble): returns (out,
-    messages tensor (msg_cap*40 bytes), count tensor)."""
+    messages tensor (msg_cap*40 bytes), count tensor). out / msgs: the
+    caller's device uint8 tensors (out_cap defaults to out's size, msg_cap to
+    the records msgs holds) instead of fresh zeroed ones."""
     import torch
     t = _dev_u8(src)
     ctx = context(t.device.index)
-    cap = t.numel() if out_cap is None else out_cap
-    mcap = max(n, 1) if msg_cap is None else msg_cap
-    out = torch.zeros(max(cap, 1), dtype=torch.uint8, device=t.device)
-    msgs = torch.zeros(max(mcap, 1) * 40, dtype=torch.uint8, device=t.device)
+    if out is not None:
+        out = _dev_u8(out)
+        cap = out.numel() if out_cap is None else out_cap
+        if cap > out.numel():
+            raise XywsError(-1, "out_cap exceeds the out tensor")
+    else:
+        cap = t.numel() if out_cap is None else out_cap
+        out = torch.zeros(max(cap, 1), dtype=torch.uint8, device=t.device)
+    if msgs is not None:
+        msgs = _dev_u8(msgs)
+        mcap = msgs.numel() // 40 if msg_cap is None else msg_cap
+        if mcap * 40 > msgs.numel():
+            raise XywsError(-1, "msg_cap exceeds the msgs tensor")
+    else:
+        mcap = max(n, 1) if msg_cap is None else msg_cap
+        msgs = torch.zeros(max(mcap, 1) * 40, dtype=torch.uint8, device=t.device)
     cnt = torch.zeros(1, dtype=torch.int64, device=t.device)
     check(ctx.L.xyws_reassemble(ctx.h, C.c_void_p(t.data_ptr()), t.numel(), _opt_ptr(frames_t), n, _opt_ptr(dev_n),
                                 opts, C.c_void_p(out.data_ptr()), cap, C.c_void_p(msgs.data_ptr()), mcap,
