@@ -22,7 +22,10 @@
  *     example/websocket/websocket_echo.cpp:18-27
  *   websocket_check_parser_result (close policy)             xyws_classify_frames
  *     example/include/common/websocket.h:81-108
- *   (new) FIN=0 message reassembly + UTF-8 validation        xyws_reassemble
+ *   (new) FIN=0 message reassembly + UTF-8 validation        xyws_reassemble (one batch),
+ *                                                              xyws_reassemble_stream (messages, frames
+ *                                                              and UTF-8 sequences cut by a recv
+ *                                                              boundary, state in xyws_msg_carry)
  *   recv_all / io_service remote-queue eventfd               xyws_arena_* (pinned recv arena,
  *     include/xynet/socket/impl/recv_all.h:86-121              H2D -> decode -> D2H, completion
  *     include/xynet/io_service.h:362-381                       written to an eventfd)
@@ -370,6 +373,82 @@ int xyws_reassemble(xyws_ctx* ctx, const void* dev_src, uint64_t src_len,
                     const xyws_frame* dev_frames, uint64_t n, const uint64_t* dev_n, uint32_t opts,
                     void* dev_out, uint64_t out_cap, xyws_message* dev_msgs, uint64_t msg_cap,
                     uint64_t* dev_nmsgs, void* stream);
+
+/* ---- message reassembly across batch boundaries --------------------------
+ * xyws_reassemble for a stream cut at any point into batches: the frame table
+ * is the one xyws_decode_stream wrote for this same dev_src (unmasked, every
+ * frame of the batch, in order; frame_off < 0 allowed for the first frame),
+ * and xyws_msg_carry continues the open message, the frame cut by the batch
+ * end, pending orphans and a cut UTF-8 sequence into the next call. Both
+ * carries are device pointers; dev_mc_in NULL = a fresh stream; dev_mc_in may
+ * equal dev_mc_out. Asynchronous, no host read of device state; scratch and
+ * the capture rule are xyws_reassemble's.
+ *
+ * Bytes. The first min(mc_in.frame_remaining, src_len) bytes of dev_src are
+ * the rest of the frame the previous batch end cut: they join the open
+ * message when frame_member is set and are skipped otherwise. A frame's
+ * payload contributes the bytes that lie in this batch,
+ * min(payload_len, src_len - payload_off) (only the last frame can be
+ * clipped; the missing part becomes mc_out.frame_remaining). Clipping never
+ * sets DERR_SRC_OOB. Everything goes to dev_out back to back in stream order.
+ *
+ * Records. With a message open in mc_in, record 0 is always its continuation
+ * (also with no bytes and no frames): XYWS_MSG_CONTINUED, first_frame =
+ * XYWS_NPOS, nframes = its data frames with a descriptor in this table,
+ * length = the bytes this call delivered, out_off 0, opcode and the sticky
+ * bits (UTF8_BAD, UNCHECKED) from the carry. Every other record is
+ * xyws_reassemble's for this table (first_frame an index into it). COMPLETE
+ * is reported by the call that delivers the message's LAST BYTE: when the FIN
+ * fragment's descriptor is in the table but its payload is cut, the message
+ * stays open in mc_out (status has XYWS_MSG_COMPLETE there: "closing") and
+ * the call that delivers the last of frame_remaining emits CONTINUED|COMPLETE.
+ * INTERRUPTED: a text/binary frame started before the FIN. A message open at
+ * the batch end has neither bit and goes to mc_out. A continuation is an
+ * orphan only when no message is open (the carry counted); orphans with no
+ * message after them are carried (status ORPHANS with opcode 0) and flagged
+ * on the next message start, in whichever call; DERR_ORPHANS is never raised.
+ * TRUNCATED and msg_cap act per call. A text message becomes UNCHECKED for the
+ * rest of its life (sticky; later calls neither validate it nor keep a UTF-8
+ * tail) when a call truncated its bytes by out_cap, could not store its
+ * record (msg_cap), or ran without validation (no XYWS_REASM_UTF8, or out_cap
+ * or msg_cap 0). The structural carry fields (opcode, length, nframes,
+ * first_frame, frame_remaining, frame_member, frames_seen, pending orphans)
+ * are exact whatever out_cap and msg_cap.
+ *
+ * UTF-8. A lead byte in the last 3 bytes of a message that stays open, whose
+ * sequence runs past the batch end, is not judged in that call: the bytes
+ * from the earliest such lead on go to mc_out.utf8 (1..3; a short batch may
+ * extend them), and the sequence is judged whole (second-byte rules of E0, ED,
+ * F0, F4 included) by the call that supplies its last byte; if the message
+ * completes first it is invalid. UTF8_BAD is sticky through the carry. So the
+ * record that completes a message has UTF8_BAD exactly when xyws_reassemble
+ * on the unsplit stream sets it. */
+#define XYWS_MSG_CONTINUED 0x20u /* stream mode: the message began in an earlier call; this record holds
+                                    only the part delivered by this call */
+#define XYWS_MSG_UNCHECKED 0x40u /* stream mode: text message whose UTF-8 validation was abandoned in an
+                                    earlier call (see above); UTF8_BAD, if set, was found before that */
+typedef struct xyws_msg_carry {  /* 64 bytes; all zero = a fresh stream */
+  uint64_t length;          /* payload bytes of the open message delivered by all calls so far */
+  uint64_t nframes;         /* its data frames whose descriptor was in a table so far */
+  uint64_t first_frame;     /* stream-wide index of its first frame (frames_seen at that call + index) */
+  uint64_t frame_remaining; /* payload bytes of the frame cut by the last batch end, still to come */
+  uint64_t frames_seen;     /* sum of n_eff over all calls so far */
+  uint32_t status;          /* sticky bits ORed into the open message's next record (UTF8_BAD, UNCHECKED),
+                               and XYWS_MSG_COMPLETE while it is closing (FIN fragment seen, bytes to
+                               come); with no message open: XYWS_MSG_ORPHANS = orphans seen, no message
+                               since */
+  uint8_t  opcode;          /* 0 = no message open, else XYWS_FLAG_OP_TEXT / _BINARY */
+  uint8_t  frame_member;    /* 1: the frame_remaining bytes belong to the open message; 0: skip them
+                               (control frame or orphan continuation) */
+  uint8_t  utf8_len;        /* 0..3 bytes of a UTF-8 sequence cut by the last batch end ... */
+  uint8_t  utf8[3];         /* ... from its lead byte on */
+  uint8_t  reserved[14];    /* zero */
+} xyws_msg_carry;
+int xyws_reassemble_stream(xyws_ctx* ctx, const void* dev_src, uint64_t src_len,
+                           const xyws_frame* dev_frames, uint64_t n, const uint64_t* dev_n, uint32_t opts,
+                           const xyws_msg_carry* dev_mc_in, xyws_msg_carry* dev_mc_out,
+                           void* dev_out, uint64_t out_cap, xyws_message* dev_msgs, uint64_t msg_cap,
+                           uint64_t* dev_nmsgs, void* stream);
 
 /* ---- recv arenas: the io_uring side (recv_all.h:86-121, io_service.h:362-381)
  * One arena per connection: a receive area in pinned host memory (allocated

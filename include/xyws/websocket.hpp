@@ -24,6 +24,8 @@
 //     mask / reset / npos
 //   echo_once reply build (websocket_echo.cpp:18-27)      xyws::encode_frames (batched, device)
 //   websocket_check_parser_result (websocket.h:81-108)    xyws::classify_frames (device)
+//   (new) FIN=0 chains -> messages, UTF-8 validation      xyws::reassemble (one batch),
+//                                                           xyws::message_assembler (across recvs)
 //
 // Nothing here computes on the host: every call goes through libxyws.so to
 // HIP kernels for gfx950. Buffers are caller-owned device memory (hipMalloc);
@@ -422,6 +424,43 @@ inline void classify_frames(context& ctx, std::span<const std::byte> dev_src, st
                              dev_n, max_payload, policy, dev_verdicts, dev_first_close, stream),
         "xyws_classify_frames");
 }
+
+// FIN=0 chains of one batch gathered into messages, with UTF-8 validation
+// under XYWS_REASM_UTF8 (xyws_reassemble): dev_out receives the payloads back
+// to back, dev_msgs the records, *dev_nmsgs (nullable) their count.
+inline void reassemble(context& ctx, std::span<const std::byte> dev_src, std::span<const xyws_frame> dev_frames,
+                       const std::uint64_t* dev_n, std::uint32_t opts, std::span<std::byte> dev_out,
+                       std::span<xyws_message> dev_msgs, std::uint64_t* dev_nmsgs, void* stream = nullptr) {
+  check(xyws_reassemble(ctx.native(), dev_src.data(), dev_src.size(), dev_frames.data(), dev_frames.size(), dev_n,
+                        opts, dev_out.data(), dev_out.size(), dev_msgs.data(), dev_msgs.size(), dev_nmsgs, stream),
+        "xyws_reassemble");
+}
+
+// Reassembly across batch boundaries (xyws_reassemble_stream): feed() takes
+// each batch frame_decoder::decode decoded, with that call's frame table, in
+// order; a message, a frame or a UTF-8 sequence cut by the batch end continues
+// in the next batch through the device-resident carry. Record 0 of a call is
+// the continuation of the message the last one left open (XYWS_MSG_CONTINUED).
+class message_assembler {
+ public:
+  // dev_carry: 64 B of caller-owned device memory, zero-filled = fresh stream.
+  message_assembler(context& ctx, xyws_msg_carry* dev_carry, std::uint32_t opts = XYWS_REASM_UTF8)
+      : ctx_(&ctx), carry_(dev_carry), opts_(opts) {}
+
+  void feed(std::span<const std::byte> dev_batch, std::span<const xyws_frame> dev_frames, const std::uint64_t* dev_n,
+            std::span<std::byte> dev_out, std::span<xyws_message> dev_msgs, std::uint64_t* dev_nmsgs,
+            void* stream = nullptr) {
+    check(xyws_reassemble_stream(ctx_->native(), dev_batch.data(), dev_batch.size(), dev_frames.data(),
+                                 dev_frames.size(), dev_n, opts_, carry_, carry_, dev_out.data(), dev_out.size(),
+                                 dev_msgs.data(), dev_msgs.size(), dev_nmsgs, stream),
+          "xyws_reassemble_stream");
+  }
+
+ private:
+  context* ctx_;
+  xyws_msg_carry* carry_;
+  std::uint32_t opts_;
+};
 
 }  // namespace xyws
 

@@ -115,6 +115,14 @@ class Message(C.Structure):
                 ("reserved", C.c_uint8 * 3)]
 
 
+class MsgCarry(C.Structure):
+    """xyws_msg_carry (include/xyws.h), 64 bytes."""
+    _fields_ = [("length", C.c_uint64), ("nframes", C.c_uint64), ("first_frame", C.c_uint64),
+                ("frame_remaining", C.c_uint64), ("frames_seen", C.c_uint64), ("status", C.c_uint32),
+                ("opcode", C.c_uint8), ("frame_member", C.c_uint8), ("utf8_len", C.c_uint8),
+                ("utf8", C.c_uint8 * 3), ("reserved", C.c_uint8 * 14)]
+
+
 class ArenaResult(C.Structure):
     """xyws_arena_result (include/xyws.h)."""
     _fields_ = [("seq", C.c_uint64), ("offset", C.c_uint64), ("len", C.c_uint64), ("nframes", C.c_uint64),
@@ -125,13 +133,14 @@ assert C.sizeof(Frame) == 32 and C.sizeof(Carry) == 64
 assert C.sizeof(ArenaResult) == 104
 XYWS_ERR_AGAIN = -6
 ARENA_SLOTS = 8
-assert C.sizeof(Verdict) == 8 and C.sizeof(Message) == 40
+assert C.sizeof(Verdict) == 8 and C.sizeof(Message) == 40 and C.sizeof(MsgCarry) == 64
 NPOS = (1 << 64) - 1
 ENC_FRAME_OPCODE = 0x1
 ACT_DATA, ACT_PING, ACT_PONG, ACT_CLOSE = 0, 1, 2, 3
 POL_FRAGMENTS, POL_UNMASKED, POL_STRICT = 0x1, 0x2, 0x4
 REASM_UTF8 = 0x1
 MSG_COMPLETE, MSG_UTF8_BAD, MSG_INTERRUPTED, MSG_TRUNCATED, MSG_ORPHANS = 0x1, 0x2, 0x4, 0x8, 0x10
+MSG_CONTINUED, MSG_UNCHECKED = 0x20, 0x40  # xyws_reassemble_stream only
 
 _lib = None
 _tools = None
@@ -215,6 +224,8 @@ def load():
     L.xyws_classify_frames.argtypes = [vp, vp, u64, vp, u64, vp, u64, u32, vp, vp, vp]
     L.xyws_reassemble.restype = i32
     L.xyws_reassemble.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, u64, vp, u64, vp, vp]
+    L.xyws_reassemble_stream.restype = i32
+    L.xyws_reassemble_stream.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, vp, vp, u64, vp, u64, vp, vp]
     L.xyws_arena_create.restype = i32
     L.xyws_arena_create.argtypes = [vp, vp, u64, u64, i32, C.POINTER(vp)]
     L.xyws_arena_destroy.restype = i32

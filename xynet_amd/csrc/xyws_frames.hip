@@ -9,8 +9,11 @@
 //   xyws_classify_frames  websocket_check_parser_result's close policy
 //                         (example/include/common/websocket.h:81-108)
 //   xyws_reassemble       FIN=0 chains gathered into messages + UTF-8 check
+//   xyws_reassemble_stream  the same across batch boundaries: the same kernels
+//                         over a view of the table that starts with one item
+//                         made from the device-resident xyws_msg_carry
 //
-// All three are byte/integer work bound by HBM (the gathers) or by launch
+// All of them are byte/integer work bound by HBM (the gathers) or by launch
 // latency (the per-frame passes): per-frame passes are one lane per frame;
 // frame-order offsets come from a three-kernel scan (block partials, one block
 // over the partials, fix-up); the gathers write 16 KiB output tiles per
@@ -75,6 +78,81 @@ XYWS_DEV uint64_t n_eff(uint64_t n, const uint64_t* dev_n) {
   const uint64_t m = *dev_n;
   return m < n ? m : n;
 }
+
+// ---------------------------------------------------------------- table views
+// The frame table as the reassembly kernels index it. tab_plain is the
+// caller's table (xyws_reassemble). tab_stream (xyws_reassemble_stream)
+// presents one virtual item in front of frame 0, made on the device from
+// *mc, and clips every payload at the batch end; the kernels' count n then
+// includes the virtual item. The virtual item is
+//   a message open in the carry   a start of its opcode (with FIN while the
+//                                 message is closing: FIN fragment seen, bytes
+//                                 to come), payload offset 0, as many bytes as
+//                                 the cut frame still delivers here when they
+//                                 belong to the message, else none;
+//   orphans pending in the carry  an orphan continuation of no bytes;
+//   else                          a control frame of no bytes (skipped).
+// So the marks, sizes, records and the gather need no rule of their own for
+// the carry: the table is never copied or patched.
+struct tab_plain {
+  static constexpr bool stream = false;
+  const xyws_frame* frames;
+  XYWS_DEV uint64_t ne(uint64_t n, const uint64_t* dev_n) const { return n_eff(n, dev_n); }
+  XYWS_DEV uint32_t flags(uint64_t i) const { return frames[i].flags; }
+  XYWS_DEV xyws_frame get(uint64_t i) const { return frames[i]; }
+};
+
+struct tab_stream {
+  static constexpr bool stream = true;
+  const xyws_frame* frames;
+  const xyws_msg_carry* mc;  // null: a fresh stream
+  uint64_t src_len;
+  XYWS_DEV uint64_t ne(uint64_t n, const uint64_t* dev_n) const {
+    uint64_t real = n - 1;
+    if (dev_n) {
+      const uint64_t m = *dev_n;
+      if (m < real) real = m;
+    }
+    return real + 1;
+  }
+  XYWS_DEV bool open() const { return mc && (mc->opcode == XYWS_FLAG_OP_TEXT || mc->opcode == XYWS_FLAG_OP_BINARY); }
+  // bytes at the front of the batch that end the frame the last batch end cut, and what is still missing
+  XYWS_DEV uint64_t head() const {
+    const uint64_t r = mc ? mc->frame_remaining : 0;
+    return r < src_len ? r : src_len;
+  }
+  XYWS_DEV uint64_t head_rem() const { return mc ? mc->frame_remaining - head() : 0; }
+  XYWS_DEV uint32_t vflags() const {
+    if (open()) return mc->opcode | ((mc->status & XYWS_MSG_COMPLETE) ? XYWS_FLAG_FIN : 0u);
+    return (mc && (mc->status & XYWS_MSG_ORPHANS)) ? XYWS_FLAG_OP_CONTINUE : (XYWS_FLAG_OP_PONG | XYWS_FLAG_FIN);
+  }
+  XYWS_DEV uint32_t flags(uint64_t i) const { return i ? frames[i - 1].flags : vflags(); }
+  // payload bytes of frame f that lie in the batch
+  XYWS_DEV uint64_t clip(const xyws_frame& f) const {
+    const uint64_t av = (f.payload_off >= 0 && (uint64_t)f.payload_off < src_len) ? src_len - (uint64_t)f.payload_off : 0;
+    return f.payload_len < av ? f.payload_len : av;
+  }
+  XYWS_DEV xyws_frame get(uint64_t i) const {
+    xyws_frame f;
+    if (i) {
+      f = frames[i - 1];
+      f.payload_len = clip(f);
+    } else {
+      f.frame_off = f.payload_off = 0;
+      f.payload_len = (open() && mc->frame_member) ? head() : 0;
+      f.key[0] = f.key[1] = f.key[2] = f.key[3] = 0;
+      f.flags = (uint8_t)vflags();
+      f.hdr_len = f.status = f.reserved = 0;
+    }
+    return f;
+  }
+  // bytes of item i (the last one) that lie past the batch end
+  XYWS_DEV uint64_t rem(uint64_t i) const {
+    if (!i) return head_rem();
+    const xyws_frame f = frames[i - 1];
+    return f.payload_len - clip(f);
+  }
+};
 
 // ---------------------------------------------------------------- scans
 // Inclusive/exclusive scans of n u64 values in three kernels: block partials,
@@ -278,7 +356,15 @@ struct gparams {
   uint8_t* out;  // 16-byte aligned base; output byte q lives at out[out_lo + q]
   uint64_t out_lo, out_cap;
   uint32_t* err;
+  const xyws_msg_carry* mc;  // the gather's stream instantiation: tab_stream's carry (else unused)
 };
+
+// The items of a gather<S>: n_eff items of the frame table, or tab_stream's view of it.
+template <bool S>
+XYWS_DEV uint64_t items_of(const gparams& G) {
+  if constexpr (S) return tab_stream{G.frames, G.mc, G.src_len}.ne(G.n, G.dev_n);
+  else return n_eff(G.n, G.dev_n);
+}
 
 XYWS_DEV uint32_t reply_flags(const gparams& G, uint32_t fflags) {
   if (!(G.enc_opts & XYWS_ENC_FRAME_OPCODE)) return G.flags;
@@ -287,9 +373,12 @@ XYWS_DEV uint32_t reply_flags(const gparams& G, uint32_t fflags) {
   return op | (fflags & XYWS_FLAG_FIN) | (G.flags & XYWS_FLAG_HAS_MASK);
 }
 
+template <bool S = false>
 XYWS_DEV gitem item_of(const gparams& G, uint64_t i) {
   gitem it;
-  const xyws_frame f = G.frames[i];
+  xyws_frame f;
+  if constexpr (S) f = tab_stream{G.frames, G.mc, G.src_len}.get(i);
+  else f = G.frames[i];
   it.dst = G.off[i];
   const uint64_t size = G.off[i + 1] - it.dst;
   it.soff = (uint64_t)f.payload_off;
@@ -349,9 +438,10 @@ XYWS_DEV uint64_t find_item(const uint64_t* ls, const uint64_t* off, uint64_t a,
 // byte is q = max(t*GTILE - out_lo, 0)). One lane per item writes the tiles
 // whose first byte it holds (a 1 MiB reply spans 64 of them), so a tile finds
 // its items with one load instead of a binary search of the offsets.
+template <bool S>
 __global__ void __launch_bounds__(FT) k_tile_map(gparams G, uint64_t* map, uint64_t ntiles) {
   const uint64_t i = (uint64_t)blockIdx.x * FT + threadIdx.x;
-  const uint64_t ne = n_eff(G.n, G.dev_n);
+  const uint64_t ne = items_of<S>(G);
   if (i >= ne) return;
   const uint64_t total = G.off[ne];
   const uint64_t lim = total < G.out_cap ? total : G.out_cap;
@@ -481,10 +571,11 @@ XYWS_DEV uint32_t chunk_at(int64_t d, int64_t base) {
 // a funnel shift, XORed with the rotated key word, each selected by its byte
 // mask. One 16-byte store per chunk (byte stores only at the output's ends).
 // Tiles with more items than fit in LDS take the per-byte path.
+template <bool ST>
 __global__ void __launch_bounds__(FT) k_gather(gparams G, const uint64_t* __restrict__ map, uint64_t ntiles) {
   __shared__ gstage S;
   __shared__ uint64_t s_f0, s_f1;
-  const uint64_t ne = n_eff(G.n, G.dev_n);
+  const uint64_t ne = items_of<ST>(G);
   const uint64_t total = G.off[ne];
   const uint64_t lim = total < G.out_cap ? total : G.out_cap;  // bytes written
   if (!lim || !ne) return;
@@ -506,7 +597,7 @@ __global__ void __launch_bounds__(FT) k_gather(gparams G, const uint64_t* __rest
     if (in_lds) {
       const int64_t base = (int64_t)t0 - (int64_t)o0;
       for (uint64_t k = threadIdx.x; k < f1 - f0; k += FT) {
-        const gitem it = item_of(G, f0 + k);
+        const gitem it = item_of<ST>(G, f0 + k);
         S.dst[k] = it.dst;
         S.soff[k] = it.soff;
         S.hw[k][0] = it.hw[0]; S.hw[k][1] = it.hw[1]; S.hw[k][2] = it.hw[2]; S.hw[k][3] = it.hw[3];
@@ -617,7 +708,7 @@ __global__ void __launch_bounds__(FT) k_gather(gparams G, const uint64_t* __rest
       if (!in_lds) {
         // many tiny items: byte by byte from memory
         uint64_t gi = find_item(nullptr, G.off, f0, f1, f0, qa);
-        gitem it = item_of(G, gi);
+        gitem it = item_of<ST>(G, gi);
         uint64_t nxt = gi + 1 < ne ? G.off[gi + 1] : U64MAX;
         for (uint32_t t = 0; t < 16; t++) {
           const uint64_t p = a + t;
@@ -625,7 +716,7 @@ __global__ void __launch_bounds__(FT) k_gather(gparams G, const uint64_t* __rest
           const uint64_t q = p - o0;
           while (q >= nxt) {
             gi++;
-            it = item_of(G, gi);
+            it = item_of<ST>(G, gi);
             nxt = gi + 1 < ne ? G.off[gi + 1] : U64MAX;
           }
           G.out[p] = item_byte(G, it, q);
@@ -752,14 +843,15 @@ __global__ void __launch_bounds__(FT) k_classify(const uint8_t* src, uint64_t sr
 // start <= i); b[i] = i for a data frame with FIN, else UINT64_MAX
 // (min-scanned from the end: the next FIN >= i); st[i] = 1 for a start
 // (exclusive sum: message ranks).
+template <class Tab>
 struct gen_marks {
-  const xyws_frame* frames;
+  Tab T;
   uint64_t n;
   const uint64_t* dev_n;
   template <int K>
   XYWS_DEV uint64_t val(const uint64_t*, uint64_t i) const {
-    if (i >= n_eff(n, dev_n)) return K == 1 ? U64MAX : 0;
-    const uint32_t fl = frames[i].flags, op = fl & XYWS_FLAG_OP_MASK;
+    if (i >= T.ne(n, dev_n)) return K == 1 ? U64MAX : 0;
+    const uint32_t fl = T.flags(i), op = fl & XYWS_FLAG_OP_MASK;
     const bool start = op == XYWS_FLAG_OP_TEXT || op == XYWS_FLAG_OP_BINARY;
     if (K == 0) return start ? i + 1 : 0;
     if (K == 1) return (op <= XYWS_FLAG_OP_BINARY && (fl & XYWS_FLAG_FIN)) ? i : U64MAX;
@@ -771,16 +863,17 @@ struct gen_marks {
 // data frame with FIN >= i. Frame i belongs to the message of s = a[i] - 1
 // when it is a data frame and i <= b[s]. sz[i] = its payload bytes, cnt[i] =
 // 1 for members; orphan continuations raise orph[the next start's rank].
-__global__ void __launch_bounds__(FT) k_rs_sizes(const xyws_frame* frames, uint64_t n, const uint64_t* dev_n,
+template <class Tab>
+__global__ void __launch_bounds__(FT) k_rs_sizes(Tab T, uint64_t n, const uint64_t* dev_n,
                                                  const uint64_t* a, const uint64_t* b, uint64_t* sz,
                                                  uint64_t* cnt, uint64_t* orphan_flag, const uint64_t* rank,
                                                  uint64_t* starts) {
   const uint64_t i = (uint64_t)blockIdx.x * FT + threadIdx.x;
   if (i >= n) return;
-  const uint64_t ne = n_eff(n, dev_n);
+  const uint64_t ne = T.ne(n, dev_n);
   uint64_t s = 0, c = 0, o = 0;
   if (i < ne) {
-    const xyws_frame f = frames[i];
+    const xyws_frame f = T.get(i);
     const uint32_t op = f.flags & XYWS_FLAG_OP_MASK;
     if (op <= XYWS_FLAG_OP_BINARY) {
       const uint64_t st = a[i];
@@ -815,7 +908,14 @@ constexpr uint32_t UT = 65536;  // UTF-8 tile: bytes of out[] (k_utf8)
 // the messages whose bytes start a tile (a 1 MiB message spans 16), so that a
 // tile finds its messages with two loads and skips at once when none of them
 // is a text message.
-__global__ void __launch_bounds__(FT) k_rs_msgs(const xyws_frame* frames, const uint64_t* dev_n, uint64_t n,
+// Through tab_stream: record 0 of a message open in the carry is its
+// continuation (CONTINUED, first_frame NPOS, the virtual item not counted,
+// the carry's sticky bits); the other records index the caller's table; a
+// message whose FIN fragment is cut by the batch end is not COMPLETE yet;
+// orphans with no message after them go to the carry (k_rs_carry), not to the
+// error word.
+template <class Tab>
+__global__ void __launch_bounds__(FT) k_rs_msgs(Tab T, const uint64_t* dev_n, uint64_t n,
                                                 const uint64_t* nmsg_p,
                                                 const uint64_t* off, const uint64_t* cntoff, const uint64_t* b,
                                                 const uint64_t* starts, const uint64_t* orph_rank,
@@ -823,18 +923,22 @@ __global__ void __launch_bounds__(FT) k_rs_msgs(const xyws_frame* frames, const 
                                                 uint64_t* dev_nmsgs, uint32_t* err, uint64_t* umap,
                                                 uint64_t utiles, uint64_t out_lo) {
   const uint64_t m = (uint64_t)blockIdx.x * FT + threadIdx.x;
-  const uint64_t ne = n_eff(n, dev_n), nm = *nmsg_p;
+  const uint64_t ne = T.ne(n, dev_n), nm = *nmsg_p;
   if (m == 0) {
     if (dev_nmsgs) *dev_nmsgs = nm;
-    const uint64_t before = nm ? orph_rank[starts[nm - 1]] : 0;
-    if (orph_rank[ne] > before) atomicOr(err, DERR_ORPHANS);
+    if constexpr (!Tab::stream) {
+      const uint64_t before = nm ? orph_rank[starts[nm - 1]] : 0;
+      if (orph_rank[ne] > before) atomicOr(err, DERR_ORPHANS);
+    }
   }
   if (m >= nm || m >= msg_cap) return;
   const uint64_t s = starts[m];
   const uint64_t ns = m + 1 < nm ? starts[m + 1] : ne;
-  const uint64_t op = frames[s].flags & XYWS_FLAG_OP_MASK;
+  const uint64_t op = T.flags(s) & XYWS_FLAG_OP_MASK;
   uint32_t st = 0;
-  if (b[s] < ns) st |= XYWS_MSG_COMPLETE;
+  bool fin = b[s] < ns;
+  if constexpr (Tab::stream) fin = fin && !(b[s] == ne - 1 && T.rem(ne - 1));  // (the FIN fragment's bytes cut)
+  if (fin) st |= XYWS_MSG_COMPLETE;
   else if (m + 1 < nm) st |= XYWS_MSG_INTERRUPTED;
   if (off[ns] > out_cap) st |= XYWS_MSG_TRUNCATED;
   // orphans between the previous start (or the batch start) and this one:
@@ -846,8 +950,15 @@ __global__ void __launch_bounds__(FT) k_rs_msgs(const xyws_frame* frames, const 
   // reserved bytes as one little-endian word)
   static_assert(sizeof(xyws_message) == 40 && offsetof(xyws_message, status) == 32, "xyws_message layout");
   uint64_t* r = reinterpret_cast<uint64_t*>(msgs + m);
-  r[0] = s;
-  r[1] = cntoff[ns] - cntoff[s];
+  if constexpr (Tab::stream) {
+    const bool cont = s == 0 && T.open();  // (item 0 is a start only for an open message)
+    if (cont) st |= XYWS_MSG_CONTINUED | (T.mc->status & (XYWS_MSG_UTF8_BAD | XYWS_MSG_UNCHECKED));
+    r[0] = cont ? U64MAX : s - 1;
+    r[1] = cntoff[ns] - cntoff[s] - (cont ? 1 : 0);
+  } else {
+    r[0] = s;
+    r[1] = cntoff[ns] - cntoff[s];
+  }
   r[2] = off[s];
   r[3] = off[ns] - off[s];
   r[4] = (uint64_t)st | (op << 32);
@@ -875,8 +986,25 @@ XYWS_DEV uint32_t lead_len(uint32_t c) { return c >= 0xF0u ? 4u : c >= 0xE0u ? 3
 // code points above U+10FFFF; a sequence cut by the message end is invalid
 // only in a complete, untruncated message). For the probe pass (the first
 // bytes of each message), not the streaming pass.
+// A carried UTF-8 tail as one word: its 0..3 bytes in bits 0..23, their
+// count in bits 24..31 (0: none). tail_prev: the byte `back` (>= 1) before
+// the message's first byte in this call, or 0x100 when the tail is shorter.
+XYWS_DEV uint32_t tail_word(const xyws_msg_carry* mc) {
+  if (!mc || mc->opcode != XYWS_FLAG_OP_TEXT || !mc->utf8_len || mc->utf8_len > 3) return 0;
+  return (uint32_t)mc->utf8[0] | ((uint32_t)mc->utf8[1] << 8) | ((uint32_t)mc->utf8[2] << 16) |
+         ((uint32_t)mc->utf8_len << 24);
+}
+XYWS_DEV uint32_t tail_prev(uint32_t tw, uint32_t back) {
+  const uint32_t tl = tw >> 24;
+  if (back > tl) return 0x100u;
+  return (tw >> (8u * (tl - back))) & 0xFFu;
+}
+
+// (tw: the carried tail of the message when it is a stream call's record 0:
+// its bytes are the bytes before mo for the claim rule; S: a stream call)
+template <bool S>
 XYWS_DEV bool utf8_span_bad(const uint8_t* out, uint64_t out_lo, uint64_t total, uint64_t q0, uint64_t q1,
-                            uint64_t mo, uint64_t me, uint32_t ty) {
+                            uint64_t mo, uint64_t me, uint32_t ty, uint32_t tw = 0) {
   // (q1 - q0 <= 16: the bytes [q0 - 3, q0 + 19) the rules look at come from
   // three aligned 16-byte lines loaded at once — one memory round trip, not
   // one per byte; lines at or past the bytes written read as zero, and the
@@ -899,8 +1027,19 @@ XYWS_DEV bool utf8_span_bad(const uint8_t* out, uint64_t out_lo, uint64_t total,
     if (ch < 0xC0u) {
       bool claimed = false;
       for (uint32_t d = 1; d <= 3 && !claimed; d++) {
-        if (q < mo + d) break;
-        if (lead_len(at(q - d)) > d) claimed = true;
+        if constexpr (S) {
+          uint32_t pb;
+          if (q < mo + d) {
+            pb = tail_prev(tw, (uint32_t)(mo + d - q));
+            if (pb > 0xFFu) break;
+          } else {
+            pb = at(q - d);
+          }
+          if (lead_len(pb) > d) claimed = true;
+        } else {
+          if (q < mo + d) break;
+          if (lead_len(at(q - d)) > d) claimed = true;
+        }
       }
       if (!claimed) return true;
     } else if (ch == 0xC0u || ch == 0xC1u || ch >= 0xF5u) {
@@ -934,10 +1073,19 @@ struct ustage {
 constexpr uint32_t UTEXT = 1u << 31;
 constexpr uint32_t UPROBE = 16;  // bytes of each message the probe pass checks
 
+// S (xyws_reassemble_stream): a message UNCHECKED in the carry is not
+// validated, and record 0's first bytes see the carried tail as the bytes
+// before them (the tail's own sequence is judged by k_rs_carry).
+template <bool S>
 __global__ void __launch_bounds__(FT) k_utf8(const uint8_t* out, uint64_t out_lo, uint64_t out_cap,
                                              const uint64_t* nmsg_p, xyws_message* msgs, uint64_t msg_cap,
-                                             const uint64_t* map, uint64_t ntiles) {
+                                             const uint64_t* map, uint64_t ntiles, const xyws_msg_carry* mc) {
   __shared__ ustage U;
+  const uint32_t tw = S ? tail_word(mc) : 0u;
+  // (a record is text for this kernel unless its validation was abandoned)
+  auto is_text = [](const xyws_message& r) {
+    return r.opcode == XYWS_FLAG_OP_TEXT && !(S && (r.status & XYWS_MSG_UNCHECKED));
+  };
   __shared__ uint32_t s_text;
   __shared__ uint64_t s_m0, s_m1;
   const uint64_t nm0 = *nmsg_p, nm = nm0 < msg_cap ? nm0 : msg_cap;
@@ -957,13 +1105,13 @@ __global__ void __launch_bounds__(FT) k_utf8(const uint8_t* out, uint64_t out_lo
     const bool inl = m1 - m0 < UMS;  // the tile's messages staged in LDS
     for (uint64_t m = m0 + threadIdx.x; m <= m1; m += FT) {
       const xyws_message r = msgs[m];
-      const bool text = r.opcode == XYWS_FLAG_OP_TEXT && r.length;
+      const bool text = is_text(r) && r.length;
       if (text) s_text = 1;
       if (inl) {
         const uint32_t k = (uint32_t)(m - m0);
         U.mo[k] = r.out_off;
         U.me[k] = r.out_off + r.length;
-        U.ty[k] = r.status | (r.opcode == XYWS_FLAG_OP_TEXT ? UTEXT : 0u);
+        U.ty[k] = r.status | (is_text(r) ? UTEXT : 0u);
         U.bad[k] = 0;
       }
     }
@@ -973,7 +1121,7 @@ __global__ void __launch_bounds__(FT) k_utf8(const uint8_t* out, uint64_t out_lo
     auto me_of = [&](uint64_t m) -> uint64_t { return inl ? U.me[m - m0] : msgs[m].out_off + msgs[m].length; };
     auto ty_of = [&](uint64_t m) -> uint32_t {
       return inl ? U.ty[m - m0] | (U.bad[m - m0] ? XYWS_MSG_UTF8_BAD : 0u)
-                 : msgs[m].status | (msgs[m].opcode == XYWS_FLAG_OP_TEXT ? UTEXT : 0u);
+                 : msgs[m].status | (is_text(msgs[m]) ? UTEXT : 0u);
     };
     auto mark = [&](uint64_t m, uint32_t ty) {
       if (ty & XYWS_MSG_UTF8_BAD) return;
@@ -994,7 +1142,7 @@ __global__ void __launch_bounds__(FT) k_utf8(const uint8_t* out, uint64_t out_lo
           if (!(ty & UTEXT) || (ty & XYWS_MSG_UTF8_BAD)) continue;
           const uint64_t mo = mo_of(m), me = me_of(m);
           if (mo < tq0) continue;  // (its first bytes are an earlier tile's probe)
-          if (utf8_span_bad(out, out_lo, total, mo, mo + UPROBE, mo, me, ty)) mark(m, ty);
+          if (utf8_span_bad<S>(out, out_lo, total, mo, mo + UPROBE, mo, me, ty, S && m == 0 ? tw : 0u)) mark(m, ty);
         }
         __syncthreads();
       }
@@ -1074,10 +1222,21 @@ __global__ void __launch_bounds__(FT) k_utf8(const uint8_t* out, uint64_t out_lo
             // a continuation byte: a lead within 3 bytes before must claim it
             bool claimed = false;
             for (uint32_t d = 1; d <= 3 && !claimed; d++) {
-              if (q < mo + d) break;
-              const uint32_t pb = t >= d ? (w[(t - d) >> 2] >> (8u * ((t - d) & 3u))) & 0xFFu
-                                         : out[out_lo + q - d];
-              if (lead_len(pb) > d) claimed = true;
+              if constexpr (S) {
+                uint32_t pb;
+                if (q < mo + d) {
+                  pb = tail_prev(m == 0 ? tw : 0u, (uint32_t)(mo + d - q));
+                  if (pb > 0xFFu) break;
+                } else {
+                  pb = t >= d ? (w[(t - d) >> 2] >> (8u * ((t - d) & 3u))) & 0xFFu : out[out_lo + q - d];
+                }
+                if (lead_len(pb) > d) claimed = true;
+              } else {
+                if (q < mo + d) break;
+                const uint32_t pb = t >= d ? (w[(t - d) >> 2] >> (8u * ((t - d) & 3u))) & 0xFFu
+                                           : out[out_lo + q - d];
+                if (lead_len(pb) > d) claimed = true;
+              }
             }
             bad = !claimed;
           } else if (ch == 0xC0u || ch == 0xC1u || ch >= 0xF5u) {
@@ -1121,6 +1280,120 @@ __global__ void __launch_bounds__(FT) k_utf8(const uint8_t* out, uint64_t out_lo
 
 __global__ void k_put(uint64_t* p, uint64_t v) { *p = v; }
 
+// xyws_reassemble_stream's last kernel, one lane, after the gather and k_utf8
+// (whose marks have landed in the records): judges the carried UTF-8 tail's
+// sequence with record 0's first bytes, then writes *mc_out: the frame cut by
+// the batch end, the message still open (its totals, the sticky status bits,
+// the new tail from the last bytes written to out[]) or the pending orphans.
+// *mc_in is read whole before *mc_out is written (they may be one object).
+// (small sequences are packed into a u64, byte i at bits 8i: no private array)
+__global__ void k_rs_carry(tab_stream T, uint64_t n, const uint64_t* dev_n, const uint64_t* nmsg_p,
+                           const uint64_t* off, const uint64_t* cntoff, const uint64_t* orph_rank,
+                           const uint64_t* b, const uint64_t* starts, xyws_message* msgs, uint64_t msg_cap,
+                           const uint8_t* out, uint64_t out_lo, uint64_t out_cap, uint32_t utf8,
+                           xyws_msg_carry* mc_out) {
+  static_assert(sizeof(xyws_msg_carry) == 64 && offsetof(xyws_msg_carry, status) == 40 &&
+                    offsetof(xyws_msg_carry, utf8) == 47, "xyws_msg_carry layout");
+  if (blockIdx.x || threadIdx.x) return;
+  xyws_msg_carry in;
+  {
+    uint64_t* w = reinterpret_cast<uint64_t*>(&in);
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(T.mc);
+    for (uint32_t i = 0; i < 8; i++) w[i] = src ? src[i] : 0ull;
+  }
+  const bool in_open = T.open();
+  const uint32_t tw = tail_word(T.mc);
+  const uint64_t ne = T.ne(n, dev_n), nm = *nmsg_p;
+  const uint64_t rem = T.rem(ne - 1);
+  // the carried tail's sequence: whole once record 0 holds the bytes it lacks
+  if (utf8 && in_open && tw && !(in.status & (XYWS_MSG_UTF8_BAD | XYWS_MSG_UNCHECKED))) {
+    const xyws_message r0 = msgs[0];
+    const uint64_t avail = r0.length < out_cap ? r0.length : out_cap;
+    const uint32_t tl = tw >> 24, L = lead_len(tw & 0xFFu);
+    bool bad = false;
+    if (L > tl) {
+      const uint32_t need = L - tl;
+      if (avail >= need) {
+        uint64_t seq = tw & 0xFFFFFFu;
+        for (uint32_t j = 0; j < need; j++) seq |= (uint64_t)out[out_lo + j] << (8u * (tl + j));
+        const uint32_t c0 = (uint32_t)(seq & 0xFFu), c1 = (uint32_t)((seq >> 8) & 0xFFu);
+        for (uint32_t j = 1; j < L; j++)
+          if (((seq >> (8u * j)) & 0xC0u) != 0x80u) bad = true;
+        if ((c0 == 0xE0u && c1 < 0xA0u) || (c0 == 0xEDu && c1 > 0x9Fu) || (c0 == 0xF0u && c1 < 0x90u) ||
+            (c0 == 0xF4u && c1 > 0x8Fu))
+          bad = true;
+      } else if ((r0.status & XYWS_MSG_COMPLETE) && !(r0.status & XYWS_MSG_TRUNCATED)) {
+        bad = true;  // (the message ended inside it)
+      }
+    }
+    if (bad) msgs[0].status = r0.status | XYWS_MSG_UTF8_BAD;
+  }
+  xyws_msg_carry o;
+  {
+    uint64_t* w = reinterpret_cast<uint64_t*>(&o);
+    for (uint32_t i = 0; i < 8; i++) w[i] = 0;
+  }
+  o.frames_seen = in.frames_seen + (ne - 1);
+  o.frame_remaining = rem;
+  bool open = false;
+  uint64_t s = 0;
+  if (nm) {
+    s = starts[nm - 1];
+    const bool fin = b[s] < ne;
+    open = !(fin && !(b[s] == ne - 1 && rem));
+    if (open) {
+      const uint64_t m = nm - 1;
+      const bool cont = s == 0;  // (item 0 is a start only for an open message)
+      const uint32_t op = T.flags(s) & XYWS_FLAG_OP_MASK;
+      const uint64_t len_call = off[ne] - off[s];
+      const bool stored = m < msg_cap, text = op == XYWS_FLAG_OP_TEXT;
+      const uint32_t st_in = cont ? in.status : 0u;
+      const uint32_t st_rec = stored ? msgs[m].status : 0u;
+      const bool bad = ((st_in | st_rec) & XYWS_MSG_UTF8_BAD) != 0;
+      const bool unchecked = text && ((st_in & XYWS_MSG_UNCHECKED) || !utf8 || off[ne] > out_cap || !stored);
+      o.opcode = (uint8_t)op;
+      o.length = (cont ? in.length : 0) + len_call;
+      o.nframes = (cont ? in.nframes - 1 : 0) + (cntoff[ne] - cntoff[s]);
+      o.first_frame = cont ? in.first_frame : in.frames_seen + (s - 1);
+      // (the cut frame is the table's last: a member when it was counted)
+      o.frame_member = rem && (ne == 1 ? in.frame_member != 0 : cntoff[ne] != cntoff[ne - 1]) ? 1 : 0;
+      o.status = (fin ? XYWS_MSG_COMPLETE : 0u) | (bad ? XYWS_MSG_UTF8_BAD : 0u) |
+                 (unchecked ? XYWS_MSG_UNCHECKED : 0u);
+      if (text && !bad && !unchecked) {
+        // the last 3 bytes of (carried tail, this call's bytes): all of them in out[] (not truncated)
+        uint64_t seq = 0;
+        uint32_t k = 0;
+        const uint32_t take = len_call < 3 ? (uint32_t)len_call : 3u;
+        // bytes before this call's last `take`: the tail's last 3 - take
+        const uint32_t tl = cont ? tw >> 24 : 0u, from_tail = tl < 3u - take ? tl : 3u - take;
+        for (uint32_t j = 0; j < from_tail; j++) seq |= (uint64_t)tail_prev(tw, from_tail - j) << (8u * k++);
+        for (uint32_t j = 0; j < take; j++)
+          seq |= (uint64_t)out[out_lo + off[ne] - take + j] << (8u * k++);
+        // from the earliest lead whose sequence runs past the end
+        for (uint32_t d = k; d >= 1; d--) {
+          const uint32_t c = (uint32_t)((seq >> (8u * (k - d))) & 0xFFu);
+          if (lead_len(c) > d) {
+            o.utf8_len = (uint8_t)d;
+            o.utf8[0] = (uint8_t)c;
+            if (d > 1) o.utf8[1] = (uint8_t)(seq >> (8u * (k - d + 1)));
+            if (d > 2) o.utf8[2] = (uint8_t)(seq >> (8u * (k - d + 2)));
+            break;
+          }
+        }
+      }
+    }
+  }
+  if (!open) {
+    const uint64_t before = nm ? orph_rank[s] : 0;
+    if (orph_rank[ne] > before) o.status = XYWS_MSG_ORPHANS;
+  }
+  {
+    const uint64_t* w = reinterpret_cast<const uint64_t*>(&o);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(mc_out);
+    for (uint32_t i = 0; i < 8; i++) dst[i] = w[i];
+  }
+}
+
 // The gather's parameters for reassembly; encode adds its flags, options and keys.
 gparams gather_params(uint32_t mode, const void* src, uint64_t src_len, const xyws_frame* frames,
                       const uint64_t* off, uint64_t n, const uint64_t* dev_n, void* out, uint64_t out_cap,
@@ -1132,6 +1405,7 @@ gparams gather_params(uint32_t mode, const void* src, uint64_t src_len, const xy
   G.mode = mode; G.flags = 0; G.enc_opts = 0; G.keys = nullptr;
   G.out = ro.base; G.out_lo = ro.lo; G.out_cap = out_cap;
   G.err = err;
+  G.mc = nullptr;
   return G;
 }
 
@@ -1141,12 +1415,83 @@ uint64_t gather_tiles(const void* out, uint64_t out_cap) {
 }
 
 // The items' bytes into the output: the tile map (ntiles = gather_tiles), then the gather.
+template <bool S = false>
 int launch_gather(const gparams& G, uint64_t* tmap, uint64_t ntiles, hipStream_t s) {
   if (!G.n || !G.out_cap) return XYWS_OK;
   const uint64_t tiles = (G.out_lo + G.out_cap + GTILE - 1) / GTILE;
-  hipLaunchKernelGGL(k_tile_map, dim3((G.n + FT - 1) / FT), dim3(FT), 0, s, G, tmap, ntiles);
-  hipLaunchKernelGGL(k_gather, dim3(grid_for(tiles, 1, 8192)), dim3(FT), 0, s, G, (const uint64_t*)tmap, ntiles);
+  hipLaunchKernelGGL(k_tile_map<S>, dim3((G.n + FT - 1) / FT), dim3(FT), 0, s, G, tmap, ntiles);
+  hipLaunchKernelGGL(k_gather<S>, dim3(grid_for(tiles, 1, 8192)), dim3(FT), 0, s, G, (const uint64_t*)tmap, ntiles);
   return hip_err(hipGetLastError());
+}
+
+// The reassembly pipeline of xyws_reassemble (Tab = tab_plain over n frames)
+// and xyws_reassemble_stream (Tab = tab_stream; n counts the virtual item too,
+// and the carry kernel follows).
+template <class Tab>
+int reassemble_run(xyws_ctx* ctx, call_scope& c, Tab T, const void* dev_src, uint64_t src_len, uint64_t n,
+                   const uint64_t* dev_n, uint32_t opts, void* dev_out, uint64_t out_cap, xyws_message* dev_msgs,
+                   uint64_t msg_cap, uint64_t* dev_nmsgs, xyws_msg_carry* dev_mc_out) {
+  constexpr bool S = Tab::stream;
+  int rc;
+  hipStream_t s = c.s;
+  // scratch: a, b, st/rank, sz/off, cnt/cntoff, orphan flags/prefix (n + 1
+  // each), block partials, totals
+  const uint64_t w = n + 1, nb = (n + SB - 1) / SB + 1;
+  const range16 ro = xyws_internal::span16(dev_out, out_cap);
+  const uint64_t ntiles = gather_tiles(dev_out, out_cap);
+  const uint64_t utiles = (ro.hi + UT - 1) / UT + 1;
+  if ((rc = ensure_aux(c.sl, 8 * (7 * w + 3 * nb + 4 + ntiles + utiles), c.capt))) return rc;
+  uint64_t* A = static_cast<uint64_t*>(c.sl->aux.mem);
+  uint64_t *a = A, *b = A + w, *st = A + 2 * w, *off = A + 3 * w, *cnt = A + 4 * w, *orph = A + 5 * w;
+  uint64_t* starts = A + 6 * w;   // every message's first frame
+  uint64_t* part = A + 7 * w;     // 3 * nb: one slice per scan of a group
+  uint64_t* tot = part + 3 * nb;  // tot[0]: bytes, tot[1]: messages, tot[2], tot[3]: scratch totals
+  uint64_t* tmap = tot + 4;       // gather tile map
+  uint64_t* umap = tmap + ntiles; // UTF-8 tile map
+  const bool utf8 = (opts & XYWS_REASM_UTF8) && out_cap && msg_cap;
+  const dim3 gn((uint32_t)((n + FT - 1) / FT > 0 ? (n + FT - 1) / FT : 1));
+  // the last start at or before each frame, the next FIN at or after it, and
+  // the message ranks of the starts (the marks made in the first pass)
+  if ((rc = scan3<scan3_spec<op_max, false, false>, scan3_spec<op_min, true, false>, scan3_spec<op_sum, false, true>>(
+           scan3_args{{a, b, st}, {tot + 2, tot + 3, tot + 1}}, n, part, gen_marks<Tab>{T, n, dev_n}, s)))
+    return rc;
+  // (the sizes in a kernel of their own: made inside the scan, each of its
+  // three values repeated the frame's random loads, c2 0.238 -> 0.307 ms)
+  if (n) {
+    hipLaunchKernelGGL(k_rs_sizes<Tab>, gn, dim3(FT), 0, s, T, n, dev_n, (const uint64_t*)a,
+                       (const uint64_t*)b, off, cnt, orph, (const uint64_t*)st, starts);
+    if ((rc = hip_err(hipGetLastError()))) return rc;
+  }
+  // output offsets, frame counts and orphan ranks
+  if ((rc = scan3<scan3_spec<op_sum, false, true>, scan3_spec<op_sum, false, true>, scan3_spec<op_sum, false, true>>(
+           scan3_args{{off, cnt, orph}, {tot + 0, tot + 2, tot + 3}}, n, part, gen_load{}, s)))
+    return rc;
+  hipLaunchKernelGGL(k_rs_msgs<Tab>, gn, dim3(FT), 0, s, T, dev_n, n, (const uint64_t*)(tot + 1),
+                     (const uint64_t*)off,
+                     (const uint64_t*)cnt, (const uint64_t*)b, (const uint64_t*)starts, (const uint64_t*)orph,
+                     out_cap, dev_msgs, msg_cap, dev_nmsgs, ctx->err, utf8 ? umap : nullptr, utiles, ro.lo);
+  if ((rc = hip_err(hipGetLastError()))) return rc;
+  gparams G = gather_params(G_REASM, dev_src, src_len, T.frames, off, n, dev_n, dev_out, out_cap, ctx->err);
+  const xyws_msg_carry* mc_in = nullptr;
+  if constexpr (S) mc_in = G.mc = T.mc;
+  if ((rc = launch_gather<S>(G, tmap, ntiles, s))) return rc;
+  if (utf8) {
+    // (the UTF-8 tile map: k_rs_msgs)
+    hipLaunchKernelGGL(k_utf8<S>, dim3(grid_for(utiles, 1, 4096)), dim3(FT), 0, s, (const uint8_t*)G.out, G.out_lo,
+                       out_cap, (const uint64_t*)(tot + 1), dev_msgs, msg_cap, (const uint64_t*)umap, utiles, mc_in);
+    if ((rc = hip_err(hipGetLastError()))) return rc;
+  }
+  if constexpr (S) {
+    // the carry out, once k_utf8's marks have landed
+    if (dev_mc_out) {
+      hipLaunchKernelGGL(k_rs_carry, dim3(1), dim3(64), 0, s, T, n, dev_n, (const uint64_t*)(tot + 1),
+                         (const uint64_t*)off, (const uint64_t*)cnt, (const uint64_t*)orph, (const uint64_t*)b,
+                         (const uint64_t*)starts, dev_msgs, msg_cap, (const uint8_t*)G.out, G.out_lo, out_cap,
+                         utf8 ? 1u : 0u, dev_mc_out);
+      if ((rc = hip_err(hipGetLastError()))) return rc;
+    }
+  }
+  return XYWS_OK;
 }
 
 }  // namespace
@@ -1219,55 +1564,23 @@ int xyws_reassemble(xyws_ctx* ctx, const void* dev_src, uint64_t src_len, const 
   if (!ctx || (!dev_frames && n) || (!dev_src && src_len) || (!dev_out && out_cap) || (!dev_msgs && msg_cap))
     return XYWS_ERR_INVALID;
   call_scope c(ctx, stream);
-  int rc = c.rc;
-  if (rc) return rc;
-  hipStream_t s = c.s;
-  // scratch: a, b, st/rank, sz/off, cnt/cntoff, orphan flags/prefix (n + 1
-  // each), block partials, totals
-  const uint64_t w = n + 1, nb = (n + SB - 1) / SB + 1;
-  const range16 ro = xyws_internal::span16(dev_out, out_cap);
-  const uint64_t ntiles = gather_tiles(dev_out, out_cap);
-  const uint64_t utiles = (ro.hi + UT - 1) / UT + 1;
-  if ((rc = ensure_aux(c.sl, 8 * (7 * w + 3 * nb + 4 + ntiles + utiles), c.capt))) return rc;
-  uint64_t* A = static_cast<uint64_t*>(c.sl->aux.mem);
-  uint64_t *a = A, *b = A + w, *st = A + 2 * w, *off = A + 3 * w, *cnt = A + 4 * w, *orph = A + 5 * w;
-  uint64_t* starts = A + 6 * w;   // every message's first frame
-  uint64_t* part = A + 7 * w;     // 3 * nb: one slice per scan of a group
-  uint64_t* tot = part + 3 * nb;  // tot[0]: bytes, tot[1]: messages, tot[2], tot[3]: scratch totals
-  uint64_t* tmap = tot + 4;       // gather tile map
-  uint64_t* umap = tmap + ntiles; // UTF-8 tile map
-  const bool utf8 = (opts & XYWS_REASM_UTF8) && out_cap && msg_cap;
-  const dim3 gn((uint32_t)((n + FT - 1) / FT > 0 ? (n + FT - 1) / FT : 1));
-  // the last start at or before each frame, the next FIN at or after it, and
-  // the message ranks of the starts (the marks made in the first pass)
-  if ((rc = scan3<scan3_spec<op_max, false, false>, scan3_spec<op_min, true, false>, scan3_spec<op_sum, false, true>>(
-           scan3_args{{a, b, st}, {tot + 2, tot + 3, tot + 1}}, n, part, gen_marks{dev_frames, n, dev_n}, s)))
-    return rc;
-  // (the sizes in a kernel of their own: made inside the scan, each of its
-  // three values repeated the frame's random loads, c2 0.238 -> 0.307 ms)
-  if (n) {
-    hipLaunchKernelGGL(k_rs_sizes, gn, dim3(FT), 0, s, dev_frames, n, dev_n, (const uint64_t*)a,
-                       (const uint64_t*)b, off, cnt, orph, (const uint64_t*)st, starts);
-    if ((rc = hip_err(hipGetLastError()))) return rc;
-  }
-  // output offsets, frame counts and orphan ranks
-  if ((rc = scan3<scan3_spec<op_sum, false, true>, scan3_spec<op_sum, false, true>, scan3_spec<op_sum, false, true>>(
-           scan3_args{{off, cnt, orph}, {tot + 0, tot + 2, tot + 3}}, n, part, gen_load{}, s)))
-    return rc;
-  hipLaunchKernelGGL(k_rs_msgs, gn, dim3(FT), 0, s, dev_frames, dev_n, n, (const uint64_t*)(tot + 1),
-                     (const uint64_t*)off,
-                     (const uint64_t*)cnt, (const uint64_t*)b, (const uint64_t*)starts, (const uint64_t*)orph,
-                     out_cap, dev_msgs, msg_cap, dev_nmsgs, ctx->err, utf8 ? umap : nullptr, utiles, ro.lo);
-  if ((rc = hip_err(hipGetLastError()))) return rc;
-  const gparams G = gather_params(G_REASM, dev_src, src_len, dev_frames, off, n, dev_n, dev_out, out_cap, ctx->err);
-  if ((rc = launch_gather(G, tmap, ntiles, s))) return rc;
-  if (utf8) {
-    // (the UTF-8 tile map: k_rs_msgs)
-    hipLaunchKernelGGL(k_utf8, dim3(grid_for(utiles, 1, 4096)), dim3(FT), 0, s, (const uint8_t*)G.out, G.out_lo,
-                       out_cap, (const uint64_t*)(tot + 1), dev_msgs, msg_cap, (const uint64_t*)umap, utiles);
-    if ((rc = hip_err(hipGetLastError()))) return rc;
-  }
-  return XYWS_OK;
+  if (c.rc) return c.rc;
+  return reassemble_run(ctx, c, tab_plain{dev_frames}, dev_src, src_len, n, dev_n, opts, dev_out, out_cap, dev_msgs,
+                        msg_cap, dev_nmsgs, nullptr);
+}
+
+int xyws_reassemble_stream(xyws_ctx* ctx, const void* dev_src, uint64_t src_len, const xyws_frame* dev_frames,
+                           uint64_t n, const uint64_t* dev_n, uint32_t opts, const xyws_msg_carry* dev_mc_in,
+                           xyws_msg_carry* dev_mc_out, void* dev_out, uint64_t out_cap, xyws_message* dev_msgs,
+                           uint64_t msg_cap, uint64_t* dev_nmsgs, void* stream) {
+  if (!ctx || (!dev_frames && n) || (!dev_src && src_len) || (!dev_out && out_cap) || (!dev_msgs && msg_cap) ||
+      n == U64MAX)
+    return XYWS_ERR_INVALID;
+  call_scope c(ctx, stream);
+  if (c.rc) return c.rc;
+  // (the kernels' count includes the virtual item in front of frame 0)
+  return reassemble_run(ctx, c, tab_stream{dev_frames, dev_mc_in, src_len}, dev_src, src_len, n + 1, dev_n, opts,
+                        dev_out, out_cap, dev_msgs, msg_cap, dev_nmsgs, dev_mc_out);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@ Names, argument meaning and error behaviour follow the reference headers
   classify_frames                  websocket_check_parser_result's policy
                                    (example/include/common/websocket.h:81-108)
   reassemble                       FIN=0 chains -> messages (+ UTF-8 check)
+  message_assembler.feed           the same across recv boundaries (xyws_reassemble_stream)
   shard_plan / shard_plan_frames   one batch cut at frame boundaries across devices
                                    (a host-side header walk)
 
@@ -447,6 +448,57 @@ def reassemble(src, frames_t, n, opts=0, out_cap=None, msg_cap=None, dev_n=None,
                                 opts, C.c_void_p(out.data_ptr()), cap, C.c_void_p(msgs.data_ptr()), mcap,
                                 C.c_void_p(cnt.data_ptr()), _stream(t)), "xyws_reassemble")
     return out, msgs, cnt
+
+
+class message_assembler:
+    """xyws_reassemble across batch boundaries (xyws_reassemble_stream): holds
+    the device-resident xyws_msg_carry of one connection, as frame_decoder
+    holds its xyws_carry. feed() takes each batch frame_decoder.decode()
+    decoded, with that call's frame table, in order."""
+
+    def __init__(self, device=None, opts=_lib.REASM_UTF8, ctx=None):
+        import torch
+        self.ctx = ctx if ctx is not None else context(device)
+        self.device = torch.device("cuda", self.ctx.device)
+        self.carry_t = torch.zeros(64, dtype=torch.uint8, device=self.device)
+        self.opts = opts
+
+    def reset(self):
+        self.carry_t.zero_()
+
+    def carry(self):
+        """Host copy of the carry (synchronizes)."""
+        return _lib.MsgCarry.from_buffer_copy(self.carry_t.cpu().numpy().tobytes())
+
+    def feed(self, src, frames_t, n, dev_n=None, out=None, msgs=None, out_cap=None, msg_cap=None):
+        """One batch: returns (out, messages tensor (msg_cap*40 bytes), count
+        tensor) like reassemble(); record 0 continues the message the last
+        batch left open (MSG_CONTINUED). msg_cap defaults to n + 1 records."""
+        import torch
+        t = _dev_u8(src)
+        if out is not None:
+            out = _dev_u8(out)
+            cap = out.numel() if out_cap is None else out_cap
+            if cap > out.numel():
+                raise XywsError(-1, "out_cap exceeds the out tensor")
+        else:
+            cap = t.numel() if out_cap is None else out_cap
+            out = torch.zeros(max(cap, 1), dtype=torch.uint8, device=t.device)
+        if msgs is not None:
+            msgs = _dev_u8(msgs)
+            mcap = msgs.numel() // 40 if msg_cap is None else msg_cap
+            if mcap * 40 > msgs.numel():
+                raise XywsError(-1, "msg_cap exceeds the msgs tensor")
+        else:
+            mcap = n + 1 if msg_cap is None else msg_cap
+            msgs = torch.zeros(max(mcap, 1) * 40, dtype=torch.uint8, device=t.device)
+        cnt = torch.zeros(1, dtype=torch.int64, device=t.device)
+        cp = C.c_void_p(self.carry_t.data_ptr())
+        check(self.ctx.L.xyws_reassemble_stream(
+            self.ctx.h, C.c_void_p(t.data_ptr()), t.numel(), _opt_ptr(frames_t), n, _opt_ptr(dev_n), self.opts,
+            cp, cp, C.c_void_p(out.data_ptr()), cap, C.c_void_p(msgs.data_ptr()), mcap,
+            C.c_void_p(cnt.data_ptr()), _stream(t)), "xyws_reassemble_stream")
+        return out, msgs, cnt
 
 
 class RecvArena:
