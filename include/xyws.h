@@ -12,6 +12,9 @@
  *     include/xynet/http/websocket_frame_header.h:226-385      state carried in xyws_carry)
  *   websocket_recv_data: parse -> result -> websocket_mask   xyws_decode_stream,
  *     example/include/common/websocket.h:110-134               xyws_decode_indexed
+ *   the websocket_recv_data loop of every connection, run    xyws_decode_streams (the recv
+ *     once per coroutine                                       buffers of many connections,
+ *     example/include/common/websocket.h:110-134               one launch)
  *   enum class websocket_flags                               XYWS_FLAG_* (same encoding)
  *     include/xynet/http/websocket_frame_header.h:42-58
  *   websocket_frame_header_parser (incremental, one header)  xyws_parser_* (runs the stream
@@ -531,6 +534,47 @@ int xyws_shard_plan(const void* host_batch, uint64_t len, const xyws_carry* carr
  * values (a negative frame_off, a header carried in, is not one) and len. */
 int xyws_shard_plan_frames(const xyws_frame* frames, uint64_t n, uint64_t len, uint32_t n_shards,
                            uint64_t* bounds);
+
+/* ---- many connections, one call ------------------------------------------
+ * What an io_uring service holds after one sweep of its completion queue: a
+ * few hundred bytes to a few KiB for each of hundreds or thousands of
+ * connections, every connection with a parser state of its own. One launch
+ * decodes them all, one wave per connection, thousands side by side.
+ *
+ *  - Entry i is decoded exactly as xyws_decode_stream(ctx, buf_i, len_i,
+ *    carry_i, carry_i, frames_i, cap_i, &dev_nframes[i], opts, stream) would
+ *    decode it: the bytes, the descriptors with their status bits, the count
+ *    (which may exceed cap_i), the carry and its frames_total.
+ *  - Buffers may have any alignment and any length. Bytes outside
+ *    [buf_i, buf_i + len_i) are never written; two connections' buffers may
+ *    share a 16-byte line, as adjacent ranges of one receive slab do.
+ *  - dev_conns is device memory. The entries' buffers must not overlap, and a
+ *    carry must not appear in two entries of one call.
+ *  - n == 0 returns XYWS_OK and launches nothing.
+ *  - opts may be XYWS_OPT_PARSE_ONLY or XYWS_OPT_UNMASKED_HINT (accepted and
+ *    ignored: nothing is speculated here); every other bit is
+ *    XYWS_ERR_INVALID. A null ctx, or null dev_conns with n > 0, is
+ *    XYWS_ERR_INVALID.
+ *  - The call is one launch. It uses no context scratch, binds no scratch
+ *    slot of the stream and reads or writes no policy word: it needs no
+ *    reserve and can be captured into a hipGraph at once, calls on different
+ *    streams run concurrently, and the stream's history for
+ *    xyws_decode_stream stays as it was.
+ *  - Meant for many connections of up to about 1 MiB each. It is correct for
+ *    any length, but one wave walks a connection from end to end: one very
+ *    long stream belongs to xyws_decode_stream. */
+/* One connection's share of a multi-connection decode. 64 bytes. */
+typedef struct xyws_conn {
+  void*       buf;         /* device: the bytes this connection received since its last call */
+  uint64_t    len;         /* 0 allowed: the connection is left as it is, its count is 0 */
+  xyws_carry* carry;       /* device; read, then written (in == out). NULL: a fresh stream, no state kept */
+  xyws_frame* frames;      /* device, nullable: up to cap descriptors, offsets relative to buf */
+  uint64_t    cap;
+  uint64_t    reserved[3]; /* zero */
+} xyws_conn;
+int xyws_decode_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, uint64_t n,
+                        uint64_t* dev_nframes /* n entries, nullable */,
+                        uint32_t opts, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

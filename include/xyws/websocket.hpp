@@ -297,6 +297,15 @@ class frame_decoder {
   std::uint32_t opts_;
 };
 
+// The recv buffers of many connections in one launch (xyws_decode_streams):
+// dev_conns is a device table of n xyws_conn entries, each decoded as
+// frame_decoder::decode would decode it from its own carry; dev_nframes
+// (nullable device pointer, n entries) receives the counts.
+inline void decode_streams(context& ctx, const xyws_conn* dev_conns, std::uint64_t n, std::uint64_t* dev_nframes,
+                           std::uint32_t opts = 0, void* stream = nullptr) {
+  check(xyws_decode_streams(ctx.native(), dev_conns, n, dev_nframes, opts, stream), "xyws_decode_streams");
+}
+
 // class websocket_frame_header (websocket_frame_header.h:179-224): a header in
 // a 14-byte array. As in the reference, the masked constructors keep the key
 // beside the header and build it with the key bytes zero (:183-202); with_key()

@@ -129,7 +129,14 @@ class ArenaResult(C.Structure):
                 ("frames", C.POINTER(Frame)), ("carry", Carry)]
 
 
-assert C.sizeof(Frame) == 32 and C.sizeof(Carry) == 64
+class Conn(C.Structure):
+    """xyws_conn (include/xyws.h), 64 bytes: one connection's entry of an
+    xyws_decode_streams table (every pointer a device address)."""
+    _fields_ = [("buf", C.c_void_p), ("len", C.c_uint64), ("carry", C.c_void_p), ("frames", C.c_void_p),
+                ("cap", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+assert C.sizeof(Frame) == 32 and C.sizeof(Carry) == 64 and C.sizeof(Conn) == 64
 assert C.sizeof(ArenaResult) == 104
 XYWS_ERR_AGAIN = -6
 ARENA_SLOTS = 8
@@ -205,6 +212,11 @@ def load():
     L.xyws_decode_stream.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, u32, vp]
     L.xyws_decode_stream_iov.restype = i32
     L.xyws_decode_stream_iov.argtypes = [vp, vp, u32, vp, vp, vp, u64, vp, u32, vp]
+    L.xyws_decode_streams.restype = i32
+    L.xyws_decode_streams.argtypes = [vp, vp, u64, vp, u32, vp]
+    # (no HIP call: window bytes, lanes per connection, connections per workgroup, grid cap)
+    L.xyws_debug_streams_geometry.restype = i32
+    L.xyws_debug_streams_geometry.argtypes = [C.POINTER(u64)]
     # ABI 2
     L.xyws_parser_create.restype = i32
     L.xyws_parser_create.argtypes = [vp, C.POINTER(vp)]

@@ -11,6 +11,8 @@ Names, argument meaning and error behaviour follow the reference headers
   websocket_mask                   include/xynet/http/websocket_frame_mask.h:6-25
   frame_decoder.decode             the batched websocket_recv_data
                                    (example/include/common/websocket.h:110-134)
+  connection_group.decode          the same for many connections at once, one launch
+                                   (xyws_decode_streams: one coroutine's loop per wave)
   encode_frames                    echo_once's replies, batched on the device
                                    (example/websocket/websocket_echo.cpp:18-27)
   classify_frames                  websocket_check_parser_result's policy
@@ -284,6 +286,98 @@ class frame_decoder:
             _stream(ts[0]) if ts else C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
             "xyws_decode_stream_iov")
         return DecodeResult(frames_t, n_t, cap)
+
+
+class GroupResult:
+    """Counts and frames of one connection_group.decode call, item k being the
+    k-th (conn_id, buffer) pair of that call (host copies on demand). They
+    live in the group's tensors: valid until the group's next decode."""
+
+    def __init__(self, group, ids):
+        self.group, self.ids = group, ids
+        self._counts = None
+
+    def nframes(self, k):
+        if self._counts is None:
+            self._counts = self.group.counts_t[:max(len(self.ids), 1)].cpu().tolist()
+        if not 0 <= k < len(self.ids):
+            raise IndexError(k)
+        return self._counts[k]
+
+    def frames(self, k):
+        g = self.group
+        n = min(self.nframes(k), g.cap)
+        row = g.frames_t[self.ids[k] * g.cap * 32:]
+        return _frames_from_device(row, n)[0]
+
+
+class connection_group:
+    """The decoder states of n connections and one xyws_decode_streams call
+    for whatever a sweep of the completion queue brought: decode() takes the
+    (conn_id, device buffer) pairs of the connections that received bytes
+    and decodes them all in one launch, each from its own device-resident
+    carry, as frame_decoder.decode would one by one. Owns the carries (n x 64
+    bytes, zeroed), a descriptor table of cap rows per connection and a count
+    vector."""
+    RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
+
+    def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
+        import torch
+        self.ctx = ctx if ctx is not None else context(device)
+        self.device = torch.device("cuda", self.ctx.device)
+        self.n, self.cap = int(n), int(cap)
+        self.opts = _lib.OPT_PARSE_ONLY if parse_only else 0
+        self.carry_t = torch.zeros(max(self.n, 1) * 64, dtype=torch.uint8, device=self.device)
+        self.frames_t = torch.empty(max(self.n * self.cap, 1) * 32, dtype=torch.uint8, device=self.device)
+        self.counts_t = torch.zeros(max(self.n, 1), dtype=torch.int64, device=self.device)
+        self._host = [torch.zeros(max(self.n, 1) * 8, dtype=torch.int64).pin_memory() for _ in range(self.RING)]
+        self._dev = [torch.empty(max(self.n, 1) * 8, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
+        self._done = [None] * self.RING
+        self._turn = 0
+
+    def reset(self, ids=None):
+        """Fresh streams: every connection, or those in `ids`."""
+        if ids is None:
+            self.carry_t.zero_()
+        else:
+            for i in ids:
+                self.carry_t[64 * i:64 * i + 64].zero_()
+
+    def carry(self, conn_id):
+        """Host copy of a connection's carry (synchronizes)."""
+        if not 0 <= conn_id < self.n:
+            raise XywsError(-1, "no such connection")
+        return Carry.from_buffer_copy(self.carry_t[64 * conn_id:64 * conn_id + 64].cpu().numpy().tobytes())
+
+    def decode(self, items):
+        """items: (conn_id, device uint8 tensor) pairs, each id at most once.
+        Every buffer is decoded in place; returns a GroupResult."""
+        import torch
+        items = [(int(i), _dev_u8(t)) for i, t in items]
+        ids = [i for i, _ in items]
+        if len(set(ids)) != len(ids) or any(not 0 <= i < self.n for i in ids):
+            raise XywsError(-1, "connection ids must be distinct and below n")
+        if any(t.device != self.device for _, t in items):
+            raise XywsError(-1, "a buffer on another device than the group's")
+        k = self._turn
+        self._turn = (k + 1) % self.RING
+        if self._done[k] is not None:
+            self._done[k].synchronize()
+        tab = self._host[k].numpy().reshape(-1, 8)  # xyws_conn: buf, len, carry, frames, cap, reserved[3]
+        cbase, fbase = self.carry_t.data_ptr(), self.frames_t.data_ptr()
+        for row, (i, t) in zip(tab, items):
+            row[0], row[1], row[2] = t.data_ptr(), t.numel(), cbase + 64 * i
+            row[3], row[4] = (fbase + 32 * self.cap * i, self.cap) if self.cap else (0, 0)
+        m = len(items)
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            self._dev[k][:8 * m].copy_(self._host[k][:8 * m], non_blocking=True)
+            check(self.ctx.L.xyws_decode_streams(self.ctx.h, C.c_void_p(self._dev[k].data_ptr()), m,
+                                                 C.c_void_p(self.counts_t.data_ptr()), self.opts,
+                                                 C.c_void_p(stream.cuda_stream)), "xyws_decode_streams")
+            self._done[k] = torch.cuda.Event()
+            self._done[k].record(stream)
+        return GroupResult(self, ids)
 
 
 def decode_indexed(buf, starts, frames=True, parse_only=False):
