@@ -51,6 +51,22 @@ def test_abi_version_and_strerror():
     assert lib.xyws_strerror(-2) == b"HIP runtime error"
 
 
+def test_unmask_geometry_without_a_device():
+    """xyws_debug_unmask_geometry (internal): exported, bound, refuses null,
+    and reads k_unmask_range's geometry with no device."""
+    lib = L.load()
+    out = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True).stdout
+    assert "xyws_debug_unmask_geometry" in {line.split()[-1] for line in out.splitlines() if " T " in line}
+    assert lib.xyws_debug_unmask_geometry(None) == -1
+    g = (C.c_uint64 * 4)()
+    assert lib.xyws_debug_unmask_geometry(g) == 0
+    tile, threads, per_cu, slots = g
+    assert tile % (16 * threads) == 0 and tile >= 16 * threads  # (whole 16-byte chunks per lane)
+    assert threads % 64 == 0 and 64 <= threads <= 1024
+    assert per_cu >= 1 and per_cu * threads <= 2048
+    assert slots >= 2
+
+
 def test_null_arguments_rejected():
     lib = L.load()
     assert lib.xyws_ctx_create(0, None) == -1

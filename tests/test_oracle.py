@@ -84,6 +84,30 @@ def test_unmask_vectors(oracle):
             assert oracle.digest(data) == v["out_digest"]
 
 
+def test_mask_is_the_plain_formula_at_the_unmask_tests_ranges(oracle):
+    """tests/golden/unmask.json pins oracle.mask to the reference up to 1 MiB;
+    tests/test_gpu_unmask.py takes expected bytes from it at tens of MiB. At
+    every (n, phase) those tests use: oracle.mask is data[j] ^= key_le[(phase
+    + j) % 4] in numpy, returns phase + n, and is the reference's own
+    websocket_mask where oracle/_ref was built."""
+    import os
+    import unmask_cases as uc
+    from oracle.oracle import Reference, ref_lib_path
+    T, G = uc.tiles_and_grid()
+    ranges = uc.all_ranges(T, G)
+    assert len(ranges) == 24 + 7
+    ref = Reference() if os.path.exists(ref_lib_path()) else None
+    src = uc.source(max(n for n, _, _ in ranges))
+    for n, phase, key in ranges:
+        data = src[:n].copy()
+        assert oracle.mask(data, key, phase) == phase + n
+        assert np.array_equal(data, uc.plain_mask(src[:n], key, phase)), (n, phase)
+        if ref is not None:
+            r = src[:n].copy()
+            assert ref.mask(r, key, phase) == phase + n
+            assert np.array_equal(r, data), (n, phase)
+
+
 def _frames(fr):
     return [[f.frame_off, f.payload_off, f.payload_len, bytes(f.key).hex(), f.flags, f.hdr_len,
              f.status & 1] for f in fr]

@@ -217,6 +217,9 @@ def load():
     # (no HIP call: window bytes, lanes per connection, connections per workgroup, grid cap)
     L.xyws_debug_streams_geometry.restype = i32
     L.xyws_debug_streams_geometry.argtypes = [C.POINTER(u64)]
+    # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
+    L.xyws_debug_unmask_geometry.restype = i32
+    L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]
     # ABI 2
     L.xyws_parser_create.restype = i32
     L.xyws_parser_create.argtypes = [vp, C.POINTER(vp)]

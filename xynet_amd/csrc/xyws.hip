@@ -540,6 +540,18 @@ int xyws_debug_plan_reserve(int ncu, uint64_t max_batch_bytes, uint64_t max_fram
   return XYWS_OK;
 }
 
+// Internal (tests, no HIP call): the geometry of k_unmask_range and of the
+// scratch slots its claim counters live in. out: {tile bytes, threads per
+// workgroup, workgroups per CU, scratch slots of a context}.
+int xyws_debug_unmask_geometry(uint64_t out[4]) {
+  if (!out) return XYWS_ERR_INVALID;
+  out[0] = (uint64_t)UNMASK_NT * UNMASK_U * 16;
+  out[1] = UNMASK_NT;
+  out[2] = UNMASK_WPC;
+  out[3] = XYWS_SLOTS;
+  return XYWS_OK;
+}
+
 // xyws_unmask with ctx->mu held: the claim counter is the stream's scratch
 // slot's when the stream has one bound or a free slot to bind (eager launches
 // only); a captured launch, or a stream finding every slot bound to others,
