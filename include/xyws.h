@@ -21,10 +21,15 @@
  *     include/xynet/http/websocket_frame_header.h:226-385      decoder in parse-only mode)
  *   detail::websocket_frame_header_builder                   xyws_header_build (one header),
  *     include/xynet/http/websocket_frame_header.h:136-175      xyws_encode_frames (batched, device)
- *   echo_once: header{FIN|TEXT, len} + send(header, data)    xyws_encode_frames
- *     example/websocket/websocket_echo.cpp:18-27
- *   websocket_check_parser_result (close policy)             xyws_classify_frames
- *     example/include/common/websocket.h:81-108
+ *   echo_once: header{FIN|TEXT, len} + send(header, data)    xyws_encode_frames (one connection),
+ *     example/websocket/websocket_echo.cpp:18-27               xyws_reply_streams (many)
+ *   websocket_check_parser_result (close policy)             xyws_classify_frames (one connection),
+ *     example/include/common/websocket.h:81-108                xyws_reply_streams (many)
+ *   websocket_send_close: header{FIN|CLOSE, 2} + code        xyws_reply_streams (the close frame
+ *     example/include/common/websocket.h:70-76                 ends the connection's reply)
+ *   websocket_echo's loop: recv_data, check, echo_once or    xyws_decode_streams, then
+ *     send_close, once per coroutine                           xyws_reply_streams: two launches
+ *     example/websocket/websocket_echo.cpp:29-50               for a whole sweep
  *   (new) FIN=0 message reassembly + UTF-8 validation        xyws_reassemble (one batch),
  *                                                              xyws_reassemble_stream (messages, frames
  *                                                              and UTF-8 sequences cut by a recv
@@ -575,6 +580,108 @@ typedef struct xyws_conn {
 int xyws_decode_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, uint64_t n,
                         uint64_t* dev_nframes /* n entries, nullable */,
                         uint32_t opts, void* stream);
+
+/* ---- many connections, one reply call -------------------------------------
+ * The other half of the reference's per-connection loop, for every connection
+ * of an xyws_decode_streams call at once: websocket_check_parser_result,
+ * echo_once and websocket_send_close (example/include/common/websocket.h:70-108,
+ * example/websocket/websocket_echo.cpp:18-27). dev_conns and dev_nframes are
+ * the table and the counts the xyws_decode_streams call just before it used
+ * and wrote (of dev_conns[i] only buf, len, frames and cap are read; buf holds
+ * the decoded bytes); dev_replies[i] names connection i's send buffer, its
+ * reply carry and (nullable) a row of verdicts. Server role: replies are
+ * unmasked. Per connection, with t = dev_nframes[i] and the carry rc:
+ *
+ *  1. Overflow. rc.status has XYWS_RPL_OVERFLOW, or t > cap, or frames is
+ *     NULL while t > 0: nothing is written to out or verdicts, the result is
+ *     reply_len 0 with status OVERFLOW, and rc.status keeps OVERFLOW (the
+ *     table no longer covers the stream: the caller closes the connection).
+ *  2. Closed. rc.close_code != 0: nothing is written; the result is reply_len
+ *     0, status CLOSED, close_code from the carry, first_close XYWS_NPOS. The
+ *     carry is unchanged.
+ *  3. Continued frame. k = min(rc.frame_remaining, len); with rc.echoing the
+ *     bytes buf[0..k) go to the reply first. frame_remaining -= k.
+ *  4. Verdict j is xyws_classify_frames' for this table with src = buf,
+ *     src_len = len, max_payload and policy; it is stored to verdicts[j] when a
+ *     row is given. c = the first j with a close code, or t.
+ *  5. Every frame j < c with (action_mask >> action_j) & 1 is answered:
+ *     header(reply_flags_j, payload_len_j), built as xyws_encode_frames builds
+ *     it without keys (XYWS_ENC_FRAME_OPCODE: the frame's own opcode and FIN, a
+ *     ping answered as a pong), then the payload bytes that lie in this batch:
+ *     inb = min(payload_len, len - payload_off), 0 if payload_off >= len (only
+ *     the last frame can be clipped). Nothing outside [buf, buf + len) is
+ *     read, whatever the table says (whole 16-byte lines that hold one of its
+ *     bytes are loaded). After frame j: frame_remaining = payload_len - inb,
+ *     echoing = answered.
+ *  6. Close. If c < t the reference's close frame 0x88 0x02 hi lo with
+ *     verdict c's close_code ends the reply; rc.close_code = that code,
+ *     first_close = c, status CLOSED. Frames after c get verdicts, no reply.
+ *     The close is decided on the header alone: a cut frame that is too long
+ *     closes 1009 in the call that sees its header.
+ *  7. frames_seen += t, replies_total += answered.
+ *  8. Reply bytes at positions >= out_cap are not written; reply_len is the
+ *     full length, XYWS_RPL_TRUNCATED is set when reply_len > out_cap, and the
+ *     carry is exact whatever out_cap. No byte outside
+ *     [out, out + min(reply_len, out_cap)) is written: neighbouring
+ *     connections' out ranges may share a 16-byte line, as in a send slab.
+ *  9. out_cap >= len + 13 always suffices for a table xyws_decode_streams
+ *     wrote: a frame whose header bytes lie in this batch has a reply header
+ *     no longer than them (2, 4 or 10 bytes against 2..14 received, the reply
+ *     length form being the minimal one), so it adds nothing; only the one
+ *     frame whose header was carried in (frame_off < 0) can have a reply
+ *     header longer than its header bytes in this batch, by at most 10 - 1
+ *     bytes (at least one header byte arrives with the batch that completes
+ *     it); the close frame adds 4: len + 9 + 4.
+ *
+ * So for a stream cut at any points into calls, the concatenation of the
+ * calls' replies equals xyws_encode_frames of the unsplit stream's frames
+ * before its first close (verdicts of xyws_classify_frames), followed by the
+ * close frame if any; while the connection is open rc.frame_remaining equals
+ * xyws_carry.payload_remaining after every call.
+ *
+ * Like xyws_decode_streams the call is one launch (one wave per connection),
+ * uses no context scratch, no scratch slot and no policy word, reads no
+ * device state on the host, needs no reserve, can be captured into a hipGraph
+ * at once and runs concurrently on different streams. n == 0 returns XYWS_OK
+ * and launches nothing. XYWS_ERR_INVALID: a null ctx; null dev_conns,
+ * dev_nframes or dev_replies with n > 0; flags with XYWS_FLAG_HAS_MASK;
+ * enc_opts bits other than XYWS_ENC_FRAME_OPCODE; unknown policy bits;
+ * action_mask bits above 1 << XYWS_ACT_CLOSE. The out ranges must not overlap
+ * each other or a recv buffer; a reply carry must not appear twice in a call. */
+typedef struct xyws_reply_carry {   /* 32 bytes; all zero = a fresh connection */
+  uint64_t frame_remaining; /* payload bytes of the frame cut by the last batch end, still to come */
+  uint64_t frames_seen;     /* sum of the table sizes of all calls so far */
+  uint64_t replies_total;   /* frames answered so far */
+  uint16_t close_code;      /* != 0: closed with this code (sticky; later calls write nothing) */
+  uint8_t  echoing;         /* 1: the frame_remaining bytes belong to a reply already begun */
+  uint8_t  status;          /* XYWS_RPL_OVERFLOW, sticky */
+  uint8_t  reserved[4];     /* zero */
+} xyws_reply_carry;
+
+typedef struct xyws_reply_conn {    /* 32 bytes; entry i goes with dev_conns[i] */
+  void*             out;      /* device: this connection's send buffer */
+  uint64_t          out_cap;
+  xyws_reply_carry* rc;       /* device; read, then written. NULL: fresh, no state kept */
+  xyws_verdict*     verdicts; /* device, nullable: one per frame of its table */
+} xyws_reply_conn;
+
+typedef struct xyws_reply_result {  /* 32 bytes */
+  uint64_t reply_len;   /* bytes of the reply (may exceed out_cap: then TRUNCATED) */
+  uint64_t first_close; /* index in this call's table of the frame that closed it, or XYWS_NPOS */
+  uint32_t answered;    /* frames whose reply header this call wrote */
+  uint16_t close_code;  /* the carry's after this call */
+  uint16_t status;      /* XYWS_RPL_* */
+  uint64_t reserved;
+} xyws_reply_result;
+#define XYWS_RPL_TRUNCATED 0x1u
+#define XYWS_RPL_CLOSED    0x2u  /* closed by this call or an earlier one */
+#define XYWS_RPL_OVERFLOW  0x4u
+
+int xyws_reply_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const uint64_t* dev_nframes,
+                       const xyws_reply_conn* dev_replies, uint64_t n,
+                       uint64_t max_payload, uint32_t policy, uint8_t flags, uint32_t enc_opts,
+                       uint32_t action_mask, xyws_reply_result* dev_results /* n, nullable */,
+                       void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -306,6 +306,25 @@ inline void decode_streams(context& ctx, const xyws_conn* dev_conns, std::uint64
   check(xyws_decode_streams(ctx.native(), dev_conns, n, dev_nframes, opts, stream), "xyws_decode_streams");
 }
 
+// The answers to what decode_streams found, in one launch (xyws_reply_streams):
+// dev_conns and dev_nframes are that call's table and counts, dev_replies[i]
+// names connection i's send buffer, reply carry and verdict row. Every frame
+// before the connection's first close whose action is in action_mask is echoed
+// with `flags` (default: echo_once's FIN | TEXT; with XYWS_ENC_FRAME_OPCODE its
+// own opcode, a ping as a pong), a frame cut by the batch end is continued by
+// the next call, and a close verdict ends the reply with websocket_send_close's
+// frame. dev_results (nullable device pointer, n entries) receives the lengths.
+inline void reply_streams(context& ctx, const xyws_conn* dev_conns, const std::uint64_t* dev_nframes,
+                          const xyws_reply_conn* dev_replies, std::uint64_t n, std::uint64_t max_payload,
+                          std::uint32_t policy = 0,
+                          websocket_flags flags = websocket_flags::WS_FINAL_FRAME | websocket_flags::WS_OP_TEXT,
+                          std::uint32_t enc_opts = 0, std::uint32_t action_mask = 1u << XYWS_ACT_DATA,
+                          xyws_reply_result* dev_results = nullptr, void* stream = nullptr) {
+  check(xyws_reply_streams(ctx.native(), dev_conns, dev_nframes, dev_replies, n, max_payload, policy,
+                           static_cast<std::uint8_t>(flags), enc_opts, action_mask, dev_results, stream),
+        "xyws_reply_streams");
+}
+
 // class websocket_frame_header (websocket_frame_header.h:179-224): a header in
 // a 14-byte array. As in the reference, the masked constructors keep the key
 // beside the header and build it with the key bytes zero (:183-202); with_key()

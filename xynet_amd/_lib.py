@@ -136,7 +136,26 @@ class Conn(C.Structure):
                 ("cap", C.c_uint64), ("reserved", C.c_uint64 * 3)]
 
 
+class ReplyCarry(C.Structure):
+    """xyws_reply_carry (include/xyws.h), 32 bytes: one connection's state between xyws_reply_streams calls."""
+    _fields_ = [("frame_remaining", C.c_uint64), ("frames_seen", C.c_uint64), ("replies_total", C.c_uint64),
+                ("close_code", C.c_uint16), ("echoing", C.c_uint8), ("status", C.c_uint8),
+                ("reserved", C.c_uint8 * 4)]
+
+
+class ReplyConn(C.Structure):
+    """xyws_reply_conn (include/xyws.h), 32 bytes: entry i goes with entry i of the xyws_conn table."""
+    _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("rc", C.c_void_p), ("verdicts", C.c_void_p)]
+
+
+class ReplyResult(C.Structure):
+    """xyws_reply_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("reply_len", C.c_uint64), ("first_close", C.c_uint64), ("answered", C.c_uint32),
+                ("close_code", C.c_uint16), ("status", C.c_uint16), ("reserved", C.c_uint64)]
+
+
 assert C.sizeof(Frame) == 32 and C.sizeof(Carry) == 64 and C.sizeof(Conn) == 64
+assert C.sizeof(ReplyCarry) == 32 and C.sizeof(ReplyConn) == 32 and C.sizeof(ReplyResult) == 32
 assert C.sizeof(ArenaResult) == 104
 XYWS_ERR_AGAIN = -6
 ARENA_SLOTS = 8
@@ -145,6 +164,8 @@ NPOS = (1 << 64) - 1
 ENC_FRAME_OPCODE = 0x1
 ACT_DATA, ACT_PING, ACT_PONG, ACT_CLOSE = 0, 1, 2, 3
 POL_FRAGMENTS, POL_UNMASKED, POL_STRICT = 0x1, 0x2, 0x4
+POL_REFERENCE = 0x8
+RPL_TRUNCATED, RPL_CLOSED, RPL_OVERFLOW = 0x1, 0x2, 0x4  # xyws_reply_result.status
 REASM_UTF8 = 0x1
 MSG_COMPLETE, MSG_UTF8_BAD, MSG_INTERRUPTED, MSG_TRUNCATED, MSG_ORPHANS = 0x1, 0x2, 0x4, 0x8, 0x10
 MSG_CONTINUED, MSG_UNCHECKED = 0x20, 0x40  # xyws_reassemble_stream only
@@ -217,6 +238,11 @@ def load():
     # (no HIP call: window bytes, lanes per connection, connections per workgroup, grid cap)
     L.xyws_debug_streams_geometry.restype = i32
     L.xyws_debug_streams_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_reply_streams.restype = i32
+    L.xyws_reply_streams.argtypes = [vp, vp, vp, vp, u64, u64, u32, u8, u32, u32, vp, vp]
+    # (no HIP call: frames per tile, bytes per copy step, grid cap, wave size)
+    L.xyws_debug_reply_geometry.restype = i32
+    L.xyws_debug_reply_geometry.argtypes = [C.POINTER(u64)]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]

@@ -25,6 +25,7 @@
 #include "xyws.h"
 #include "xyws_device.h"
 #include "xyws_ctx.h"
+#include "xyws_frameops.h"
 
 using namespace xyws_internal;
 
@@ -36,43 +37,7 @@ constexpr uint32_t GTILE = 16384;      // gather tile (bytes of output)
 constexpr uint32_t GLDS = 512;         // items staged per tile
 constexpr uint64_t U64MAX = ~0ull;
 
-// ---------------------------------------------------------------- header build
-// detail::websocket_frame_header_builder (:136-175) into four little-endian
-// words (byte i = w[i/4] >> 8*(i%4)); returns H. The key word kw (wire bytes,
-// little-endian) is written only when has_key, as the builder copies the
-// key only for a non-null mask (:168-173). Register-only (no byte array).
-__host__ __device__ inline uint32_t build_header(uint32_t flags, uint64_t len, bool has_key, uint32_t kw,
-                                                 uint32_t w[4]) {
-  const uint32_t b0 = ((flags & XYWS_FLAG_FIN) ? 0x80u : 0u) | (flags & XYWS_FLAG_OP_MASK);
-  uint32_t b1 = (flags & XYWS_FLAG_HAS_MASK) ? 0x80u : 0u;
-  const bool masked = (flags & XYWS_FLAG_HAS_MASK) != 0;
-  const uint32_t k = has_key ? kw : 0u;
-  w[0] = w[1] = w[2] = w[3] = 0;
-  uint32_t h;
-  if (len < 126u) {
-    b1 |= (uint32_t)len;
-    w[0] = b0 | (b1 << 8);
-    if (masked) { w[0] |= k << 16; w[1] = k >> 16; }
-    h = 2;
-  } else if (len <= 0xFFFFu) {
-    b1 |= 126u;
-    w[0] = b0 | (b1 << 8) | ((uint32_t)(len >> 8) << 16) | ((uint32_t)(len & 0xFFu) << 24);
-    if (masked) w[1] = k;
-    h = 4;
-  } else {
-    b1 |= 127u;
-    // bytes 2..9: the length big-endian = the little-endian bytes of bswap64(len)
-    uint64_t be = 0;
-    for (int i = 0; i < 8; i++) be |= ((len >> (8 * i)) & 0xFFull) << (56 - 8 * i);
-    w[0] = b0 | (b1 << 8) | ((uint32_t)(be & 0xFFFFu) << 16);
-    w[1] = (uint32_t)(be >> 16);
-    w[2] = (uint32_t)(be >> 48);
-    if (masked) { w[2] |= k << 16; w[3] = k >> 16; }
-    h = 10;
-  }
-  return masked ? h + 4 : h;
-}
-
+// (build_header, reply_flags_of and classify_frame: xyws_frameops.h)
 XYWS_DEV uint64_t n_eff(uint64_t n, const uint64_t* dev_n) {
   if (!dev_n) return n;
   const uint64_t m = *dev_n;
@@ -367,10 +332,7 @@ XYWS_DEV uint64_t items_of(const gparams& G) {
 }
 
 XYWS_DEV uint32_t reply_flags(const gparams& G, uint32_t fflags) {
-  if (!(G.enc_opts & XYWS_ENC_FRAME_OPCODE)) return G.flags;
-  uint32_t op = fflags & XYWS_FLAG_OP_MASK;
-  if (op == XYWS_FLAG_OP_PING) op = XYWS_FLAG_OP_PONG;
-  return op | (fflags & XYWS_FLAG_FIN) | (G.flags & XYWS_FLAG_HAS_MASK);
+  return reply_flags_of(G.flags, G.enc_opts, fflags);
 }
 
 template <bool S = false>
@@ -809,31 +771,9 @@ __global__ void __launch_bounds__(FT) k_classify(const uint8_t* src, uint64_t sr
   const uint64_t ne = n_eff(n, dev_n);
   if (i >= ne) return;
   const xyws_frame f = frames[i];
-  const uint32_t op = f.flags & XYWS_FLAG_OP_MASK;
-  xyws_verdict v;
-  v.close_code = 0;
-  v.peer_code = 0;
-  v.action = op == XYWS_FLAG_OP_PING ? XYWS_ACT_PING : op == XYWS_FLAG_OP_PONG ? XYWS_ACT_PONG : XYWS_ACT_DATA;
-  v.reserved[0] = v.reserved[1] = v.reserved[2] = 0;
-  const bool proto = (f.status & (XYWS_ST_RSV | XYWS_ST_RESERVED_OPCODE | XYWS_ST_BAD_CONTROL)) != 0;
-  uint16_t code = 0;
-  if ((policy & XYWS_POL_STRICT) && proto) code = 1002;
-  else if (op == XYWS_FLAG_OP_CLOSE || ((policy & XYWS_POL_REFERENCE) && (op & 8u)))
-    code = 1000;  // (websocket.h:87-90: the opcode compared exactly, or its bit 3 as the reference tests it)
-  else if (!(f.flags & XYWS_FLAG_FIN) && !(policy & XYWS_POL_FRAGMENTS)) code = 1003;
-  else if (!(f.flags & XYWS_FLAG_HAS_MASK) && !(policy & XYWS_POL_UNMASKED)) code = 1008;
-  else if (f.payload_len > max_payload) code = 1009;
-  if (op == XYWS_FLAG_OP_CLOSE) {
-    v.action = XYWS_ACT_CLOSE;
-    const uint64_t p = (uint64_t)f.payload_off;
-    v.peer_code = 1005;  // (RFC 6455 7.4.1: no status code present)
-    if (f.payload_len >= 2 && p + 2 <= src_len) v.peer_code = (uint16_t)((src[p] << 8) | src[p + 1]);
-  }
-  if (code) {
-    v.close_code = code;
-    v.action = XYWS_ACT_CLOSE;
-    if (first) atomicMin(reinterpret_cast<unsigned long long*>(first), (unsigned long long)i);
-  }
+  const xyws_verdict v =
+      classify_frame(f.flags, f.status, (uint64_t)f.payload_off, f.payload_len, src, src_len, max_payload, policy);
+  if (v.close_code && first) atomicMin(reinterpret_cast<unsigned long long*>(first), (unsigned long long)i);
   out[i] = v;
 }
 

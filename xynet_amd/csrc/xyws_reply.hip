@@ -1,0 +1,352 @@
+// xyws_reply.hip — xyws_reply_streams: the answers to many connections' frames
+// written by one launch (the reference's websocket_check_parser_result,
+// echo_once and websocket_send_close, example/include/common/websocket.h:70-108
+// and example/websocket/websocket_echo.cpp:18-27, run once per coroutine).
+// The semantics are stated in include/xyws.h; this is how they are computed.
+//
+// As in k_decode_streams (xyws_streams.hip) connections are independent: one
+// wave (a 64-thread workgroup) takes one connection, connections are
+// grid-strided, no workgroup talks to another and nothing spins.
+//
+// A connection's table is taken in tiles of REPLY_TILE frames, one frame per
+// lane:
+//   1. each lane classifies its frame (classify_frame, xyws_frameops.h) and
+//      stores the verdict; the first close of the tile comes from a ballot;
+//   2. a frame before the close that is to be answered has the reply size
+//      header + the payload bytes that lie in this batch; the sizes are
+//      scanned across the wave (shuffles), and the tile's items go to LDS:
+//      start offset in the reply, header words and length, source offset.
+//      Item 0 is the carried prefix (the rest of a frame whose reply an earlier
+//      call began; first tile only), items 1..REPLY_TILE the frames, the last
+//      item the close frame (a 4-byte header without payload);
+//   3. the copy phase covers the tile's output range in 16-byte lines of the
+//      send buffer, one line per lane per step: the lane finds the item of its
+//      line's first byte by a binary search in the LDS offsets, walks the items
+//      that touch the line and composes their header and payload bytes in
+//      registers (payload bytes: one or two aligned 16-byte loads funnelled to
+//      the byte offset), then stores 16 bytes where the line lies wholly
+//      inside the tile's range and the connection's capacity, and byte by byte
+//      on the range's first and last line (a tile edge, or a line shared with a
+//      neighbouring connection's send buffer).
+// The state between tiles (reply length so far, frame_remaining, echoing,
+// answered, first close) is wave-uniform and held in scalars.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <mutex>
+
+#include "xyws.h"
+#include "xyws_device.h"
+#include "xyws_ctx.h"
+#include "xyws_frameops.h"
+
+#define REPLY_TILE 64u       // frames per tile: one per lane
+#define REPLY_LANES 64u      // lanes per connection: one wave
+#define REPLY_LINE 16u       // bytes a lane writes per copy step
+#define REPLY_GRID_CAP 8192u // 256 CUs x 32 one-wave workgroups; further connections are grid-strided
+#define REPLY_ITEMS (REPLY_TILE + 2u)  // the carried prefix, the frames, the close frame
+#define REPLY_CLOSE_ITEM (REPLY_TILE + 1u)
+
+typedef XYWS_GLOBAL uint16_t g_u16;
+
+using namespace xyws_internal;
+
+XYWS_DEV bytes16 line_of(const g_u8* aligned) {
+  const u32x4 x = *reinterpret_cast<const g_u32x4*>(aligned);
+  return bytes16{(uint64_t)x.x | ((uint64_t)x.y << 32), (uint64_t)x.z | ((uint64_t)x.w << 32)};
+}
+// The nb (1..16) bytes at address g, in the low bytes of the result (the bytes
+// above them are not defined). Only the 16-byte lines that hold one of the nb
+// bytes are loaded.
+XYWS_DEV bytes16 load_bytes(uint64_t g, uint32_t nb) {
+  const g_u8* const a = (const g_u8*)(g & ~15ull);
+  const uint32_t sh = (uint32_t)(g & 15u);
+  bytes16 v = shr_bytes(line_of(a), sh);
+  if (sh + nb > 16) {  // (sh >= 1 here)
+    const bytes16 y = shl_bytes(line_of(a + 16), 16 - sh);
+    v.lo |= y.lo;
+    v.hi |= y.hi;
+  }
+  return v;
+}
+
+XYWS_DEV uint64_t shfl64(uint64_t v, uint32_t src) {
+  return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, (int)src) |
+         ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src) << 32);
+}
+XYWS_DEV uint64_t shfl_up64(uint64_t v, uint32_t d) {
+  return (uint64_t)(uint32_t)__shfl_up((int)(uint32_t)v, d) |
+         ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d) << 32);
+}
+
+// The reply bytes [o0, o1) of one tile, whose items are in LDS, into the send
+// buffer: reply byte q lives at position olo + q from obase (16-byte aligned);
+// positions at or above wlim (olo + out_cap) are not written.
+XYWS_DEV void copy_tile(const uint64_t* s_off, const uint64_t* s_soff, const uint64_t* s_h01, const uint32_t* s_h2,
+                        uint32_t lane, uint64_t src, g_u8* obase, uint64_t olo, uint64_t wlim, uint64_t o0,
+                        uint64_t o1) {
+  const uint64_t P0 = olo + o0, P1 = olo + o1;
+  const uint64_t wl = P1 < wlim ? P1 : wlim;
+  if (wl <= P0) return;
+  for (uint64_t A = ((P0 >> 4) + lane) << 4; A < wl; A += (uint64_t)REPLY_LINE * REPLY_LANES) {
+    const uint64_t s = A > P0 ? A : P0, e = A + 16 < P1 ? A + 16 : P1;
+    uint64_t q = s - olo;
+    // the last item whose start is at or before q: it holds byte q (q < o1)
+    uint32_t i = 0, hi = REPLY_ITEMS;
+    while (hi - i > 1) {
+      const uint32_t m = (i + hi) >> 1;
+      if (s_off[m] <= q) i = m;
+      else hi = m;
+    }
+    bytes16 acc = {0, 0};
+    uint32_t a = (uint32_t)(s - A);
+    const uint32_t ae = (uint32_t)(e - A);
+    while (a < ae && i < REPLY_ITEMS) {
+      const uint64_t start = s_off[i], next = s_off[i + 1];
+      if (next > q) {
+        uint64_t r = q - start;
+        const uint32_t h2 = s_h2[i], h = h2 >> 16;
+        if (r < h) {  // header bytes r.. at line offset a
+          const uint32_t nb = h - (uint32_t)r < ae - a ? h - (uint32_t)r : ae - a;
+          const bytes16 p = shl_bytes(low_bytes(shr_bytes(bytes16{s_h01[i], h2 & 0xFFFFu}, (uint32_t)r), nb), a);
+          acc.lo |= p.lo;
+          acc.hi |= p.hi;
+          a += nb;
+          q += nb;
+          r += nb;
+        }
+        if (a < ae && q < next) {  // payload bytes r - h.. at line offset a
+          const uint32_t nb = next - q < ae - a ? (uint32_t)(next - q) : ae - a;
+          const bytes16 p = shl_bytes(low_bytes(load_bytes(src + s_soff[i] + (r - h), nb), nb), a);
+          acc.lo |= p.lo;
+          acc.hi |= p.hi;
+          a += nb;
+          q += nb;
+        }
+      }
+      i++;
+    }
+    if (s == A && e == A + 16 && A >= olo && A + 16 <= wlim) {
+      *reinterpret_cast<g_u32x4*>(obase + A) =
+          u32x4{(uint32_t)acc.lo, (uint32_t)(acc.lo >> 32), (uint32_t)acc.hi, (uint32_t)(acc.hi >> 32)};
+    } else {
+      // the range's first or last line: its own bytes only
+      const uint64_t we = e < wlim ? e : wlim;
+#pragma unroll 1
+      for (uint64_t p = s; p < we; p++) {
+        const uint32_t b = (uint32_t)(p - A);
+        obase[p] = (uint8_t)(b < 8 ? acc.lo >> (8u * b) : acc.hi >> (8u * (b - 8)));
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(REPLY_LANES) k_reply_streams(const xyws_conn* __restrict__ conns,
+                                                               const uint64_t* __restrict__ nframes,
+                                                               const xyws_reply_conn* __restrict__ replies,
+                                                               uint64_t n, uint64_t max_payload, uint32_t policy,
+                                                               uint32_t flags, uint32_t enc_opts, uint32_t amask,
+                                                               xyws_reply_result* __restrict__ results) {
+  // one tile's items: start offset in the reply (and the end after the last),
+  // source offset of the payload, header bytes 0..7, header bytes 8..9 | length << 16
+  __shared__ uint64_t s_off[REPLY_ITEMS + 1];
+  __shared__ uint64_t s_soff[REPLY_ITEMS];
+  __shared__ uint64_t s_h01[REPLY_ITEMS];
+  __shared__ uint32_t s_h2[REPLY_ITEMS];
+  const uint32_t lane = threadIdx.x;
+  for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
+    const g_u64* const cq = (const g_u64*)(conns + ci);
+    const uint64_t buf = uniform64(cq[0]), len = uniform64(cq[1]);
+    const uint64_t frames = uniform64(cq[3]), cap = uniform64(cq[4]);
+    const uint64_t t = uniform64(((const g_u64*)nframes)[ci]);
+    const g_u64* const rq = (const g_u64*)(replies + ci);
+    const uint64_t out = uniform64(rq[0]), out_cap = uniform64(rq[1]);
+    g_u64* const rc = (g_u64*)uniform64(rq[2]);
+    const uint64_t verd = uniform64(rq[3]);
+    g_u64* const res = results ? (g_u64*)(results + ci) : nullptr;
+
+    // the carry: frame_remaining, frames_seen, replies_total, close_code | echoing << 16 | status << 24
+    uint64_t rem = 0, seen = 0, total = 0, w3 = 0;
+    if (rc) {
+      rem = uniform64(rc[0]);
+      seen = uniform64(rc[1]);
+      total = uniform64(rc[2]);
+      w3 = uniform64(rc[3]);
+    }
+    const uint32_t code_in = (uint32_t)w3 & 0xFFFFu;
+    uint32_t echoing = (uint32_t)(w3 >> 16) & 0xFFu;
+
+    if (((w3 >> 24) & XYWS_RPL_OVERFLOW) || t > cap || (!frames && t)) {  // the table does not cover the stream
+      if (lane == 0) {
+        if (rc) rc[3] = w3 | ((uint64_t)XYWS_RPL_OVERFLOW << 24);
+        if (res) {
+          res[0] = 0;
+          res[1] = XYWS_NPOS;
+          res[2] = ((uint64_t)code_in << 32) | ((uint64_t)XYWS_RPL_OVERFLOW << 48);
+          res[3] = 0;
+        }
+      }
+      continue;
+    }
+    if (code_in) {  // closed by an earlier call
+      if (lane == 0 && res) {
+        res[0] = 0;
+        res[1] = XYWS_NPOS;
+        res[2] = ((uint64_t)code_in << 32) | ((uint64_t)XYWS_RPL_CLOSED << 48);
+        res[3] = 0;
+      }
+      continue;
+    }
+
+    g_u8* const obase = (g_u8*)(out & ~15ull);
+    const uint64_t olo = out & 15u;
+    const uint64_t wlim = sat_add(olo, out_cap);
+
+    // the rest of the frame the last batch end cut
+    uint64_t pk = 0;
+    {
+      const uint64_t k = rem < len ? rem : len;
+      if (echoing) pk = k;
+      rem -= k;
+    }
+
+    uint64_t opos = 0, first_close = XYWS_NPOS;
+    uint32_t answered = 0, ccode = 0;
+    for (uint64_t base = 0; base < t || (base == 0 && pk); base += REPLY_TILE) {
+      const uint64_t j = base + lane;
+      const bool valid = j < t;
+      uint64_t poff = 0, plen = 0;
+      uint32_t fflags = 0, fstatus = 0;
+      if (valid) {  // xyws_frame as four words: offsets, length, key | flags | hdr_len | status | reserved
+        const g_u64* const f = (const g_u64*)(frames + 32 * j);
+        poff = f[1];
+        plen = f[2];
+        const uint32_t w = (uint32_t)(f[3] >> 32);
+        fflags = w & 0xFFu;
+        fstatus = (w >> 16) & 0xFFu;
+      }
+      xyws_verdict v;
+      v.close_code = 0;
+      v.peer_code = 0;
+      v.action = 0;
+      v.reserved[0] = v.reserved[1] = v.reserved[2] = 0;
+      if (valid) {
+        v = classify_frame(fflags, fstatus, poff, plen, (const g_u8*)buf, len, max_payload, policy);
+        if (verd) {  // (xyws_verdict is 2-byte aligned: four half-words)
+          g_u16* const vo = (g_u16*)(verd + 8 * j);
+          vo[0] = v.close_code;
+          vo[1] = v.peer_code;
+          vo[2] = v.action;
+          vo[3] = 0;
+        }
+      }
+      const uint64_t closes = __ballot(valid && v.close_code != 0);
+      if (first_close != XYWS_NPOS) continue;  // closed in an earlier tile: verdicts only
+
+      // the frames before the first close: lanes below nrep
+      uint32_t nrep = t - base < REPLY_TILE ? (uint32_t)(t - base) : REPLY_TILE;
+      uint32_t closing = 0;
+      if (closes) {
+        nrep = (uint32_t)__builtin_ctzll(closes);
+        first_close = base + nrep;
+        ccode = uniform32((uint32_t)__shfl((int)v.close_code, (int)nrep));
+        closing = 1;
+      }
+      const bool live = lane < nrep;
+      const bool ans = live && ((amask >> v.action) & 1u);
+      uint64_t inb = 0;
+      if (live && poff < len) inb = plen < len - poff ? plen : len - poff;
+      uint32_t hw[4] = {0, 0, 0, 0};
+      uint32_t h = 0;
+      if (ans) h = build_header(reply_flags_of(flags, enc_opts, fflags), plen, false, 0, hw);
+      const uint64_t size = ans ? h + inb : 0;
+      answered += (uint32_t)__popcll(__ballot(ans));
+      if (nrep) {
+        rem = uniform64(shfl64(plen - inb, nrep - 1));
+        echoing = uniform32((uint32_t)__shfl((int)ans, (int)(nrep - 1)));
+      }
+
+      // reply offsets: an inclusive scan of the sizes across the wave
+      uint64_t incl = size;
+#pragma unroll
+      for (uint32_t d = 1; d < REPLY_LANES; d <<= 1) {
+        const uint64_t o = shfl_up64(incl, d);
+        if (lane >= d) incl += o;
+      }
+      const uint64_t o0 = opos, fstart = opos + pk;
+      const uint64_t cstart = fstart + uniform64(shfl64(incl, REPLY_LANES - 1));
+      const uint64_t o1 = cstart + 4u * closing;
+      s_off[1 + lane] = fstart + (incl - size);
+      s_soff[1 + lane] = poff;
+      s_h01[1 + lane] = (uint64_t)hw[0] | ((uint64_t)hw[1] << 32);
+      s_h2[1 + lane] = (hw[2] & 0xFFFFu) | (h << 16);
+      if (lane == 0) {
+        s_off[0] = o0;  // the carried prefix: buf[0, pk)
+        s_soff[0] = 0;
+        s_h01[0] = 0;
+        s_h2[0] = 0;
+        // websocket_send_close (websocket.h:70-76): FIN | CLOSE, length 2, the code big-endian
+        s_off[REPLY_CLOSE_ITEM] = cstart;
+        s_soff[REPLY_CLOSE_ITEM] = 0;
+        s_h01[REPLY_CLOSE_ITEM] = closing ? 0x0288ull | ((uint64_t)(ccode >> 8) << 16) | ((uint64_t)(ccode & 0xFFu) << 24) : 0;
+        s_h2[REPLY_CLOSE_ITEM] = closing ? 4u << 16 : 0;
+        s_off[REPLY_ITEMS] = o1;
+      }
+      pk = 0;
+      __syncthreads();
+      copy_tile(s_off, s_soff, s_h01, s_h2, lane, buf, obase, olo, wlim, o0, o1);
+      opos = o1;
+      __syncthreads();  // (LDS is rewritten by the next tile)
+    }
+
+    if (lane == 0) {
+      if (rc) {
+        rc[0] = rem;
+        rc[1] = seen + t;
+        rc[2] = total + answered;
+        rc[3] = (w3 & ~0xFFFFFFull) | ccode | ((uint64_t)(echoing ? 1u : 0u) << 16);
+      }
+      if (res) {
+        const uint32_t st = (opos > out_cap ? XYWS_RPL_TRUNCATED : 0u) | (first_close != XYWS_NPOS ? XYWS_RPL_CLOSED : 0u);
+        res[0] = opos;
+        res[1] = first_close;
+        res[2] = (uint64_t)answered | ((uint64_t)ccode << 32) | ((uint64_t)st << 48);
+        res[3] = 0;
+      }
+    }
+  }
+}
+
+extern "C" {
+
+int xyws_reply_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const uint64_t* dev_nframes,
+                       const xyws_reply_conn* dev_replies, uint64_t n, uint64_t max_payload, uint32_t policy,
+                       uint8_t flags, uint32_t enc_opts, uint32_t action_mask, xyws_reply_result* dev_results,
+                       void* stream) {
+  if (!ctx || (n && (!dev_conns || !dev_nframes || !dev_replies))) return XYWS_ERR_INVALID;
+  if (flags & XYWS_FLAG_HAS_MASK) return XYWS_ERR_INVALID;  // server role only
+  if (enc_opts & ~XYWS_ENC_FRAME_OPCODE) return XYWS_ERR_INVALID;
+  if (policy & ~(XYWS_POL_FRAGMENTS | XYWS_POL_UNMASKED | XYWS_POL_STRICT | XYWS_POL_REFERENCE)) return XYWS_ERR_INVALID;
+  if (action_mask & ~((2u << XYWS_ACT_CLOSE) - 1u)) return XYWS_ERR_INVALID;
+  if (!n) return XYWS_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  device_guard g(ctx->device);
+  if (!g.ok) return XYWS_ERR_HIP;
+  const uint32_t grid = grid_for(n, 1, REPLY_GRID_CAP);
+  hipLaunchKernelGGL(k_reply_streams, dim3(grid), dim3(REPLY_LANES), 0, (hipStream_t)stream, dev_conns, dev_nframes,
+                     dev_replies, n, max_payload, policy, (uint32_t)flags, enc_opts, action_mask, dev_results);
+  return hip_err(hipGetLastError());
+}
+
+// Internal (tests and measurements, no HIP call): the geometry of
+// k_reply_streams. out: {frames per tile, bytes per copy step, grid cap,
+// wave size}.
+int xyws_debug_reply_geometry(uint64_t out[4]) {
+  if (!out) return XYWS_ERR_INVALID;
+  out[0] = REPLY_TILE;
+  out[1] = REPLY_LINE * REPLY_LANES;
+  out[2] = REPLY_GRID_CAP;
+  out[3] = REPLY_LANES;
+  return XYWS_OK;
+}
+
+}  // extern "C"

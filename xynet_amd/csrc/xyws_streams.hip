@@ -40,31 +40,6 @@
 #define STREAMS_GRID_CAP 8192u   // 256 CUs x 32 one-wave workgroups; further connections are grid-strided
 #define STREAMS_LPL (STREAMS_WINDOW / 16u / STREAMS_LANES)  // lines per lane
 
-// Everything a connection names is device memory: global loads and stores,
-// not flat ones (a pointer read from the table has no address space).
-#define XYWS_GLOBAL __attribute__((address_space(1)))
-typedef XYWS_GLOBAL uint8_t g_u8;
-typedef XYWS_GLOBAL uint64_t g_u64;
-typedef XYWS_GLOBAL u32x4 g_u32x4;
-
-// 16 bytes as two little-endian halves (header bytes carried in / out).
-struct bytes16 {
-  uint64_t lo, hi;
-};
-// v moved up by nb bytes (0..15).
-XYWS_DEV bytes16 shl_bytes(bytes16 v, uint32_t nb) {
-  const uint32_t s = 8u * nb;
-  if (!s) return v;
-  if (s >= 64) return bytes16{0, v.lo << (s - 64)};
-  return bytes16{v.lo << s, (v.hi << s) | (v.lo >> (64 - s))};
-}
-// The first nb bytes (0..16) of v, the rest zero.
-XYWS_DEV bytes16 low_bytes(bytes16 v, uint32_t nb) {
-  if (nb >= 16) return v;
-  if (nb >= 8) return bytes16{v.lo, nb == 8 ? 0 : v.hi & ((1ull << (8u * (nb - 8))) - 1)};
-  return bytes16{nb ? v.lo & ((1ull << (8u * nb)) - 1) : 0, 0};
-}
-
 // The rotated key kw XORed into the lines this lane holds, over the window's
 // bytes [a, b) (offsets from the window start, which is 16-byte aligned: kw is
 // aligned_key's for the absolute positions too). Most lines lie outside a

@@ -13,6 +13,8 @@ Names, argument meaning and error behaviour follow the reference headers
                                    (example/include/common/websocket.h:110-134)
   connection_group.decode          the same for many connections at once, one launch
                                    (xyws_decode_streams: one coroutine's loop per wave)
+  connection_group.reply           the rest of that loop for many connections at once: close policy,
+                                   echo_once, websocket_send_close (xyws_reply_streams, one launch)
   encode_frames                    echo_once's replies, batched on the device
                                    (example/websocket/websocket_echo.cpp:18-27)
   classify_frames                  websocket_check_parser_result's policy
@@ -293,9 +295,10 @@ class GroupResult:
     k-th (conn_id, buffer) pair of that call (host copies on demand). They
     live in the group's tensors: valid until the group's next decode."""
 
-    def __init__(self, group, ids):
+    def __init__(self, group, ids, slot=None):
         self.group, self.ids = group, ids
         self._counts = None
+        self._slot, self._replied = slot, False  # (the ring slot that holds this call's table: connection_group.reply)
 
     def nframes(self, k):
         if self._counts is None:
@@ -311,6 +314,35 @@ class GroupResult:
         return _frames_from_device(row, n)[0]
 
 
+class GroupReply:
+    """Results and verdicts of one connection_group.reply call, item k as in
+    the decode result it answered (host copies on demand; valid until the
+    group's next reply)."""
+
+    def __init__(self, group, decoded):
+        self.group, self.decoded = group, decoded
+        self._rows = None
+
+    def result(self, k):
+        """xyws_reply_result of item k."""
+        if self._rows is None:
+            self._rows = self.group.results_t[:32 * max(len(self.decoded.ids), 1)].cpu().numpy().tobytes()
+        if not 0 <= k < len(self.decoded.ids):
+            raise IndexError(k)
+        return _lib.ReplyResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+
+    def verdicts(self, k):
+        """The verdicts of item k's frames (empty when its reply overflowed or the connection was closed)."""
+        g, res = self.group, self.result(k)
+        if res.status & _lib.RPL_OVERFLOW or (res.status & _lib.RPL_CLOSED and res.first_close == _lib.NPOS):
+            return []
+        n = min(self.decoded.nframes(k), g.cap)
+        i = self.decoded.ids[k]
+        raw = g.verdicts_t[8 * g.cap * i:8 * (g.cap * i + n)].cpu().numpy().tobytes() if n else b""
+        arr = (_lib.Verdict * max(n, 1)).from_buffer_copy(raw.ljust(8 * max(n, 1), b"\0"))
+        return [arr[j] for j in range(n)]
+
+
 class connection_group:
     """The decoder states of n connections and one xyws_decode_streams call
     for whatever a sweep of the completion queue brought: decode() takes the
@@ -318,7 +350,8 @@ class connection_group:
     and decodes them all in one launch, each from its own device-resident
     carry, as frame_decoder.decode would one by one. Owns the carries (n x 64
     bytes, zeroed), a descriptor table of cap rows per connection and a count
-    vector."""
+    vector. reply() then answers what decode() found, again in one launch
+    (xyws_reply_streams): a whole echo sweep is two launches."""
     RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
 
     def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
@@ -334,14 +367,23 @@ class connection_group:
         self._dev = [torch.empty(max(self.n, 1) * 8, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
         self._done = [None] * self.RING
         self._turn = 0
+        # reply(): the reply carries, a verdict row of cap per connection, a result row per item, and the
+        # xyws_reply_conn tables in the same ring
+        self.rcarry_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
+        self.verdicts_t = torch.empty(max(self.n * self.cap, 1) * 8, dtype=torch.uint8, device=self.device)
+        self.results_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
+        self._rhost = [torch.zeros(max(self.n, 1) * 4, dtype=torch.int64).pin_memory() for _ in range(self.RING)]
+        self._rdev = [torch.empty(max(self.n, 1) * 4, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
 
     def reset(self, ids=None):
         """Fresh streams: every connection, or those in `ids`."""
         if ids is None:
             self.carry_t.zero_()
+            self.rcarry_t.zero_()
         else:
             for i in ids:
                 self.carry_t[64 * i:64 * i + 64].zero_()
+                self.rcarry_t[32 * i:32 * i + 32].zero_()
 
     def carry(self, conn_id):
         """Host copy of a connection's carry (synchronizes)."""
@@ -377,7 +419,50 @@ class connection_group:
                                                  C.c_void_p(stream.cuda_stream)), "xyws_decode_streams")
             self._done[k] = torch.cuda.Event()
             self._done[k].record(stream)
-        return GroupResult(self, ids)
+        return GroupResult(self, ids, k)
+
+    def reply_carry(self, conn_id):
+        """Host copy of a connection's reply carry (synchronizes)."""
+        if not 0 <= conn_id < self.n:
+            raise XywsError(-1, "no such connection")
+        return _lib.ReplyCarry.from_buffer_copy(self.rcarry_t[32 * conn_id:32 * conn_id + 32].cpu().numpy().tobytes())
+
+    def reply(self, result, out_items, max_payload, policy=0, flags=0x11, enc_opts=0, action_mask=1):
+        """Answer the frames of the decode() call that returned `result`
+        (xyws_reply_streams, one launch): out_items[k] is the device uint8
+        tensor that receives item k's reply (len + 13 bytes always suffice).
+        Every answered frame is echoed with `flags` (default FIN | TEXT, the
+        reference's echo_once), or with XYWS_ENC_FRAME_OPCODE under its own
+        opcode; action_mask selects the verdict actions that are answered; a
+        frame the policy closes on ends the reply with the close frame. The
+        group owns the reply carries; the verdict rows (cap per connection)
+        and the result rows live in its tensors until the next reply().
+        Call it before the group's next decode(): the counts are that call's."""
+        import torch
+        if result.group is not self or result._slot is None or not self.cap:
+            raise XywsError(-1, "reply() takes the result of this group's decode(), and a group with cap > 0")
+        outs = [_dev_u8(t) for t in out_items]
+        if len(outs) != len(result.ids) or any(t.device != self.device for t in outs):
+            raise XywsError(-1, "one send buffer on the group's device per decoded item")
+        k = result._slot
+        if result._replied and self._done[k] is not None:
+            self._done[k].synchronize()  # (the slot's reply table is rewritten)
+        result._replied = True
+        tab = self._rhost[k].numpy().reshape(-1, 4)  # xyws_reply_conn: out, out_cap, rc, verdicts
+        rbase, vbase = self.rcarry_t.data_ptr(), self.verdicts_t.data_ptr()
+        for row, i, t in zip(tab, result.ids, outs):
+            row[0], row[1], row[2], row[3] = t.data_ptr(), t.numel(), rbase + 32 * i, vbase + 8 * self.cap * i
+        m = len(outs)
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            self._rdev[k][:4 * m].copy_(self._rhost[k][:4 * m], non_blocking=True)
+            check(self.ctx.L.xyws_reply_streams(
+                self.ctx.h, C.c_void_p(self._dev[k].data_ptr()), C.c_void_p(self.counts_t.data_ptr()),
+                C.c_void_p(self._rdev[k].data_ptr()), m, int(max_payload), policy, flags, enc_opts, action_mask,
+                C.c_void_p(self.results_t.data_ptr()), C.c_void_p(stream.cuda_stream)), "xyws_reply_streams")
+            self._done[k] = torch.cuda.Event()
+            self._done[k].record(stream)
+        return GroupReply(self, result)
 
 
 def decode_indexed(buf, starts, frames=True, parse_only=False):
