@@ -34,6 +34,9 @@
  *                                                              xyws_reassemble_stream (messages, frames
  *                                                              and UTF-8 sequences cut by a recv
  *                                                              boundary, state in xyws_msg_carry)
+ *   chat session's receive loop: one text message per        xyws_reassemble_streams (every
+ *     connection and sweep, handed on to the room              connection's messages, one launch,
+ *     example/websocket/websocket_chat.cpp:177-200             after xyws_decode_streams)
  *   recv_all / io_service remote-queue eventfd               xyws_arena_* (pinned recv arena,
  *     include/xynet/socket/impl/recv_all.h:86-121              H2D -> decode -> D2H, completion
  *     include/xynet/io_service.h:362-381                       written to an eventfd)
@@ -682,6 +685,75 @@ int xyws_reply_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const uint64_t
                        uint64_t max_payload, uint32_t policy, uint8_t flags, uint32_t enc_opts,
                        uint32_t action_mask, xyws_reply_result* dev_results /* n, nullable */,
                        void* stream);
+
+/* ---- many connections, one reassembly call --------------------------------
+ * The message side of the same sweep: what the reference's chat server does
+ * with every connection's frames (example/websocket/websocket_chat.cpp:177-200,
+ * one text message per connection handed on to a room), for every connection
+ * of an xyws_decode_streams call at once. dev_conns and dev_nframes are the
+ * table and the counts of the xyws_decode_streams call just before it (of
+ * dev_conns[i] only buf, len, frames and cap are read); dev_reasm[i] names
+ * connection i's message buffer, its message carry and its record row. The
+ * call does not write buf: it may run before or after xyws_reply_streams for
+ * the same sweep. Per connection, with t = dev_nframes[i]:
+ *
+ *  1. Overflow. mc->status has XYWS_MSG_OVERFLOW, or t > cap, or frames is
+ *     NULL while t > 0: nothing is written to out or msgs, the result is
+ *     out_len 0, nmsgs 0, status OVERFLOW, and the carry is left as it was
+ *     except that status gains XYWS_MSG_OVERFLOW (the table no longer covers
+ *     the stream: the caller closes the connection). A carry with this bit
+ *     belongs to this call only: xyws_reassemble_stream does not know it.
+ *  2. Otherwise the entry is processed exactly as
+ *     xyws_reassemble_stream(ctx, buf, len, frames, t, NULL, opts, mc, mc, out,
+ *     out_cap, msgs, msg_cap, &nmsgs, stream) processes it: the bytes
+ *     out[0 .. min(out_len, out_cap)), the first min(nmsgs, msg_cap) records,
+ *     the count and all 64 carry bytes. Everything said there holds here per
+ *     connection (the continued frame, CONTINUED, closing / COMPLETE,
+ *     INTERRUPTED, carried orphans, TRUNCATED, UNCHECKED, the cut UTF-8 tail,
+ *     the structural carry exact whatever the caps); len == 0 with a message
+ *     open still emits the empty CONTINUED record. out_cap >= len and
+ *     msg_cap >= t + 1 always suffice.
+ *  3. Nothing outside [buf, buf + len) is read, whatever the table says (whole
+ *     16-byte lines that hold one of its bytes are loaded); a payload_off
+ *     outside [0, len) contributes no bytes. No byte outside
+ *     [out, out + min(out_len, out_cap)) and no record beyond
+ *     min(nmsgs, msg_cap) is written: neighbouring connections' out ranges may
+ *     share a 16-byte line, as in a slab. The out ranges must not overlap each
+ *     other or a recv buffer; a carry must not appear twice in a call.
+ *
+ * Like its two siblings the call is one launch (one wave per connection), uses
+ * no context scratch, no scratch slot and no policy word, never touches the
+ * device error word, reads no device state on the host, needs no reserve, can
+ * be captured into a hipGraph at once and runs concurrently on different
+ * streams. n == 0 returns XYWS_OK and launches nothing. XYWS_ERR_INVALID: a
+ * null ctx; null dev_conns, dev_nframes or dev_reasm with n > 0; opts bits
+ * other than XYWS_REASM_UTF8. */
+typedef struct xyws_reasm_conn {   /* 64 bytes; entry i goes with dev_conns[i] */
+  void*           out;      /* device: this connection's message bytes; NULL = out_cap 0 */
+  uint64_t        out_cap;
+  xyws_msg_carry* mc;       /* device; read, then written. NULL: fresh, no state kept */
+  xyws_message*   msgs;     /* device, nullable (then msg_cap counts as 0) */
+  uint64_t        msg_cap;
+  uint64_t        reserved[3]; /* zero */
+} xyws_reasm_conn;
+
+typedef struct xyws_reasm_result { /* 32 bytes */
+  uint64_t out_len;   /* message bytes this call delivered (may exceed out_cap) */
+  uint64_t nmsgs;     /* records of this call (may exceed msg_cap) */
+  uint32_t completed; /* stored records with XYWS_MSG_COMPLETE */
+  uint32_t status;    /* XYWS_RSM_* */
+  uint64_t reserved;
+} xyws_reasm_result;
+#define XYWS_RSM_TRUNCATED 0x1u  /* out_len > out_cap */
+#define XYWS_RSM_MSG_CAP   0x2u  /* nmsgs > msg_cap */
+#define XYWS_RSM_OVERFLOW  0x4u
+#define XYWS_RSM_OPEN      0x8u  /* a message is open in the carry after this call */
+#define XYWS_RSM_UTF8_BAD  0x10u /* a stored record of this call has XYWS_MSG_UTF8_BAD */
+#define XYWS_MSG_OVERFLOW  0x80u /* xyws_msg_carry.status, this call only: sticky */
+
+int xyws_reassemble_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const uint64_t* dev_nframes,
+                            const xyws_reasm_conn* dev_reasm, uint64_t n, uint32_t opts,
+                            xyws_reasm_result* dev_results /* n, nullable */, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -325,6 +325,22 @@ inline void reply_streams(context& ctx, const xyws_conn* dev_conns, const std::u
         "xyws_reply_streams");
 }
 
+// The messages of what decode_streams found, in one launch
+// (xyws_reassemble_streams): dev_conns and dev_nframes are that call's table
+// and counts, dev_reasm[i] names connection i's message buffer, message carry
+// and record row. Each connection is processed as message_assembler::feed
+// would process it from its own carry (fragments gathered, text validated,
+// a message, frame or UTF-8 sequence cut by the recv boundary continued by the
+// next call). Runs before or after reply_streams for the same sweep.
+// dev_results (nullable device pointer, n entries) receives lengths and counts.
+inline void reassemble_streams(context& ctx, const xyws_conn* dev_conns, const std::uint64_t* dev_nframes,
+                               const xyws_reasm_conn* dev_reasm, std::uint64_t n,
+                               std::uint32_t opts = XYWS_REASM_UTF8, xyws_reasm_result* dev_results = nullptr,
+                               void* stream = nullptr) {
+  check(xyws_reassemble_streams(ctx.native(), dev_conns, dev_nframes, dev_reasm, n, opts, dev_results, stream),
+        "xyws_reassemble_streams");
+}
+
 // class websocket_frame_header (websocket_frame_header.h:179-224): a header in
 // a 14-byte array. As in the reference, the masked constructors keep the key
 // beside the header and build it with the key bytes zero (:183-202); with_key()

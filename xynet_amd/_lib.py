@@ -155,7 +155,20 @@ class ReplyResult(C.Structure):
 
 
 assert C.sizeof(Frame) == 32 and C.sizeof(Carry) == 64 and C.sizeof(Conn) == 64
+class ReasmConn(C.Structure):
+    """xyws_reasm_conn (include/xyws.h), 64 bytes: entry i goes with entry i of the xyws_conn table."""
+    _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("mc", C.c_void_p), ("msgs", C.c_void_p),
+                ("msg_cap", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class ReasmResult(C.Structure):
+    """xyws_reasm_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("out_len", C.c_uint64), ("nmsgs", C.c_uint64), ("completed", C.c_uint32),
+                ("status", C.c_uint32), ("reserved", C.c_uint64)]
+
+
 assert C.sizeof(ReplyCarry) == 32 and C.sizeof(ReplyConn) == 32 and C.sizeof(ReplyResult) == 32
+assert C.sizeof(ReasmConn) == 64 and C.sizeof(ReasmResult) == 32
 assert C.sizeof(ArenaResult) == 104
 XYWS_ERR_AGAIN = -6
 ARENA_SLOTS = 8
@@ -169,6 +182,8 @@ RPL_TRUNCATED, RPL_CLOSED, RPL_OVERFLOW = 0x1, 0x2, 0x4  # xyws_reply_result.sta
 REASM_UTF8 = 0x1
 MSG_COMPLETE, MSG_UTF8_BAD, MSG_INTERRUPTED, MSG_TRUNCATED, MSG_ORPHANS = 0x1, 0x2, 0x4, 0x8, 0x10
 MSG_CONTINUED, MSG_UNCHECKED = 0x20, 0x40  # xyws_reassemble_stream only
+MSG_OVERFLOW = 0x80  # xyws_msg_carry.status, xyws_reassemble_streams only
+RSM_TRUNCATED, RSM_MSG_CAP, RSM_OVERFLOW, RSM_OPEN, RSM_UTF8_BAD = 0x1, 0x2, 0x4, 0x8, 0x10  # xyws_reasm_result.status
 
 _lib = None
 _tools = None
@@ -243,6 +258,11 @@ def load():
     # (no HIP call: frames per tile, bytes per copy step, grid cap, wave size)
     L.xyws_debug_reply_geometry.restype = i32
     L.xyws_debug_reply_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_reassemble_streams.restype = i32
+    L.xyws_reassemble_streams.argtypes = [vp, vp, vp, vp, u64, u32, vp, vp]
+    # (no HIP call: frames per tile, bytes per copy step, grid cap, wave size)
+    L.xyws_debug_reasm_streams_geometry.restype = i32
+    L.xyws_debug_reasm_streams_geometry.argtypes = [C.POINTER(u64)]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]

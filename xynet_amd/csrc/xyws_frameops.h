@@ -93,4 +93,59 @@ XYWS_DEV xyws_verdict classify_frame(uint32_t fflags, uint32_t fstatus, uint64_t
   return v;
 }
 
+// ---------------------------------------------------------------- UTF-8 rules
+// (RFC 3629, shared by k_utf8 / k_rs_carry in xyws_frames.hip and by
+// k_reasm_streams in xyws_reasm_streams.hip)
+// Bytes of the sequence a lead byte announces (0: not a lead).
+XYWS_DEV uint32_t lead_len(uint32_t c) { return c >= 0xF0u ? 4u : c >= 0xE0u ? 3u : c >= 0xC0u ? 2u : 0u; }
+// The second-byte rules of lead c0: overlongs (E0, F0), surrogates (ED), code
+// points above U+10FFFF (F4).
+XYWS_DEV bool utf8_second_bad(uint32_t c0, uint32_t c1) {
+  return (c0 == 0xE0u && c1 < 0xA0u) || (c0 == 0xEDu && c1 > 0x9Fu) || (c0 == 0xF0u && c1 < 0x90u) ||
+         (c0 == 0xF4u && c1 > 0x8Fu);
+}
+// A carried UTF-8 tail as one word: its 0..3 bytes in bits 0..23, their
+// count in bits 24..31 (0: none). tail_prev: the byte `back` (>= 1) before
+// the message's first byte in this call, or 0x100 when the tail is shorter.
+XYWS_DEV uint32_t tail_word(const xyws_msg_carry* mc) {
+  if (!mc || mc->opcode != XYWS_FLAG_OP_TEXT || !mc->utf8_len || mc->utf8_len > 3) return 0;
+  return (uint32_t)mc->utf8[0] | ((uint32_t)mc->utf8[1] << 8) | ((uint32_t)mc->utf8[2] << 16) |
+         ((uint32_t)mc->utf8_len << 24);
+}
+XYWS_DEV uint32_t tail_prev(uint32_t tw, uint32_t back) {
+  const uint32_t tl = tw >> 24;
+  if (back > tl) return 0x100u;
+  return (tw >> (8u * (tl - back))) & 0xFFu;
+}
+
+// ---------------------------------------------------------------- line loads, lane moves
+// (the per-connection copy phases: xyws_reply.hip, xyws_reasm_streams.hip)
+XYWS_DEV bytes16 line_of(const g_u8* aligned) {
+  const u32x4 x = *reinterpret_cast<const g_u32x4*>(aligned);
+  return bytes16{(uint64_t)x.x | ((uint64_t)x.y << 32), (uint64_t)x.z | ((uint64_t)x.w << 32)};
+}
+// The nb (1..16) bytes at address g, in the low bytes of the result (the bytes
+// above them are not defined). Only the 16-byte lines that hold one of the nb
+// bytes are loaded.
+XYWS_DEV bytes16 load_bytes(uint64_t g, uint32_t nb) {
+  const g_u8* const a = (const g_u8*)(g & ~15ull);
+  const uint32_t sh = (uint32_t)(g & 15u);
+  bytes16 v = shr_bytes(line_of(a), sh);
+  if (sh + nb > 16) {  // (sh >= 1 here)
+    const bytes16 y = shl_bytes(line_of(a + 16), 16 - sh);
+    v.lo |= y.lo;
+    v.hi |= y.hi;
+  }
+  return v;
+}
+
+XYWS_DEV uint64_t shfl64(uint64_t v, uint32_t src) {
+  return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, (int)src) |
+         ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src) << 32);
+}
+XYWS_DEV uint64_t shfl_up64(uint64_t v, uint32_t d) {
+  return (uint64_t)(uint32_t)__shfl_up((int)(uint32_t)v, d) |
+         ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d) << 32);
+}
+
 }  // namespace xyws_internal

@@ -916,7 +916,7 @@ __global__ void __launch_bounds__(FT) k_rs_msgs(Tab T, const uint64_t* dev_n, ui
 
 // UTF-8 (RFC 3629) over every text message's bytes in out[out_lo + ...]; one
 // lane per 16-byte chunk, neighbours read for sequences crossing chunks.
-XYWS_DEV uint32_t lead_len(uint32_t c) { return c >= 0xF0u ? 4u : c >= 0xE0u ? 3u : c >= 0xC0u ? 2u : 0u; }
+// (lead_len, tail_word, tail_prev, utf8_second_bad: xyws_frameops.h)
 
 // True when the bytes at out[] positions q in [q0, q1) of message [mo, me)
 // (out coordinates q = position - out_lo, total written) hold an invalid
@@ -926,21 +926,7 @@ XYWS_DEV uint32_t lead_len(uint32_t c) { return c >= 0xF0u ? 4u : c >= 0xE0u ? 3
 // code points above U+10FFFF; a sequence cut by the message end is invalid
 // only in a complete, untruncated message). For the probe pass (the first
 // bytes of each message), not the streaming pass.
-// A carried UTF-8 tail as one word: its 0..3 bytes in bits 0..23, their
-// count in bits 24..31 (0: none). tail_prev: the byte `back` (>= 1) before
-// the message's first byte in this call, or 0x100 when the tail is shorter.
-XYWS_DEV uint32_t tail_word(const xyws_msg_carry* mc) {
-  if (!mc || mc->opcode != XYWS_FLAG_OP_TEXT || !mc->utf8_len || mc->utf8_len > 3) return 0;
-  return (uint32_t)mc->utf8[0] | ((uint32_t)mc->utf8[1] << 8) | ((uint32_t)mc->utf8[2] << 16) |
-         ((uint32_t)mc->utf8_len << 24);
-}
-XYWS_DEV uint32_t tail_prev(uint32_t tw, uint32_t back) {
-  const uint32_t tl = tw >> 24;
-  if (back > tl) return 0x100u;
-  return (tw >> (8u * (tl - back))) & 0xFFu;
-}
-
-// (tw: the carried tail of the message when it is a stream call's record 0:
+// (tw: the carried tail as tail_word makes it, of the message of the message when it is a stream call's record 0:
 // its bytes are the bytes before mo for the claim rule; S: a stream call)
 template <bool S>
 XYWS_DEV bool utf8_span_bad(const uint8_t* out, uint64_t out_lo, uint64_t total, uint64_t q0, uint64_t q1,
@@ -993,9 +979,7 @@ XYWS_DEV bool utf8_span_bad(const uint8_t* out, uint64_t out_lo, uint64_t total,
         if ((cb & 0xC0u) != 0x80u) return true;
         if (d == 1) c1 = cb;
       }
-      if ((ch == 0xE0u && c1 < 0xA0u) || (ch == 0xEDu && c1 > 0x9Fu) || (ch == 0xF0u && c1 < 0x90u) ||
-          (ch == 0xF4u && c1 > 0x8Fu))
-        return true;
+      if (utf8_second_bad(ch, c1)) return true;
     }
   }
   return false;
@@ -1195,10 +1179,7 @@ __global__ void __launch_bounds__(FT) k_utf8(const uint8_t* out, uint64_t out_lo
                 if ((cb & 0xC0u) != 0x80u) bad = true;
                 if (d == 1) c1 = cb;
               }
-              if (ch == 0xE0u && c1 < 0xA0u) bad = true;  // overlong
-              if (ch == 0xEDu && c1 > 0x9Fu) bad = true;  // surrogates
-              if (ch == 0xF0u && c1 < 0x90u) bad = true;  // overlong
-              if (ch == 0xF4u && c1 > 0x8Fu) bad = true;  // above U+10FFFF
+              if (utf8_second_bad(ch, c1)) bad = true;
             }
           }
         }
@@ -1259,9 +1240,7 @@ __global__ void k_rs_carry(tab_stream T, uint64_t n, const uint64_t* dev_n, cons
         const uint32_t c0 = (uint32_t)(seq & 0xFFu), c1 = (uint32_t)((seq >> 8) & 0xFFu);
         for (uint32_t j = 1; j < L; j++)
           if (((seq >> (8u * j)) & 0xC0u) != 0x80u) bad = true;
-        if ((c0 == 0xE0u && c1 < 0xA0u) || (c0 == 0xEDu && c1 > 0x9Fu) || (c0 == 0xF0u && c1 < 0x90u) ||
-            (c0 == 0xF4u && c1 > 0x8Fu))
-          bad = true;
+        if (utf8_second_bad(c0, c1)) bad = true;
       } else if ((r0.status & XYWS_MSG_COMPLETE) && !(r0.status & XYWS_MSG_TRUNCATED)) {
         bad = true;  // (the message ended inside it)
       }

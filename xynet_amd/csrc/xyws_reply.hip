@@ -50,33 +50,7 @@ typedef XYWS_GLOBAL uint16_t g_u16;
 
 using namespace xyws_internal;
 
-XYWS_DEV bytes16 line_of(const g_u8* aligned) {
-  const u32x4 x = *reinterpret_cast<const g_u32x4*>(aligned);
-  return bytes16{(uint64_t)x.x | ((uint64_t)x.y << 32), (uint64_t)x.z | ((uint64_t)x.w << 32)};
-}
-// The nb (1..16) bytes at address g, in the low bytes of the result (the bytes
-// above them are not defined). Only the 16-byte lines that hold one of the nb
-// bytes are loaded.
-XYWS_DEV bytes16 load_bytes(uint64_t g, uint32_t nb) {
-  const g_u8* const a = (const g_u8*)(g & ~15ull);
-  const uint32_t sh = (uint32_t)(g & 15u);
-  bytes16 v = shr_bytes(line_of(a), sh);
-  if (sh + nb > 16) {  // (sh >= 1 here)
-    const bytes16 y = shl_bytes(line_of(a + 16), 16 - sh);
-    v.lo |= y.lo;
-    v.hi |= y.hi;
-  }
-  return v;
-}
-
-XYWS_DEV uint64_t shfl64(uint64_t v, uint32_t src) {
-  return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, (int)src) |
-         ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src) << 32);
-}
-XYWS_DEV uint64_t shfl_up64(uint64_t v, uint32_t d) {
-  return (uint64_t)(uint32_t)__shfl_up((int)(uint32_t)v, d) |
-         ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d) << 32);
-}
+// (line_of, load_bytes, shfl64, shfl_up64: xyws_frameops.h)
 
 // The reply bytes [o0, o1) of one tile, whose items are in LDS, into the send
 // buffer: reply byte q lives at position olo + q from obase (16-byte aligned);

@@ -299,6 +299,7 @@ class GroupResult:
         self.group, self.ids = group, ids
         self._counts = None
         self._slot, self._replied = slot, False  # (the ring slot that holds this call's table: connection_group.reply)
+        self._reassembled = False                # (... and connection_group.reassemble)
 
     def nframes(self, k):
         if self._counts is None:
@@ -343,6 +344,33 @@ class GroupReply:
         return [arr[j] for j in range(n)]
 
 
+class GroupMessages:
+    """Results and message records of one connection_group.reassemble call,
+    item k as in the decode result it took (host copies on demand; valid until
+    the group's next reassemble)."""
+
+    def __init__(self, group, decoded, msg_cap):
+        self.group, self.decoded, self.msg_cap = group, decoded, msg_cap
+        self._rows = None
+
+    def result(self, k):
+        """xyws_reasm_result of item k."""
+        if self._rows is None:
+            self._rows = self.group.mresults_t[:32 * max(len(self.decoded.ids), 1)].cpu().numpy().tobytes()
+        if not 0 <= k < len(self.decoded.ids):
+            raise IndexError(k)
+        return _lib.ReasmResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+
+    def messages(self, k):
+        """The stored records of item k (xyws_message; out_off counts from its out buffer's start)."""
+        g = self.group
+        n = min(self.result(k).nmsgs, self.msg_cap)
+        row = 40 * (g.cap + 1) * self.decoded.ids[k]
+        raw = g.msgs_t[row:row + 40 * n].cpu().numpy().tobytes() if n else b""
+        arr = (_lib.Message * max(n, 1)).from_buffer_copy(raw.ljust(40 * max(n, 1), b"\0"))
+        return [arr[j] for j in range(n)]
+
+
 class connection_group:
     """The decoder states of n connections and one xyws_decode_streams call
     for whatever a sweep of the completion queue brought: decode() takes the
@@ -351,7 +379,9 @@ class connection_group:
     carry, as frame_decoder.decode would one by one. Owns the carries (n x 64
     bytes, zeroed), a descriptor table of cap rows per connection and a count
     vector. reply() then answers what decode() found, again in one launch
-    (xyws_reply_streams): a whole echo sweep is two launches."""
+    (xyws_reply_streams): a whole echo sweep is two launches. reassemble()
+    gathers and validates the messages of what decode() found, in one launch
+    too (xyws_reassemble_streams), before or after reply()."""
     RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
 
     def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
@@ -374,16 +404,25 @@ class connection_group:
         self.results_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
         self._rhost = [torch.zeros(max(self.n, 1) * 4, dtype=torch.int64).pin_memory() for _ in range(self.RING)]
         self._rdev = [torch.empty(max(self.n, 1) * 4, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
+        # reassemble(): the message carries, a record row of cap + 1 per connection, a result row per item, and
+        # the xyws_reasm_conn tables in the same ring
+        self.mcarry_t = torch.zeros(max(self.n, 1) * 64, dtype=torch.uint8, device=self.device)
+        self.msgs_t = torch.empty(max(self.n, 1) * (self.cap + 1) * 40, dtype=torch.uint8, device=self.device)
+        self.mresults_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
+        self._mhost = [torch.zeros(max(self.n, 1) * 8, dtype=torch.int64).pin_memory() for _ in range(self.RING)]
+        self._mdev = [torch.empty(max(self.n, 1) * 8, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
 
     def reset(self, ids=None):
         """Fresh streams: every connection, or those in `ids`."""
         if ids is None:
             self.carry_t.zero_()
             self.rcarry_t.zero_()
+            self.mcarry_t.zero_()
         else:
             for i in ids:
                 self.carry_t[64 * i:64 * i + 64].zero_()
                 self.rcarry_t[32 * i:32 * i + 32].zero_()
+                self.mcarry_t[64 * i:64 * i + 64].zero_()
 
     def carry(self, conn_id):
         """Host copy of a connection's carry (synchronizes)."""
@@ -463,6 +502,52 @@ class connection_group:
             self._done[k] = torch.cuda.Event()
             self._done[k].record(stream)
         return GroupReply(self, result)
+
+    def reassemble(self, result, out_items, opts=_lib.REASM_UTF8, msg_cap=None):
+        """Gather and validate the messages of the decode() call that returned
+        `result` (xyws_reassemble_streams, one launch): out_items[k] is the device
+        uint8 tensor that receives item k's message bytes (as many bytes as its
+        recv buffer held always suffice). Each item is processed as
+        message_assembler.feed would process it from the connection's own message
+        carry. The group owns the carries; the record rows (cap + 1 per
+        connection, msg_cap of them used: default all) and the result rows live in
+        its tensors until the next reassemble(). Works before or after reply() on
+        the same result; call it before the group's next decode()."""
+        import torch
+        if result.group is not self or result._slot is None or not self.cap:
+            raise XywsError(-1, "reassemble() takes the result of this group's decode(), and a group with cap > 0")
+        outs = [_dev_u8(t) for t in out_items]
+        if len(outs) != len(result.ids) or any(t.device != self.device for t in outs):
+            raise XywsError(-1, "one message buffer on the group's device per decoded item")
+        mcap = self.cap + 1 if msg_cap is None else int(msg_cap)
+        if not 0 <= mcap <= self.cap + 1:
+            raise XywsError(-1, "msg_cap above the group's record row (cap + 1)")
+        k = result._slot
+        if result._reassembled and self._done[k] is not None:
+            self._done[k].synchronize()  # (the slot's table is rewritten)
+        result._reassembled = True
+        tab = self._mhost[k].numpy().reshape(-1, 8)  # xyws_reasm_conn: out, out_cap, mc, msgs, msg_cap, reserved[3]
+        cbase, mbase = self.mcarry_t.data_ptr(), self.msgs_t.data_ptr()
+        for row, i, t in zip(tab, result.ids, outs):
+            row[0], row[1], row[2] = t.data_ptr(), t.numel(), cbase + 64 * i
+            row[3], row[4] = mbase + 40 * (self.cap + 1) * i, mcap
+        m = len(outs)
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            self._mdev[k][:8 * m].copy_(self._mhost[k][:8 * m], non_blocking=True)
+            check(self.ctx.L.xyws_reassemble_streams(
+                self.ctx.h, C.c_void_p(self._dev[k].data_ptr()), C.c_void_p(self.counts_t.data_ptr()),
+                C.c_void_p(self._mdev[k].data_ptr()), m, opts, C.c_void_p(self.mresults_t.data_ptr()),
+                C.c_void_p(stream.cuda_stream)), "xyws_reassemble_streams")
+            self._done[k] = torch.cuda.Event()
+            self._done[k].record(stream)
+        return GroupMessages(self, result, mcap)
+
+    def msg_carry(self, conn_id):
+        """Host copy of a connection's message carry (synchronizes)."""
+        if not 0 <= conn_id < self.n:
+            raise XywsError(-1, "no such connection")
+        return _lib.MsgCarry.from_buffer_copy(self.mcarry_t[64 * conn_id:64 * conn_id + 64].cpu().numpy().tobytes())
 
 
 def decode_indexed(buf, starts, frames=True, parse_only=False):
