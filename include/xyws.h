@@ -37,6 +37,9 @@
  *   chat session's receive loop: one text message per        xyws_reassemble_streams (every
  *     connection and sweep, handed on to the room              connection's messages, one launch,
  *     example/websocket/websocket_chat.cpp:177-200             after xyws_decode_streams)
+ *   chat_room::deliver + chat_session::writer: each message  xyws_broadcast_streams (a room's
+ *     framed and sent once per member                          messages framed once, the wire
+ *     example/websocket/websocket_chat.cpp:89-101, 148-175     copied to every member's send range)
  *   recv_all / io_service remote-queue eventfd               xyws_arena_* (pinned recv arena,
  *     include/xynet/socket/impl/recv_all.h:86-121              H2D -> decode -> D2H, completion
  *     include/xynet/io_service.h:362-381                       written to an eventfd)
@@ -754,6 +757,137 @@ typedef struct xyws_reasm_result { /* 32 bytes */
 int xyws_reassemble_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const uint64_t* dev_nframes,
                             const xyws_reasm_conn* dev_reasm, uint64_t n, uint32_t opts,
                             xyws_reasm_result* dev_results /* n, nullable */, void* stream);
+
+/* ---- many connections, one broadcast call ---------------------------------
+ * The room of the same chat server: chat_room::deliver hands each message to
+ * every participant, the sender included, and each chat_session::writer sends
+ * websocket_frame_header{FIN | TEXT, size} + (message head + payload)
+ * (example/websocket/websocket_chat.cpp:89-101, 148-175). Here every room's
+ * messages of one sweep are framed once into the room's wire, and the wire is
+ * appended to every member's send range behind its reply: decode, reassemble,
+ * reply, broadcast, with no host read of device state between the calls.
+ * Server role: the frames are unmasked.
+ *
+ *  1. Inputs. dev_reasm is the table the xyws_reassemble_streams call of this
+ *     sweep used, dev_reasm_results the rows that call wrote; both are
+ *     required. Of dev_reasm[i] only out, out_cap, msgs and msg_cap are read
+ *     (a NULL out counts as out_cap 0). With s_i = min(nmsgs_i, msg_cap_i) (0
+ *     for a null msgs), connection i's stored records are msgs[0 .. s_i).
+ *     dev_bconns[i] goes with dev_reasm[i]: the connection's message head, its
+ *     send buffer, its row of this sweep's xyws_reply_streams results
+ *     (nullable) and its room.
+ *  2. Deliverable record. Record r of connection i is deliverable when all of
+ *     these hold:
+ *       - its status has XYWS_MSG_COMPLETE and none of CONTINUED, TRUNCATED,
+ *         UTF8_BAD: a whole message delivered by this sweep. A message that
+ *         spans sweeps is the caller's to deliver and counts as skipped;
+ *       - out_off + length <= out_cap_i: nothing outside [out, out + out_cap)
+ *         is ever read, whatever a record says (whole 16-byte lines that hold
+ *         one of its bytes are loaded);
+ *       - the reassembly row has no XYWS_RSM_OVERFLOW;
+ *       - when reply is given: its status has no XYWS_RPL_OVERFLOW; with
+ *         c = first_close != XYWS_NPOS the record's first_frame < c (messages
+ *         begun before the close frame); with status CLOSED and first_close ==
+ *         XYWS_NPOS (closed by an earlier sweep) no record is deliverable.
+ *     Known approximation: a message whose FIN fragment follows the close
+ *     frame within the same sweep, its first frame lying before it, is
+ *     delivered (the peer violated the protocol).
+ *  3. The room's wire. Its valid members in members[] order, each member's
+ *     deliverable records in record order: for each the wire gets
+ *     header(f, head_len_i + length) | head_i | the message bytes, the header
+ *     built as xyws_encode_frames builds it without keys (the minimal length
+ *     form: 2, 4 or 10 bytes), f = flags, or with XYWS_ENC_FRAME_OPCODE flags
+ *     with its opcode replaced by the record's. That is byte for byte what each
+ *     chat_session::writer sends for each message, in one fixed order. Wire
+ *     bytes at positions >= wire_cap are not written; wire_len, nmsgs and
+ *     skipped are exact whatever wire_cap. No byte outside
+ *     [wire, wire + min(wire_len, wire_cap)) is written.
+ *  4. Fan-out. Connection i with room r is a receiver unless reply is given
+ *     and has CLOSED or OVERFLOW: nothing follows a close frame.
+ *     base = reply ? reply->reply_len : 0. A receiver gets wire_r[0 .. w),
+ *     w = min(wire_len_r, wire_cap_r), at out + base; positions >= out_cap are
+ *     not written; bcast_len = w, send_len = base + w, XYWS_BC_TRUNCATED is set
+ *     when send_len > out_cap. A non-receiver gets bcast_len 0, send_len =
+ *     base, NOT_RECEIVER; a connection with no room (XYWS_ROOM_NONE, or a room
+ *     >= n_rooms) bcast_len 0, send_len = base, NO_ROOM. No byte outside
+ *     [out + min(base, out_cap), out + min(send_len, out_cap)) is written:
+ *     neighbouring connections' ranges may share a 16-byte line, as in a send
+ *     slab, and out, wire, head and the message buffers may have any alignment.
+ *  5. The caller's duties. Out ranges, wires and message buffers must not
+ *     overlap; a connection must be a member of at most one room;
+ *     dev_bconns[i].room must name the room that lists i. When the caller
+ *     breaks these the results are unspecified; the call still touches no
+ *     memory outside the ranges the tables name. A members[] entry >= n is
+ *     ignored, never dereferenced, and reported (XYWS_ROOM_BAD_MEMBER).
+ *  6. Sizing. A frame is its message's length_ir plus head_len_i plus a header
+ *     of at most 10 bytes, and a member's deliverable messages are disjoint
+ *     parts of its out_len_i message bytes, at most s_i of them, so
+ *     wire_cap >= sum over members (out_len_i + s_i * (10 + head_len_i)) always
+ *     suffices. The reply is at most len_i + 13 bytes (xyws_reply_streams, 9.)
+ *     and the wire appended at most wire_cap_r, so
+ *     out_cap >= (len_i + 13) + wire_cap_r always suffices for a send buffer.
+ *  7. Properties. At most two launches on `stream`: the wire build (one
+ *     workgroup per room; omitted when n_rooms == 0), then the fan-out;
+ *     dev_room_results is the hand-over between them, which is why it is
+ *     required. Like its siblings the call uses no context scratch, no scratch
+ *     slot and no policy word, never touches the device error word, reads no
+ *     device state on the host, needs no reserve, can be captured into a
+ *     hipGraph at once and runs concurrently on different streams. n == 0
+ *     returns XYWS_OK and launches nothing. XYWS_ERR_INVALID: a null ctx; null
+ *     dev_reasm, dev_reasm_results or dev_bconns with n > 0; null dev_rooms or
+ *     dev_room_results with n_rooms > 0; n >= UINT32_MAX; flags with
+ *     XYWS_FLAG_HAS_MASK; enc_opts bits other than XYWS_ENC_FRAME_OPCODE. Every
+ *     refusal is decided on the arguments alone, before the context is used. */
+#define XYWS_ROOM_NONE UINT32_MAX
+
+typedef struct xyws_room {            /* 32 bytes */
+  const uint32_t* members;   /* device: indices into the connection tables, in delivery order */
+  uint64_t        n_members;
+  void*           wire;      /* device, nullable (then wire_cap counts as 0): the room's outbound bytes of this sweep */
+  uint64_t        wire_cap;
+} xyws_room;
+
+typedef struct xyws_room_result {     /* 32 bytes */
+  uint64_t wire_len;   /* full length of the room's wire (may exceed wire_cap) */
+  uint32_t nmsgs;      /* messages framed onto it */
+  uint32_t skipped;    /* stored records of its members that were not delivered */
+  uint32_t receivers;  /* members that receive the wire */
+  uint32_t status;     /* XYWS_ROOM_* */
+  uint64_t reserved;
+} xyws_room_result;
+#define XYWS_ROOM_TRUNCATED  0x1u /* wire_len > wire_cap */
+#define XYWS_ROOM_BAD_MEMBER 0x2u /* a members[] entry >= n: ignored, never dereferenced */
+#define XYWS_ROOM_MSG_CAP    0x4u /* a member had nmsgs > msg_cap: unstored records cannot be delivered */
+
+typedef struct xyws_bcast_conn {      /* 64 bytes; entry i goes with dev_reasm[i] */
+  const void* head;      /* device, nullable: bytes put before each of this connection's messages
+                            (chat_session::make_message_head, websocket_chat.cpp:139-146) */
+  uint64_t    head_len;  /* 0 when head is NULL */
+  void*       out;       /* device: this connection's send buffer (the one xyws_reply_streams wrote) */
+  uint64_t    out_cap;
+  const xyws_reply_result* reply; /* device, nullable: this connection's row of the same sweep's reply call */
+  uint32_t    room;      /* index into dev_rooms, or XYWS_ROOM_NONE; >= n_rooms counts as NONE */
+  uint32_t    reserved0;
+  uint64_t    reserved[2];
+} xyws_bcast_conn;
+
+typedef struct xyws_bcast_result {    /* 32 bytes */
+  uint64_t send_len;   /* base + bcast_len: the caller sends out[0 .. min(send_len, out_cap)) */
+  uint64_t bcast_len;  /* bytes of the room's wire appended for this connection */
+  uint32_t status;     /* XYWS_BC_* */
+  uint32_t reserved0;
+  uint64_t reserved;
+} xyws_bcast_result;
+#define XYWS_BC_TRUNCATED    0x1u /* send_len > out_cap */
+#define XYWS_BC_NOT_RECEIVER 0x2u /* closed or overflowed: nothing appended */
+#define XYWS_BC_NO_ROOM      0x4u
+
+int xyws_broadcast_streams(xyws_ctx* ctx,
+                           const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                           const xyws_bcast_conn* dev_bconns, uint64_t n,
+                           const xyws_room* dev_rooms, xyws_room_result* dev_room_results, uint64_t n_rooms,
+                           uint8_t flags, uint32_t enc_opts,
+                           xyws_bcast_result* dev_results /* n, nullable */, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

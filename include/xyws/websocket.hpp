@@ -341,6 +341,28 @@ inline void reassemble_streams(context& ctx, const xyws_conn* dev_conns, const s
         "xyws_reassemble_streams");
 }
 
+// The room of the same sweep, in at most two launches (xyws_broadcast_streams):
+// dev_reasm and dev_reasm_results are the table and the rows of the
+// reassemble_streams call, dev_bconns[i] names connection i's message head,
+// send buffer, reply result row (nullable) and room. Every room's whole
+// messages are framed once with `flags` (default: the chat writer's
+// FIN | TEXT; with XYWS_ENC_FRAME_OPCODE each message's own opcode) into the
+// room's wire, and the wire is appended to every member's send range behind
+// its reply. dev_room_results (n_rooms entries) is required with n_rooms > 0;
+// dev_results (nullable device pointer, n entries) receives the send lengths.
+inline void broadcast_streams(context& ctx, const xyws_reasm_conn* dev_reasm,
+                              const xyws_reasm_result* dev_reasm_results, const xyws_bcast_conn* dev_bconns,
+                              std::uint64_t n, const xyws_room* dev_rooms, xyws_room_result* dev_room_results,
+                              std::uint64_t n_rooms,
+                              websocket_flags flags = websocket_flags::WS_FINAL_FRAME | websocket_flags::WS_OP_TEXT,
+                              std::uint32_t enc_opts = 0, xyws_bcast_result* dev_results = nullptr,
+                              void* stream = nullptr) {
+  check(xyws_broadcast_streams(ctx.native(), dev_reasm, dev_reasm_results, dev_bconns, n, dev_rooms,
+                               dev_room_results, n_rooms, static_cast<std::uint8_t>(flags), enc_opts, dev_results,
+                               stream),
+        "xyws_broadcast_streams");
+}
+
 // class websocket_frame_header (websocket_frame_header.h:179-224): a header in
 // a 14-byte array. As in the reference, the masked constructors keep the key
 // beside the header and build it with the key bytes zero (:183-202); with_key()

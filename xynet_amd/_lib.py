@@ -169,6 +169,36 @@ class ReasmResult(C.Structure):
 
 assert C.sizeof(ReplyCarry) == 32 and C.sizeof(ReplyConn) == 32 and C.sizeof(ReplyResult) == 32
 assert C.sizeof(ReasmConn) == 64 and C.sizeof(ReasmResult) == 32
+
+
+class Room(C.Structure):
+    """xyws_room (include/xyws.h), 32 bytes: one room of an xyws_broadcast_streams call."""
+    _fields_ = [("members", C.c_void_p), ("n_members", C.c_uint64), ("wire", C.c_void_p), ("wire_cap", C.c_uint64)]
+
+
+class RoomResult(C.Structure):
+    """xyws_room_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("wire_len", C.c_uint64), ("nmsgs", C.c_uint32), ("skipped", C.c_uint32),
+                ("receivers", C.c_uint32), ("status", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class BcastConn(C.Structure):
+    """xyws_bcast_conn (include/xyws.h), 64 bytes: entry i goes with entry i of the xyws_reasm_conn table."""
+    _fields_ = [("head", C.c_void_p), ("head_len", C.c_uint64), ("out", C.c_void_p), ("out_cap", C.c_uint64),
+                ("reply", C.c_void_p), ("room", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+class BcastResult(C.Structure):
+    """xyws_bcast_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("send_len", C.c_uint64), ("bcast_len", C.c_uint64), ("status", C.c_uint32),
+                ("reserved0", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(Room) == 32 and C.sizeof(RoomResult) == 32 and C.sizeof(BcastConn) == 64
+assert C.sizeof(BcastResult) == 32
+ROOM_NONE = 0xFFFFFFFF
+ROOM_TRUNCATED, ROOM_BAD_MEMBER, ROOM_MSG_CAP = 0x1, 0x2, 0x4  # xyws_room_result.status
+BC_TRUNCATED, BC_NOT_RECEIVER, BC_NO_ROOM = 0x1, 0x2, 0x4  # xyws_bcast_result.status
 assert C.sizeof(ArenaResult) == 104
 XYWS_ERR_AGAIN = -6
 ARENA_SLOTS = 8
@@ -263,6 +293,11 @@ def load():
     # (no HIP call: frames per tile, bytes per copy step, grid cap, wave size)
     L.xyws_debug_reasm_streams_geometry.restype = i32
     L.xyws_debug_reasm_streams_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_broadcast_streams.restype = i32
+    L.xyws_broadcast_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, u64, u8, u32, vp, vp]
+    # (no HIP call: members per tile of the wire build, bytes per fan-out step, grid cap, wave size)
+    L.xyws_debug_broadcast_geometry.restype = i32
+    L.xyws_debug_broadcast_geometry.argtypes = [C.POINTER(u64)]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]

@@ -1,0 +1,416 @@
+// xyws_broadcast.hip — xyws_broadcast_streams: a sweep's messages framed once
+// per room and copied to every member's send range (the reference's
+// chat_room::deliver and chat_session::writer,
+// example/websocket/websocket_chat.cpp:89-101, 148-175, run once per message
+// and member). The semantics are stated in include/xyws.h; this is how they
+// are computed.
+//
+// Two launches, the room result rows the hand-over between them. No workgroup
+// waits for another inside a launch, nothing spins, there are no atomics.
+//
+// k_room_wire: one workgroup per room, rooms grid-strided. The members are
+// taken in tiles of BC_TILE, one member per thread:
+//   1. the thread reads its member's table entries (bounds-checked index),
+//      decides the gate (reassembly overflow, reply overflow, closed, the
+//      first close of this sweep), walks the stored records, tests each
+//      (frame_of) and sums the frame sizes header + head + message;
+//   2. a workgroup scan gives each member's offset in the wire; the offsets
+//      and what the copy needs of a member go to LDS; the running sum is
+//      carried between tiles in a register;
+//   3. the copy phase covers the tile's wire range in 16-byte lines, one line
+//      per thread per step: a binary search in the LDS offsets finds the
+//      member of the line's first byte, the member's records are walked to the
+//      frame that holds it, and header, head and message bytes are composed in
+//      registers (source bytes: one or two aligned 16-byte loads funnelled to
+//      the byte offset); a 16-byte store inside the range and the capacity,
+//      byte stores on the range's first and last line.
+// The result row is written once, after the last tile.
+//
+// k_room_fanout: blockIdx.x strides over the connections, blockIdx.y over
+// BC_STEP-byte chunks of the connection's destination range, so a few
+// connections with a long wire still fill the machine (the host cannot know
+// the wire lengths: the chunks are strided, whatever the length). A thread
+// takes one destination-aligned 16-byte line: the source is one or two
+// aligned loads funnelled to (wire - out - base) mod 16. The first and last
+// line of the range are stored byte by byte (a send slab's neighbours share
+// them). The y == 0 workgroup writes the connection's result row.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <mutex>
+
+#include "xyws.h"
+#include "xyws_device.h"
+#include "xyws_ctx.h"
+#include "xyws_frameops.h"
+
+#define BC_THREADS 256u     // the fan-out: four waves
+#define BC_WAVE 64u
+#define BC_WIRE_THREADS 1024u  // the wire build: sixteen waves, the one workgroup a room gets
+#define BC_TILE BC_WIRE_THREADS  // members per tile of the wire build: one per thread
+#define BC_LINE 16u         // bytes a thread writes per copy step
+#define BC_STEP (BC_LINE * BC_THREADS)  // bytes a workgroup writes per step (the fan-out)
+#define BC_GRID_CAP 8192u   // rooms / connections per launch in x; further ones are grid-strided
+#define BC_BLOCKS_AIM 4096u // fan-out: workgroups wanted in flight (256 CUs x 16)
+#define BC_SLICES_MAX 256u  // fan-out: at most this many workgroups share one connection
+
+using namespace xyws_internal;
+
+namespace {
+
+XYWS_DEV void or_into(bytes16& acc, bytes16 p) {
+  acc.lo |= p.lo;
+  acc.hi |= p.hi;
+}
+
+XYWS_DEV void store_line(g_u8* obase, uint64_t A, bytes16 v) {
+  *reinterpret_cast<g_u32x4*>(obase + A) =
+      u32x4{(uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32)};
+}
+
+// Bytes [s, we) of the line at A, byte by byte (v holds the line's bytes at their line offsets).
+XYWS_DEV void store_edge(g_u8* obase, uint64_t A, uint64_t s, uint64_t we, bytes16 v) {
+#pragma unroll 1
+  for (uint64_t p = s; p < we; p++) {
+    const uint32_t b = (uint32_t)(p - A);
+    obase[p] = (uint8_t)(b < 8 ? v.lo >> (8u * b) : v.hi >> (8u * (b - 8)));
+  }
+}
+
+// What the wire build keeps of a member: gate = records with first_frame
+// below it can be delivered (0: none; XYWS_NPOS: no close in this sweep).
+struct member {
+  uint64_t msgs, gate, out, out_cap, head, head_len;
+  uint32_t stored;
+};
+
+// One stored record (its five words at rec) of a member: deliverable or not;
+// if so its frame: header words hw, header length h, message at out + off,
+// length len.
+struct frame_info {
+  uint64_t off, len;
+  uint32_t hw[4], h;
+};
+XYWS_DEV bool frame_of(const g_u64* rec, const member& m, uint32_t flags, uint32_t enc_opts, frame_info& f) {
+  const uint64_t first = rec[0], off = rec[2], len = rec[3], w4 = rec[4];
+  const uint32_t st = (uint32_t)w4, op = (uint32_t)(w4 >> 32) & XYWS_FLAG_OP_MASK;
+  if (!(st & XYWS_MSG_COMPLETE) || (st & (XYWS_MSG_CONTINUED | XYWS_MSG_TRUNCATED | XYWS_MSG_UTF8_BAD))) return false;
+  if (off > m.out_cap || len > m.out_cap - off) return false;  // (nothing outside [out, out + out_cap) is read)
+  if (m.gate != XYWS_NPOS && first >= m.gate) return false;
+  f.off = off;
+  f.len = len;
+  const uint32_t fl = (enc_opts & XYWS_ENC_FRAME_OPCODE) ? (flags & ~(uint32_t)XYWS_FLAG_OP_MASK) | op : flags;
+  f.h = build_header(fl, m.head_len + len, false, 0, f.hw);
+  return true;
+}
+
+// Inclusive scan of v over the workgroup (s_w: one slot per wave); total: the sum.
+XYWS_DEV uint64_t block_scan(uint64_t v, uint32_t tid, uint64_t* s_w, uint64_t& total) {
+  const uint32_t lane = tid & (BC_WAVE - 1u), wave = tid / BC_WAVE;
+  uint64_t incl = v;
+#pragma unroll
+  for (uint32_t d = 1; d < BC_WAVE; d <<= 1) {
+    const uint64_t o = shfl_up64(incl, d);
+    if (lane >= d) incl += o;
+  }
+  if (lane == BC_WAVE - 1u) s_w[wave] = incl;
+  __syncthreads();
+  uint64_t before = 0, all = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < BC_WIRE_THREADS / BC_WAVE; w++) {
+    const uint64_t x = s_w[w];
+    if (w < wave) before += x;
+    all += x;
+  }
+  total = all;
+  __syncthreads();  // (s_w is reused)
+  return incl + before;
+}
+
+__global__ void __launch_bounds__(BC_WIRE_THREADS)
+    k_room_wire(const xyws_reasm_conn* __restrict__ reasm, const xyws_reasm_result* __restrict__ rres,
+                const xyws_bcast_conn* __restrict__ bconns, uint64_t n, const xyws_room* __restrict__ rooms,
+                xyws_room_result* __restrict__ room_results, uint64_t n_rooms, uint32_t flags, uint32_t enc_opts) {
+  static_assert(sizeof(xyws_room) == 32 && sizeof(xyws_room_result) == 32 && sizeof(xyws_bcast_conn) == 64 &&
+                    sizeof(xyws_bcast_result) == 32 && sizeof(xyws_reply_result) == 32 &&
+                    offsetof(xyws_reply_result, status) == 22 && offsetof(xyws_bcast_conn, room) == 40,
+                "layouts");
+  __shared__ uint64_t s_off[BC_TILE + 1];  // members: start in the wire (and the end after the last)
+  __shared__ uint64_t s_msgs[BC_TILE], s_gate[BC_TILE], s_out[BC_TILE], s_ocap[BC_TILE], s_head[BC_TILE],
+      s_hlen[BC_TILE];
+  __shared__ uint32_t s_stored[BC_TILE];
+  __shared__ uint64_t s_w[BC_WIRE_THREADS / BC_WAVE];
+  const uint32_t tid = threadIdx.x;
+  for (uint64_t ri = blockIdx.x; ri < n_rooms; ri += gridDim.x) {
+    const g_u64* const rq = (const g_u64*)(rooms + ri);
+    const uint64_t members = uniform64(rq[0]);
+    const uint64_t nm = members ? uniform64(rq[1]) : 0;
+    const uint64_t wire = uniform64(rq[2]);
+    const uint64_t wire_cap = wire ? uniform64(rq[3]) : 0;
+    g_u8* const wbase = (g_u8*)(wire & ~15ull);
+    const uint64_t wlo = wire & 15u;
+    const uint64_t wlim = sat_add(wlo, wire_cap);
+
+    uint64_t wpos = 0;                                       // the wire so far (uniform)
+    uint32_t c_msgs = 0, c_skip = 0, c_recv = 0, c_st = 0;   // this thread's members
+    for (uint64_t base = 0; base < nm; base += BC_TILE) {
+      // 1. this thread's member
+      member m = {0, 0, 0, 0, 0, 0, 0};
+      uint64_t size = 0;
+      if (base + tid < nm) {
+        const uint64_t ci = ((const XYWS_GLOBAL uint32_t*)members)[base + tid];
+        if (ci >= n) {
+          c_st |= XYWS_ROOM_BAD_MEMBER;
+        } else {
+          const g_u64* const aq = (const g_u64*)(reasm + ci);
+          const g_u64* const ar = (const g_u64*)(rres + ci);
+          const g_u64* const bq = (const g_u64*)(bconns + ci);
+          m.out = aq[0];
+          m.out_cap = m.out ? aq[1] : 0;
+          m.msgs = aq[3];
+          const uint64_t msg_cap = m.msgs ? aq[4] : 0;
+          const uint64_t nmsgs = ar[1];
+          const uint32_t rst = (uint32_t)(ar[2] >> 32);
+          const uint64_t kept = nmsgs < msg_cap ? nmsgs : msg_cap;
+          m.stored = kept < 0xFFFFFFFFull ? (uint32_t)kept : 0xFFFFFFFFu;  // (the counts are 32 bits)
+          if (nmsgs > msg_cap) c_st |= XYWS_ROOM_MSG_CAP;
+          m.head = bq[0];
+          m.head_len = m.head ? bq[1] : 0;
+          m.gate = (rst & XYWS_RSM_OVERFLOW) ? 0 : XYWS_NPOS;
+          const g_u64* const rp = (const g_u64*)bq[4];
+          bool receiver = true;
+          if (rp) {
+            const uint64_t fc = rp[1];
+            const uint32_t pst = (uint32_t)(rp[2] >> 48);
+            if (pst & (XYWS_RPL_CLOSED | XYWS_RPL_OVERFLOW)) receiver = false;
+            if ((pst & XYWS_RPL_OVERFLOW) || ((pst & XYWS_RPL_CLOSED) && fc == XYWS_NPOS)) m.gate = 0;
+            else if (fc != XYWS_NPOS && m.gate) m.gate = fc;
+          }
+          c_recv += receiver ? 1u : 0u;
+#pragma unroll 1
+          for (uint32_t r = 0; r < m.stored; r++) {
+            frame_info f;
+            if (frame_of((const g_u64*)(m.msgs + 40ull * r), m, flags, enc_opts, f)) {
+              size += f.h + m.head_len + f.len;
+              c_msgs++;
+            } else {
+              c_skip++;
+            }
+          }
+        }
+      }
+      // 2. offsets in the wire
+      uint64_t total;
+      const uint64_t incl = block_scan(size, tid, s_w, total);
+      const uint64_t o0 = wpos, o1 = wpos + total;
+      s_off[tid] = o0 + (incl - size);
+      s_msgs[tid] = m.msgs;
+      s_gate[tid] = m.gate;
+      s_out[tid] = m.out;
+      s_ocap[tid] = m.out_cap;
+      s_head[tid] = m.head;
+      s_hlen[tid] = m.head_len;
+      s_stored[tid] = size ? m.stored : 0u;  // (a member without a frame is not walked)
+      if (tid == 0) s_off[BC_TILE] = o1;
+      __syncthreads();
+
+      // 3. the tile's bytes [o0, o1)
+      const uint64_t P0 = wlo + o0, P1 = wlo + o1;
+      const uint64_t wl = P1 < wlim ? P1 : wlim;
+      if (wl > P0) {
+        for (uint64_t A = ((P0 >> 4) + tid) << 4; A < wl; A += (uint64_t)BC_LINE * BC_WIRE_THREADS) {
+          const uint64_t s = A > P0 ? A : P0, e = A + 16 < P1 ? A + 16 : P1;
+          uint64_t q = s - wlo;
+          // the last member whose start is at or before q: it holds byte q (q < o1)
+          uint32_t i = 0, hi = BC_TILE;
+          while (hi - i > 1) {
+            const uint32_t mid = (i + hi) >> 1;
+            if (s_off[mid] <= q) i = mid;
+            else hi = mid;
+          }
+          bytes16 acc = {0, 0};
+          uint32_t a = (uint32_t)(s - A);
+          const uint32_t ae = (uint32_t)(e - A);
+          while (a < ae && i < BC_TILE) {
+            member k;
+            k.msgs = s_msgs[i];
+            k.gate = s_gate[i];
+            k.out = s_out[i];
+            k.out_cap = s_ocap[i];
+            k.head = s_head[i];
+            k.head_len = s_hlen[i];
+            k.stored = s_stored[i];
+            uint64_t fo = s_off[i];  // the start of the frame under test
+#pragma unroll 1
+            for (uint32_t r = 0; r < k.stored && a < ae; r++) {
+              frame_info f;
+              if (!frame_of((const g_u64*)(k.msgs + 40ull * r), k, flags, enc_opts, f)) continue;
+              const uint64_t fsz = f.h + k.head_len + f.len;
+              if (fo + fsz > q) {
+                uint64_t rr = q - fo;
+                if (rr < f.h) {  // header bytes rr.. at line offset a
+                  const uint32_t nb = f.h - (uint32_t)rr < ae - a ? f.h - (uint32_t)rr : ae - a;
+                  const bytes16 hd = {(uint64_t)f.hw[0] | ((uint64_t)f.hw[1] << 32), (uint64_t)f.hw[2]};
+                  or_into(acc, shl_bytes(low_bytes(shr_bytes(hd, (uint32_t)rr), nb), a));
+                  a += nb;
+                  q += nb;
+                  rr += nb;
+                }
+                if (a < ae && rr < f.h + k.head_len) {  // head bytes
+                  const uint64_t left = f.h + k.head_len - rr;
+                  const uint32_t nb = left < ae - a ? (uint32_t)left : ae - a;
+                  or_into(acc, shl_bytes(low_bytes(load_bytes(k.head + (rr - f.h), nb), nb), a));
+                  a += nb;
+                  q += nb;
+                  rr += nb;
+                }
+                if (a < ae && rr < fsz) {  // message bytes
+                  const uint64_t left = fsz - rr;
+                  const uint32_t nb = left < ae - a ? (uint32_t)left : ae - a;
+                  or_into(acc, shl_bytes(low_bytes(load_bytes(k.out + f.off + (rr - f.h - k.head_len), nb), nb), a));
+                  a += nb;
+                  q += nb;
+                }
+              }
+              fo += fsz;
+            }
+            i++;
+          }
+          if (s == A && e == A + 16 && A >= wlo && A + 16 <= wlim) store_line(wbase, A, acc);
+          else store_edge(wbase, A, s, e < wlim ? e : wlim, acc);  // the range's first or last line
+        }
+      }
+      wpos = o1;
+      __syncthreads();  // (LDS is rewritten by the next tile)
+    }
+
+    // the result row: the threads' counts summed
+    uint64_t t0, t1;
+    block_scan((uint64_t)c_msgs | ((uint64_t)c_skip << 32), tid, s_w, t0);
+    block_scan((uint64_t)c_recv, tid, s_w, t1);
+    uint32_t st = c_st;
+#pragma unroll
+    for (uint32_t d = 1; d < BC_WAVE; d <<= 1) st |= (uint32_t)__shfl_xor((int)st, (int)d);
+    if ((tid & (BC_WAVE - 1u)) == 0) s_w[tid / BC_WAVE] = st;
+    __syncthreads();
+    if (tid == 0) {
+      st = 0;
+      for (uint32_t w = 0; w < BC_WIRE_THREADS / BC_WAVE; w++) st |= (uint32_t)s_w[w];
+      if (wpos > wire_cap) st |= XYWS_ROOM_TRUNCATED;
+      g_u64* const res = (g_u64*)(room_results + ri);
+      res[0] = wpos;
+      res[1] = t0;  // nmsgs | skipped << 32
+      res[2] = (t1 & 0xFFFFFFFFull) | ((uint64_t)st << 32);
+      res[3] = 0;
+    }
+    __syncthreads();  // (s_w is reused by the next room)
+  }
+}
+
+__global__ void __launch_bounds__(BC_THREADS) k_room_fanout(const xyws_bcast_conn* __restrict__ bconns, uint64_t n,
+                                                            const xyws_room* __restrict__ rooms,
+                                                            const xyws_room_result* __restrict__ room_results,
+                                                            uint64_t n_rooms, xyws_bcast_result* __restrict__ results) {
+  const uint32_t tid = threadIdx.x;
+  for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
+    const g_u64* const bq = (const g_u64*)(bconns + ci);
+    const uint64_t out = uniform64(bq[2]);
+    const uint64_t out_cap = out ? uniform64(bq[3]) : 0;
+    const g_u64* const rp = (const g_u64*)uniform64(bq[4]);
+    const uint64_t room = uniform64(bq[5]) & 0xFFFFFFFFull;
+    uint64_t base = 0;
+    uint32_t pst = 0;
+    if (rp) {
+      base = uniform64(rp[0]);
+      pst = (uint32_t)(uniform64(rp[2]) >> 48);
+    }
+    uint32_t st = 0;
+    uint64_t w = 0, wire = 0;
+    if (room >= n_rooms) {  // (XYWS_ROOM_NONE is above every index)
+      st = XYWS_BC_NO_ROOM;
+    } else if (pst & (XYWS_RPL_CLOSED | XYWS_RPL_OVERFLOW)) {
+      st = XYWS_BC_NOT_RECEIVER;
+    } else {
+      const g_u64* const rq = (const g_u64*)(rooms + room);
+      wire = uniform64(rq[2]);
+      const uint64_t wire_cap = wire ? uniform64(rq[3]) : 0;
+      const uint64_t wire_len = uniform64(((const g_u64*)(room_results + room))[0]);
+      w = wire_len < wire_cap ? wire_len : wire_cap;
+    }
+    const uint64_t send_len = sat_add(base, w);
+    if (send_len > out_cap) st |= XYWS_BC_TRUNCATED;
+    if (results && blockIdx.y == 0 && tid == 0) {
+      g_u64* const res = (g_u64*)(results + ci);
+      res[0] = send_len;
+      res[1] = w;
+      res[2] = st;
+      res[3] = 0;
+    }
+    if (!w || base >= out_cap) continue;
+
+    // destination positions count from obase (16-byte aligned): out[k] is at olo + k
+    g_u8* const obase = (g_u8*)(out & ~15ull);
+    const uint64_t olo = out & 15u;
+    const uint64_t wlim = sat_add(olo, out_cap);
+    const uint64_t P0 = olo + base, P1 = sat_add(P0, w);
+    const uint64_t wl = P1 < wlim ? P1 : wlim;
+    const uint64_t A00 = (P0 >> 4) << 4;
+    for (uint64_t A0 = A00 + (uint64_t)blockIdx.y * BC_STEP; A0 < wl; A0 += (uint64_t)gridDim.y * BC_STEP) {
+      const uint64_t A = A0 + 16u * tid;
+      if (A >= wl) break;
+      if (A >= P0 && A + 16 <= wl) {  // a whole line inside the range: wire bytes A - P0 ..
+        store_line(obase, A, load_bytes(wire + (A - P0), 16));
+      } else {  // the range's first or last line: its own bytes only
+        const uint64_t s = A > P0 ? A : P0, e = A + 16 < wl ? A + 16 : wl;
+        const bytes16 v = shl_bytes(load_bytes(wire + (s - P0), (uint32_t)(e - s)), (uint32_t)(s - A));
+        store_edge(obase, A, s, e, v);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int xyws_broadcast_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                           const xyws_bcast_conn* dev_bconns, uint64_t n, const xyws_room* dev_rooms,
+                           xyws_room_result* dev_room_results, uint64_t n_rooms, uint8_t flags, uint32_t enc_opts,
+                           xyws_bcast_result* dev_results, void* stream) {
+  if (!ctx || (n && (!dev_reasm || !dev_reasm_results || !dev_bconns))) return XYWS_ERR_INVALID;
+  if (n_rooms && (!dev_rooms || !dev_room_results)) return XYWS_ERR_INVALID;
+  if (n >= UINT32_MAX) return XYWS_ERR_INVALID;            // (a member index is 32 bits, UINT32_MAX is no index)
+  if (flags & XYWS_FLAG_HAS_MASK) return XYWS_ERR_INVALID;  // server role only
+  if (enc_opts & ~XYWS_ENC_FRAME_OPCODE) return XYWS_ERR_INVALID;
+  if (!n) return XYWS_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  device_guard g(ctx->device);
+  if (!g.ok) return XYWS_ERR_HIP;
+  if (n_rooms) {
+    const uint32_t grid = grid_for(n_rooms, 1, BC_GRID_CAP);
+    hipLaunchKernelGGL(k_room_wire, dim3(grid), dim3(BC_WIRE_THREADS), 0, (hipStream_t)stream, dev_reasm,
+                       dev_reasm_results, dev_bconns, n, dev_rooms, dev_room_results, n_rooms, (uint32_t)flags, enc_opts);
+    const int rc = hip_err(hipGetLastError());
+    if (rc != XYWS_OK) return rc;
+  }
+  const uint32_t gx = grid_for(n, 1, BC_GRID_CAP);
+  uint32_t gy = (BC_BLOCKS_AIM + gx - 1u) / gx;
+  if (gy > BC_SLICES_MAX) gy = BC_SLICES_MAX;
+  if (!n_rooms) gy = 1;  // (result rows only)
+  hipLaunchKernelGGL(k_room_fanout, dim3(gx, gy), dim3(BC_THREADS), 0, (hipStream_t)stream, dev_bconns, n, dev_rooms,
+                     dev_room_results, n_rooms, dev_results);
+  return hip_err(hipGetLastError());
+}
+
+// Internal (tests and measurements, no HIP call): the geometry of
+// k_room_wire and k_room_fanout. out: {members per tile of the wire build,
+// bytes per fan-out step, grid cap, wave size}.
+int xyws_debug_broadcast_geometry(uint64_t out[4]) {
+  if (!out) return XYWS_ERR_INVALID;
+  out[0] = BC_TILE;
+  out[1] = BC_STEP;
+  out[2] = BC_GRID_CAP;
+  out[3] = BC_WAVE;
+  return XYWS_OK;
+}
+
+}  // extern "C"

@@ -371,6 +371,39 @@ class GroupMessages:
         return [arr[j] for j in range(n)]
 
 
+class GroupBroadcast:
+    """Results, room results and wires of one connection_group.broadcast call,
+    item k as in the decode result of its sweep, room r as in the `rooms`
+    argument (host copies on demand). It owns the call's tables, wires and
+    result rows."""
+
+    def __init__(self, group, decoded, tensors, wires):
+        self.group, self.decoded, self._tensors, self._wires = group, decoded, tensors, wires
+        self._rows = self._rrows = None
+
+    def result(self, k):
+        """xyws_bcast_result of item k."""
+        if self._rows is None:
+            self._rows = self._tensors["results"].cpu().numpy().tobytes()
+        if not 0 <= k < len(self.decoded.ids):
+            raise IndexError(k)
+        return _lib.BcastResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+
+    def room_result(self, r):
+        """xyws_room_result of room r."""
+        if self._rrows is None:
+            self._rrows = self._tensors["room_results"].cpu().numpy().tobytes()
+        if not 0 <= r < len(self._wires):
+            raise IndexError(r)
+        return _lib.RoomResult.from_buffer_copy(self._rrows[32 * r:32 * r + 32])
+
+    def wire(self, r):
+        """Room r's outbound bytes of this sweep (a device tensor: the first
+        min(wire_len, wire_cap) bytes)."""
+        res = self.room_result(r)
+        return self._wires[r][:min(res.wire_len, self._wires[r].numel())]
+
+
 class connection_group:
     """The decoder states of n connections and one xyws_decode_streams call
     for whatever a sweep of the completion queue brought: decode() takes the
@@ -381,7 +414,9 @@ class connection_group:
     vector. reply() then answers what decode() found, again in one launch
     (xyws_reply_streams): a whole echo sweep is two launches. reassemble()
     gathers and validates the messages of what decode() found, in one launch
-    too (xyws_reassemble_streams), before or after reply()."""
+    too (xyws_reassemble_streams), before or after reply(). broadcast() then
+    delivers those messages to their rooms (xyws_broadcast_streams): each
+    room's wire behind every member's reply."""
     RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
 
     def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
@@ -541,7 +576,85 @@ class connection_group:
                 C.c_void_p(stream.cuda_stream)), "xyws_reassemble_streams")
             self._done[k] = torch.cuda.Event()
             self._done[k].record(stream)
-        return GroupMessages(self, result, mcap)
+        got = GroupMessages(self, result, mcap)
+        got.out_caps = [t.numel() for t in outs]  # (broadcast() sizes the wires by them)
+        return got
+
+    def broadcast(self, messages, rooms, out_items, heads=None, reply=None, flags=0x11, enc_opts=0, wire_caps=None):
+        """Deliver the whole messages of the reassemble() call that returned
+        `messages` to their rooms (xyws_broadcast_streams, two launches):
+        rooms[r] lists the connection ids of room r in delivery order; every
+        one must be an item of this sweep (a member that received nothing is
+        decoded with an empty buffer) and belongs to one room. Each room's
+        messages are framed once with `flags` (default FIN | TEXT, the chat
+        writer's; with XYWS_ENC_FRAME_OPCODE each message's own opcode),
+        heads[k] (a device uint8 tensor or None) before every message of item
+        k, and the room's wire is appended to out_items[k] of every member:
+        behind its reply when `reply` is the GroupReply of the same sweep
+        (out_items are then the tensors reply() wrote), from the start
+        otherwise. wire_caps[r]: room r's wire capacity (default: the bound
+        that always suffices). Returns a GroupBroadcast. Call it before the
+        group's next decode(), reply() or reassemble()."""
+        import numpy as np
+        import torch
+        dec = messages.decoded
+        if messages.group is not self or dec._slot is None or not hasattr(messages, "out_caps"):
+            raise XywsError(-1, "broadcast() takes the result of this group's reassemble()")
+        if reply is not None and (reply.group is not self or reply.decoded is not dec):
+            raise XywsError(-1, "reply must be the reply() result of the same sweep")
+        outs = [_dev_u8(t) for t in out_items]
+        m = len(dec.ids)
+        if len(outs) != m or any(t.device != self.device for t in outs):
+            raise XywsError(-1, "one send buffer on the group's device per decoded item")
+        hds = [None] * m if heads is None else [None if h is None else _dev_u8(h) for h in heads]
+        if len(hds) != m or any(h is not None and h.device != self.device for h in hds):
+            raise XywsError(-1, "one head (or None) on the group's device per decoded item")
+        item = {i: k for k, i in enumerate(dec.ids)}
+        room_of, flat = {}, []
+        for r, ids in enumerate(rooms):
+            for i in ids:
+                if int(i) not in item or int(i) in room_of:
+                    raise XywsError(-1, "a room member must be an item of this sweep and in one room only")
+                room_of[int(i)] = r
+                flat.append(item[int(i)])
+        nr = len(rooms)
+        if wire_caps is not None and len(wire_caps) != nr:
+            raise XywsError(-1, "one wire capacity per room")
+        hlen = [0 if h is None else h.numel() for h in hds]
+        wires = []
+        for r, ids in enumerate(rooms):
+            need = sum(messages.out_caps[item[int(i)]] + messages.msg_cap * (10 + hlen[item[int(i)]]) for i in ids)
+            wires.append(torch.empty(max(need if wire_caps is None else int(wire_caps[r]), 1), dtype=torch.uint8,
+                                     device=self.device))
+        btab = np.zeros((max(m, 1), 8), np.uint64)  # xyws_bcast_conn: head, head_len, out, out_cap, reply, room, reserved[2]
+        rbase = self.results_t.data_ptr()
+        for k, (i, t, h) in enumerate(zip(dec.ids, outs, hds)):
+            btab[k, 0], btab[k, 1] = (h.data_ptr(), h.numel()) if h is not None and h.numel() else (0, 0)
+            btab[k, 2], btab[k, 3] = t.data_ptr(), t.numel()
+            btab[k, 4] = rbase + 32 * k if reply is not None else 0
+            btab[k, 5] = room_of.get(i, _lib.ROOM_NONE)
+        with torch.cuda.device(self.device):
+            members_t = torch.from_numpy(np.asarray(flat + [0], np.uint32).view(np.uint8)).to(self.device)
+            rtab = np.zeros((max(nr, 1), 4), np.uint64)  # xyws_room: members, n_members, wire, wire_cap
+            pos = 0
+            for r, ids in enumerate(rooms):
+                cap = wires[r].numel() if wire_caps is None else int(wire_caps[r])
+                rtab[r] = [members_t.data_ptr() + 4 * pos, len(ids), wires[r].data_ptr() if cap else 0, cap]
+                pos += len(ids)
+            tensors = dict(members=members_t, rooms=torch.from_numpy(rtab.reshape(-1).view(np.uint8)).to(self.device),
+                           bconns=torch.from_numpy(btab.reshape(-1).view(np.uint8)).to(self.device),
+                           room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
+                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
+                           outs=outs, heads=hds)
+            stream = torch.cuda.current_stream(self.device)
+            check(self.ctx.L.xyws_broadcast_streams(
+                self.ctx.h, C.c_void_p(self._mdev[dec._slot].data_ptr()), C.c_void_p(self.mresults_t.data_ptr()),
+                C.c_void_p(tensors["bconns"].data_ptr()), m, C.c_void_p(tensors["rooms"].data_ptr()),
+                C.c_void_p(tensors["room_results"].data_ptr()), nr, flags, enc_opts,
+                C.c_void_p(tensors["results"].data_ptr()), C.c_void_p(stream.cuda_stream)), "xyws_broadcast_streams")
+            self._done[dec._slot] = torch.cuda.Event()
+            self._done[dec._slot].record(stream)
+        return GroupBroadcast(self, dec, tensors, wires)
 
     def msg_carry(self, conn_id):
         """Host copy of a connection's message carry (synchronizes)."""
