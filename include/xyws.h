@@ -40,6 +40,9 @@
  *   chat_room::deliver + chat_session::writer: each message  xyws_broadcast_streams (a room's
  *     framed and sent once per member                          messages framed once, the wire
  *     example/websocket/websocket_chat.cpp:89-101, 148-175     copied to every member's send range)
+ *   (new) a chat message cut by a recv boundary, which the   xyws_hold_streams (its parts kept
+ *     reference's session reads to its end before deliver      on the device between sweeps, the
+ *     example/websocket/websocket_chat.cpp:177-200              whole message handed to the room)
  *   recv_all / io_service remote-queue eventfd               xyws_arena_* (pinned recv arena,
  *     include/xynet/socket/impl/recv_all.h:86-121              H2D -> decode -> D2H, completion
  *     include/xynet/io_service.h:362-381                       written to an eventfd)
@@ -780,7 +783,8 @@ int xyws_reassemble_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const uin
  *     these hold:
  *       - its status has XYWS_MSG_COMPLETE and none of CONTINUED, TRUNCATED,
  *         UTF8_BAD: a whole message delivered by this sweep. A message that
- *         spans sweeps is the caller's to deliver and counts as skipped;
+ *         spans sweeps counts as skipped here; xyws_hold_streams (below),
+ *         called before this call, hands it over as such a whole record;
  *       - out_off + length <= out_cap_i: nothing outside [out, out + out_cap)
  *         is ever read, whatever a record says (whole 16-byte lines that hold
  *         one of its bytes are loaded);
@@ -888,6 +892,132 @@ int xyws_broadcast_streams(xyws_ctx* ctx,
                            const xyws_room* dev_rooms, xyws_room_result* dev_room_results, uint64_t n_rooms,
                            uint8_t flags, uint32_t enc_opts,
                            xyws_bcast_result* dev_results /* n, nullable */, void* stream);
+
+/* ---- many connections, one hold call ---------------------------------------
+ * The message a recv boundary cut: xyws_reassemble_streams reports it as an
+ * open record in one sweep and as XYWS_MSG_CONTINUED records in the next, and
+ * xyws_broadcast_streams delivers neither. This call, between the two, keeps
+ * the parts of such a message in a per-connection hold on the device and, in
+ * the sweep that completes it, hands the broadcast a view of the reassembly
+ * table in which the whole message is one ordinary record: decode, reassemble,
+ * hold, reply, broadcast, still with no host read of device state. dev_reasm
+ * and dev_reasm_results are the table and rows of this sweep's
+ * xyws_reassemble_streams call; dev_view and dev_view_results (n entries each)
+ * are written here and passed to xyws_broadcast_streams in their place. The
+ * call is independent of xyws_reply_streams.
+ *
+ * Where the hold lives. The hold of connection i is the hold_cap bytes
+ * immediately in front of its reassembly range: hold = out - hold_cap. The
+ * caller allocates one area per connection and gives xyws_reassemble_streams
+ * out = area + hold_cap (that call never writes in front of out), so the view
+ * names hold and message bytes with one base. With H = (hold_cap / 2) & ~15
+ * the hold is used as two halves [0, H) and [H, 2H): a held message never
+ * exceeds H, and a message delivered from one half stays readable there while
+ * the next one begins in the other. hold_cap >= 2 * (largest message accepted)
+ * + 30 always suffices (H rounds hold_cap / 2 down to a 16-byte line).
+ *
+ * Per connection, with s = min(nmsgs, msg_cap) (0 for a null msgs) and the
+ * carry hc:
+ *
+ *  0. Pass-through. out NULL, hc NULL or H == 0: dev_view[i] and
+ *     dev_view_results[i] are the inputs copied verbatim, the result is
+ *     {0, 0, XYWS_HOLD_PASSTHROUGH}; nothing else is touched.
+ *  1. The view. Otherwise dev_view[i] = {out - hold_cap, hold_cap + out_cap,
+ *     mc, vmsgs, min(msg_cap, vmsg_cap), 0...} (a null vmsgs counts as
+ *     vmsg_cap 0) and dev_view_results[i] is the input row, with
+ *     XYWS_RSM_MSG_CAP added when s > vmsg_cap. View record j, j <
+ *     min(s, vmsg_cap), is record j with out_off += hold_cap; the one
+ *     exception is the delivered record of step 3.
+ *  2. Overflow. The row has XYWS_RSM_OVERFLOW: the carry becomes
+ *     {status = LOST} and stays so, as XYWS_MSG_OVERFLOW does (DROPPED when a
+ *     message was held).
+ *  3. Record 0 with XYWS_MSG_CONTINUED (stored). With an ACTIVE carry the
+ *     record's bytes out[out_off .. +length) are appended at
+ *     hold[start + held ..), held += length, nframes += the record's. If the
+ *     record has TRUNCATED, or out_off + length > out_cap, or held + length >
+ *     H, the message becomes LOST instead and nothing is copied: the result
+ *     has DROPPED, and TOO_LONG in the last of those cases (the caller closes
+ *     with 1009). An ACTIVE carry whose start is neither 0 nor H or whose held
+ *     exceeds H (a hold_cap that changed between sweeps) is LOST and DROPPED
+ *     likewise. A carry neither ACTIVE nor LOST (attached mid-message) becomes
+ *     LOST and DROPPED. Then, if the record has COMPLETE: an ACTIVE message is
+ *     delivered: view record 0 is {first_frame 0, nframes = carry.nframes,
+ *     out_off = start, length = held, status = the record's without
+ *     CONTINUED, the carry's opcode}, the result has DELIVERED and
+ *     delivered_len = held, the carry clears; a LOST message clears, its view
+ *     record stays CONTINUED and the broadcast skips it as before. With
+ *     INTERRUPTED the carry clears and nothing is delivered. UTF8_BAD and
+ *     UNCHECKED ride along in the status: the broadcast's own rule then skips
+ *     a bad message.
+ *  4. The message open at the end. The row has XYWS_RSM_OPEN and record
+ *     nmsgs - 1 is stored, is not CONTINUED and has neither COMPLETE nor
+ *     INTERRUPTED: it starts a hold in the half the message delivered by this
+ *     call does not occupy (half 0 if none was): its bytes
+ *     out[out_off .. +length) go to hold[target ..), the carry becomes
+ *     {start = target, held = length, nframes, ACTIVE, opcode}. With TRUNCATED,
+ *     out_off + length > out_cap, or length > H the carry becomes LOST, the
+ *     result has DROPPED, and TOO_LONG in the last case.
+ *  5. Closing rule (records msg_cap did not store). An ACTIVE carry whose
+ *     record 0 is not a stored CONTINUED record becomes LOST (DROPPED). After
+ *     the walk: with XYWS_RSM_OPEN set a carry neither ACTIVE nor LOST becomes
+ *     LOST (DROPPED); with it clear the carry clears. The carry is exact
+ *     whatever vmsg_cap. The result row is {carry.held, delivered_len, the
+ *     bits above | the carry's ACTIVE and LOST}.
+ *  6. Bounds. Nothing outside [out, out + out_cap) is read as message bytes
+ *     (whole 16-byte lines that hold one of them are loaded); nothing outside
+ *     the part of the hold a copy names is written: whole lines inside it,
+ *     byte stores on its first and last line (neighbouring connections' areas
+ *     may abut, every alignment of out, hold_cap and out_off is legal); view
+ *     records at index >= min(s, vmsg_cap) are never written.
+ *
+ * Known approximation: the delivered record has first_frame 0, so the
+ * broadcast's rule first_frame < first_close drops it in the one sweep whose
+ * frame 0 is the close frame.
+ *
+ * Like its siblings the call is one launch (one wave per connection), uses no
+ * context scratch, no scratch slot and no policy word, never touches the
+ * device error word, reads no device state on the host, needs no reserve, can
+ * be captured into a hipGraph at once and runs concurrently on different
+ * streams. n == 0 returns XYWS_OK and launches nothing. XYWS_ERR_INVALID: a
+ * null ctx; a null dev_reasm, dev_reasm_results, dev_hold, dev_view or
+ * dev_view_results with n > 0; decided on the arguments alone. The areas must
+ * not overlap; a hold carry or a view row must not appear twice in a call;
+ * vmsgs must not be the reassembly's msgs. */
+typedef struct xyws_hold_carry {     /* 32 bytes; all zero = nothing held */
+  uint64_t start;    /* the half in use: 0 or H */
+  uint64_t held;     /* bytes of the open message in hold[start ..) */
+  uint64_t nframes;  /* its data frames so far */
+  uint32_t status;   /* XYWS_HOLD_ACTIVE or XYWS_HOLD_LOST; without ACTIVE every other field is zero */
+  uint8_t  opcode;   /* XYWS_FLAG_OP_TEXT / _BINARY of the held message */
+  uint8_t  reserved[3];
+} xyws_hold_carry;
+
+typedef struct xyws_hold_conn {      /* 32 bytes; entry i goes with dev_reasm[i] */
+  uint64_t         hold_cap; /* bytes in front of dev_reasm[i].out that are this connection's hold */
+  xyws_hold_carry* hc;       /* device; read, then written. NULL: pass-through */
+  xyws_message*    vmsgs;    /* device, nullable (then vmsg_cap counts as 0): the view's record row */
+  uint64_t         vmsg_cap;
+} xyws_hold_conn;
+
+typedef struct xyws_hold_result {    /* 32 bytes */
+  uint64_t held;          /* the carry's after this call */
+  uint64_t delivered_len; /* length of the message this call delivered (0: none) */
+  uint32_t status;        /* XYWS_HOLD_* */
+  uint32_t reserved0;
+  uint64_t reserved;
+} xyws_hold_result;
+#define XYWS_HOLD_DELIVERED   0x1u  /* view record 0 is a whole message out of the hold */
+#define XYWS_HOLD_ACTIVE      0x2u  /* carry and result: a message is held */
+#define XYWS_HOLD_LOST        0x4u  /* carry and result: the open message cannot be delivered */
+#define XYWS_HOLD_DROPPED     0x8u  /* this call lost a message */
+#define XYWS_HOLD_TOO_LONG    0x10u /* ... because it exceeds H: the caller closes with 1009 */
+#define XYWS_HOLD_PASSTHROUGH 0x20u
+
+int xyws_hold_streams(xyws_ctx* ctx,
+                      const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                      const xyws_hold_conn* dev_hold, uint64_t n,
+                      xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
+                      xyws_hold_result* dev_results /* n, nullable */, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

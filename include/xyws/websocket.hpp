@@ -363,6 +363,24 @@ inline void broadcast_streams(context& ctx, const xyws_reasm_conn* dev_reasm,
         "xyws_broadcast_streams");
 }
 
+// The messages a recv boundary cut, between reassemble_streams and
+// broadcast_streams of the same sweep, in one launch (xyws_hold_streams):
+// dev_hold[i] names connection i's hold (the hold_cap bytes in front of its
+// reassembly range), its hold carry and the view's record row. The call keeps
+// the parts of an open message in the hold and writes dev_view and
+// dev_view_results (n entries each), which broadcast_streams takes in place of
+// dev_reasm and dev_reasm_results: in the sweep that completes a held message
+// the view names it as one whole record. dev_results (nullable device pointer,
+// n entries) receives what was held, delivered or lost.
+inline void hold_streams(context& ctx, const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                         const xyws_hold_conn* dev_hold, std::uint64_t n, xyws_reasm_conn* dev_view,
+                         xyws_reasm_result* dev_view_results, xyws_hold_result* dev_results = nullptr,
+                         void* stream = nullptr) {
+  check(xyws_hold_streams(ctx.native(), dev_reasm, dev_reasm_results, dev_hold, n, dev_view, dev_view_results,
+                          dev_results, stream),
+        "xyws_hold_streams");
+}
+
 // class websocket_frame_header (websocket_frame_header.h:179-224): a header in
 // a 14-byte array. As in the reference, the masked constructors keep the key
 // beside the header and build it with the key bytes zero (:183-202); with_key()

@@ -199,6 +199,27 @@ assert C.sizeof(BcastResult) == 32
 ROOM_NONE = 0xFFFFFFFF
 ROOM_TRUNCATED, ROOM_BAD_MEMBER, ROOM_MSG_CAP = 0x1, 0x2, 0x4  # xyws_room_result.status
 BC_TRUNCATED, BC_NOT_RECEIVER, BC_NO_ROOM = 0x1, 0x2, 0x4  # xyws_bcast_result.status
+
+
+class HoldCarry(C.Structure):
+    """xyws_hold_carry (include/xyws.h), 32 bytes: one connection's state between xyws_hold_streams calls."""
+    _fields_ = [("start", C.c_uint64), ("held", C.c_uint64), ("nframes", C.c_uint64), ("status", C.c_uint32),
+                ("opcode", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class HoldConn(C.Structure):
+    """xyws_hold_conn (include/xyws.h), 32 bytes: entry i goes with entry i of the xyws_reasm_conn table."""
+    _fields_ = [("hold_cap", C.c_uint64), ("hc", C.c_void_p), ("vmsgs", C.c_void_p), ("vmsg_cap", C.c_uint64)]
+
+
+class HoldResult(C.Structure):
+    """xyws_hold_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("held", C.c_uint64), ("delivered_len", C.c_uint64), ("status", C.c_uint32),
+                ("reserved0", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(HoldCarry) == 32 and C.sizeof(HoldConn) == 32 and C.sizeof(HoldResult) == 32
+HOLD_DELIVERED, HOLD_ACTIVE, HOLD_LOST, HOLD_DROPPED, HOLD_TOO_LONG, HOLD_PASSTHROUGH = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 assert C.sizeof(ArenaResult) == 104
 XYWS_ERR_AGAIN = -6
 ARENA_SLOTS = 8
@@ -298,6 +319,11 @@ def load():
     # (no HIP call: members per tile of the wire build, bytes per fan-out step, grid cap, wave size)
     L.xyws_debug_broadcast_geometry.restype = i32
     L.xyws_debug_broadcast_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_hold_streams.restype = i32
+    L.xyws_hold_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp]
+    # (no HIP call: lanes per connection, bytes per line, bytes per copy step, grid cap)
+    L.xyws_debug_hold_geometry.restype = i32
+    L.xyws_debug_hold_geometry.argtypes = [C.POINTER(u64)]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]

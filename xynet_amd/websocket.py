@@ -371,6 +371,50 @@ class GroupMessages:
         return [arr[j] for j in range(n)]
 
 
+class GroupHold:
+    """The view and results of one connection_group.hold call, item k as in
+    the decode result of its sweep (host copies on demand). broadcast() takes
+    it in place of the reassemble() result: in the sweep that completes a
+    message a recv boundary cut, the view names the whole message. It owns the
+    call's tables, view rows and result rows."""
+
+    def __init__(self, group, messages, tensors, hold_cap):
+        self.group, self.decoded, self.messages_in = group, messages.decoded, messages
+        self._tensors, self.hold_cap = tensors, hold_cap
+        self.msg_cap = messages.msg_cap
+        self.out_caps = [c + hold_cap for c in messages.out_caps]  # (broadcast() sizes the wires by them)
+        self._rows = self._vrows = None
+
+    def _tables(self):
+        """The device addresses broadcast() reads instead of the reassembly's."""
+        return self._tensors["view"].data_ptr(), self._tensors["view_results"].data_ptr()
+
+    def result(self, k):
+        """xyws_hold_result of item k."""
+        if self._rows is None:
+            self._rows = self._tensors["results"].cpu().numpy().tobytes()
+        if not 0 <= k < len(self.decoded.ids):
+            raise IndexError(k)
+        return _lib.HoldResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+
+    def view_result(self, k):
+        """Item k's row of the view (xyws_reasm_result)."""
+        if self._vrows is None:
+            self._vrows = self._tensors["view_results"].cpu().numpy().tobytes()
+        if not 0 <= k < len(self.decoded.ids):
+            raise IndexError(k)
+        return _lib.ReasmResult.from_buffer_copy(self._vrows[32 * k:32 * k + 32])
+
+    def messages(self, k):
+        """The view's stored records of item k (out_off counts from the hold's
+        start, hold_cap bytes in front of its out buffer)."""
+        n = min(self.view_result(k).nmsgs, self.msg_cap)
+        row = 40 * (self.group.cap + 1) * k
+        raw = self._tensors["vmsgs"][row:row + 40 * n].cpu().numpy().tobytes() if n else b""
+        arr = (_lib.Message * max(n, 1)).from_buffer_copy(raw.ljust(40 * max(n, 1), b"\0"))
+        return [arr[j] for j in range(n)]
+
+
 class GroupBroadcast:
     """Results, room results and wires of one connection_group.broadcast call,
     item k as in the decode result of its sweep, room r as in the `rooms`
@@ -416,7 +460,10 @@ class connection_group:
     gathers and validates the messages of what decode() found, in one launch
     too (xyws_reassemble_streams), before or after reply(). broadcast() then
     delivers those messages to their rooms (xyws_broadcast_streams): each
-    room's wire behind every member's reply."""
+    room's wire behind every member's reply. hold(), between the two, keeps
+    the parts of a message a recv boundary cut on the device
+    (xyws_hold_streams) and hands broadcast() the whole message in the sweep
+    that completes it."""
     RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
 
     def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
@@ -446,6 +493,8 @@ class connection_group:
         self.mresults_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
         self._mhost = [torch.zeros(max(self.n, 1) * 8, dtype=torch.int64).pin_memory() for _ in range(self.RING)]
         self._mdev = [torch.empty(max(self.n, 1) * 8, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
+        # hold(): the hold carries (its tables and rows belong to the GroupHold it returns)
+        self.hcarry_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
 
     def reset(self, ids=None):
         """Fresh streams: every connection, or those in `ids`."""
@@ -453,11 +502,13 @@ class connection_group:
             self.carry_t.zero_()
             self.rcarry_t.zero_()
             self.mcarry_t.zero_()
+            self.hcarry_t.zero_()
         else:
             for i in ids:
                 self.carry_t[64 * i:64 * i + 64].zero_()
                 self.rcarry_t[32 * i:32 * i + 32].zero_()
                 self.mcarry_t[64 * i:64 * i + 64].zero_()
+                self.hcarry_t[32 * i:32 * i + 32].zero_()
 
     def carry(self, conn_id):
         """Host copy of a connection's carry (synchronizes)."""
@@ -578,11 +629,64 @@ class connection_group:
             self._done[k].record(stream)
         got = GroupMessages(self, result, mcap)
         got.out_caps = [t.numel() for t in outs]  # (broadcast() sizes the wires by them)
+        got.outs = outs                           # (hold() looks in front of them)
         return got
+
+    def hold_carry(self, conn_id):
+        """Host copy of a connection's hold carry (synchronizes)."""
+        if not 0 <= conn_id < self.n:
+            raise XywsError(-1, "no such connection")
+        return _lib.HoldCarry.from_buffer_copy(self.hcarry_t[32 * conn_id:32 * conn_id + 32].cpu().numpy().tobytes())
+
+    def hold(self, messages, hold_cap):
+        """Keep the messages that span sweeps (xyws_hold_streams, one launch),
+        between reassemble() and broadcast() of the same sweep: `messages` is
+        the reassemble() result, and the hold of item k is the hold_cap bytes
+        in front of the out tensor reassemble() wrote for it, so every out
+        tensor must be a slice that starts at least hold_cap bytes into its
+        storage, the same bytes for the connection in every sweep (ValueError
+        otherwise). hold_cap >= 2 * (largest message accepted) + 30 always
+        suffices. The group owns the hold carries. Returns a GroupHold, which
+        broadcast() takes in place of `messages`. Call it before the group's
+        next decode(), reply() or reassemble()."""
+        import numpy as np
+        import torch
+        dec = messages.decoded
+        if messages.group is not self or dec._slot is None or not hasattr(messages, "outs"):
+            raise XywsError(-1, "hold() takes the result of this group's reassemble()")
+        hold_cap = int(hold_cap)
+        if hold_cap < 0:
+            raise ValueError("hold_cap must not be negative")
+        for k, t in enumerate(messages.outs):
+            if t.storage_offset() * t.element_size() < hold_cap:
+                raise ValueError(f"item {k}: the out tensor needs hold_cap = {hold_cap} bytes of its storage in front "
+                                 f"of it, has {t.storage_offset() * t.element_size()}")
+        m = len(dec.ids)
+        htab = np.zeros((max(m, 1), 4), np.uint64)  # xyws_hold_conn: hold_cap, hc, vmsgs, vmsg_cap
+        with torch.cuda.device(self.device):
+            tensors = dict(vmsgs=torch.empty(max(m, 1) * (self.cap + 1) * 40, dtype=torch.uint8, device=self.device),
+                           view=torch.zeros(64 * max(m, 1), dtype=torch.uint8, device=self.device),
+                           view_results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
+                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
+                           outs=messages.outs)
+            hbase, vbase = self.hcarry_t.data_ptr(), tensors["vmsgs"].data_ptr()
+            for k, i in enumerate(dec.ids):
+                htab[k] = [hold_cap, hbase + 32 * i, vbase + 40 * (self.cap + 1) * k, messages.msg_cap]
+            tensors["hold"] = torch.from_numpy(htab.reshape(-1).view(np.uint8)).to(self.device)
+            stream = torch.cuda.current_stream(self.device)
+            check(self.ctx.L.xyws_hold_streams(
+                self.ctx.h, C.c_void_p(self._mdev[dec._slot].data_ptr()), C.c_void_p(self.mresults_t.data_ptr()),
+                C.c_void_p(tensors["hold"].data_ptr()), m, C.c_void_p(tensors["view"].data_ptr()),
+                C.c_void_p(tensors["view_results"].data_ptr()), C.c_void_p(tensors["results"].data_ptr()),
+                C.c_void_p(stream.cuda_stream)), "xyws_hold_streams")
+            self._done[dec._slot] = torch.cuda.Event()
+            self._done[dec._slot].record(stream)
+        return GroupHold(self, messages, tensors, hold_cap)
 
     def broadcast(self, messages, rooms, out_items, heads=None, reply=None, flags=0x11, enc_opts=0, wire_caps=None):
         """Deliver the whole messages of the reassemble() call that returned
-        `messages` to their rooms (xyws_broadcast_streams, two launches):
+        `messages` (or of the hold() call that followed it: then also the
+        messages that call completed) to their rooms (xyws_broadcast_streams, two launches):
         rooms[r] lists the connection ids of room r in delivery order; every
         one must be an item of this sweep (a member that received nothing is
         decoded with an empty buffer) and belongs to one room. Each room's
@@ -599,7 +703,9 @@ class connection_group:
         import torch
         dec = messages.decoded
         if messages.group is not self or dec._slot is None or not hasattr(messages, "out_caps"):
-            raise XywsError(-1, "broadcast() takes the result of this group's reassemble()")
+            raise XywsError(-1, "broadcast() takes the result of this group's reassemble() or hold()")
+        reasm_p, rres_p = messages._tables() if isinstance(messages, GroupHold) else \
+            (self._mdev[dec._slot].data_ptr(), self.mresults_t.data_ptr())
         if reply is not None and (reply.group is not self or reply.decoded is not dec):
             raise XywsError(-1, "reply must be the reply() result of the same sweep")
         outs = [_dev_u8(t) for t in out_items]
@@ -645,12 +751,11 @@ class connection_group:
                            bconns=torch.from_numpy(btab.reshape(-1).view(np.uint8)).to(self.device),
                            room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
                            results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
-                           outs=outs, heads=hds)
+                           outs=outs, heads=hds, messages=messages)
             stream = torch.cuda.current_stream(self.device)
             check(self.ctx.L.xyws_broadcast_streams(
-                self.ctx.h, C.c_void_p(self._mdev[dec._slot].data_ptr()), C.c_void_p(self.mresults_t.data_ptr()),
-                C.c_void_p(tensors["bconns"].data_ptr()), m, C.c_void_p(tensors["rooms"].data_ptr()),
-                C.c_void_p(tensors["room_results"].data_ptr()), nr, flags, enc_opts,
+                self.ctx.h, C.c_void_p(reasm_p), C.c_void_p(rres_p), C.c_void_p(tensors["bconns"].data_ptr()), m,
+                C.c_void_p(tensors["rooms"].data_ptr()), C.c_void_p(tensors["room_results"].data_ptr()), nr, flags, enc_opts,
                 C.c_void_p(tensors["results"].data_ptr()), C.c_void_p(stream.cuda_stream)), "xyws_broadcast_streams")
             self._done[dec._slot] = torch.cuda.Event()
             self._done[dec._slot].record(stream)
