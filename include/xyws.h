@@ -43,6 +43,9 @@
  *   (new) a chat message cut by a recv boundary, which the   xyws_hold_streams (its parts kept
  *     reference's session reads to its end before deliver      on the device between sweeps, the
  *     example/websocket/websocket_chat.cpp:177-200              whole message handed to the room)
+ *   chat_room::join + deliver_recent_messages: the last 10    xyws_backlog_streams (each room's
+ *     messages (m_recent_messages) sent to a newcomer           newest frames kept in a log on the
+ *     example/websocket/websocket_chat.cpp:34-47, 89-95         device, copied behind a joiner's send bytes)
  *   recv_all / io_service remote-queue eventfd               xyws_arena_* (pinned recv arena,
  *     include/xynet/socket/impl/recv_all.h:86-121              H2D -> decode -> D2H, completion
  *     include/xynet/io_service.h:362-381                       written to an eventfd)
@@ -1018,6 +1021,172 @@ int xyws_hold_streams(xyws_ctx* ctx,
                       const xyws_hold_conn* dev_hold, uint64_t n,
                       xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
                       xyws_hold_result* dev_results /* n, nullable */, void* stream);
+
+/* ---- many rooms, one backlog call -------------------------------------------
+ * The room's memory: chat_room::deliver keeps the last 10 messages in
+ * m_recent_messages and chat_room::join sends them to every newcomer through
+ * deliver_recent_messages (example/websocket/websocket_chat.cpp:34-47, 89-95).
+ * Here a room's framed wire exists only for one sweep. This call, after
+ * xyws_broadcast_streams, folds the sweep's newest frames into a per-room
+ * backlog on the device and copies the backlog behind the send bytes of every
+ * connection marked as joining: decode, reassemble, hold, reply, broadcast,
+ * backlog, still with no host read of device state. The welcome and farewell
+ * lines of the reference's room (:49-87) are server-authored text and are not
+ * part of this call.
+ *
+ * dev_reasm, dev_reasm_results, dev_bconns, n, dev_rooms and n_rooms are what
+ * this sweep's xyws_broadcast_streams call was given (the hold's view when
+ * there is one), dev_room_results the rows that call wrote. dev_brooms[r] goes
+ * with dev_rooms[r], dev_jconns[i] with dev_bconns[i].
+ *
+ * The log. With H = (log_cap / 2) & ~15 the log is used as two halves [0, H)
+ * and [H, 2H), as the hold is: a fold writes the half the backlog does not
+ * occupy, so the copy never overlaps its source. With B the most bytes the
+ * backlog is to hold, log_cap >= 2 * B + 30 always gives H >= B.
+ *
+ *  0. Pass-through. log NULL, bc NULL, keep == 0 or H == 0: neither the log
+ *     nor the carry is touched, the room result is
+ *     {0, 0, 0, 0, XYWS_BL_PASSTHROUGH} and the room's joiners get nothing.
+ *
+ * The fold, per room, N = dev_room_results[r].nmsgs, the bytes out of the
+ * room's wire:
+ *
+ *  1. No new message. N == 0: the carry and the log stay as they are (the
+ *     carry is not checked), and the row reports the carry's len and count.
+ *  2. The carry is valid when start is 0 or H, len <= H, count <=
+ *     XYWS_BACKLOG_MAX and the first count entries of flen[] sum to len.
+ *     Anything else counts as empty (gaps and total are kept) and sets
+ *     XYWS_BL_BAD_CARRY.
+ *  3. The new frames are the room's deliverable records (xyws_broadcast_streams
+ *     2. and 3.) in wire order. A frame's size is the header size for head_len
+ *     + length (2, 4 or 10 bytes) plus head_len + length; flags do not enter
+ *     it. The call recounts and resizes them from the tables: when the count
+ *     differs from the room row's nmsgs or the total from its wire_len, the
+ *     caller passed other tables and the backlog is cleared with
+ *     XYWS_BL_MISMATCH | XYWS_BL_GAP.
+ *  4. Truncated wire. The room row has XYWS_ROOM_TRUNCATED (or wire_len >
+ *     wire_cap): the newest frames cannot be read, the backlog is cleared with
+ *     XYWS_BL_GAP.
+ *  5. Selection. The candidates are the old frames, oldest first, then the N
+ *     new ones. From the newest backwards a frame is taken while fewer than
+ *     keep are taken (keep > XYWS_BACKLOG_MAX counts as it) and the bytes
+ *     taken plus its size stay <= H; the walk stops at the first frame that
+ *     fails either test, the count test first. When the byte budget ended it,
+ *     XYWS_BL_EVICTED is set; when the newest frame alone exceeds H the
+ *     backlog ends empty and XYWS_BL_TOO_LONG is set too.
+ *  6. Copy. target = H when the valid carry had count > 0 and start == 0 and
+ *     the backlog does not end empty, else 0. The surviving old bytes are a
+ *     suffix of the old half's held bytes, the surviving new bytes the suffix
+ *     wire[wire_len - b .. wire_len); both go to log[target ..), old first.
+ *  7. The carry becomes {target, bytes, count, gaps, total + folded, flen
+ *     oldest first, zeros}; gaps counts XYWS_BL_GAP events. Every clear, and a
+ *     backlog that ends empty, leaves start, len, count and flen zero. The
+ *     room row is {len, count, folded = new frames taken, dropped = old frames
+ *     let go, status}; a clear folds none and drops every old frame.
+ *  8. Bounds. Nothing outside the part of the half a copy names is written:
+ *     whole 16-byte lines inside it, byte stores on its first and last line.
+ *     Every alignment of log, wire and both suffixes is legal, neighbouring
+ *     rooms' logs may abut. Nothing outside [wire, wire + wire_cap) and the
+ *     old half's held bytes is read, apart from the whole lines that hold
+ *     them. Logs, wires and send buffers must not overlap.
+ *
+ * Delivery, per connection with XYWS_BL_JOIN in flags, after the fold (a
+ * joiner sees this sweep's talk):
+ *
+ *  9. base = bcast ? bcast->send_len : reply ? reply->reply_len : 0. A room >=
+ *     n_rooms or a pass-through room: {base, 0, XYWS_BLC_NO_ROOM}. Otherwise,
+ *     when reply has CLOSED or OVERFLOW or bcast has XYWS_BC_NOT_RECEIVER:
+ *     {base, 0, XYWS_BLC_NOT_RECEIVER}. Otherwise log[start .. start + len)
+ *     goes to out + base (a carry whose start is neither 0 nor H or whose len
+ *     exceeds H counts as len 0); positions >= out_cap are not written;
+ *     backlog_len = len, send_len = base + len, XYWS_BLC_JOINED is set, and
+ *     XYWS_BLC_TRUNCATED when send_len > out_cap. A connection without the
+ *     flag gets {base, 0, 0} and nothing written. No byte outside
+ *     [out + min(base, out_cap), out + min(send_len, out_cap)) is written:
+ *     send-slab neighbours share lines.
+ * 10. The caller's duty. A joiner is added to its room's members[] from the
+ *     next sweep on. If it is a member already it receives the wire and the
+ *     same frames again in the backlog. That is the reference's order with the
+ *     join placed after the sweep's messages: the last keep messages, then
+ *     everything later.
+ * 11. Properties. At most two launches on `stream`: the fold (one workgroup
+ *     per room; omitted when n_rooms == 0), then the delivery (omitted when
+ *     dev_jconns is NULL or n == 0); the carries are the hand-over between
+ *     them. Like its siblings the call uses no context scratch, no scratch
+ *     slot and no policy word, never touches the device error word, reads no
+ *     device state on the host, needs no reserve, can be captured into a
+ *     hipGraph at once and runs concurrently on different streams. n == 0 &&
+ *     n_rooms == 0 returns XYWS_OK and launches nothing. XYWS_ERR_INVALID: a
+ *     null ctx; null dev_reasm, dev_reasm_results or dev_bconns with n > 0 and
+ *     n_rooms > 0; null dev_rooms, dev_room_results or dev_brooms with n_rooms
+ *     > 0; n >= UINT32_MAX. Every refusal is decided on the arguments alone,
+ *     before the context is used. */
+#define XYWS_BACKLOG_MAX 16u            /* the reference keeps 10 */
+
+typedef struct xyws_backlog_carry {     /* 192 bytes; all zero = empty */
+  uint64_t start;      /* the half of the log in use: 0 or H */
+  uint64_t len;        /* bytes held: whole server frames, oldest first */
+  uint32_t count;      /* frames held, <= XYWS_BACKLOG_MAX */
+  uint32_t gaps;       /* times the history was lost (XYWS_BL_GAP) */
+  uint64_t total;      /* frames folded in over all calls */
+  uint64_t flen[XYWS_BACKLOG_MAX]; /* their lengths, oldest first; zero from count on */
+  uint64_t reserved[4];
+} xyws_backlog_carry;
+
+typedef struct xyws_backlog_room {      /* 32 bytes; entry r goes with dev_rooms[r] */
+  void*               log;      /* device, any alignment */
+  uint64_t            log_cap;
+  xyws_backlog_carry* bc;       /* device; read, then written */
+  uint32_t            keep;     /* frames to keep; > XYWS_BACKLOG_MAX counts as it */
+  uint32_t            reserved0;
+} xyws_backlog_room;
+
+typedef struct xyws_backlog_room_result { /* 32 bytes */
+  uint64_t len;        /* the carry's after this call */
+  uint32_t count;      /* the carry's after this call */
+  uint32_t folded;     /* new frames taken */
+  uint32_t dropped;    /* old frames let go */
+  uint32_t status;     /* XYWS_BL_* */
+  uint64_t reserved;
+} xyws_backlog_room_result;
+#define XYWS_BL_PASSTHROUGH 0x1u
+#define XYWS_BL_BAD_CARRY   0x2u  /* the carry was not valid: counted as empty */
+#define XYWS_BL_MISMATCH    0x4u  /* the tables are not the ones the room row was made from */
+#define XYWS_BL_GAP         0x8u  /* the history was lost: the backlog is cleared */
+#define XYWS_BL_EVICTED     0x10u /* the byte budget H, not keep, ended the selection */
+#define XYWS_BL_TOO_LONG    0x20u /* the newest frame alone exceeds H */
+
+typedef struct xyws_backlog_conn {      /* 64 bytes; entry i goes with dev_bconns[i] */
+  void*    out;        /* device: the connection's send buffer */
+  uint64_t out_cap;
+  const xyws_bcast_result* bcast; /* device, nullable: this sweep's broadcast row */
+  const xyws_reply_result* reply; /* device, nullable: this sweep's reply row */
+  uint32_t room;       /* the room joined; >= n_rooms counts as none */
+  uint32_t flags;      /* XYWS_BL_JOIN */
+  uint64_t reserved[3];
+} xyws_backlog_conn;
+#define XYWS_BL_JOIN 0x1u
+
+typedef struct xyws_backlog_result {    /* 32 bytes */
+  uint64_t send_len;    /* base + backlog_len: the caller sends out[0 .. min(send_len, out_cap)) */
+  uint64_t backlog_len; /* bytes of the room's backlog appended for this connection */
+  uint32_t status;      /* XYWS_BLC_* */
+  uint32_t reserved0;
+  uint64_t reserved;
+} xyws_backlog_result;
+#define XYWS_BLC_JOINED       0x1u
+#define XYWS_BLC_TRUNCATED    0x2u /* send_len > out_cap */
+#define XYWS_BLC_NO_ROOM      0x4u /* no such room, or a pass-through room */
+#define XYWS_BLC_NOT_RECEIVER 0x8u /* closed or overflowed: nothing appended */
+
+int xyws_backlog_streams(xyws_ctx* ctx,
+                         const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                         const xyws_bcast_conn* dev_bconns, uint64_t n,
+                         const xyws_room* dev_rooms, const xyws_room_result* dev_room_results,
+                         const xyws_backlog_room* dev_brooms,
+                         xyws_backlog_room_result* dev_broom_results /* n_rooms, nullable */, uint64_t n_rooms,
+                         const xyws_backlog_conn* dev_jconns /* n, nullable: fold only */,
+                         xyws_backlog_result* dev_results /* n, nullable */, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -381,6 +381,27 @@ inline void hold_streams(context& ctx, const xyws_reasm_conn* dev_reasm, const x
         "xyws_hold_streams");
 }
 
+// The room's recent messages, after broadcast_streams of the same sweep, in at
+// most two launches (xyws_backlog_streams; the reference's m_recent_messages
+// and deliver_recent_messages): the first seven table arguments are the ones
+// broadcast_streams was given plus the room rows it wrote. dev_brooms[r] names
+// room r's log, its carry and how many frames to keep: the sweep's newest
+// frames are folded into the log. dev_jconns[i] (nullable table: fold only)
+// names connection i's send buffer, its broadcast and reply rows and, with
+// XYWS_BL_JOIN, the room it joins: the room's backlog is appended behind its
+// send bytes. A joiner becomes a member of its room from the next sweep on.
+// dev_broom_results (n_rooms entries) and dev_results (n entries) are nullable.
+inline void backlog_streams(context& ctx, const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                            const xyws_bcast_conn* dev_bconns, std::uint64_t n, const xyws_room* dev_rooms,
+                            const xyws_room_result* dev_room_results, const xyws_backlog_room* dev_brooms,
+                            xyws_backlog_room_result* dev_broom_results, std::uint64_t n_rooms,
+                            const xyws_backlog_conn* dev_jconns = nullptr, xyws_backlog_result* dev_results = nullptr,
+                            void* stream = nullptr) {
+  check(xyws_backlog_streams(ctx.native(), dev_reasm, dev_reasm_results, dev_bconns, n, dev_rooms, dev_room_results,
+                             dev_brooms, dev_broom_results, n_rooms, dev_jconns, dev_results, stream),
+        "xyws_backlog_streams");
+}
+
 // class websocket_frame_header (websocket_frame_header.h:179-224): a header in
 // a 14-byte array. As in the reference, the masked constructors keep the key
 // beside the header and build it with the key bytes zero (:183-202); with_key()

@@ -220,6 +220,46 @@ class HoldResult(C.Structure):
 
 assert C.sizeof(HoldCarry) == 32 and C.sizeof(HoldConn) == 32 and C.sizeof(HoldResult) == 32
 HOLD_DELIVERED, HOLD_ACTIVE, HOLD_LOST, HOLD_DROPPED, HOLD_TOO_LONG, HOLD_PASSTHROUGH = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+
+
+BACKLOG_MAX = 16
+
+
+class BacklogCarry(C.Structure):
+    """xyws_backlog_carry (include/xyws.h), 192 bytes: one room's state between xyws_backlog_streams calls."""
+    _fields_ = [("start", C.c_uint64), ("len", C.c_uint64), ("count", C.c_uint32), ("gaps", C.c_uint32),
+                ("total", C.c_uint64), ("flen", C.c_uint64 * BACKLOG_MAX), ("reserved", C.c_uint64 * 4)]
+
+
+class BacklogRoom(C.Structure):
+    """xyws_backlog_room (include/xyws.h), 32 bytes: entry r goes with entry r of the xyws_room table."""
+    _fields_ = [("log", C.c_void_p), ("log_cap", C.c_uint64), ("bc", C.c_void_p), ("keep", C.c_uint32),
+                ("reserved0", C.c_uint32)]
+
+
+class BacklogRoomResult(C.Structure):
+    """xyws_backlog_room_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("len", C.c_uint64), ("count", C.c_uint32), ("folded", C.c_uint32), ("dropped", C.c_uint32),
+                ("status", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class BacklogConn(C.Structure):
+    """xyws_backlog_conn (include/xyws.h), 64 bytes: entry i goes with entry i of the xyws_bcast_conn table."""
+    _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("bcast", C.c_void_p), ("reply", C.c_void_p),
+                ("room", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64 * 3)]
+
+
+class BacklogResult(C.Structure):
+    """xyws_backlog_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("send_len", C.c_uint64), ("backlog_len", C.c_uint64), ("status", C.c_uint32),
+                ("reserved0", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(BacklogCarry) == 192 and C.sizeof(BacklogRoom) == 32 and C.sizeof(BacklogRoomResult) == 32
+assert C.sizeof(BacklogConn) == 64 and C.sizeof(BacklogResult) == 32
+BL_PASSTHROUGH, BL_BAD_CARRY, BL_MISMATCH, BL_GAP, BL_EVICTED, BL_TOO_LONG = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+BL_JOIN = 0x1  # xyws_backlog_conn.flags
+BLC_JOINED, BLC_TRUNCATED, BLC_NO_ROOM, BLC_NOT_RECEIVER = 0x1, 0x2, 0x4, 0x8  # xyws_backlog_result.status
 assert C.sizeof(ArenaResult) == 104
 XYWS_ERR_AGAIN = -6
 ARENA_SLOTS = 8
@@ -324,6 +364,11 @@ def load():
     # (no HIP call: lanes per connection, bytes per line, bytes per copy step, grid cap)
     L.xyws_debug_hold_geometry.restype = i32
     L.xyws_debug_hold_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_backlog_streams.restype = i32
+    L.xyws_backlog_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp]
+    # (no HIP call: members per tile of the fold, bytes per delivery step, grid cap, wave size)
+    L.xyws_debug_backlog_geometry.restype = i32
+    L.xyws_debug_backlog_geometry.argtypes = [C.POINTER(u64)]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]

@@ -448,6 +448,32 @@ class GroupBroadcast:
         return self._wires[r][:min(res.wire_len, self._wires[r].numel())]
 
 
+class GroupBacklog:
+    """Results of one connection_group.backlog call: item k as in the decode
+    result of its sweep, room r as in the broadcast's `rooms` argument (host
+    copies on demand). The logs and carries belong to the group."""
+
+    def __init__(self, group, decoded, tensors, nr):
+        self.group, self.decoded, self._tensors, self.nr = group, decoded, tensors, nr
+        self._rows = self._rrows = None
+
+    def result(self, k):
+        """xyws_backlog_result of item k."""
+        if not 0 <= k < len(self.decoded.ids):
+            raise IndexError(k)
+        if self._rows is None:
+            self._rows = self._tensors["results"].cpu().numpy().tobytes()
+        return _lib.BacklogResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+
+    def room_result(self, r):
+        """xyws_backlog_room_result of room r."""
+        if not 0 <= r < self.nr:
+            raise IndexError(r)
+        if self._rrows is None:
+            self._rrows = self._tensors["room_results"].cpu().numpy().tobytes()
+        return _lib.BacklogRoomResult.from_buffer_copy(self._rrows[32 * r:32 * r + 32])
+
+
 class connection_group:
     """The decoder states of n connections and one xyws_decode_streams call
     for whatever a sweep of the completion queue brought: decode() takes the
@@ -463,7 +489,9 @@ class connection_group:
     room's wire behind every member's reply. hold(), between the two, keeps
     the parts of a message a recv boundary cut on the device
     (xyws_hold_streams) and hands broadcast() the whole message in the sweep
-    that completes it."""
+    that completes it. backlog(), after broadcast(), keeps each room's recent
+    messages on the device (xyws_backlog_streams) and sends them to the
+    connections that join."""
     RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
 
     def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
@@ -495,6 +523,8 @@ class connection_group:
         self._mdev = [torch.empty(max(self.n, 1) * 8, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
         # hold(): the hold carries (its tables and rows belong to the GroupHold it returns)
         self.hcarry_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
+        # backlog(): per room a log and a carry, made when the room is first seen and kept across sweeps
+        self._blogs, self._bcarries = [], []
 
     def reset(self, ids=None):
         """Fresh streams: every connection, or those in `ids`."""
@@ -751,7 +781,7 @@ class connection_group:
                            bconns=torch.from_numpy(btab.reshape(-1).view(np.uint8)).to(self.device),
                            room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
                            results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
-                           outs=outs, heads=hds, messages=messages)
+                           outs=outs, heads=hds, messages=messages, replied=reply is not None)
             stream = torch.cuda.current_stream(self.device)
             check(self.ctx.L.xyws_broadcast_streams(
                 self.ctx.h, C.c_void_p(reasm_p), C.c_void_p(rres_p), C.c_void_p(tensors["bconns"].data_ptr()), m,
@@ -760,6 +790,84 @@ class connection_group:
             self._done[dec._slot] = torch.cuda.Event()
             self._done[dec._slot].record(stream)
         return GroupBroadcast(self, dec, tensors, wires)
+
+    def backlog_carry(self, room):
+        """Host copy of a room's backlog carry (synchronizes)."""
+        if not 0 <= room < len(self._bcarries):
+            raise XywsError(-1, "no such room")
+        return _lib.BacklogCarry.from_buffer_copy(self._bcarries[room].cpu().numpy().tobytes())
+
+    def backlog_bytes(self, room):
+        """The frames room `room` holds for its next joiner, oldest first (a device tensor; synchronizes)."""
+        c = self.backlog_carry(room)
+        return self._blogs[room][0][c.start:c.start + c.len]
+
+    def backlog(self, bcast, joiners=None, keep=10, log_cap=None):
+        """Keep each room's recent messages and send them to joiners
+        (xyws_backlog_streams, at most two launches), after broadcast() of the
+        same sweep: `bcast` is its GroupBroadcast. The sweep's newest frames
+        are folded into each room's log on the device, `keep` of them at most
+        (the reference keeps 10; 16 at most), and the log is appended to the
+        send tensor of every joiner behind what broadcast() left there.
+        joiners: (conn_id, room) pairs, or a dict; a joiner must be an item of
+        this sweep, and the caller lists it in rooms[room] from the next
+        sweep on. The group allocates a room's log (log_cap bytes, default
+        2 * keep * 4096 + 30) and carry when the room is first seen and keeps
+        them across sweeps: room r is the same room in every call, and a
+        log_cap other than the one its log was made with is refused. When
+        broadcast() was given the sweep's reply, a joiner whose reply closed
+        or overflowed is sent nothing (XYWS_BLC_NOT_RECEIVER). Returns a
+        GroupBacklog. Call it before the group's next decode()."""
+        import numpy as np
+        import torch
+        if not isinstance(bcast, GroupBroadcast) or bcast.group is not self:
+            raise XywsError(-1, "backlog() takes the result of this group's broadcast()")
+        dec, bt = bcast.decoded, bcast._tensors
+        messages = bt["messages"]
+        reasm_p, rres_p = messages._tables() if isinstance(messages, GroupHold) else \
+            (self._mdev[dec._slot].data_ptr(), self.mresults_t.data_ptr())
+        m, nr = len(dec.ids), len(bcast._wires)
+        keep = int(keep)
+        cap = 2 * max(min(keep, _lib.BACKLOG_MAX), 1) * 4096 + 30 if log_cap is None else int(log_cap)
+        if keep < 0 or cap < 0:
+            raise ValueError("keep and log_cap must not be negative")
+        item = {i: k for k, i in enumerate(dec.ids)}
+        pairs = list(joiners.items()) if isinstance(joiners, dict) else list(joiners or [])
+        joined = {}
+        for i, r in pairs:
+            if int(i) not in item or int(i) in joined or not 0 <= int(r) < nr:
+                raise XywsError(-1, "a joiner must be an item of this sweep, join once, and name a room of the sweep")
+            joined[int(i)] = int(r)
+        with torch.cuda.device(self.device):
+            if log_cap is not None and any(lcap != cap for _, lcap in self._blogs[:nr]):
+                raise XywsError(-1, "a room's log keeps the log_cap it was made with")
+            while len(self._blogs) < nr:
+                self._blogs.append((torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device), cap))
+                self._bcarries.append(torch.zeros(192, dtype=torch.uint8, device=self.device))
+            rtab = np.zeros((max(nr, 1), 4), np.uint64)  # xyws_backlog_room: log, log_cap, bc, keep
+            for r in range(nr):
+                log, lcap = self._blogs[r]
+                rtab[r] = [log.data_ptr(), lcap, self._bcarries[r].data_ptr(), keep]
+            jtab = np.zeros((max(m, 1), 8), np.uint64)  # xyws_backlog_conn: out, out_cap, bcast, reply, room | flags
+            bbase, rbase = bt["results"].data_ptr(), self.results_t.data_ptr()
+            for k, (i, t) in enumerate(zip(dec.ids, bt["outs"])):
+                # (the reply row broadcast() named: only it says that a joiner, not yet a member, closed or overflowed)
+                jtab[k, :4] = [t.data_ptr(), t.numel(), bbase + 32 * k, rbase + 32 * k if bt["replied"] else 0]
+                jtab[k, 4] = joined[i] | (_lib.BL_JOIN << 32) if i in joined else _lib.ROOM_NONE
+            tensors = dict(brooms=torch.from_numpy(rtab.reshape(-1).view(np.uint8)).to(self.device),
+                           jconns=torch.from_numpy(jtab.reshape(-1).view(np.uint8)).to(self.device),
+                           room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
+                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device), bcast=bcast)
+            stream = torch.cuda.current_stream(self.device)
+            check(self.ctx.L.xyws_backlog_streams(
+                self.ctx.h, C.c_void_p(reasm_p), C.c_void_p(rres_p), C.c_void_p(bt["bconns"].data_ptr()), m,
+                C.c_void_p(bt["rooms"].data_ptr()), C.c_void_p(bt["room_results"].data_ptr()),
+                C.c_void_p(tensors["brooms"].data_ptr()), C.c_void_p(tensors["room_results"].data_ptr()), nr,
+                C.c_void_p(tensors["jconns"].data_ptr()), C.c_void_p(tensors["results"].data_ptr()),
+                C.c_void_p(stream.cuda_stream)), "xyws_backlog_streams")
+            self._done[dec._slot] = torch.cuda.Event()
+            self._done[dec._slot].record(stream)
+        return GroupBacklog(self, dec, tensors, nr)
 
     def msg_carry(self, conn_id):
         """Host copy of a connection's message carry (synchronizes)."""
