@@ -26,7 +26,8 @@ TARGETS = {
                    "xyws_backlog.hip"],
     "libxyws_tools.so": ["xyws_tools.hip"],
 }
-DEPS = ["xyws_device.h", "xyws_host.h", "xyws_stream.h", "xyws_ctx.h", "xyws_lattice.h", "xyws_frameops.h", "xyws_room.h"]
+DEPS = ["xyws_device.h", "xyws_host.h", "xyws_stream.h", "xyws_ctx.h", "xyws_lattice.h", "xyws_frameops.h", "xyws_lines.h",
+        "xyws_room.h"]
 
 
 def _stale(out, srcs):

@@ -10,9 +10,9 @@
 // k_backlog_fold: one workgroup per room, rooms grid-strided, shaped like the
 // broadcast's wire build. The members are taken in tiles of BL_TILE, one
 // member per thread:
-//   1. the thread reads its member's table entries (bounds-checked index),
-//      decides the gate (the wire build's rule, repeated here), walks the stored records,
-//      tests each (frame_of, xyws_room.h) and counts and sizes the frames;
+//   1. the thread loads its member and its gate as the wire build does
+//      (bounds-checked index; load_member, xyws_room.h), walks the stored
+//      records, tests each (frame_of) and counts and sizes the frames;
 //   2. two workgroup scans give each member the index of its first message
 //      and its byte offset in the wire; the fold uses the index (step 3) and
 //      of the second scan only the total (the copy takes the wire's suffix as
@@ -22,14 +22,14 @@
 //      XYWS_BACKLOG_MAX LDS slots.
 // After the last tile every thread computes the same selection from the slots
 // and the carry, and the workgroup copies the surviving old bytes and the
-// surviving wire suffix into the other half of the log in destination-aligned
-// 16-byte lines: the line on the seam is composed from both sources in
-// registers, the first and last line of the range are stored byte by byte.
+// surviving wire suffix into the other half of the log in 16-byte lines
+// (xyws_lines.h): the line on the seam is composed from both sources in
+// registers.
 //
-// k_backlog_deliver: the fan-out's geometry: blockIdx.x strides over the
-// connections, blockIdx.y over BL_STEP-byte chunks of the destination range.
-// The source is log + start, its length the carry's. The y == 0 workgroup
-// writes the connection's result row.
+// k_backlog_deliver: the fan-out's geometry and copy (xyws_room.h, copy_span):
+// blockIdx.x strides over the connections, blockIdx.y over BC_STEP-byte chunks
+// of the destination range. The source is log + start, its length the
+// carry's. The y == 0 workgroup writes the connection's result row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
@@ -38,40 +38,16 @@
 #include "xyws_device.h"
 #include "xyws_ctx.h"
 #include "xyws_frameops.h"
+#include "xyws_lines.h"
 #include "xyws_room.h"
 
 #define BL_THREADS BC_WIRE_THREADS  // the fold: the one workgroup a room gets (block_scan's size)
 #define BL_TILE BL_THREADS          // members per tile of the fold: one per thread
-#define BL_FAN_THREADS 256u         // the delivery: four waves
-#define BL_LINE 16u                 // bytes a thread writes per copy step
-#define BL_STEP (BL_LINE * BL_FAN_THREADS)  // bytes a workgroup writes per step (the delivery)
-#define BL_GRID_CAP 8192u           // rooms / connections per launch in x; further ones are grid-strided
-#define BL_BLOCKS_AIM 4096u         // delivery: workgroups wanted in flight (256 CUs x 16)
-#define BL_SLICES_MAX 256u          // delivery: at most this many workgroups share one connection
 #define BL_CARRY_WORDS 24u          // sizeof(xyws_backlog_carry) / 8
 
 using namespace xyws_internal;
 
 namespace {
-
-XYWS_DEV void or_into(bytes16& acc, bytes16 p) {
-  acc.lo |= p.lo;
-  acc.hi |= p.hi;
-}
-
-XYWS_DEV void store_line(g_u8* obase, uint64_t A, bytes16 v) {
-  *reinterpret_cast<g_u32x4*>(obase + A) =
-      u32x4{(uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32)};
-}
-
-// Bytes [s, we) of the line at A, byte by byte (v holds the line's bytes at their line offsets).
-XYWS_DEV void store_edge(g_u8* obase, uint64_t A, uint64_t s, uint64_t we, bytes16 v) {
-#pragma unroll 1
-  for (uint64_t p = s; p < we; p++) {
-    const uint32_t b = (uint32_t)(p - A);
-    obase[p] = (uint8_t)(b < 8 ? v.lo >> (8u * b) : v.hi >> (8u * (b - 8)));
-  }
-}
 
 // The half size of a log (0: no log).
 XYWS_DEV uint64_t half_of(uint64_t log, uint64_t log_cap) { return log ? (log_cap >> 1) & ~15ull : 0; }
@@ -155,26 +131,8 @@ __global__ void __launch_bounds__(BL_THREADS)
       if (base + tid < nm) {
         const uint64_t ci = ((const XYWS_GLOBAL uint32_t*)members)[base + tid];
         if (ci < n) {  // (an entry >= n is ignored, never dereferenced)
-          const g_u64* const aq = (const g_u64*)(reasm + ci);
-          const g_u64* const ar = (const g_u64*)(rres + ci);
-          const g_u64* const bq = (const g_u64*)(bconns + ci);
-          m.out = aq[0];
-          m.out_cap = m.out ? aq[1] : 0;
-          m.msgs = aq[3];
-          const uint64_t msg_cap = m.msgs ? aq[4] : 0;
-          const uint64_t nmsgs = ar[1];
-          const uint32_t ast = (uint32_t)(ar[2] >> 32);
-          const uint64_t kept = nmsgs < msg_cap ? nmsgs : msg_cap;
-          m.stored = kept < 0xFFFFFFFFull ? (uint32_t)kept : 0xFFFFFFFFu;
-          m.head_len = bq[0] ? bq[1] : 0;
-          m.gate = (ast & XYWS_RSM_OVERFLOW) ? 0 : XYWS_NPOS;
-          const g_u64* const rp = (const g_u64*)bq[4];
-          if (rp) {
-            const uint64_t fc = rp[1];
-            const uint32_t pst = (uint32_t)(rp[2] >> 48);
-            if ((pst & XYWS_RPL_OVERFLOW) || ((pst & XYWS_RPL_CLOSED) && fc == XYWS_NPOS)) m.gate = 0;
-            else if (fc != XYWS_NPOS && m.gate) m.gate = fc;
-          }
+          bool receiver, over_cap;  // (the wire build's: not used here)
+          load_member(reasm, rres, bconns, ci, m, receiver, over_cap);
 #pragma unroll 1
           for (uint32_t r = 0; r < m.stored; r++) {
             frame_info f;
@@ -257,7 +215,7 @@ __global__ void __launch_bounds__(BL_THREADS)
       const uint64_t dst = log + target;
       g_u8* const dbase = (g_u8*)(dst & ~15ull);
       const uint64_t P0 = dst & 15u, P1 = P0 + T;
-      for (uint64_t A = (uint64_t)BL_LINE * tid; A < P1; A += (uint64_t)BL_LINE * BL_THREADS) {
+      for (uint64_t A = (uint64_t)BC_LINE * tid; A < P1; A += (uint64_t)BC_LINE * BL_THREADS) {
         const uint64_t s = A > P0 ? A : P0, e = A + 16 < P1 ? A + 16 : P1;
         uint64_t q = s - P0;
         uint32_t a = (uint32_t)(s - A);
@@ -266,16 +224,10 @@ __global__ void __launch_bounds__(BL_THREADS)
         if (q < b_old) {  // old bytes q.. at line offset a
           const uint64_t left = b_old - q;
           const uint32_t nb = left < ae - a ? (uint32_t)left : ae - a;
-          or_into(acc, shl_bytes(low_bytes(load_bytes(src_old + q, nb), nb), a));
-          a += nb;
-          q += nb;
+          add_bytes(acc, a, q, load_bytes(src_old + q, nb), nb);
         }
-        if (a < ae) {  // new bytes
-          const uint32_t nb = ae - a;
-          or_into(acc, shl_bytes(low_bytes(load_bytes(src_new + (q - b_old), nb), nb), a));
-        }
-        if (s == A && e == A + 16) store_line(dbase, A, acc);
-        else store_edge(dbase, A, s, e, acc);  // the range's first or last line
+        if (a < ae) add_bytes(acc, a, q, load_bytes(src_new + (q - b_old), ae - a), ae - a);  // new bytes
+        put_line(dbase, A, s, e, P0, P1, acc);
       }
     }
 
@@ -303,7 +255,7 @@ __global__ void __launch_bounds__(BL_THREADS)
   }
 }
 
-__global__ void __launch_bounds__(BL_FAN_THREADS)
+__global__ void __launch_bounds__(BC_THREADS)
     k_backlog_deliver(const xyws_backlog_conn* __restrict__ jconns, uint64_t n,
                       const xyws_backlog_room* __restrict__ brooms, uint64_t n_rooms,
                       xyws_backlog_result* __restrict__ results) {
@@ -368,18 +320,7 @@ __global__ void __launch_bounds__(BL_FAN_THREADS)
     const uint64_t wlim = sat_add(olo, out_cap);
     const uint64_t P0 = olo + base, P1 = sat_add(P0, w);
     const uint64_t wl = P1 < wlim ? P1 : wlim;
-    const uint64_t A00 = (P0 >> 4) << 4;
-    for (uint64_t A0 = A00 + (uint64_t)blockIdx.y * BL_STEP; A0 < wl; A0 += (uint64_t)gridDim.y * BL_STEP) {
-      const uint64_t A = A0 + 16u * tid;
-      if (A >= wl) break;
-      if (A >= P0 && A + 16 <= wl) {  // a whole line inside the range: backlog bytes A - P0 ..
-        store_line(obase, A, load_bytes(src + (A - P0), 16));
-      } else {  // the range's first or last line: its own bytes only
-        const uint64_t s = A > P0 ? A : P0, e = A + 16 < wl ? A + 16 : wl;
-        const bytes16 v = shl_bytes(load_bytes(src + (s - P0), (uint32_t)(e - s)), (uint32_t)(s - A));
-        store_edge(obase, A, s, e, v);
-      }
-    }
+    copy_span(obase, P0, wl, src, (uint64_t)blockIdx.y * BC_STEP, (uint64_t)gridDim.y * BC_STEP, tid);
   }
 }
 
@@ -402,7 +343,7 @@ int xyws_backlog_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm, const 
   device_guard g(ctx->device);
   if (!g.ok) return XYWS_ERR_HIP;
   if (n_rooms) {
-    const uint32_t grid = grid_for(n_rooms, 1, BL_GRID_CAP);
+    const uint32_t grid = grid_for(n_rooms, 1, BC_GRID_CAP);
     hipLaunchKernelGGL(k_backlog_fold, dim3(grid), dim3(BL_THREADS), 0, (hipStream_t)stream, dev_reasm,
                        dev_reasm_results, dev_bconns, n, dev_rooms, dev_room_results, dev_brooms, dev_broom_results,
                        n_rooms);
@@ -410,11 +351,8 @@ int xyws_backlog_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm, const 
     if (rc != XYWS_OK) return rc;
   }
   if (!n || !dev_jconns) return XYWS_OK;
-  const uint32_t gx = grid_for(n, 1, BL_GRID_CAP);
-  uint32_t gy = (BL_BLOCKS_AIM + gx - 1u) / gx;
-  if (gy > BL_SLICES_MAX) gy = BL_SLICES_MAX;
-  if (!n_rooms) gy = 1;  // (result rows only)
-  hipLaunchKernelGGL(k_backlog_deliver, dim3(gx, gy), dim3(BL_FAN_THREADS), 0, (hipStream_t)stream, dev_jconns, n,
+  const dim3 grid = fanout_grid(n, n_rooms != 0, BC_GRID_CAP, BC_BLOCKS_AIM, BC_SLICES_MAX);
+  hipLaunchKernelGGL(k_backlog_deliver, grid, dim3(BC_THREADS), 0, (hipStream_t)stream, dev_jconns, n,
                      dev_brooms, n_rooms, dev_results);
   return hip_err(hipGetLastError());
 }
@@ -425,8 +363,8 @@ int xyws_backlog_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm, const 
 int xyws_debug_backlog_geometry(uint64_t out[4]) {
   if (!out) return XYWS_ERR_INVALID;
   out[0] = BL_TILE;
-  out[1] = BL_STEP;
-  out[2] = BL_GRID_CAP;
+  out[1] = BC_STEP;
+  out[2] = BC_GRID_CAP;
   out[3] = BC_WAVE;
   return XYWS_OK;
 }

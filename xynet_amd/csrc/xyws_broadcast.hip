@@ -10,30 +10,26 @@
 //
 // k_room_wire: one workgroup per room, rooms grid-strided. The members are
 // taken in tiles of BC_TILE, one member per thread:
-//   1. the thread reads its member's table entries (bounds-checked index),
-//      decides the gate (reassembly overflow, reply overflow, closed, the
-//      first close of this sweep), walks the stored records, tests each
+//   1. the thread loads its member and its gate (bounds-checked index;
+//      load_member, xyws_room.h), walks the stored records, tests each
 //      (frame_of) and sums the frame sizes header + head + message;
 //   2. a workgroup scan gives each member's offset in the wire; the offsets
 //      and what the copy needs of a member go to LDS; the running sum is
 //      carried between tiles in a register;
-//   3. the copy phase covers the tile's wire range in 16-byte lines, one line
-//      per thread per step: a binary search in the LDS offsets finds the
-//      member of the line's first byte, the member's records are walked to the
-//      frame that holds it, and header, head and message bytes are composed in
-//      registers (source bytes: one or two aligned 16-byte loads funnelled to
-//      the byte offset); a 16-byte store inside the range and the capacity,
-//      byte stores on the range's first and last line.
+//   3. the copy phase covers the tile's wire range in 16-byte lines
+//      (xyws_lines.h), one line per thread per step: item_at finds the member
+//      of the line's first byte, the member's records are walked to the frame
+//      that holds it, and header, head and message bytes are composed in
+//      registers.
 // The result row is written once, after the last tile.
 //
 // k_room_fanout: blockIdx.x strides over the connections, blockIdx.y over
 // BC_STEP-byte chunks of the connection's destination range, so a few
 // connections with a long wire still fill the machine (the host cannot know
-// the wire lengths: the chunks are strided, whatever the length). A thread
-// takes one destination-aligned 16-byte line: the source is one or two
-// aligned loads funnelled to (wire - out - base) mod 16. The first and last
-// line of the range are stored byte by byte (a send slab's neighbours share
-// them). The y == 0 workgroup writes the connection's result row.
+// the wire lengths: the chunks are strided, whatever the length). The copy
+// loop is the kernel's own, built from the line primitives (xyws_lines.h): it
+// is copy_span's loop, kept here because the shared one measured slower in
+// this kernel. The y == 0 workgroup writes the connection's result row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
@@ -42,38 +38,14 @@
 #include "xyws_device.h"
 #include "xyws_ctx.h"
 #include "xyws_frameops.h"
+#include "xyws_lines.h"
 #include "xyws_room.h"
 
-#define BC_THREADS 256u     // the fan-out: four waves
 #define BC_TILE BC_WIRE_THREADS  // members per tile of the wire build: one per thread
-#define BC_LINE 16u         // bytes a thread writes per copy step
-#define BC_STEP (BC_LINE * BC_THREADS)  // bytes a workgroup writes per step (the fan-out)
-#define BC_GRID_CAP 8192u   // rooms / connections per launch in x; further ones are grid-strided
-#define BC_BLOCKS_AIM 4096u // fan-out: workgroups wanted in flight (256 CUs x 16)
-#define BC_SLICES_MAX 256u  // fan-out: at most this many workgroups share one connection
 
 using namespace xyws_internal;
 
 namespace {
-
-XYWS_DEV void or_into(bytes16& acc, bytes16 p) {
-  acc.lo |= p.lo;
-  acc.hi |= p.hi;
-}
-
-XYWS_DEV void store_line(g_u8* obase, uint64_t A, bytes16 v) {
-  *reinterpret_cast<g_u32x4*>(obase + A) =
-      u32x4{(uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32)};
-}
-
-// Bytes [s, we) of the line at A, byte by byte (v holds the line's bytes at their line offsets).
-XYWS_DEV void store_edge(g_u8* obase, uint64_t A, uint64_t s, uint64_t we, bytes16 v) {
-#pragma unroll 1
-  for (uint64_t p = s; p < we; p++) {
-    const uint32_t b = (uint32_t)(p - A);
-    obase[p] = (uint8_t)(b < 8 ? v.lo >> (8u * b) : v.hi >> (8u * (b - 8)));
-  }
-}
 
 __global__ void __launch_bounds__(BC_WIRE_THREADS)
     k_room_wire(const xyws_reasm_conn* __restrict__ reasm, const xyws_reasm_result* __restrict__ rres,
@@ -110,30 +82,9 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
         if (ci >= n) {
           c_st |= XYWS_ROOM_BAD_MEMBER;
         } else {
-          const g_u64* const aq = (const g_u64*)(reasm + ci);
-          const g_u64* const ar = (const g_u64*)(rres + ci);
-          const g_u64* const bq = (const g_u64*)(bconns + ci);
-          m.out = aq[0];
-          m.out_cap = m.out ? aq[1] : 0;
-          m.msgs = aq[3];
-          const uint64_t msg_cap = m.msgs ? aq[4] : 0;
-          const uint64_t nmsgs = ar[1];
-          const uint32_t rst = (uint32_t)(ar[2] >> 32);
-          const uint64_t kept = nmsgs < msg_cap ? nmsgs : msg_cap;
-          m.stored = kept < 0xFFFFFFFFull ? (uint32_t)kept : 0xFFFFFFFFu;  // (the counts are 32 bits)
-          if (nmsgs > msg_cap) c_st |= XYWS_ROOM_MSG_CAP;
-          m.head = bq[0];
-          m.head_len = m.head ? bq[1] : 0;
-          m.gate = (rst & XYWS_RSM_OVERFLOW) ? 0 : XYWS_NPOS;
-          const g_u64* const rp = (const g_u64*)bq[4];
-          bool receiver = true;
-          if (rp) {
-            const uint64_t fc = rp[1];
-            const uint32_t pst = (uint32_t)(rp[2] >> 48);
-            if (pst & (XYWS_RPL_CLOSED | XYWS_RPL_OVERFLOW)) receiver = false;
-            if ((pst & XYWS_RPL_OVERFLOW) || ((pst & XYWS_RPL_CLOSED) && fc == XYWS_NPOS)) m.gate = 0;
-            else if (fc != XYWS_NPOS && m.gate) m.gate = fc;
-          }
+          bool receiver, over_cap;
+          load_member(reasm, rres, bconns, ci, m, receiver, over_cap);
+          if (over_cap) c_st |= XYWS_ROOM_MSG_CAP;
           c_recv += receiver ? 1u : 0u;
 #pragma unroll 1
           for (uint32_t r = 0; r < m.stored; r++) {
@@ -169,13 +120,7 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
         for (uint64_t A = ((P0 >> 4) + tid) << 4; A < wl; A += (uint64_t)BC_LINE * BC_WIRE_THREADS) {
           const uint64_t s = A > P0 ? A : P0, e = A + 16 < P1 ? A + 16 : P1;
           uint64_t q = s - wlo;
-          // the last member whose start is at or before q: it holds byte q (q < o1)
-          uint32_t i = 0, hi = BC_TILE;
-          while (hi - i > 1) {
-            const uint32_t mid = (i + hi) >> 1;
-            if (s_off[mid] <= q) i = mid;
-            else hi = mid;
-          }
+          uint32_t i = item_at(s_off, BC_TILE, q);  // the member that holds byte q (q < o1)
           bytes16 acc = {0, 0};
           uint32_t a = (uint32_t)(s - A);
           const uint32_t ae = (uint32_t)(e - A);
@@ -199,33 +144,26 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
                 if (rr < f.h) {  // header bytes rr.. at line offset a
                   const uint32_t nb = f.h - (uint32_t)rr < ae - a ? f.h - (uint32_t)rr : ae - a;
                   const bytes16 hd = {(uint64_t)f.hw[0] | ((uint64_t)f.hw[1] << 32), (uint64_t)f.hw[2]};
-                  or_into(acc, shl_bytes(low_bytes(shr_bytes(hd, (uint32_t)rr), nb), a));
-                  a += nb;
-                  q += nb;
+                  add_bytes(acc, a, q, shr_bytes(hd, (uint32_t)rr), nb);
                   rr += nb;
                 }
                 if (a < ae && rr < f.h + k.head_len) {  // head bytes
                   const uint64_t left = f.h + k.head_len - rr;
                   const uint32_t nb = left < ae - a ? (uint32_t)left : ae - a;
-                  or_into(acc, shl_bytes(low_bytes(load_bytes(k.head + (rr - f.h), nb), nb), a));
-                  a += nb;
-                  q += nb;
+                  add_bytes(acc, a, q, load_bytes(k.head + (rr - f.h), nb), nb);
                   rr += nb;
                 }
                 if (a < ae && rr < fsz) {  // message bytes
                   const uint64_t left = fsz - rr;
                   const uint32_t nb = left < ae - a ? (uint32_t)left : ae - a;
-                  or_into(acc, shl_bytes(low_bytes(load_bytes(k.out + f.off + (rr - f.h - k.head_len), nb), nb), a));
-                  a += nb;
-                  q += nb;
+                  add_bytes(acc, a, q, load_bytes(k.out + f.off + (rr - f.h - k.head_len), nb), nb);
                 }
               }
               fo += fsz;
             }
             i++;
           }
-          if (s == A && e == A + 16 && A >= wlo && A + 16 <= wlim) store_line(wbase, A, acc);
-          else store_edge(wbase, A, s, e < wlim ? e : wlim, acc);  // the range's first or last line
+          put_line(wbase, A, s, e, wlo, wlim, acc);
         }
       }
       wpos = o1;
@@ -302,16 +240,16 @@ __global__ void __launch_bounds__(BC_THREADS) k_room_fanout(const xyws_bcast_con
     const uint64_t wlim = sat_add(olo, out_cap);
     const uint64_t P0 = olo + base, P1 = sat_add(P0, w);
     const uint64_t wl = P1 < wlim ? P1 : wlim;
+    // (not copy_span: the shared loop measured slower here, profiles/room_rate.jsonl and DESIGN.md 4.9)
     const uint64_t A00 = (P0 >> 4) << 4;
     for (uint64_t A0 = A00 + (uint64_t)blockIdx.y * BC_STEP; A0 < wl; A0 += (uint64_t)gridDim.y * BC_STEP) {
       const uint64_t A = A0 + 16u * tid;
       if (A >= wl) break;
       if (A >= P0 && A + 16 <= wl) {  // a whole line inside the range: wire bytes A - P0 ..
         store_line(obase, A, load_bytes(wire + (A - P0), 16));
-      } else {  // the range's first or last line: its own bytes only
+      } else {  // the range's first or last line: its own bytes only (put_line's rule with lo = P0, lim = wl)
         const uint64_t s = A > P0 ? A : P0, e = A + 16 < wl ? A + 16 : wl;
-        const bytes16 v = shl_bytes(load_bytes(wire + (s - P0), (uint32_t)(e - s)), (uint32_t)(s - A));
-        store_edge(obase, A, s, e, v);
+        store_edge(obase, A, s, e, shl_bytes(load_bytes(wire + (s - P0), (uint32_t)(e - s)), (uint32_t)(s - A)));
       }
     }
   }
@@ -341,11 +279,8 @@ int xyws_broadcast_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm, cons
     const int rc = hip_err(hipGetLastError());
     if (rc != XYWS_OK) return rc;
   }
-  const uint32_t gx = grid_for(n, 1, BC_GRID_CAP);
-  uint32_t gy = (BC_BLOCKS_AIM + gx - 1u) / gx;
-  if (gy > BC_SLICES_MAX) gy = BC_SLICES_MAX;
-  if (!n_rooms) gy = 1;  // (result rows only)
-  hipLaunchKernelGGL(k_room_fanout, dim3(gx, gy), dim3(BC_THREADS), 0, (hipStream_t)stream, dev_bconns, n, dev_rooms,
+  const dim3 grid = fanout_grid(n, n_rooms != 0, BC_GRID_CAP, BC_BLOCKS_AIM, BC_SLICES_MAX);
+  hipLaunchKernelGGL(k_room_fanout, grid, dim3(BC_THREADS), 0, (hipStream_t)stream, dev_bconns, n, dev_rooms,
                      dev_room_results, n_rooms, dev_results);
   return hip_err(hipGetLastError());
 }

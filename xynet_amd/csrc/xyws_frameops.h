@@ -118,27 +118,14 @@ XYWS_DEV uint32_t tail_prev(uint32_t tw, uint32_t back) {
   return (tw >> (8u * (tl - back))) & 0xFFu;
 }
 
-// ---------------------------------------------------------------- line loads, lane moves
-// (the per-connection copy phases: xyws_reply.hip, xyws_reasm_streams.hip)
-XYWS_DEV bytes16 line_of(const g_u8* aligned) {
-  const u32x4 x = *reinterpret_cast<const g_u32x4*>(aligned);
-  return bytes16{(uint64_t)x.x | ((uint64_t)x.y << 32), (uint64_t)x.z | ((uint64_t)x.w << 32)};
-}
-// The nb (1..16) bytes at address g, in the low bytes of the result (the bytes
-// above them are not defined). Only the 16-byte lines that hold one of the nb
-// bytes are loaded.
-XYWS_DEV bytes16 load_bytes(uint64_t g, uint32_t nb) {
-  const g_u8* const a = (const g_u8*)(g & ~15ull);
-  const uint32_t sh = (uint32_t)(g & 15u);
-  bytes16 v = shr_bytes(line_of(a), sh);
-  if (sh + nb > 16) {  // (sh >= 1 here)
-    const bytes16 y = shl_bytes(line_of(a + 16), 16 - sh);
-    v.lo |= y.lo;
-    v.hi |= y.hi;
-  }
-  return v;
-}
+// ---------------------------------------------------------------- message records
+// A stored record's bytes [off, off + len) lie in [0, out_cap): nothing outside
+// a connection's out area is read (the room kernels' frame_of, xyws_room.h;
+// xyws_hold.hip).
+XYWS_DEV bool in_range(uint64_t off, uint64_t len, uint64_t out_cap) { return off <= out_cap && len <= out_cap - off; }
 
+// ---------------------------------------------------------------- lane moves
+// (the 16-byte line loads and stores of the copy phases: xyws_lines.h)
 XYWS_DEV uint64_t shfl64(uint64_t v, uint32_t src) {
   return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, (int)src) |
          ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src) << 32);

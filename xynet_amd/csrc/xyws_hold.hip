@@ -13,10 +13,9 @@
 //      nmsgs - 1, and leaves the new carry, the result bits, the delivered
 //      record (if any) and at most two byte ranges to copy: the part appended
 //      to the held message, and the message open at the end that begins a hold;
-//   2. the copies: a lane takes one destination-aligned 16-byte line per step,
-//      the source is one or two aligned loads funnelled to the byte offset
-//      (load_bytes), a 16-byte store inside the range and byte stores on its
-//      first and last line (neighbouring areas may share them);
+//   2. the copies, by the whole wave in 16-byte lines (copy_span,
+//      xyws_lines.h; neighbouring areas may share a range's first and last
+//      line);
 //   3. the record row goes to the view one record per lane, strided, out_off
 //      moved by hold_cap; record 0 is the delivered message when there is one;
 //   4. lane 0 writes the carry, the view entry, the view row and the result.
@@ -28,6 +27,7 @@
 #include "xyws_device.h"
 #include "xyws_ctx.h"
 #include "xyws_frameops.h"
+#include "xyws_lines.h"
 
 #define HOLD_LANES 64u      // lanes per connection: one wave
 #define HOLD_LINE 16u       // bytes a lane writes per copy step
@@ -41,29 +41,8 @@ namespace {
 // L bytes from address S to address D, by the whole wave. The caller has
 // checked both ranges; they do not overlap (message bytes and hold).
 XYWS_DEV void copy_range(uint64_t D, uint64_t S, uint64_t L, uint32_t lane) {
-  if (!L) return;
-  g_u8* const dbase = (g_u8*)(D & ~15ull);
-  // destination positions count from dbase (16-byte aligned): the range is [P0, P1)
-  const uint64_t P0 = D & 15u, P1 = P0 + L;
-  for (uint64_t A0 = 0; A0 < P1; A0 += HOLD_STEP) {
-    const uint64_t A = A0 + HOLD_LINE * lane;
-    if (A >= P1) break;
-    const uint64_t s = A > P0 ? A : P0, e = A + 16 < P1 ? A + 16 : P1;
-    const uint32_t nb = (uint32_t)(e - s);
-    const bytes16 v = load_bytes(S + (s - P0), nb);
-    if (nb == 16) {  // a whole line inside the range
-      *reinterpret_cast<g_u32x4*>(dbase + A) =
-          u32x4{(uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32)};
-    } else {  // the range's first or last line: its own bytes only
-#pragma unroll 1
-      for (uint32_t b = 0; b < nb; b++)
-        dbase[s + b] = (uint8_t)(b < 8 ? v.lo >> (8u * b) : v.hi >> (8u * (b - 8)));
-    }
-  }
+  if (L) copy_span((g_u8*)(D & ~15ull), D & 15u, (D & 15u) + L, S, 0, HOLD_STEP, lane);
 }
-
-// A record's range lies in [0, out_cap).
-XYWS_DEV bool in_range(uint64_t off, uint64_t len, uint64_t out_cap) { return off <= out_cap && len <= out_cap - off; }
 
 __global__ void __launch_bounds__(HOLD_LANES)
     k_hold_streams(const xyws_reasm_conn* __restrict__ reasm, const xyws_reasm_result* __restrict__ rres,

@@ -56,6 +56,17 @@ inline int grid_for(uint64_t items, uint32_t per_block, uint32_t cap) {
   return (int)g;
 }
 
+// The grid of a fan-out launch (k_room_fanout, k_backlog_deliver): x strides
+// over the n connections, y over the copy steps of one connection's range, so
+// that about `aim` workgroups are in flight and at most slices_max share one
+// connection. !copies: the launch writes result rows only.
+inline dim3 fanout_grid(uint64_t n, bool copies, uint32_t cap, uint32_t aim, uint32_t slices_max) {
+  const uint32_t gx = (uint32_t)grid_for(n, 1, cap);
+  uint32_t gy = (aim + gx - 1u) / gx;
+  if (gy > slices_max) gy = slices_max;
+  return dim3(gx, copies ? gy : 1u);
+}
+
 // One device scratch area: every buffer a context owns is one of these, and
 // this is the only place one is allocated or freed. `units` is what the area
 // covers in its owner's unit (runs, segments, table entries, bytes); the owner

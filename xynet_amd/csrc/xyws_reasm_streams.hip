@@ -21,9 +21,7 @@
 //      first tile is the carried prefix; segment 0 is the message open at the
 //      tile's start;
 //   3. the copy phase is k_reply_streams' without headers: a lane per 16-byte
-//      line of out, a binary search for its item, payload bytes from one or
-//      two aligned loads, a 16-byte store inside the range and byte stores on
-//      its first and last line;
+//      line of out (xyws_lines.h), its item from item_at;
 //   4. UTF-8 on the composed lines, in registers: a lane looks at its line and
 //      the 3 bytes before it (the neighbour lane's, the previous step's, or a
 //      wave-uniform tail of the previous tile / the carry's utf8 bytes). Every
@@ -41,6 +39,7 @@
 #include "xyws_device.h"
 #include "xyws_ctx.h"
 #include "xyws_frameops.h"
+#include "xyws_lines.h"
 
 #define RSM_TILE 64u       // frames per tile: one per lane
 #define RSM_LANES 64u      // lanes per connection: one wave
@@ -91,39 +90,18 @@ XYWS_DEV uint32_t copy_check_tile(const uint64_t* s_off, const uint64_t* s_soff,
     bytes16 acc = {0, 0};
     if (active) {
       uint64_t q = s - olo;
-      // the last item whose start is at or before q
-      uint32_t i = 0, hi = RSM_ITEMS;
-      while (hi - i > 1) {
-        const uint32_t m = (i + hi) >> 1;
-        if (s_off[m] <= q) i = m;
-        else hi = m;
-      }
+      uint32_t i = item_at(s_off, RSM_ITEMS, q);  // the item that holds byte q
       uint32_t a = (uint32_t)(s - A);
       const uint32_t ae = (uint32_t)(e - A);
       while (a < ae && i < RSM_ITEMS) {
         const uint64_t start = s_off[i], next = s_off[i + 1];
         if (next > q) {
           const uint32_t nb = next - q < ae - a ? (uint32_t)(next - q) : ae - a;
-          const bytes16 p = shl_bytes(low_bytes(load_bytes(src + s_soff[i] + (q - start), nb), nb), a);
-          acc.lo |= p.lo;
-          acc.hi |= p.hi;
-          a += nb;
-          q += nb;
+          add_bytes(acc, a, q, load_bytes(src + s_soff[i] + (q - start), nb), nb);
         }
         i++;
       }
-      if (s == A && e == A + 16 && A >= olo && A + 16 <= wlim) {
-        *reinterpret_cast<g_u32x4*>(obase + A) =
-            u32x4{(uint32_t)acc.lo, (uint32_t)(acc.lo >> 32), (uint32_t)acc.hi, (uint32_t)(acc.hi >> 32)};
-      } else {
-        // the range's first or last line: its own bytes only
-        const uint64_t we = e < wlim ? e : wlim;
-#pragma unroll 1
-        for (uint64_t p = s; p < we; p++) {
-          const uint32_t b = (uint32_t)(p - A);
-          obase[p] = (uint8_t)(b < 8 ? acc.lo >> (8u * b) : acc.hi >> (8u * (b - 8)));
-        }
-      }
+      put_line(obase, A, s, e, olo, wlim, acc);
     }
     if (!utf8on) continue;
 
@@ -160,17 +138,7 @@ XYWS_DEV uint32_t copy_check_tile(const uint64_t* s_off, const uint64_t* s_soff,
     // from here on positions are relative to the line's first byte, clamped to [-8, 64] (every byte the
     // rules look at lies in [-3, 16)): 32-bit compares
     const int64_t qbase = (int64_t)A - (int64_t)olo;
-    uint32_t seg = 0;
-    {
-      const uint64_t q = (uint64_t)(qbase + ja);
-      // the segment of the first byte: the last one that starts at or before it
-      uint32_t hi = RSM_SEGS;
-      while (hi - seg > 1) {
-        const uint32_t m = (seg + hi) >> 1;
-        if (s_sstart[m] <= q) seg = m;
-        else hi = m;
-      }
-    }
+    uint32_t seg = item_at(s_sstart, RSM_SEGS, (uint64_t)(qbase + ja));  // the segment of the first byte
     int32_t segend, ms, cs;
     uint32_t fl;
     auto clamp = [](int64_t r) -> int32_t { return r < -8 ? -8 : r > 64 ? 64 : (int32_t)r; };

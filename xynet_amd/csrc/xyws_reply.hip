@@ -20,14 +20,9 @@
 //      call began; first tile only), items 1..REPLY_TILE the frames, the last
 //      item the close frame (a 4-byte header without payload);
 //   3. the copy phase covers the tile's output range in 16-byte lines of the
-//      send buffer, one line per lane per step: the lane finds the item of its
-//      line's first byte by a binary search in the LDS offsets, walks the items
-//      that touch the line and composes their header and payload bytes in
-//      registers (payload bytes: one or two aligned 16-byte loads funnelled to
-//      the byte offset), then stores 16 bytes where the line lies wholly
-//      inside the tile's range and the connection's capacity, and byte by byte
-//      on the range's first and last line (a tile edge, or a line shared with a
-//      neighbouring connection's send buffer).
+//      send buffer (xyws_lines.h), one line per lane per step: the lane finds
+//      the item of its line's first byte (item_at), walks the items that touch
+//      the line and composes their header and payload bytes in registers.
 // The state between tiles (reply length so far, frame_remaining, echoing,
 // answered, first close) is wave-uniform and held in scalars.
 #include <hip/hip_runtime.h>
@@ -38,6 +33,7 @@
 #include "xyws_device.h"
 #include "xyws_ctx.h"
 #include "xyws_frameops.h"
+#include "xyws_lines.h"
 
 #define REPLY_TILE 64u       // frames per tile: one per lane
 #define REPLY_LANES 64u      // lanes per connection: one wave
@@ -49,8 +45,6 @@
 typedef XYWS_GLOBAL uint16_t g_u16;
 
 using namespace xyws_internal;
-
-// (line_of, load_bytes, shfl64, shfl_up64: xyws_frameops.h)
 
 // The reply bytes [o0, o1) of one tile, whose items are in LDS, into the send
 // buffer: reply byte q lives at position olo + q from obase (16-byte aligned);
@@ -64,13 +58,7 @@ XYWS_DEV void copy_tile(const uint64_t* s_off, const uint64_t* s_soff, const uin
   for (uint64_t A = ((P0 >> 4) + lane) << 4; A < wl; A += (uint64_t)REPLY_LINE * REPLY_LANES) {
     const uint64_t s = A > P0 ? A : P0, e = A + 16 < P1 ? A + 16 : P1;
     uint64_t q = s - olo;
-    // the last item whose start is at or before q: it holds byte q (q < o1)
-    uint32_t i = 0, hi = REPLY_ITEMS;
-    while (hi - i > 1) {
-      const uint32_t m = (i + hi) >> 1;
-      if (s_off[m] <= q) i = m;
-      else hi = m;
-    }
+    uint32_t i = item_at(s_off, REPLY_ITEMS, q);  // the item that holds byte q (q < o1)
     bytes16 acc = {0, 0};
     uint32_t a = (uint32_t)(s - A);
     const uint32_t ae = (uint32_t)(e - A);
@@ -81,36 +69,17 @@ XYWS_DEV void copy_tile(const uint64_t* s_off, const uint64_t* s_soff, const uin
         const uint32_t h2 = s_h2[i], h = h2 >> 16;
         if (r < h) {  // header bytes r.. at line offset a
           const uint32_t nb = h - (uint32_t)r < ae - a ? h - (uint32_t)r : ae - a;
-          const bytes16 p = shl_bytes(low_bytes(shr_bytes(bytes16{s_h01[i], h2 & 0xFFFFu}, (uint32_t)r), nb), a);
-          acc.lo |= p.lo;
-          acc.hi |= p.hi;
-          a += nb;
-          q += nb;
+          add_bytes(acc, a, q, shr_bytes(bytes16{s_h01[i], h2 & 0xFFFFu}, (uint32_t)r), nb);
           r += nb;
         }
         if (a < ae && q < next) {  // payload bytes r - h.. at line offset a
           const uint32_t nb = next - q < ae - a ? (uint32_t)(next - q) : ae - a;
-          const bytes16 p = shl_bytes(low_bytes(load_bytes(src + s_soff[i] + (r - h), nb), nb), a);
-          acc.lo |= p.lo;
-          acc.hi |= p.hi;
-          a += nb;
-          q += nb;
+          add_bytes(acc, a, q, load_bytes(src + s_soff[i] + (r - h), nb), nb);
         }
       }
       i++;
     }
-    if (s == A && e == A + 16 && A >= olo && A + 16 <= wlim) {
-      *reinterpret_cast<g_u32x4*>(obase + A) =
-          u32x4{(uint32_t)acc.lo, (uint32_t)(acc.lo >> 32), (uint32_t)acc.hi, (uint32_t)(acc.hi >> 32)};
-    } else {
-      // the range's first or last line: its own bytes only
-      const uint64_t we = e < wlim ? e : wlim;
-#pragma unroll 1
-      for (uint64_t p = s; p < we; p++) {
-        const uint32_t b = (uint32_t)(p - A);
-        obase[p] = (uint8_t)(b < 8 ? acc.lo >> (8u * b) : acc.hi >> (8u * (b - 8)));
-      }
-    }
+    put_line(obase, A, s, e, olo, wlim, acc);
   }
 }
 

@@ -1,12 +1,11 @@
 // xyws_room.h — internal: what the kernels that walk a room's members share
-// (xyws_broadcast.hip: the wire build; xyws_backlog.hip: the backlog fold):
-// which of a member's stored records is deliverable behind a given gate and
-// how long its frame is (include/xyws.h, xyws_broadcast_streams 2. and 3.),
-// and the workgroup scan both use to place members. The record test and the
-// frame size are stated once here; how a member's gate follows from its
-// reassembly and reply rows is written in each of the two kernels (the wire
-// build's lines were left as they were), and a difference between them shows
-// as XYWS_BL_MISMATCH, never as a wrong copy.
+// (xyws_broadcast.hip: the wire build and the fan-out; xyws_backlog.hip: the
+// backlog fold and the delivery): how a member and its gate follow from its
+// reassembly and reply rows (load_member), which of its stored records is
+// deliverable behind that gate and how long its frame is (frame_of;
+// include/xyws.h, xyws_broadcast_streams 2. and 3.), the workgroup scan that
+// places members, and the geometry of the two fan-out launches. Each is stated
+// once here: the gate rule is load_member's and nobody else's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,6 +16,13 @@
 
 #define BC_WAVE 64u
 #define BC_WIRE_THREADS 1024u  // the wire build: sixteen waves, the one workgroup a room gets
+// the fan-out and the backlog delivery (xyws_host.h: fanout_grid)
+#define BC_THREADS 256u     // four waves
+#define BC_LINE 16u         // bytes a thread writes per copy step
+#define BC_STEP (BC_LINE * BC_THREADS)  // bytes a workgroup writes per step
+#define BC_GRID_CAP 8192u   // rooms / connections per launch in x; further ones are grid-strided
+#define BC_BLOCKS_AIM 4096u // workgroups wanted in flight (256 CUs x 16)
+#define BC_SLICES_MAX 256u  // at most this many workgroups share one connection
 
 namespace xyws_internal {
 
@@ -26,6 +32,40 @@ struct member {
   uint64_t msgs, gate, out, out_cap, head, head_len;
   uint32_t stored;
 };
+
+// Member ci (< n of the caller's tables) from its reassembly entry and row,
+// its broadcast entry and, where it names one, its reply row. The gate:
+// nothing after a reassembly or reply overflow or a close in an earlier sweep,
+// else the frames before the first close of this sweep. receiver: it takes
+// the room's wire (neither closed nor overflowed); over_cap: the sweep found
+// more messages than msg_cap holds.
+XYWS_DEV void load_member(const xyws_reasm_conn* reasm, const xyws_reasm_result* rres, const xyws_bcast_conn* bconns,
+                          uint64_t ci, member& m, bool& receiver, bool& over_cap) {
+  const g_u64* const aq = (const g_u64*)(reasm + ci);
+  const g_u64* const ar = (const g_u64*)(rres + ci);
+  const g_u64* const bq = (const g_u64*)(bconns + ci);
+  m.out = aq[0];
+  m.out_cap = m.out ? aq[1] : 0;
+  m.msgs = aq[3];
+  const uint64_t msg_cap = m.msgs ? aq[4] : 0;
+  const uint64_t nmsgs = ar[1];
+  const uint32_t rst = (uint32_t)(ar[2] >> 32);
+  const uint64_t kept = nmsgs < msg_cap ? nmsgs : msg_cap;
+  m.stored = kept < 0xFFFFFFFFull ? (uint32_t)kept : 0xFFFFFFFFu;  // (the counts are 32 bits)
+  over_cap = nmsgs > msg_cap;
+  m.head = bq[0];
+  m.head_len = m.head ? bq[1] : 0;
+  m.gate = (rst & XYWS_RSM_OVERFLOW) ? 0 : XYWS_NPOS;
+  const g_u64* const rp = (const g_u64*)bq[4];
+  receiver = true;
+  if (rp) {
+    const uint64_t fc = rp[1];
+    const uint32_t pst = (uint32_t)(rp[2] >> 48);
+    if (pst & (XYWS_RPL_CLOSED | XYWS_RPL_OVERFLOW)) receiver = false;
+    if ((pst & XYWS_RPL_OVERFLOW) || ((pst & XYWS_RPL_CLOSED) && fc == XYWS_NPOS)) m.gate = 0;
+    else if (fc != XYWS_NPOS && m.gate) m.gate = fc;
+  }
+}
 
 // One stored record (its five words at rec) of a member: deliverable or not;
 // if so its frame: header words hw, header length h, message at out + off,
@@ -38,7 +78,7 @@ XYWS_DEV bool frame_of(const g_u64* rec, const member& m, uint32_t flags, uint32
   const uint64_t first = rec[0], off = rec[2], len = rec[3], w4 = rec[4];
   const uint32_t st = (uint32_t)w4, op = (uint32_t)(w4 >> 32) & XYWS_FLAG_OP_MASK;
   if (!(st & XYWS_MSG_COMPLETE) || (st & (XYWS_MSG_CONTINUED | XYWS_MSG_TRUNCATED | XYWS_MSG_UTF8_BAD))) return false;
-  if (off > m.out_cap || len > m.out_cap - off) return false;  // (nothing outside [out, out + out_cap) is read)
+  if (!in_range(off, len, m.out_cap)) return false;  // (nothing outside [out, out + out_cap) is read)
   if (m.gate != XYWS_NPOS && first >= m.gate) return false;
   f.off = off;
   f.len = len;
