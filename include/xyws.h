@@ -46,6 +46,10 @@
  *   chat_room::join + deliver_recent_messages: the last 10    xyws_backlog_streams (each room's
  *     messages (m_recent_messages) sent to a newcomer           newest frames kept in a log on the
  *     example/websocket/websocket_chat.cpp:34-47, 89-95         device, copied behind a joiner's send bytes)
+ *   websocket_request_handler (parse, generate_response)     xyws_accept_streams (the opening
+ *     include/xynet/http/websocket_request_handler.h           handshakes of many connections, one
+ *     as websocket_handshake runs it, once per coroutine       launch), xyws_accept_request (one
+ *     example/include/common/websocket.h:40-68                 request in host memory)
  *   recv_all / io_service remote-queue eventfd               xyws_arena_* (pinned recv arena,
  *     include/xynet/socket/impl/recv_all.h:86-121              H2D -> decode -> D2H, completion
  *     include/xynet/io_service.h:362-381                       written to an eventfd)
@@ -1187,6 +1191,119 @@ int xyws_backlog_streams(xyws_ctx* ctx,
                          xyws_backlog_room_result* dev_broom_results /* n_rooms, nullable */, uint64_t n_rooms,
                          const xyws_backlog_conn* dev_jconns /* n, nullable: fold only */,
                          xyws_backlog_result* dev_results /* n, nullable */, void* stream);
+
+/* ---- many connections, one opening handshake call ---------------------------
+ * xyws_accept_streams: the HTTP upgrade of every connection still in HTTP
+ * state, answered by one launch (the reference's websocket_request_handler
+ * over http_parser / picohttpparser, include/xynet/http/websocket_request_handler.h,
+ * as websocket_handshake drives it, example/include/common/websocket.h:40-68).
+ * It is the first call in a connection's life and keeps no state: entry i
+ * names every byte connection i has sent so far, from its first, and its
+ * send buffer. With E = min(len, max_request) the verdict is a pure function
+ * of buf[0, E), policy and whether len >= max_request.
+ *
+ *  1. Grammar. picohttpparser's phr_parse_request as a fresh parser runs it,
+ *     defined by its sequential walk from byte 0; the first event decides:
+ *     a grammar error before byte E is REJECTED with reason PARSE, the end of
+ *     the bytes is incomplete (neither ACCEPTED nor REJECTED: call again with
+ *     more bytes; nothing is written), the blank line ends the request and
+ *     nothing behind it is looked at. Incomplete with len >= max_request is
+ *     REJECTED with reason TOO_LONG. The walk: one optional leading empty
+ *     line; LF-only line ends everywhere; method and target end at SP, reject
+ *     bytes < 0x20 and 0x7f, take bytes >= 0x80, and are non-empty; runs of SP
+ *     between the three parts (the end of the bytes is not a space); the
+ *     version wants 9 bytes left (else incomplete, whatever they are) and is
+ *     `HTTP/1.` and a digit; header names are token characters up to `:`
+ *     (empty, or SP before the colon: error); SP/HT after the colon skipped;
+ *     the value runs to CR LF or LF, another byte < 0x20 except HT, or 0x7f,
+ *     is an error, a CR as the last byte is incomplete, trailing SP/HT are
+ *     trimmed; a line that begins with SP/HT after the first header is a
+ *     nameless continuation ("folded"); a 101st header is an error.
+ *  2. Policy 0 applies RFC 6455 4.2.1 to the parsed request. The checks, in
+ *     the order of their XYWS_ACR_* codes (the lowest failing one is
+ *     reported): method GET; minor version >= 1; no folded line; a Host
+ *     header (names are matched ASCII case-insensitively); an Upgrade header
+ *     with a comma-separated element equal to `websocket` (case-insensitive,
+ *     SP/HT trimmed); a Connection header with an element `upgrade` by the
+ *     same rule; Sec-WebSocket-Key exactly once, 24 bytes: 21 base64
+ *     characters, one of `AQgw`, `==`; Sec-WebSocket-Version exactly once and
+ *     equal to `13`. Responses: 101 (129 bytes, below); 426 when the version
+ *     check is the lowest failing one (`HTTP/1.1 426 Upgrade Required`,
+ *     `Sec-WebSocket-Version: 13`, `Connection: close`, `Content-Length: 0`,
+ *     98 bytes); else 400 (`HTTP/1.1 400 Bad Request`, `Connection: close`,
+ *     `Content-Length: 0`, 66 bytes).
+ *  3. XYWS_ACC_REFERENCE is websocket_request_handler::generate_response,
+ *     bugs included: method exactly GET, minor version exactly 1; of the
+ *     headers before the first folded line (http_parser::headers() ends
+ *     there) those named exactly `Connection`, `Upgrade`,
+ *     `Sec-WebSocket-Version`, `Sec-WebSocket-Key` are checked against
+ *     `Upgrade`, `websocket`, `13`, and a length of 24; absent headers are not
+ *     missed. Any 24 key bytes pass, the last occurrence is hashed, and with
+ *     no key the placeholder `XXXXXXXXXXXXXXXXXXXXXX==` is. Responses: the
+ *     same 101; the reference's 26-byte `HTTP/1.1 400 Bad Request\r\n` (no
+ *     blank line). One departure: the reference answers an incomplete request
+ *     with that 400; here incomplete is reported as incomplete.
+ *  4. The 101 response is `HTTP/1.1 101 Switching Protocols`, `Upgrade:
+ *     websocket`, `Connection: Upgrade`, `Sec-WebSocket-Accept: ` + base64(
+ *     SHA-1(key + 258EAFA5-E914-47DA-95CA-C5AB0DC85B11)), blank line.
+ *     Subprotocols and extensions are ignored and never negotiated.
+ *  5. Nothing outside buf[0, E) is read but the whole 16-byte lines that hold
+ *     one of those bytes; no byte outside [out, out + min(resp_len, out_cap))
+ *     is written (neighbouring ranges share 16-byte lines); buffers may have
+ *     any alignment. resp_len is the full length; TRUNCATED when it exceeds
+ *     out_cap.
+ *  6. One launch, no context scratch, no host read of device state; no
+ *     reserve is needed, the call can be captured into a hipGraph at once and
+ *     runs concurrently on different streams. n == 0 returns XYWS_OK and
+ *     launches nothing. XYWS_ERR_INVALID: a null ctx; null dev_conns with
+ *     n > 0; max_request 0 or above XYWS_ACCEPT_MAX_REQUEST; unknown policy
+ *     bits.
+ *
+ * xyws_accept_request is the same function of one request in host memory:
+ * the same source compiled for the host, no context and no HIP call. */
+#define XYWS_ACCEPT_MAX_REQUEST 8192u /* a whole request fits one wave's LDS */
+#define XYWS_ACC_ACCEPTED   0x1u /* xyws_accept_result.status */
+#define XYWS_ACC_REJECTED   0x2u
+#define XYWS_ACC_TRUNCATED  0x4u /* resp_len > out_cap */
+#define XYWS_ACC_REFERENCE  0x100u /* policy bit */
+#define XYWS_ACR_NONE        0
+#define XYWS_ACR_PARSE       1
+#define XYWS_ACR_TOO_LONG    2
+#define XYWS_ACR_METHOD      3
+#define XYWS_ACR_VERSION     4
+#define XYWS_ACR_FOLDED      5
+#define XYWS_ACR_HOST        6
+#define XYWS_ACR_UPGRADE     7
+#define XYWS_ACR_CONNECTION  8
+#define XYWS_ACR_KEY         9
+#define XYWS_ACR_WS_VERSION 10
+
+typedef struct xyws_accept_conn {   /* 32 bytes */
+  const void* buf;     /* device: every byte this connection has sent so far, from its first */
+  uint64_t    len;     /* 0 allowed: incomplete, nothing written */
+  void*       out;     /* device: its send buffer; nullable with out_cap 0 */
+  uint64_t    out_cap;
+} xyws_accept_conn;
+
+typedef struct xyws_accept_result { /* 32 bytes */
+  uint32_t status;      /* XYWS_ACC_ACCEPTED | XYWS_ACC_REJECTED | XYWS_ACC_TRUNCATED; neither of the first two: incomplete */
+  uint16_t http_status; /* 101, 400, 426, or 0 while incomplete */
+  uint16_t reason;      /* XYWS_ACR_*: 0 when accepted or incomplete, else the lowest-numbered failing check */
+  uint32_t consumed;    /* accepted: bytes of the request, its blank line included (buf + consumed is the
+                           connection's first frame byte: a valid xyws_conn.buf, any alignment); the same
+                           for a whole request that a check refused (reason >= XYWS_ACR_METHOD); else 0 */
+  uint32_t resp_len;    /* full length of the response, whatever out_cap */
+  uint32_t path_off;    /* the request target, for routing; 0, 0 unless accepted */
+  uint32_t path_len;
+  uint32_t key_off;     /* accepted: offset of the 24 key bytes that were hashed; UINT32_MAX if none */
+  uint32_t reserved;
+} xyws_accept_result;
+
+int xyws_accept_streams(xyws_ctx* ctx, const xyws_accept_conn* dev_conns, uint64_t n,
+                        uint32_t max_request, uint32_t policy,
+                        xyws_accept_result* dev_results /* n, nullable */, void* stream);
+int xyws_accept_request(const void* host_req, uint64_t len, uint32_t max_request, uint32_t policy,
+                        void* host_out, uint64_t out_cap, xyws_accept_result* res /* nullable */);
 
 #ifdef __cplusplus
 } /* extern "C" */

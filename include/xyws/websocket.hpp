@@ -26,9 +26,12 @@
 //   websocket_check_parser_result (websocket.h:81-108)    xyws::classify_frames (device)
 //   (new) FIN=0 chains -> messages, UTF-8 validation      xyws::reassemble (one batch),
 //                                                           xyws::message_assembler (across recvs)
+//   class websocket_request_handler                       xyws::websocket_request_handler (host: one
+//     include/xynet/http/websocket_request_handler.h         request, xyws_accept_request),
+//     used by websocket_handshake (websocket.h:40-68)        xyws::accept_streams (many, device)
 //
-// Nothing here computes on the host: every call goes through libxyws.so to
-// HIP kernels for gfx950. Buffers are caller-owned device memory (hipMalloc);
+// Nothing but the one-request handshake handler computes on the host: every
+// other call goes through libxyws.so to HIP kernels for gfx950. Buffers are caller-owned device memory (hipMalloc);
 // `stream` is a hipStream_t passed as void*. Errors throw xyws::error.
 #pragma once
 
@@ -401,6 +404,84 @@ inline void backlog_streams(context& ctx, const xyws_reasm_conn* dev_reasm, cons
                              dev_brooms, dev_broom_results, n_rooms, dev_jconns, dev_results, stream),
         "xyws_backlog_streams");
 }
+
+// The opening handshakes of the connections still in HTTP state, in one launch
+// (xyws_accept_streams), before any of the calls above sees them: dev_conns[i]
+// names every byte connection i has sent so far and its send buffer. A whole
+// request is checked (RFC 6455 4.2.1, or the reference's handler under
+// XYWS_ACC_REFERENCE) and answered with the 101, a 400 or a 426; an incomplete
+// one is reported as incomplete and nothing is written. dev_results (nullable
+// device pointer, n entries) receives the verdicts; on ACCEPTED the bytes
+// behind `consumed` are the connection's first frame bytes.
+inline void accept_streams(context& ctx, const xyws_accept_conn* dev_conns, std::uint64_t n,
+                           xyws_accept_result* dev_results = nullptr, std::uint32_t policy = 0,
+                           std::uint32_t max_request = 1024, void* stream = nullptr) {
+  check(xyws_accept_streams(ctx.native(), dev_conns, n, max_request, policy, dev_results, stream),
+        "xyws_accept_streams");
+}
+
+// class websocket_request_handler (websocket_request_handler.h:66-264) over
+// xyws_accept_request: host memory only, no context, no device. parse() takes
+// the accumulated request and returns what the reference's does: the bytes
+// consumed, -1 for a grammar error, -2 while incomplete. generate_response()
+// returns the 101 or, as there, the bad-request response for whatever was not
+// a whole valid request (an incomplete one included). The default policy is
+// the reference's (XYWS_ACC_REFERENCE); policy 0 answers by RFC 6455 4.2.1.
+// get_path() views the caller's bytes, as in the reference.
+class websocket_request_handler {
+ public:
+  explicit websocket_request_handler(std::uint32_t policy = XYWS_ACC_REFERENCE,
+                                     std::uint32_t max_request = XYWS_ACCEPT_MAX_REQUEST)
+      : policy_(policy), max_request_(max_request) {}
+
+  int parse(std::string_view str) { return parse(str.data(), str.size()); }
+  template <typename T, std::size_t Extent>
+  int parse(std::span<T, Extent> span) {
+    const auto bytes = std::as_bytes(span);
+    return parse(reinterpret_cast<const char*>(bytes.data()), bytes.size());
+  }
+
+  std::span<const std::byte> generate_response() {
+    if (!(res_.status & XYWS_ACC_ACCEPTED) && !(res_.status & XYWS_ACC_REJECTED)) {
+      // not parsed (never, or incomplete): the handler's bad request, as in the reference
+      xyws_accept_result r{};
+      static constexpr char bad[] = "\x01";
+      check(xyws_accept_request(bad, 1, max_request_, policy_, response_.data(), response_.size(), &r),
+            "xyws_accept_request");
+      resp_len_ = r.resp_len;
+    }
+    return response();
+  }
+  std::span<const std::byte> response() const {
+    return {reinterpret_cast<const std::byte*>(response_.data()), resp_len_};
+  }
+  std::string_view response_view() const { return {response_.data(), resp_len_}; }
+  std::span<const std::byte> bad_request_response() const {
+    static constexpr char bad[] = "HTTP/1.1 400 Bad Request\r\n";
+    return {reinterpret_cast<const std::byte*>(bad), sizeof(bad) - 1};
+  }
+  std::string_view get_path() const { return {req_ + res_.path_off, res_.path_len}; }
+  bool accepted() const { return (res_.status & XYWS_ACC_ACCEPTED) != 0; }
+  const xyws_accept_result& result() const { return res_; }
+
+ private:
+  int parse(const char* p, std::size_t n) {
+    req_ = p;
+    res_ = xyws_accept_result{};
+    check(xyws_accept_request(p, n, max_request_, policy_, response_.data(), response_.size(), &res_),
+          "xyws_accept_request");
+    resp_len_ = res_.resp_len;
+    if (res_.reason == XYWS_ACR_PARSE) return -1;
+    if (!res_.consumed) return -2;  // incomplete, or longer than max_request without an end
+    return static_cast<int>(res_.consumed);
+  }
+
+  std::uint32_t policy_, max_request_;
+  const char* req_ = "";
+  xyws_accept_result res_{};
+  std::array<char, 144> response_{};
+  std::size_t resp_len_ = 0;
+};
 
 // class websocket_frame_header (websocket_frame_header.h:179-224): a header in
 // a 14-byte array. As in the reference, the masked constructors keep the key

@@ -276,6 +276,26 @@ MSG_CONTINUED, MSG_UNCHECKED = 0x20, 0x40  # xyws_reassemble_stream only
 MSG_OVERFLOW = 0x80  # xyws_msg_carry.status, xyws_reassemble_streams only
 RSM_TRUNCATED, RSM_MSG_CAP, RSM_OVERFLOW, RSM_OPEN, RSM_UTF8_BAD = 0x1, 0x2, 0x4, 0x8, 0x10  # xyws_reasm_result.status
 
+
+class AcceptConn(C.Structure):
+    """xyws_accept_conn (include/xyws.h), 32 bytes: one connection still in HTTP state."""
+    _fields_ = [("buf", C.c_void_p), ("len", C.c_uint64), ("out", C.c_void_p), ("out_cap", C.c_uint64)]
+
+
+class AcceptResult(C.Structure):
+    """xyws_accept_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("status", C.c_uint32), ("http_status", C.c_uint16), ("reason", C.c_uint16),
+                ("consumed", C.c_uint32), ("resp_len", C.c_uint32), ("path_off", C.c_uint32),
+                ("path_len", C.c_uint32), ("key_off", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(AcceptConn) == 32 and C.sizeof(AcceptResult) == 32
+ACCEPT_MAX_REQUEST = 8192
+ACC_ACCEPTED, ACC_REJECTED, ACC_TRUNCATED = 0x1, 0x2, 0x4  # xyws_accept_result.status
+ACC_REFERENCE = 0x100  # xyws_accept_streams policy
+(ACR_NONE, ACR_PARSE, ACR_TOO_LONG, ACR_METHOD, ACR_VERSION, ACR_FOLDED, ACR_HOST, ACR_UPGRADE, ACR_CONNECTION,
+ ACR_KEY, ACR_WS_VERSION) = range(11)  # xyws_accept_result.reason
+
 _lib = None
 _tools = None
 
@@ -369,6 +389,17 @@ def load():
     # (no HIP call: members per tile of the fold, bytes per delivery step, grid cap, wave size)
     L.xyws_debug_backlog_geometry.restype = i32
     L.xyws_debug_backlog_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_accept_streams.restype = i32
+    L.xyws_accept_streams.argtypes = [vp, vp, u64, u32, u32, vp, vp]
+    # (host only: no context, no HIP call)
+    L.xyws_accept_request.restype = i32
+    L.xyws_accept_request.argtypes = [vp, u64, u32, u32, vp, u64, C.POINTER(AcceptResult)]
+    # (no HIP call: lanes per connection, LDS bytes per wave at the largest max_request, lines staged per step, grid cap)
+    L.xyws_debug_accept_geometry.restype = i32
+    L.xyws_debug_accept_geometry.argtypes = [C.POINTER(u64)]
+    # (no HIP call: xyws_accept_request over a host slab of n requests, on the calling thread)
+    L.xyws_debug_accept_host.restype = i32
+    L.xyws_debug_accept_host.argtypes = [vp, u64, u64, u64, u32, u32, vp, u64, u64, vp]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]

@@ -15,6 +15,11 @@ Names, argument meaning and error behaviour follow the reference headers
                                    (xyws_decode_streams: one coroutine's loop per wave)
   connection_group.reply           the rest of that loop for many connections at once: close policy,
                                    echo_once, websocket_send_close (xyws_reply_streams, one launch)
+  connection_group.accept          websocket_handshake (example/include/common/websocket.h:40-68) for many
+                                   connections at once: the HTTP upgrade parsed, checked and answered
+                                   (xyws_accept_streams, one launch)
+  websocket_request_handler        include/xynet/http/websocket_request_handler.h:66-264, one request on
+                                   the host (xyws_accept_request: the kernel's grammar compiled for the host)
   encode_frames                    echo_once's replies, batched on the device
                                    (example/websocket/websocket_echo.cpp:18-27)
   classify_frames                  websocket_check_parser_result's policy
@@ -26,7 +31,9 @@ Names, argument meaning and error behaviour follow the reference headers
 
 Device buffers are torch uint8 tensors on a ROCm device (PyTorch is used only
 for device memory and streams). Every computing call runs HIP kernels from
-libxyws.so through its C-ABI; there is no CPU fallback.
+libxyws.so through its C-ABI; there is no CPU fallback. The one host-only
+class is websocket_request_handler: one handshake request in host memory, by
+design (the batched path is connection_group.accept, on the device).
 """
 import ctypes as C
 import enum
@@ -344,6 +351,32 @@ class GroupReply:
         return [arr[j] for j in range(n)]
 
 
+class GroupAccept:
+    """Verdicts and responses of one connection_group.accept call, item k
+    being the k-th request of that call (host copies on demand). The call
+    keeps no state in the group: the rows and the table belong to this
+    object."""
+
+    def __init__(self, group, ids, outs, table_t, results_t):
+        self.group, self.ids, self.outs = group, ids, outs
+        self._table_t, self.results_t = table_t, results_t  # (the table stays alive until the call has run)
+        self._rows = None
+
+    def result(self, k):
+        """xyws_accept_result of item k."""
+        if self._rows is None:
+            self._rows = self.results_t.cpu().numpy().tobytes()
+        if not 0 <= k < len(self.outs):
+            raise IndexError(k)
+        return _lib.AcceptResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+
+    def response(self, k):
+        """The response bytes written to item k's send buffer (empty while its request is incomplete)."""
+        res = self.result(k)
+        n = min(res.resp_len, self.outs[k].numel())
+        return self.outs[k][:n].cpu().numpy().tobytes() if n else b""
+
+
 class GroupMessages:
     """Results and message records of one connection_group.reassemble call,
     item k as in the decode result it took (host copies on demand; valid until
@@ -575,6 +608,39 @@ class connection_group:
             self._done[k] = torch.cuda.Event()
             self._done[k].record(stream)
         return GroupResult(self, ids, k)
+
+    def accept(self, items, out_items, policy=0, max_request=1024):
+        """Answer the opening handshakes of the connections still in HTTP
+        state (xyws_accept_streams, one launch), before decode() sees them:
+        items[k] is the device uint8 tensor with every byte connection k has
+        sent so far (or a (conn_id, tensor) pair; the ids are only kept for
+        the caller), out_items[k] the device uint8 tensor that receives its
+        response (129 bytes always suffice). A whole request is checked by
+        RFC 6455 4.2.1 (policy 0) or as the reference's handler does
+        (ACC_REFERENCE) and answered; an incomplete one is reported as such:
+        call again with more bytes. The call keeps no state: on ACCEPTED the
+        bytes behind result(k).consumed are the connection's first decode()
+        input. Returns a GroupAccept."""
+        import torch
+        pairs = [it if isinstance(it, tuple) else (k, it) for k, it in enumerate(items)]
+        ids = [int(i) for i, _ in pairs]
+        bufs = [_dev_u8(t) for _, t in pairs]
+        outs = [_dev_u8(t) for t in out_items]
+        if len(outs) != len(bufs) or any(t.device != self.device for t in bufs + outs):
+            raise XywsError(-1, "one request and one send buffer on the group's device per item")
+        m = len(bufs)
+        host = torch.zeros(max(m, 1) * 4, dtype=torch.int64)
+        tab = host.numpy().reshape(-1, 4)  # xyws_accept_conn: buf, len, out, out_cap
+        for row, b, o in zip(tab, bufs, outs):
+            row[0], row[1], row[2], row[3] = b.data_ptr(), b.numel(), o.data_ptr(), o.numel()
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            table_t = host.to(self.device)
+            results_t = torch.zeros(max(m, 1) * 32, dtype=torch.uint8, device=self.device)
+            check(self.ctx.L.xyws_accept_streams(self.ctx.h, C.c_void_p(table_t.data_ptr()), m, int(max_request),
+                                                 int(policy), C.c_void_p(results_t.data_ptr()),
+                                                 C.c_void_p(stream.cuda_stream)), "xyws_accept_streams")
+        return GroupAccept(self, ids, outs, table_t, results_t)
 
     def reply_carry(self, conn_id):
         """Host copy of a connection's reply carry (synchronizes)."""
@@ -963,6 +1029,49 @@ class websocket_frame_header_parser:
 
 # ---------------------------------------------------------------------------
 # the callers either side of the decode path (xyws_frames.hip)
+
+class websocket_request_handler:
+    """class websocket_request_handler (websocket_request_handler.h:66-264)
+    over xyws_accept_request: host bytes only, no context and no device (the
+    kernel's grammar compiled for the host). parse() takes the accumulated
+    request and returns what the reference's does: the bytes consumed, -1 for
+    a grammar error, -2 while incomplete. generate_response() returns the 101
+    or, as there, the bad-request response for whatever was not a whole valid
+    request. The default policy is the reference's (ACC_REFERENCE); policy 0
+    answers by RFC 6455 4.2.1."""
+
+    def __init__(self, policy=_lib.ACC_REFERENCE, max_request=_lib.ACCEPT_MAX_REQUEST):
+        self.L = _lib.load()
+        self.policy, self.max_request = policy, max_request
+        self._req, self._res, self._resp = b"", _lib.AcceptResult(), b""
+
+    def _run(self, data):
+        res, out = _lib.AcceptResult(), (C.c_uint8 * 144)()
+        check(self.L.xyws_accept_request(data, len(data), self.max_request, self.policy, out, 144, C.byref(res)),
+              "xyws_accept_request")
+        return res, bytes(out[:res.resp_len])
+
+    def parse(self, data):
+        self._req = bytes(data)
+        self._res, self._resp = self._run(self._req)
+        if self._res.reason == _lib.ACR_PARSE:
+            return -1
+        return self._res.consumed if self._res.consumed else -2
+
+    def generate_response(self):
+        if not self._res.status & (_lib.ACC_ACCEPTED | _lib.ACC_REJECTED):
+            self._resp = self._run(b"\x01")[1]  # not parsed (never, or incomplete): the handler's bad request
+        return self._resp
+
+    def response_view(self):
+        return self._resp
+
+    def get_path(self):
+        return self._req[self._res.path_off:self._res.path_off + self._res.path_len]
+
+    def result(self):
+        return self._res
+
 
 def _opt_ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
