@@ -296,6 +296,45 @@ ACC_REFERENCE = 0x100  # xyws_accept_streams policy
 (ACR_NONE, ACR_PARSE, ACR_TOO_LONG, ACR_METHOD, ACR_VERSION, ACR_FOLDED, ACR_HOST, ACR_UPGRADE, ACR_CONNECTION,
  ACR_KEY, ACR_WS_VERSION) = range(11)  # xyws_accept_result.reason
 
+
+
+class Table:
+    """n rows of the ctypes structure `struct` (one of the row types above),
+    filled by field name (`t[k].out_cap = ...`) and uploaded as they are: over
+    `host`, the pinned tensor of a ring whose storage the rows then are, or
+    freshly allocated and zero. The structures are the only statement of a
+    row's layout in Python."""
+
+    def __init__(self, struct, n, host=None):
+        self.n, self.nbytes, self.host = n, C.sizeof(struct) * n, host
+        rows = struct * max(n, 1)
+        self.rows = rows() if host is None else rows.from_address(host.data_ptr())
+
+    def __getitem__(self, k):
+        return self.rows[k]
+
+    def upload(self, to):
+        """The table on the device. to: for a ring table its device tensor,
+        whose first n rows are overwritten from the pinned rows without
+        waiting; otherwise a device, where a new uint8 tensor of max(n, 1)
+        rows is made."""
+        import torch
+        if self.host is not None:
+            w = self.nbytes // self.host.element_size()
+            to[:w].copy_(self.host[:w], non_blocking=True)
+            return to
+        import numpy as np
+        return torch.from_numpy(np.frombuffer(self.rows, np.uint8)).to(to)
+
+
+def read_rows(struct, t, n, first=0):
+    """Host copies of rows first .. first + n - 1 of the device uint8 tensor t,
+    which holds rows of the ctypes structure `struct` (synchronizes)."""
+    size = C.sizeof(struct)
+    raw = t[size * first:size * (first + n)].cpu().numpy().tobytes() if n else b""
+    return [struct.from_buffer_copy(raw, size * k) for k in range(n)]
+
+
 _lib = None
 _tools = None
 

@@ -27,7 +27,7 @@ TARGETS = {
     "libxyws_tools.so": ["xyws_tools.hip"],
 }
 DEPS = ["xyws_device.h", "xyws_host.h", "xyws_stream.h", "xyws_ctx.h", "xyws_lattice.h", "xyws_frameops.h", "xyws_lines.h",
-        "xyws_room.h", "xyws_accept.h"]
+        "xyws_room.h", "xyws_accept.h", "xyws_rows.h"]
 
 
 def _stale(out, srcs):

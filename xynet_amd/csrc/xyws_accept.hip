@@ -30,6 +30,7 @@
 #include "xyws_ctx.h"
 #include "xyws_lines.h"
 #include "xyws_accept.h"
+#include "xyws_rows.h"
 
 #define ACCEPT_LANES 64u       // lanes per connection: one wave
 #define ACCEPT_LINE 16u        // bytes a lane stages or writes per step
@@ -74,9 +75,8 @@ __global__ void __launch_bounds__(ACCEPT_LANES) k_accept_streams(const xyws_acce
   uint8_t* const s_resp = s_mem + stage_bytes(max_request);
   const uint32_t lane = threadIdx.x;
   for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
-    const g_u64* const cq = (const g_u64*)(conns + ci);
-    const uint64_t buf = uniform64(cq[0]), len = uniform64(cq[1]);
-    const uint64_t out = uniform64(cq[2]), out_cap = uniform64(cq[3]);
+    const xyws_rows::accept_conn_row cq = xyws_rows::load_accept_conn(conns + ci);
+    const uint64_t buf = cq.buf, len = cq.len, out = cq.out, out_cap = cq.out_cap;
     const uint32_t E = len < max_request ? (uint32_t)len : max_request;
     const uint32_t lo = (uint32_t)(buf & 15u);
 
@@ -110,12 +110,9 @@ __global__ void __launch_bounds__(ACCEPT_LANES) k_accept_streams(const xyws_acce
       put_line(obase, A, s, e, olo, wlim, acc);
     }
     if (lane == 0 && results) {
-      g_u64* const res = (g_u64*)(results + ci);
       const uint32_t st = v.status | (resp_len > out_cap ? XYWS_ACC_TRUNCATED : 0u);
-      res[0] = (uint64_t)st | ((uint64_t)(v.http_status | (v.reason << 16)) << 32);
-      res[1] = (uint64_t)v.consumed | ((uint64_t)resp_len << 32);
-      res[2] = (uint64_t)v.path_off | ((uint64_t)v.path_len << 32);
-      res[3] = (uint64_t)v.key_off;
+      xyws_rows::store_accept_result(results + ci, {st, v.http_status, v.reason, v.consumed, resp_len, v.path_off,
+                                                    v.path_len, v.key_off});
     }
     __syncthreads();  // (LDS is rewritten by the next connection)
   }

@@ -2,7 +2,8 @@
 // log on the device and copied behind the send bytes of every connection that
 // joins (the reference's chat_room::m_recent_messages, deliver_recent_messages
 // and join, example/websocket/websocket_chat.cpp:34-47, 89-95). The semantics
-// are stated in include/xyws.h; this is how they are computed.
+// are stated in include/xyws.h; this is how they are computed. Every table row
+// is read and written through xyws_rows.h, which names its words.
 //
 // Two launches, the rooms' carries the hand-over between them. No workgroup
 // waits for another inside a launch, nothing spins, there are no atomics.
@@ -40,12 +41,13 @@
 #include "xyws_frameops.h"
 #include "xyws_lines.h"
 #include "xyws_room.h"
+#include "xyws_rows.h"
 
 #define BL_THREADS BC_WIRE_THREADS  // the fold: the one workgroup a room gets (block_scan's size)
 #define BL_TILE BL_THREADS          // members per tile of the fold: one per thread
-#define BL_CARRY_WORDS 24u          // sizeof(xyws_backlog_carry) / 8
 
 using namespace xyws_internal;
+namespace rows = xyws_rows;
 
 namespace {
 
@@ -57,52 +59,33 @@ __global__ void __launch_bounds__(BL_THREADS)
                    const xyws_bcast_conn* __restrict__ bconns, uint64_t n, const xyws_room* __restrict__ rooms,
                    const xyws_room_result* __restrict__ room_results, const xyws_backlog_room* __restrict__ brooms,
                    xyws_backlog_room_result* __restrict__ broom_results, uint64_t n_rooms) {
-  static_assert(sizeof(xyws_backlog_carry) == 8 * BL_CARRY_WORDS && sizeof(xyws_backlog_room) == 32 &&
-                    sizeof(xyws_backlog_room_result) == 32 && sizeof(xyws_backlog_conn) == 64 &&
-                    sizeof(xyws_backlog_result) == 32 && offsetof(xyws_backlog_carry, flen) == 32 &&
-                    offsetof(xyws_backlog_conn, room) == 32 && offsetof(xyws_backlog_room, keep) == 24 &&
-                    offsetof(xyws_bcast_result, status) == 16,
-                "layouts");
-  __shared__ uint64_t s_c[BL_CARRY_WORDS];      // the carry as read
+  __shared__ uint64_t s_c[rows::BLC_WORDS];     // the carry as read
   __shared__ uint64_t s_sz[XYWS_BACKLOG_MAX];   // sizes of the last min(keep, N) new frames, in wire order
   __shared__ uint64_t s_w[BL_THREADS / BC_WAVE];
   const uint32_t tid = threadIdx.x;
   for (uint64_t ri = blockIdx.x; ri < n_rooms; ri += gridDim.x) {
-    const g_u64* const rq = (const g_u64*)(rooms + ri);
-    const g_u64* const rr = (const g_u64*)(room_results + ri);
-    const g_u64* const lq = (const g_u64*)(brooms + ri);
-    g_u64* const res = broom_results ? (g_u64*)(broom_results + ri) : nullptr;
-    const uint64_t log = uniform64(lq[0]);
-    const uint64_t H = half_of(log, uniform64(lq[1]));
-    const uint64_t bc = uniform64(lq[2]);
-    uint32_t keep = uniform32((uint32_t)lq[3]);
+    xyws_backlog_room_result* const res = broom_results ? broom_results + ri : nullptr;
+    const rows::backlog_room_row lq = rows::load_backlog_room(brooms + ri);
+    const uint64_t log = lq.log, H = half_of(log, lq.log_cap), bc = lq.bc;
+    uint32_t keep = lq.keep;
     if (!log || !bc || !keep || !H) {  // pass-through: neither the log nor the carry is touched
-      if (res && tid == 0) {
-        res[0] = 0;
-        res[1] = 0;
-        res[2] = (uint64_t)XYWS_BL_PASSTHROUGH << 32;
-        res[3] = 0;
-      }
+      if (res && tid == 0) rows::store_backlog_room_result(res, 0, {0, 0}, {0, XYWS_BL_PASSTHROUGH});
       continue;
     }
     if (keep > XYWS_BACKLOG_MAX) keep = XYWS_BACKLOG_MAX;
-    if (tid < BL_CARRY_WORDS) s_c[tid] = ((const g_u64*)bc)[tid];
+    if (tid < rows::BLC_WORDS) s_c[tid] = ((const g_u64*)bc)[tid];
     if (tid < XYWS_BACKLOG_MAX) s_sz[tid] = 0;
     __syncthreads();
-    const uint64_t wire_len = uniform64(rr[0]);
-    const uint64_t N = uniform64(rr[1]) & 0xFFFFFFFFull;
-    const uint32_t rst = (uint32_t)(uniform64(rr[2]) >> 32);
-    uint64_t o_start = s_c[0], o_len = s_c[1];
-    uint32_t o_count = (uint32_t)s_c[2];
-    const uint32_t gaps = (uint32_t)(s_c[2] >> 32);
-    const uint64_t total = s_c[3];
+    const rows::room_result_row rr = rows::load_room_result(room_results + ri);
+    const uint64_t wire_len = rr.wire_len, N = rr.nmsgs;
+    const uint32_t rst = rr.status;
+    const rows::backlog_counts oc = rows::unpack_backlog_counts(s_c[rows::BLC_COUNTS]);
+    uint64_t o_start = s_c[rows::BLC_START], o_len = s_c[rows::BLC_LEN];
+    uint32_t o_count = oc.count;
+    const uint32_t gaps = oc.gaps;
+    const uint64_t total = s_c[rows::BLC_TOTAL];
     if (N == 0) {  // 1. no new message: the carry and the log stay, the row reports them
-      if (res && tid == 0) {
-        res[0] = o_len;
-        res[1] = o_count;
-        res[2] = 0;
-        res[3] = 0;
-      }
+      if (res && tid == 0) rows::store_backlog_room_result(res, o_len, {o_count, 0}, {0, 0});
       __syncthreads();  // (s_c is rewritten by the next room)
       continue;
     }
@@ -110,17 +93,15 @@ __global__ void __launch_bounds__(BL_THREADS)
     {  // 2. the carry
       bool valid = (o_start == 0 || o_start == H) && o_len <= H && o_count <= XYWS_BACKLOG_MAX;
       uint64_t sum = 0;
-      for (uint32_t j = 0; valid && j < o_count; j++) sum = sat_add(sum, s_c[4 + j]);
+      for (uint32_t j = 0; valid && j < o_count; j++) sum = sat_add(sum, s_c[rows::BLC_FLEN + j]);
       if (!valid || sum != o_len) {
         st |= XYWS_BL_BAD_CARRY;
         o_start = o_len = 0;
         o_count = 0;
       }
     }
-    const uint64_t members = uniform64(rq[0]);
-    const uint64_t nm = members ? uniform64(rq[1]) : 0;
-    const uint64_t wire = uniform64(rq[2]);
-    const uint64_t wire_cap = wire ? uniform64(rq[3]) : 0;
+    const rows::room_row rq = rows::load_room(rooms + ri);
+    const uint64_t members = rq.members, nm = rq.n_members, wire = rq.wire, wire_cap = rq.wire_cap;
     const uint64_t K = N < keep ? N : keep;  // slots in use
 
     // 3. the new frames, counted and sized from the tables
@@ -136,7 +117,7 @@ __global__ void __launch_bounds__(BL_THREADS)
 #pragma unroll 1
           for (uint32_t r = 0; r < m.stored; r++) {
             frame_info f;
-            if (frame_of((const g_u64*)(m.msgs + 40ull * r), m, 0, 0, f)) {
+            if (frame_of(rows::row_at<const xyws_message>(m.msgs, r), m, 0, 0, f)) {
               size += f.h + m.head_len + f.len;
               cnt++;
             }
@@ -151,7 +132,7 @@ __global__ void __launch_bounds__(BL_THREADS)
 #pragma unroll 1
         for (uint32_t r = 0; r < m.stored; r++) {
           frame_info f;
-          if (!frame_of((const g_u64*)(m.msgs + 40ull * r), m, 0, 0, f)) continue;
+          if (!frame_of(rows::row_at<const xyws_message>(m.msgs, r), m, 0, 0, f)) continue;
           if (idx >= N - K && idx < N) s_sz[idx - (N - K)] = f.h + m.head_len + f.len;
           idx++;
         }
@@ -191,7 +172,7 @@ __global__ void __launch_bounds__(BL_THREADS)
       }
       if (K < N) stop = true;  // (K == keep frames are taken, or the walk ended above)
       for (uint32_t j = o_count; j-- > 0 && !stop;) {
-        const uint64_t sz = s_c[4 + j];
+        const uint64_t sz = s_c[rows::BLC_FLEN + j];
         if (taken >= keep) {
           stop = true;
         } else if (sz > H - bytes) {
@@ -232,25 +213,20 @@ __global__ void __launch_bounds__(BL_THREADS)
     }
 
     // 7. the carry after the fold
-    if (tid < BL_CARRY_WORDS) {
+    if (tid < rows::BLC_WORDS) {  // (one word per thread, the reserved ones zero)
       uint64_t w = 0;
-      if (tid == 0) w = target;
-      else if (tid == 1) w = T;
-      else if (tid == 2) w = (uint64_t)count | ((uint64_t)(gaps + (gap ? 1u : 0u)) << 32);
-      else if (tid == 3) w = total + n_new;
-      else if (tid < 4 + XYWS_BACKLOG_MAX) {
-        const uint32_t i = tid - 4;
-        if (i < n_old) w = s_c[4 + (o_count - n_old) + i];
+      if (tid == rows::BLC_START) w = target;
+      else if (tid == rows::BLC_LEN) w = T;
+      else if (tid == rows::BLC_COUNTS) w = rows::pack_backlog_counts({count, gaps + (gap ? 1u : 0u)});
+      else if (tid == rows::BLC_TOTAL) w = total + n_new;
+      else if (tid >= rows::BLC_FLEN && tid < rows::BLC_FLEN + XYWS_BACKLOG_MAX) {
+        const uint32_t i = tid - rows::BLC_FLEN;
+        if (i < n_old) w = s_c[rows::BLC_FLEN + (o_count - n_old) + i];
         else if (i < count) w = s_sz[(uint32_t)K - n_new + (i - n_old)];
       }
       ((g_u64*)bc)[tid] = w;
     }
-    if (res && tid == 0) {
-      res[0] = T;
-      res[1] = (uint64_t)count | ((uint64_t)n_new << 32);
-      res[2] = (uint64_t)dropped | ((uint64_t)st << 32);
-      res[3] = 0;
-    }
+    if (res && tid == 0) rows::store_backlog_room_result(res, T, {count, n_new}, {dropped, st});
     __syncthreads();  // (s_c and s_sz are rewritten by the next room)
   }
 }
@@ -261,23 +237,20 @@ __global__ void __launch_bounds__(BC_THREADS)
                       xyws_backlog_result* __restrict__ results) {
   const uint32_t tid = threadIdx.x;
   for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
-    const g_u64* const jq = (const g_u64*)(jconns + ci);
-    const uint64_t out = uniform64(jq[0]);
-    const uint64_t out_cap = out ? uniform64(jq[1]) : 0;
-    const g_u64* const bp = (const g_u64*)uniform64(jq[2]);
-    const g_u64* const rp = (const g_u64*)uniform64(jq[3]);
-    const uint64_t rf = uniform64(jq[4]);
-    const uint64_t room = rf & 0xFFFFFFFFull;
-    const uint32_t fl = (uint32_t)(rf >> 32);
+    const rows::backlog_conn_row jq = rows::load_backlog_conn(jconns + ci);
+    const uint64_t out = jq.out, out_cap = jq.out_cap, room = jq.join.room;
+    const uint32_t fl = jq.join.flags;
     uint64_t base = 0;
     bool receiver = true;
-    if (rp) {
-      base = uniform64(rp[0]);
-      if ((uint32_t)(uniform64(rp[2]) >> 48) & (XYWS_RPL_CLOSED | XYWS_RPL_OVERFLOW)) receiver = false;
+    if (jq.reply) {
+      const rows::reply_result_row rp = rows::load_reply_result<true>((const xyws_reply_result*)jq.reply);
+      base = rp.reply_len;
+      if (rp.status & (XYWS_RPL_CLOSED | XYWS_RPL_OVERFLOW)) receiver = false;
     }
-    if (bp) {
-      base = uniform64(bp[0]);
-      if ((uint32_t)uniform64(bp[2]) & XYWS_BC_NOT_RECEIVER) receiver = false;
+    if (jq.bcast) {
+      const rows::bcast_result_row bp = rows::load_bcast_result((const xyws_bcast_result*)jq.bcast);
+      base = bp.send_len;
+      if (bp.status & XYWS_BC_NOT_RECEIVER) receiver = false;
     }
     uint32_t st = 0;
     uint64_t w = 0, src = 0;
@@ -285,19 +258,19 @@ __global__ void __launch_bounds__(BC_THREADS)
       uint64_t log = 0, H = 0, bc = 0;
       uint32_t keep = 0;
       if (room < n_rooms) {
-        const g_u64* const lq = (const g_u64*)(brooms + room);
-        log = uniform64(lq[0]);
-        H = half_of(log, uniform64(lq[1]));
-        bc = uniform64(lq[2]);
-        keep = uniform32((uint32_t)lq[3]);
+        const rows::backlog_room_row lq = rows::load_backlog_room(brooms + room);
+        log = lq.log;
+        H = half_of(log, lq.log_cap);
+        bc = lq.bc;
+        keep = lq.keep;
       }
       if (!log || !bc || !keep || !H) {  // no such room, or a pass-through room
         st = XYWS_BLC_NO_ROOM;
       } else if (!receiver) {
         st = XYWS_BLC_NOT_RECEIVER;
       } else {
-        const g_u64* const cq = (const g_u64*)bc;
-        const uint64_t start = uniform64(cq[0]), len = uniform64(cq[1]);
+        const rows::backlog_span cq = rows::load_backlog_span((const xyws_backlog_carry*)bc);
+        const uint64_t start = cq.start, len = cq.len;
         if ((start == 0 || start == H) && len <= H) w = len;  // (another carry names nothing readable)
         src = log + start;
         st = XYWS_BLC_JOINED;
@@ -306,11 +279,7 @@ __global__ void __launch_bounds__(BC_THREADS)
     const uint64_t send_len = sat_add(base, w);
     if ((st & XYWS_BLC_JOINED) && send_len > out_cap) st |= XYWS_BLC_TRUNCATED;
     if (results && blockIdx.y == 0 && tid == 0) {
-      g_u64* const res = (g_u64*)(results + ci);
-      res[0] = send_len;
-      res[1] = w;
-      res[2] = st;
-      res[3] = 0;
+      rows::store_backlog_result(results + ci, send_len, w, st);
     }
     if (!w || base >= out_cap) continue;
 

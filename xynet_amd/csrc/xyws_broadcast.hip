@@ -3,7 +3,8 @@
 // chat_room::deliver and chat_session::writer,
 // example/websocket/websocket_chat.cpp:89-101, 148-175, run once per message
 // and member). The semantics are stated in include/xyws.h; this is how they
-// are computed.
+// are computed. Every table row is read and written through xyws_rows.h, which
+// names its words.
 //
 // Two launches, the room result rows the hand-over between them. No workgroup
 // waits for another inside a launch, nothing spins, there are no atomics.
@@ -40,10 +41,12 @@
 #include "xyws_frameops.h"
 #include "xyws_lines.h"
 #include "xyws_room.h"
+#include "xyws_rows.h"
 
 #define BC_TILE BC_WIRE_THREADS  // members per tile of the wire build: one per thread
 
 using namespace xyws_internal;
+namespace rows = xyws_rows;
 
 namespace {
 
@@ -51,10 +54,6 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
     k_room_wire(const xyws_reasm_conn* __restrict__ reasm, const xyws_reasm_result* __restrict__ rres,
                 const xyws_bcast_conn* __restrict__ bconns, uint64_t n, const xyws_room* __restrict__ rooms,
                 xyws_room_result* __restrict__ room_results, uint64_t n_rooms, uint32_t flags, uint32_t enc_opts) {
-  static_assert(sizeof(xyws_room) == 32 && sizeof(xyws_room_result) == 32 && sizeof(xyws_bcast_conn) == 64 &&
-                    sizeof(xyws_bcast_result) == 32 && sizeof(xyws_reply_result) == 32 &&
-                    offsetof(xyws_reply_result, status) == 22 && offsetof(xyws_bcast_conn, room) == 40,
-                "layouts");
   __shared__ uint64_t s_off[BC_TILE + 1];  // members: start in the wire (and the end after the last)
   __shared__ uint64_t s_msgs[BC_TILE], s_gate[BC_TILE], s_out[BC_TILE], s_ocap[BC_TILE], s_head[BC_TILE],
       s_hlen[BC_TILE];
@@ -62,11 +61,8 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
   __shared__ uint64_t s_w[BC_WIRE_THREADS / BC_WAVE];
   const uint32_t tid = threadIdx.x;
   for (uint64_t ri = blockIdx.x; ri < n_rooms; ri += gridDim.x) {
-    const g_u64* const rq = (const g_u64*)(rooms + ri);
-    const uint64_t members = uniform64(rq[0]);
-    const uint64_t nm = members ? uniform64(rq[1]) : 0;
-    const uint64_t wire = uniform64(rq[2]);
-    const uint64_t wire_cap = wire ? uniform64(rq[3]) : 0;
+    const rows::room_row rq = rows::load_room(rooms + ri);
+    const uint64_t members = rq.members, nm = rq.n_members, wire = rq.wire, wire_cap = rq.wire_cap;
     g_u8* const wbase = (g_u8*)(wire & ~15ull);
     const uint64_t wlo = wire & 15u;
     const uint64_t wlim = sat_add(wlo, wire_cap);
@@ -89,7 +85,7 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
 #pragma unroll 1
           for (uint32_t r = 0; r < m.stored; r++) {
             frame_info f;
-            if (frame_of((const g_u64*)(m.msgs + 40ull * r), m, flags, enc_opts, f)) {
+            if (frame_of(rows::row_at<const xyws_message>(m.msgs, r), m, flags, enc_opts, f)) {
               size += f.h + m.head_len + f.len;
               c_msgs++;
             } else {
@@ -137,7 +133,7 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
 #pragma unroll 1
             for (uint32_t r = 0; r < k.stored && a < ae; r++) {
               frame_info f;
-              if (!frame_of((const g_u64*)(k.msgs + 40ull * r), k, flags, enc_opts, f)) continue;
+              if (!frame_of(rows::row_at<const xyws_message>(k.msgs, r), k, flags, enc_opts, f)) continue;
               const uint64_t fsz = f.h + k.head_len + f.len;
               if (fo + fsz > q) {
                 uint64_t rr = q - fo;
@@ -172,7 +168,7 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
 
     // the result row: the threads' counts summed
     uint64_t t0, t1;
-    block_scan((uint64_t)c_msgs | ((uint64_t)c_skip << 32), tid, s_w, t0);
+    block_scan(rows::pack_room_counts({c_msgs, c_skip}), tid, s_w, t0);  // (both counts summed as one word)
     block_scan((uint64_t)c_recv, tid, s_w, t1);
     uint32_t st = c_st;
 #pragma unroll
@@ -183,11 +179,7 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
       st = 0;
       for (uint32_t w = 0; w < BC_WIRE_THREADS / BC_WAVE; w++) st |= (uint32_t)s_w[w];
       if (wpos > wire_cap) st |= XYWS_ROOM_TRUNCATED;
-      g_u64* const res = (g_u64*)(room_results + ri);
-      res[0] = wpos;
-      res[1] = t0;  // nmsgs | skipped << 32
-      res[2] = (t1 & 0xFFFFFFFFull) | ((uint64_t)st << 32);
-      res[3] = 0;
+      rows::store_room_result(room_results + ri, wpos, t0, {(uint32_t)t1, st});
     }
     __syncthreads();  // (s_w is reused by the next room)
   }
@@ -199,16 +191,14 @@ __global__ void __launch_bounds__(BC_THREADS) k_room_fanout(const xyws_bcast_con
                                                             uint64_t n_rooms, xyws_bcast_result* __restrict__ results) {
   const uint32_t tid = threadIdx.x;
   for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
-    const g_u64* const bq = (const g_u64*)(bconns + ci);
-    const uint64_t out = uniform64(bq[2]);
-    const uint64_t out_cap = out ? uniform64(bq[3]) : 0;
-    const g_u64* const rp = (const g_u64*)uniform64(bq[4]);
-    const uint64_t room = uniform64(bq[5]) & 0xFFFFFFFFull;
+    const rows::bcast_conn_row bq = rows::load_bcast_conn<true>(bconns + ci);
+    const uint64_t out = bq.out, out_cap = bq.out_cap, room = bq.room;
     uint64_t base = 0;
     uint32_t pst = 0;
-    if (rp) {
-      base = uniform64(rp[0]);
-      pst = (uint32_t)(uniform64(rp[2]) >> 48);
+    if (bq.reply) {
+      const rows::reply_result_row rp = rows::load_reply_result<true>((const xyws_reply_result*)bq.reply);
+      base = rp.reply_len;
+      pst = rp.status;
     }
     uint32_t st = 0;
     uint64_t w = 0, wire = 0;
@@ -217,20 +207,15 @@ __global__ void __launch_bounds__(BC_THREADS) k_room_fanout(const xyws_bcast_con
     } else if (pst & (XYWS_RPL_CLOSED | XYWS_RPL_OVERFLOW)) {
       st = XYWS_BC_NOT_RECEIVER;
     } else {
-      const g_u64* const rq = (const g_u64*)(rooms + room);
-      wire = uniform64(rq[2]);
-      const uint64_t wire_cap = wire ? uniform64(rq[3]) : 0;
-      const uint64_t wire_len = uniform64(((const g_u64*)(room_results + room))[0]);
+      const rows::room_row rq = rows::load_room(rooms + room);
+      wire = rq.wire;
+      const uint64_t wire_cap = rq.wire_cap, wire_len = rows::load_room_result(room_results + room).wire_len;
       w = wire_len < wire_cap ? wire_len : wire_cap;
     }
     const uint64_t send_len = sat_add(base, w);
     if (send_len > out_cap) st |= XYWS_BC_TRUNCATED;
     if (results && blockIdx.y == 0 && tid == 0) {
-      g_u64* const res = (g_u64*)(results + ci);
-      res[0] = send_len;
-      res[1] = w;
-      res[2] = st;
-      res[3] = 0;
+      rows::store_bcast_result(results + ci, send_len, w, st);
     }
     if (!w || base >= out_cap) continue;
 

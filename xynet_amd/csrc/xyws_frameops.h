@@ -134,5 +134,15 @@ XYWS_DEV uint64_t shfl_up64(uint64_t v, uint32_t d) {
   return (uint64_t)(uint32_t)__shfl_up((int)(uint32_t)v, d) |
          ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d) << 32);
 }
+// Inclusive scan of v across the 64 lanes of a wave.
+XYWS_DEV uint64_t wave_scan64(uint64_t v, uint32_t lane) {
+  uint64_t incl = v;
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint64_t o = shfl_up64(incl, d);
+    if (lane >= d) incl += o;
+  }
+  return incl;
+}
 
 }  // namespace xyws_internal

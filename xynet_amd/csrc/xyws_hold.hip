@@ -3,7 +3,8 @@
 // sweep that completes it (the reference's chat session reads a message to
 // its end before chat_room::deliver, example/websocket/websocket_chat.cpp:
 // 177-200). The semantics are stated in include/xyws.h; this is how they are
-// computed.
+// computed. Every table row is read and written through xyws_rows.h, which
+// names its words.
 //
 // As in k_reply_streams and k_reasm_streams one wave (a 64-thread workgroup)
 // takes one connection, connections are grid-strided, no workgroup talks to
@@ -28,6 +29,7 @@
 #include "xyws_ctx.h"
 #include "xyws_frameops.h"
 #include "xyws_lines.h"
+#include "xyws_rows.h"
 
 #define HOLD_LANES 64u      // lanes per connection: one wave
 #define HOLD_LINE 16u       // bytes a lane writes per copy step
@@ -35,6 +37,7 @@
 #define HOLD_GRID_CAP 8192u // 256 CUs x 32 one-wave workgroups; further connections are grid-strided
 
 using namespace xyws_internal;
+namespace rows = xyws_rows;
 
 namespace {
 
@@ -48,53 +51,43 @@ __global__ void __launch_bounds__(HOLD_LANES)
     k_hold_streams(const xyws_reasm_conn* __restrict__ reasm, const xyws_reasm_result* __restrict__ rres,
                    const xyws_hold_conn* __restrict__ hold, uint64_t n, xyws_reasm_conn* __restrict__ view,
                    xyws_reasm_result* __restrict__ vres, xyws_hold_result* __restrict__ results) {
-  static_assert(sizeof(xyws_hold_conn) == 32 && sizeof(xyws_hold_carry) == 32 && sizeof(xyws_hold_result) == 32 &&
-                    offsetof(xyws_hold_conn, hc) == 8 && offsetof(xyws_hold_conn, vmsgs) == 16 &&
-                    offsetof(xyws_hold_conn, vmsg_cap) == 24 && offsetof(xyws_hold_carry, held) == 8 &&
-                    offsetof(xyws_hold_carry, nframes) == 16 && offsetof(xyws_hold_carry, status) == 24 &&
-                    offsetof(xyws_hold_carry, opcode) == 28 && offsetof(xyws_hold_result, delivered_len) == 8 &&
-                    offsetof(xyws_hold_result, status) == 16 && sizeof(xyws_message) == 40 &&
-                    offsetof(xyws_message, status) == 32 && offsetof(xyws_message, opcode) == 36 &&
-                    sizeof(xyws_reasm_conn) == 64 && sizeof(xyws_reasm_result) == 32 &&
-                    offsetof(xyws_reasm_result, status) == 20,
-                "layouts");
   const uint32_t lane = threadIdx.x;
   for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
-    const g_u64* const rq = (const g_u64*)(reasm + ci);
-    const g_u64* const ar = (const g_u64*)(rres + ci);
-    const g_u64* const hq = (const g_u64*)(hold + ci);
-    g_u64* const vq = (g_u64*)(view + ci);
-    g_u64* const vr = (g_u64*)(vres + ci);
-    g_u64* const res = results ? (g_u64*)(results + ci) : nullptr;
-    const uint64_t out = uniform64(rq[0]);
-    const uint64_t hold_cap = uniform64(hq[0]);
-    g_u64* const hc = (g_u64*)uniform64(hq[1]);
+    // (each row named once: with `view + ci` spelled at both of its uses the per-lane addresses of the
+    // pass-through are hoisted out of this loop, and the kernel takes 75 VGPRs for 71: 6 waves for 7)
+    const xyws_reasm_conn* const rp = reasm + ci;
+    const xyws_reasm_result* const ap = rres + ci;
+    const xyws_hold_conn* const hp = hold + ci;
+    xyws_reasm_conn* const vq = view + ci;
+    xyws_reasm_result* const vr = vres + ci;
+    xyws_hold_result* const res = results ? results + ci : nullptr;
+    const rows::reasm_conn_row rq = rows::load_reasm_conn<true>(rp);
+    const rows::hold_conn_row hq = rows::load_hold_conn(hp);
+    const uint64_t out = rq.out, hold_cap = hq.hold_cap;
+    xyws_hold_carry* const hc = (xyws_hold_carry*)hq.hc;
     const uint64_t H = (hold_cap / 2) & ~15ull;
 
     // 0. pass-through: the inputs verbatim
     if (!out || !hc || !H) {
-      if (lane < 8) vq[lane] = rq[lane];
-      if (lane < 4) vr[lane] = ar[lane];
-      if (res && lane < 4) res[lane] = lane == 2 ? (uint64_t)XYWS_HOLD_PASSTHROUGH : 0;
+      rows::copy_row(vq, rp, lane);
+      rows::copy_row(vr, ap, lane);
+      if (res) rows::store_hold_status(res, XYWS_HOLD_PASSTHROUGH, lane);
       continue;
     }
 
-    const uint64_t out_cap = uniform64(rq[1]);
-    const uint64_t mcp = uniform64(rq[2]);
-    const uint64_t msgs = uniform64(rq[3]);
-    const uint64_t msg_cap = msgs ? uniform64(rq[4]) : 0;
-    const uint64_t a0 = uniform64(ar[0]), nmsgs = uniform64(ar[1]), a2 = uniform64(ar[2]), a3 = uniform64(ar[3]);
-    const uint32_t rst = (uint32_t)(a2 >> 32);
-    const uint64_t vmsgs = uniform64(hq[2]);
-    const uint64_t vmsg_cap = vmsgs ? uniform64(hq[3]) : 0;
+    const uint64_t out_cap = rq.out_cap, msgs = rq.msgs, msg_cap = rq.msg_cap;
+    const rows::reasm_result_row ar = rows::load_reasm_result<true>(ap);
+    const uint64_t nmsgs = ar.nmsgs;
+    const uint32_t rst = ar.counts.status;
+    const uint64_t vmsgs = hq.vmsgs, vmsg_cap = hq.vmsg_cap;
     const uint64_t s = nmsgs < msg_cap ? nmsgs : msg_cap;
     const uint64_t vs = s < vmsg_cap ? s : vmsg_cap;
     const uint64_t hbase = out - hold_cap;
 
     // the carry, canonical: without ACTIVE only the LOST bit counts
-    uint64_t c_start = uniform64(hc[0]), c_held = uniform64(hc[1]), c_nfr = uniform64(hc[2]);
-    const uint64_t c3 = uniform64(hc[3]);
-    uint32_t c_st = (uint32_t)c3, c_op = (uint32_t)(c3 >> 32) & 0xFFu;
+    const rows::hold_carry_row c = rows::load_hold_carry(hc);
+    uint64_t c_start = c.start, c_held = c.held, c_nfr = c.nframes;
+    uint32_t c_st = c.state.status, c_op = c.state.opcode;
     if (c_st & XYWS_HOLD_ACTIVE) {
       c_st = XYWS_HOLD_ACTIVE;
     } else {
@@ -123,15 +116,10 @@ __global__ void __launch_bounds__(HOLD_LANES)
       if (c_st & XYWS_HOLD_ACTIVE) st |= XYWS_HOLD_DROPPED;
       lose();
     } else {
-      uint64_t r0n = 0, r0o = 0, r0l = 0, r0w = 0;  // record 0: nframes, out_off, length, status | opcode << 32
-      if (s) {
-        const g_u64* const rec = (const g_u64*)msgs;
-        r0n = uniform64(rec[1]);
-        r0o = uniform64(rec[2]);
-        r0l = uniform64(rec[3]);
-        r0w = uniform64(rec[4]);
-      }
-      const uint32_t r0s = (uint32_t)r0w;
+      rows::message_row r0 = {0, 0, 0, 0, 0};  // record 0
+      if (s) r0 = rows::load_message<true>(rows::row_at<const xyws_message>(msgs, 0));
+      const uint64_t r0n = r0.nframes, r0o = r0.out_off, r0l = r0.length;
+      const uint32_t r0s = rows::unpack_message_meta(r0.meta).status;
       const bool has0 = s && (r0s & XYWS_MSG_CONTINUED);
       if ((c_st & XYWS_HOLD_ACTIVE) && !has0) {  // 5.: its record was not stored
         st |= XYWS_HOLD_DROPPED;
@@ -163,7 +151,7 @@ __global__ void __launch_bounds__(HOLD_LANES)
             d_start = c_start;
             d_len = c_held;
             d_nfr = c_nfr;
-            d_w4 = (uint64_t)(r0s & ~XYWS_MSG_CONTINUED) | ((uint64_t)c_op << 32);
+            d_w4 = rows::pack_message_meta({r0s & ~XYWS_MSG_CONTINUED, c_op});
             st |= XYWS_HOLD_DELIVERED;
           }
           clear();
@@ -173,15 +161,11 @@ __global__ void __launch_bounds__(HOLD_LANES)
       }
       // 4. the message open at the end
       if ((rst & XYWS_RSM_OPEN) && nmsgs && nmsgs - 1 < s) {
-        uint64_t ln = r0n, lo = r0o, ll = r0l, lw = r0w;
-        if (nmsgs > 1) {
-          const g_u64* const rec = (const g_u64*)(msgs + 40ull * (nmsgs - 1));
-          ln = uniform64(rec[1]);
-          lo = uniform64(rec[2]);
-          ll = uniform64(rec[3]);
-          lw = uniform64(rec[4]);
-        }
-        const uint32_t ls = (uint32_t)lw;
+        rows::message_row rl = r0;  // the last record
+        if (nmsgs > 1) rl = rows::load_message<true>(rows::row_at<const xyws_message>(msgs, nmsgs - 1));
+        const uint64_t ln = rl.nframes, lo = rl.out_off, ll = rl.length;
+        const rows::message_meta lm = rows::unpack_message_meta(rl.meta);
+        const uint32_t ls = lm.status;
         if (!(ls & (XYWS_MSG_CONTINUED | XYWS_MSG_COMPLETE | XYWS_MSG_INTERRUPTED))) {
           if ((ls & XYWS_MSG_TRUNCATED) || !in_range(lo, ll, out_cap)) {
             st |= XYWS_HOLD_DROPPED;
@@ -198,7 +182,7 @@ __global__ void __launch_bounds__(HOLD_LANES)
             c_start = target;
             c_held = ll;
             c_nfr = ln;
-            c_op = (uint32_t)(lw >> 32) & 0xFFu;
+            c_op = lm.opcode;
           }
         }
       }
@@ -219,45 +203,19 @@ __global__ void __launch_bounds__(HOLD_LANES)
 
     // 3. the record row
     for (uint64_t j = lane; j < vs; j += HOLD_LANES) {
-      const g_u64* const rec = (const g_u64*)(msgs + 40ull * j);
-      g_u64* const vrec = (g_u64*)(vmsgs + 40ull * j);
-      uint64_t w0 = rec[0], w1 = rec[1], w2 = rec[2] + hold_cap, w3 = rec[3], w4 = rec[4];
-      if (j == 0 && delivered) {
-        w0 = 0;
-        w1 = d_nfr;
-        w2 = d_start;
-        w3 = d_len;
-        w4 = d_w4;
-      }
-      vrec[0] = w0;
-      vrec[1] = w1;
-      vrec[2] = w2;
-      vrec[3] = w3;
-      vrec[4] = w4;
+      rows::message_row rec = rows::load_message<false>(rows::row_at<const xyws_message>(msgs, j));
+      rec.out_off += hold_cap;
+      if (j == 0 && delivered) rec = {0, d_nfr, d_start, d_len, d_w4};
+      rows::store_message(rows::row_at<xyws_message>(vmsgs, j), rec);
     }
 
     // 4. the carry, the view entry, the view row, the result
     if (lane == 0) {
-      hc[0] = c_start;
-      hc[1] = c_held;
-      hc[2] = c_nfr;
-      hc[3] = (uint64_t)c_st | ((uint64_t)c_op << 32);
-      vq[0] = hbase;
-      vq[1] = hold_cap + out_cap;
-      vq[2] = mcp;
-      vq[3] = vmsgs;
-      vq[4] = msg_cap < vmsg_cap ? msg_cap : vmsg_cap;
-      vq[5] = vq[6] = vq[7] = 0;
-      vr[0] = a0;
-      vr[1] = nmsgs;
-      vr[2] = a2 | (s > vmsg_cap ? (uint64_t)XYWS_RSM_MSG_CAP << 32 : 0);
-      vr[3] = a3;
-      if (res) {
-        res[0] = c_held;
-        res[1] = delivered ? d_len : 0;
-        res[2] = st | (c_st & (XYWS_HOLD_ACTIVE | XYWS_HOLD_LOST));
-        res[3] = 0;
-      }
+      rows::store_hold_carry(hc, {c_start, c_held, c_nfr, {c_st, c_op}});
+      rows::store_reasm_conn(vq, {hbase, hold_cap + out_cap, rq.mc, vmsgs, msg_cap < vmsg_cap ? msg_cap : vmsg_cap});
+      rows::store_reasm_result(vr, {ar.out_len, nmsgs, {ar.counts.completed, rst | (s > vmsg_cap ? XYWS_RSM_MSG_CAP : 0u)},
+                                           ar.reserved});
+      if (res) rows::store_hold_result(res, c_held, delivered ? d_len : 0, st | (c_st & (XYWS_HOLD_ACTIVE | XYWS_HOLD_LOST)));
     }
   }
 }

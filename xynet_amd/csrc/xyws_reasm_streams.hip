@@ -3,7 +3,8 @@
 // reference's chat server does once per connection and sweep,
 // example/websocket/websocket_chat.cpp:177-200). The semantics are those of
 // xyws_reassemble_stream per connection, stated in include/xyws.h; this is how
-// they are computed.
+// they are computed. Every table row is read and written through xyws_rows.h,
+// which names its words.
 //
 // As in k_reply_streams (xyws_reply.hip) one wave (a 64-thread workgroup)
 // takes one connection, connections are grid-strided, no workgroup talks to
@@ -40,6 +41,7 @@
 #include "xyws_ctx.h"
 #include "xyws_frameops.h"
 #include "xyws_lines.h"
+#include "xyws_rows.h"
 
 #define RSM_TILE 64u       // frames per tile: one per lane
 #define RSM_LANES 64u      // lanes per connection: one wave
@@ -53,6 +55,7 @@
 #define SEG_PL_SHIFT 4u   // bytes of the carried UTF-8 tail before its first byte
 
 using namespace xyws_internal;
+namespace rows = xyws_rows;
 
 namespace {
 
@@ -191,10 +194,6 @@ __global__ void __launch_bounds__(RSM_LANES) k_reasm_streams(const xyws_conn* __
                                                              const uint64_t* __restrict__ nframes,
                                                              const xyws_reasm_conn* __restrict__ reasm, uint64_t n,
                                                              uint32_t opts, xyws_reasm_result* __restrict__ results) {
-  static_assert(sizeof(xyws_msg_carry) == 64 && offsetof(xyws_msg_carry, status) == 40 &&
-                    offsetof(xyws_msg_carry, utf8) == 47 && sizeof(xyws_message) == 40 &&
-                    sizeof(xyws_reasm_conn) == 64 && sizeof(xyws_reasm_result) == 32,
-                "layouts");
   __shared__ uint64_t s_off[RSM_ITEMS + 1];   // items: start in out (and the end after the last)
   __shared__ uint64_t s_soff[RSM_ITEMS];      //        source offset
   __shared__ uint64_t s_sstart[RSM_SEGS + 1]; // segments: start in out (unused ones and the end: o1)
@@ -205,42 +204,24 @@ __global__ void __launch_bounds__(RSM_LANES) k_reasm_streams(const xyws_conn* __
   const uint32_t lane = threadIdx.x;
   const uint64_t lbit = 1ull << lane, lbelow = lbit - 1ull;
   for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
-    const g_u64* const cq = (const g_u64*)(conns + ci);
-    const uint64_t buf = uniform64(cq[0]), len = uniform64(cq[1]);
-    const uint64_t frames = uniform64(cq[3]), cap = uniform64(cq[4]);
+    const rows::conn_row cn = rows::load_conn(conns + ci);
+    const uint64_t buf = cn.buf, len = cn.len, frames = cn.frames, cap = cn.cap;
     const uint64_t t = uniform64(((const g_u64*)nframes)[ci]);
-    const g_u64* const rq = (const g_u64*)(reasm + ci);
-    const uint64_t out = uniform64(rq[0]);
-    const uint64_t out_cap = out ? uniform64(rq[1]) : 0;
-    g_u64* const mc = (g_u64*)uniform64(rq[2]);
-    const uint64_t msgs = uniform64(rq[3]);
-    const uint64_t msg_cap = msgs ? uniform64(rq[4]) : 0;
-    g_u64* const res = results ? (g_u64*)(results + ci) : nullptr;
+    const rows::reasm_conn_row rq = rows::load_reasm_conn<true>(reasm + ci);
+    const uint64_t out = rq.out, out_cap = rq.out_cap, msgs = rq.msgs, msg_cap = rq.msg_cap;
+    xyws_msg_carry* const mc = (xyws_msg_carry*)rq.mc;
+    xyws_reasm_result* const res = results ? results + ci : nullptr;
 
-    // the carry: length, nframes, first_frame, frame_remaining, frames_seen,
-    // status | opcode << 32 | frame_member << 40 | utf8_len << 48 | utf8[0] << 56, utf8[1..2] | reserved
-    uint64_t c_len = 0, c_nfr = 0, c_first = 0, c_rem = 0, c_seen = 0, w5 = 0, w6 = 0;
-    if (mc) {
-      c_len = uniform64(mc[0]);
-      c_nfr = uniform64(mc[1]);
-      c_first = uniform64(mc[2]);
-      c_rem = uniform64(mc[3]);
-      c_seen = uniform64(mc[4]);
-      w5 = uniform64(mc[5]);
-      w6 = uniform64(mc[6]);
-    }
-    const uint32_t c_status = (uint32_t)w5, c_op = (uint32_t)(w5 >> 32) & 0xFFu;
-    const uint32_t c_member = (uint32_t)(w5 >> 40) & 0xFFu;
+    rows::msg_carry_row c = {0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0}};
+    if (mc) c = rows::load_msg_carry(mc);
+    const uint64_t c_len = c.length, c_nfr = c.nframes, c_first = c.first_frame, c_rem = c.frame_remaining,
+                   c_seen = c.frames_seen;
+    const uint32_t c_status = c.state.status, c_op = c.state.opcode, c_member = c.state.frame_member;
 
     if ((c_status & XYWS_MSG_OVERFLOW) || t > cap || (!frames && t)) {  // the table does not cover the stream
       if (lane == 0) {
-        if (mc) mc[5] = w5 | XYWS_MSG_OVERFLOW;
-        if (res) {
-          res[0] = 0;
-          res[1] = 0;
-          res[2] = (uint64_t)XYWS_RSM_OVERFLOW << 32;
-          res[3] = 0;
-        }
+        if (mc) rows::raise_msg_status(mc, c.state_word, XYWS_MSG_OVERFLOW);
+        if (res) rows::store_reasm_result(res, {0, 0, {0, XYWS_RSM_OVERFLOW}, 0});
       }
       continue;
     }
@@ -253,11 +234,10 @@ __global__ void __launch_bounds__(RSM_LANES) k_reasm_streams(const xyws_conn* __
     // the carried tail as the bytes at out positions -3 .. -1
     uint32_t c_pl = 0, tail3 = 0;
     if (c_op == XYWS_FLAG_OP_TEXT) {
-      const uint32_t ul = (uint32_t)(w5 >> 48) & 0xFFu;
+      const uint32_t ul = c.state.utf8_len;
       if (ul >= 1 && ul <= 3) {
         c_pl = ul;
-        const uint32_t b = (uint32_t)(w5 >> 56) | ((uint32_t)(w6 & 0xFFFFu) << 8);
-        tail3 = (b << (8u * (3 - ul))) & 0xFFFFFFu;
+        tail3 = (c.state.utf8 << (8u * (3 - ul))) & 0xFFFFFFu;
       }
     }
 
@@ -291,11 +271,11 @@ __global__ void __launch_bounds__(RSM_LANES) k_reasm_streams(const xyws_conn* __
       const bool valid = j < t;
       uint64_t poff = 0, plen = 0;
       uint32_t fflags = 0;
-      if (valid) {  // xyws_frame as four words: offsets, length, key | flags | hdr_len | status | reserved
-        const g_u64* const f = (const g_u64*)(frames + 32 * j);
-        poff = f[1];
-        plen = f[2];
-        fflags = (uint32_t)(f[3] >> 32) & 0xFFu;
+      if (valid) {
+        const rows::frame_row f = rows::load_frame(rows::row_at<const xyws_frame>(frames, j));
+        poff = f.payload_off;
+        plen = f.payload_len;
+        fflags = f.flags;
       }
       const uint32_t op = fflags & XYWS_FLAG_OP_MASK;
       uint64_t avail = 0;
@@ -346,12 +326,7 @@ __global__ void __launch_bounds__(RSM_LANES) k_reasm_streams(const xyws_conn* __
       // 2. out offsets: an inclusive scan of the joined sizes
       const bool isj = (joined & lbit) != 0;
       const uint64_t size = isj ? avail : 0;
-      uint64_t incl = size;
-#pragma unroll
-      for (uint32_t d = 1; d < RSM_LANES; d <<= 1) {
-        const uint64_t o = shfl_up64(incl, d);
-        if (lane >= d) incl += o;
-      }
+      const uint64_t incl = wave_scan64(size, lane);
       const uint64_t o0 = opos, fstart = opos + pk;
       const uint64_t o1 = fstart + uniform64(shfl64(incl, RSM_LANES - 1));
       const uint64_t myoff = fstart + (incl - size);
@@ -423,14 +398,9 @@ __global__ void __launch_bounds__(RSM_LANES) k_reasm_streams(const xyws_conn* __
                               (cur_off + cur_len > out_cap ? XYWS_MSG_TRUNCATED : 0u) |
                               (cur_checked && cur_bad ? XYWS_MSG_UTF8_BAD : 0u);
           if (cur_k < msg_cap) {
-            if (lane == 0) {
-              g_u64* const r = (g_u64*)(msgs + 40 * cur_k);
-              r[0] = cur_first;
-              r[1] = cur_nfr;
-              r[2] = cur_off;
-              r[3] = cur_len;
-              r[4] = (uint64_t)st | ((uint64_t)cur_op << 32);
-            }
+            if (lane == 0)
+              rows::store_message(rows::row_at<xyws_message>(msgs, cur_k),
+                                  {cur_first, cur_nfr, cur_off, cur_len, rows::pack_message_meta({st, cur_op})});
             if (complete0) completed++;
             if (st & XYWS_MSG_UTF8_BAD) anybad = 1;
           }
@@ -447,14 +417,9 @@ __global__ void __launch_bounds__(RSM_LANES) k_reasm_streams(const xyws_conn* __
                             (utf8on && text && sbad ? XYWS_MSG_UTF8_BAD : 0u);
         const uint64_t nfr = (uint64_t)__popcll(joined & range);
         const bool stored = ended && k < msg_cap;
-        if (stored) {
-          g_u64* const r = (g_u64*)(msgs + 40 * k);
-          r[0] = j;
-          r[1] = nfr;
-          r[2] = myoff;
-          r[3] = mend - myoff;
-          r[4] = (uint64_t)st | ((uint64_t)op << 32);
-        }
+        if (stored)
+          rows::store_message(rows::row_at<xyws_message>(msgs, k),
+                              {j, nfr, myoff, mend - myoff, rows::pack_message_meta({st, op})});
         completed += (uint32_t)__popcll(__ballot(stored && complete));
         if (__ballot(stored && (st & XYWS_MSG_UTF8_BAD))) anybad = 1;
         // the last start's message, when it goes on after this tile
@@ -491,14 +456,9 @@ __global__ void __launch_bounds__(RSM_LANES) k_reasm_streams(const xyws_conn* __
       const bool trunc = cur_off + cur_len > out_cap, stored = cur_k < msg_cap;
       const uint32_t st = cur_st | (trunc ? XYWS_MSG_TRUNCATED : 0u) | (cur_checked && cur_bad ? XYWS_MSG_UTF8_BAD : 0u);
       if (stored) {
-        if (lane == 0) {
-          g_u64* const r = (g_u64*)(msgs + 40 * cur_k);
-          r[0] = cur_first;
-          r[1] = cur_nfr;
-          r[2] = cur_off;
-          r[3] = cur_len;
-          r[4] = (uint64_t)st | ((uint64_t)cur_op << 32);
-        }
+        if (lane == 0)
+          rows::store_message(rows::row_at<xyws_message>(msgs, cur_k),
+                              {cur_first, cur_nfr, cur_off, cur_len, rows::pack_message_meta({st, cur_op})});
         if (st & XYWS_MSG_UTF8_BAD) anybad = 1;
       }
       const bool text = cur_op == XYWS_FLAG_OP_TEXT;
@@ -525,24 +485,11 @@ __global__ void __launch_bounds__(RSM_LANES) k_reasm_streams(const xyws_conn* __
       }
     }
     if (lane == 0) {
-      if (mc) {
-        mc[0] = o_len;
-        mc[1] = o_nfr;
-        mc[2] = o_first;
-        mc[3] = rem;
-        mc[4] = c_seen + t;
-        mc[5] = (uint64_t)o_status | ((uint64_t)o_op << 32) | ((uint64_t)o_member << 40) | ((uint64_t)o_ul << 48) |
-                ((uint64_t)(o_u & 0xFFu) << 56);
-        mc[6] = (uint64_t)(o_u >> 8);
-        mc[7] = 0;
-      }
+      if (mc) rows::store_msg_carry(mc, o_len, o_nfr, o_first, rem, c_seen + t, {o_status, o_op, o_member, o_ul, o_u});
       if (res) {
         const uint32_t st = (opos > out_cap ? XYWS_RSM_TRUNCATED : 0u) | (nrec > msg_cap ? XYWS_RSM_MSG_CAP : 0u) |
                             (o_op ? XYWS_RSM_OPEN : 0u) | (anybad ? XYWS_RSM_UTF8_BAD : 0u);
-        res[0] = opos;
-        res[1] = nrec;
-        res[2] = (uint64_t)completed | ((uint64_t)st << 32);
-        res[3] = 0;
+        rows::store_reasm_result(res, {opos, nrec, {completed, st}, 0});
       }
     }
   }

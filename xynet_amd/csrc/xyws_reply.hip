@@ -3,6 +3,7 @@
 // echo_once and websocket_send_close, example/include/common/websocket.h:70-108
 // and example/websocket/websocket_echo.cpp:18-27, run once per coroutine).
 // The semantics are stated in include/xyws.h; this is how they are computed.
+// Every table row is read and written through xyws_rows.h, which names its words.
 //
 // As in k_decode_streams (xyws_streams.hip) connections are independent: one
 // wave (a 64-thread workgroup) takes one connection, connections are
@@ -34,6 +35,7 @@
 #include "xyws_ctx.h"
 #include "xyws_frameops.h"
 #include "xyws_lines.h"
+#include "xyws_rows.h"
 
 #define REPLY_TILE 64u       // frames per tile: one per lane
 #define REPLY_LANES 64u      // lanes per connection: one wave
@@ -42,9 +44,8 @@
 #define REPLY_ITEMS (REPLY_TILE + 2u)  // the carried prefix, the frames, the close frame
 #define REPLY_CLOSE_ITEM (REPLY_TILE + 1u)
 
-typedef XYWS_GLOBAL uint16_t g_u16;
-
 using namespace xyws_internal;
+namespace rows = xyws_rows;
 
 // The reply bytes [o0, o1) of one tile, whose items are in LDS, into the send
 // buffer: reply byte q lives at position olo + q from obase (16-byte aligned);
@@ -97,46 +98,29 @@ __global__ void __launch_bounds__(REPLY_LANES) k_reply_streams(const xyws_conn* 
   __shared__ uint32_t s_h2[REPLY_ITEMS];
   const uint32_t lane = threadIdx.x;
   for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
-    const g_u64* const cq = (const g_u64*)(conns + ci);
-    const uint64_t buf = uniform64(cq[0]), len = uniform64(cq[1]);
-    const uint64_t frames = uniform64(cq[3]), cap = uniform64(cq[4]);
+    const rows::conn_row cn = rows::load_conn(conns + ci);
+    const uint64_t buf = cn.buf, len = cn.len, frames = cn.frames, cap = cn.cap;
     const uint64_t t = uniform64(((const g_u64*)nframes)[ci]);
-    const g_u64* const rq = (const g_u64*)(replies + ci);
-    const uint64_t out = uniform64(rq[0]), out_cap = uniform64(rq[1]);
-    g_u64* const rc = (g_u64*)uniform64(rq[2]);
-    const uint64_t verd = uniform64(rq[3]);
-    g_u64* const res = results ? (g_u64*)(results + ci) : nullptr;
+    const rows::reply_conn_row rq = rows::load_reply_conn(replies + ci);
+    const uint64_t out = rq.out, out_cap = rq.out_cap, verd = rq.verdicts;
+    xyws_reply_carry* const rc = (xyws_reply_carry*)rq.rc;
+    xyws_reply_result* const res = results ? results + ci : nullptr;
 
-    // the carry: frame_remaining, frames_seen, replies_total, close_code | echoing << 16 | status << 24
-    uint64_t rem = 0, seen = 0, total = 0, w3 = 0;
-    if (rc) {
-      rem = uniform64(rc[0]);
-      seen = uniform64(rc[1]);
-      total = uniform64(rc[2]);
-      w3 = uniform64(rc[3]);
-    }
-    const uint32_t code_in = (uint32_t)w3 & 0xFFFFu;
-    uint32_t echoing = (uint32_t)(w3 >> 16) & 0xFFu;
+    rows::reply_carry_row c = {0, 0, 0, 0, {0, 0, 0}};
+    if (rc) c = rows::load_reply_carry(rc);
+    const uint32_t code_in = c.state.close_code;
+    uint64_t rem = c.frame_remaining;
+    uint32_t echoing = c.state.echoing;
 
-    if (((w3 >> 24) & XYWS_RPL_OVERFLOW) || t > cap || (!frames && t)) {  // the table does not cover the stream
+    if ((c.state.status & XYWS_RPL_OVERFLOW) || t > cap || (!frames && t)) {  // the table does not cover the stream
       if (lane == 0) {
-        if (rc) rc[3] = w3 | ((uint64_t)XYWS_RPL_OVERFLOW << 24);
-        if (res) {
-          res[0] = 0;
-          res[1] = XYWS_NPOS;
-          res[2] = ((uint64_t)code_in << 32) | ((uint64_t)XYWS_RPL_OVERFLOW << 48);
-          res[3] = 0;
-        }
+        if (rc) rows::raise_reply_status(rc, c.state_word, XYWS_RPL_OVERFLOW);
+        if (res) rows::store_reply_result(res, 0, XYWS_NPOS, {0, code_in, XYWS_RPL_OVERFLOW});
       }
       continue;
     }
     if (code_in) {  // closed by an earlier call
-      if (lane == 0 && res) {
-        res[0] = 0;
-        res[1] = XYWS_NPOS;
-        res[2] = ((uint64_t)code_in << 32) | ((uint64_t)XYWS_RPL_CLOSED << 48);
-        res[3] = 0;
-      }
+      if (lane == 0 && res) rows::store_reply_result(res, 0, XYWS_NPOS, {0, code_in, XYWS_RPL_CLOSED});
       continue;
     }
 
@@ -159,13 +143,12 @@ __global__ void __launch_bounds__(REPLY_LANES) k_reply_streams(const xyws_conn* 
       const bool valid = j < t;
       uint64_t poff = 0, plen = 0;
       uint32_t fflags = 0, fstatus = 0;
-      if (valid) {  // xyws_frame as four words: offsets, length, key | flags | hdr_len | status | reserved
-        const g_u64* const f = (const g_u64*)(frames + 32 * j);
-        poff = f[1];
-        plen = f[2];
-        const uint32_t w = (uint32_t)(f[3] >> 32);
-        fflags = w & 0xFFu;
-        fstatus = (w >> 16) & 0xFFu;
+      if (valid) {
+        const rows::frame_row f = rows::load_frame(rows::row_at<const xyws_frame>(frames, j));
+        poff = f.payload_off;
+        plen = f.payload_len;
+        fflags = f.flags;
+        fstatus = f.status;
       }
       xyws_verdict v;
       v.close_code = 0;
@@ -174,13 +157,7 @@ __global__ void __launch_bounds__(REPLY_LANES) k_reply_streams(const xyws_conn* 
       v.reserved[0] = v.reserved[1] = v.reserved[2] = 0;
       if (valid) {
         v = classify_frame(fflags, fstatus, poff, plen, (const g_u8*)buf, len, max_payload, policy);
-        if (verd) {  // (xyws_verdict is 2-byte aligned: four half-words)
-          g_u16* const vo = (g_u16*)(verd + 8 * j);
-          vo[0] = v.close_code;
-          vo[1] = v.peer_code;
-          vo[2] = v.action;
-          vo[3] = 0;
-        }
+        if (verd) rows::store_verdict(rows::row_at<xyws_verdict>(verd, j), v);
       }
       const uint64_t closes = __ballot(valid && v.close_code != 0);
       if (first_close != XYWS_NPOS) continue;  // closed in an earlier tile: verdicts only
@@ -209,12 +186,7 @@ __global__ void __launch_bounds__(REPLY_LANES) k_reply_streams(const xyws_conn* 
       }
 
       // reply offsets: an inclusive scan of the sizes across the wave
-      uint64_t incl = size;
-#pragma unroll
-      for (uint32_t d = 1; d < REPLY_LANES; d <<= 1) {
-        const uint64_t o = shfl_up64(incl, d);
-        if (lane >= d) incl += o;
-      }
+      const uint64_t incl = wave_scan64(size, lane);
       const uint64_t o0 = opos, fstart = opos + pk;
       const uint64_t cstart = fstart + uniform64(shfl64(incl, REPLY_LANES - 1));
       const uint64_t o1 = cstart + 4u * closing;
@@ -242,18 +214,12 @@ __global__ void __launch_bounds__(REPLY_LANES) k_reply_streams(const xyws_conn* 
     }
 
     if (lane == 0) {
-      if (rc) {
-        rc[0] = rem;
-        rc[1] = seen + t;
-        rc[2] = total + answered;
-        rc[3] = (w3 & ~0xFFFFFFull) | ccode | ((uint64_t)(echoing ? 1u : 0u) << 16);
-      }
+      if (rc)
+        rows::store_reply_carry(rc, rem, c.frames_seen + t, c.replies_total + answered, c.state_word,
+                                {ccode, echoing ? 1u : 0u, c.state.status});
       if (res) {
         const uint32_t st = (opos > out_cap ? XYWS_RPL_TRUNCATED : 0u) | (first_close != XYWS_NPOS ? XYWS_RPL_CLOSED : 0u);
-        res[0] = opos;
-        res[1] = first_close;
-        res[2] = (uint64_t)answered | ((uint64_t)ccode << 32) | ((uint64_t)st << 48);
-        res[3] = 0;
+        rows::store_reply_result(res, opos, first_close, {answered, ccode, st});
       }
     }
   }

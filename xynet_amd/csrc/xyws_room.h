@@ -5,7 +5,8 @@
 // deliverable behind that gate and how long its frame is (frame_of;
 // include/xyws.h, xyws_broadcast_streams 2. and 3.), the workgroup scan that
 // places members, and the geometry of the two fan-out launches. Each is stated
-// once here: the gate rule is load_member's and nobody else's.
+// once here: the gate rule is load_member's and nobody else's. The rows are
+// read through xyws_rows.h, which names their words.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,6 +14,7 @@
 #include "xyws.h"
 #include "xyws_device.h"
 #include "xyws_frameops.h"
+#include "xyws_rows.h"
 
 #define BC_WAVE 64u
 #define BC_WIRE_THREADS 1024u  // the wire build: sixteen waves, the one workgroup a room gets
@@ -41,42 +43,43 @@ struct member {
 // more messages than msg_cap holds.
 XYWS_DEV void load_member(const xyws_reasm_conn* reasm, const xyws_reasm_result* rres, const xyws_bcast_conn* bconns,
                           uint64_t ci, member& m, bool& receiver, bool& over_cap) {
-  const g_u64* const aq = (const g_u64*)(reasm + ci);
-  const g_u64* const ar = (const g_u64*)(rres + ci);
-  const g_u64* const bq = (const g_u64*)(bconns + ci);
-  m.out = aq[0];
-  m.out_cap = m.out ? aq[1] : 0;
-  m.msgs = aq[3];
-  const uint64_t msg_cap = m.msgs ? aq[4] : 0;
-  const uint64_t nmsgs = ar[1];
-  const uint32_t rst = (uint32_t)(ar[2] >> 32);
+  const xyws_rows::reasm_conn_row aq = xyws_rows::load_reasm_conn<false>(reasm + ci);
+  const xyws_rows::reasm_result_row ar = xyws_rows::load_reasm_result<false>(rres + ci);
+  const xyws_rows::bcast_conn_row bq = xyws_rows::load_bcast_conn<false>(bconns + ci);
+  m.out = aq.out;
+  m.out_cap = aq.out_cap;
+  m.msgs = aq.msgs;
+  const uint64_t msg_cap = aq.msg_cap, nmsgs = ar.nmsgs;
+  const uint32_t rst = ar.counts.status;
   const uint64_t kept = nmsgs < msg_cap ? nmsgs : msg_cap;
   m.stored = kept < 0xFFFFFFFFull ? (uint32_t)kept : 0xFFFFFFFFu;  // (the counts are 32 bits)
   over_cap = nmsgs > msg_cap;
-  m.head = bq[0];
-  m.head_len = m.head ? bq[1] : 0;
+  m.head = bq.head;
+  m.head_len = bq.head_len;
   m.gate = (rst & XYWS_RSM_OVERFLOW) ? 0 : XYWS_NPOS;
-  const g_u64* const rp = (const g_u64*)bq[4];
   receiver = true;
-  if (rp) {
-    const uint64_t fc = rp[1];
-    const uint32_t pst = (uint32_t)(rp[2] >> 48);
+  if (bq.reply) {
+    const xyws_rows::reply_result_row rp = xyws_rows::load_reply_result<false>((const xyws_reply_result*)bq.reply);
+    const uint64_t fc = rp.first_close;
+    const uint32_t pst = rp.status;
     if (pst & (XYWS_RPL_CLOSED | XYWS_RPL_OVERFLOW)) receiver = false;
     if ((pst & XYWS_RPL_OVERFLOW) || ((pst & XYWS_RPL_CLOSED) && fc == XYWS_NPOS)) m.gate = 0;
     else if (fc != XYWS_NPOS && m.gate) m.gate = fc;
   }
 }
 
-// One stored record (its five words at rec) of a member: deliverable or not;
+// One stored record (rec) of a member: deliverable or not;
 // if so its frame: header words hw, header length h, message at out + off,
 // length len.
 struct frame_info {
   uint64_t off, len;
   uint32_t hw[4], h;
 };
-XYWS_DEV bool frame_of(const g_u64* rec, const member& m, uint32_t flags, uint32_t enc_opts, frame_info& f) {
-  const uint64_t first = rec[0], off = rec[2], len = rec[3], w4 = rec[4];
-  const uint32_t st = (uint32_t)w4, op = (uint32_t)(w4 >> 32) & XYWS_FLAG_OP_MASK;
+XYWS_DEV bool frame_of(const xyws_message* rec, const member& m, uint32_t flags, uint32_t enc_opts, frame_info& f) {
+  const xyws_rows::message_row r = xyws_rows::load_message<false>(rec);
+  const xyws_rows::message_meta meta = xyws_rows::unpack_message_meta(r.meta);
+  const uint64_t first = r.first_frame, off = r.out_off, len = r.length;
+  const uint32_t st = meta.status, op = meta.opcode & XYWS_FLAG_OP_MASK;
   if (!(st & XYWS_MSG_COMPLETE) || (st & (XYWS_MSG_CONTINUED | XYWS_MSG_TRUNCATED | XYWS_MSG_UTF8_BAD))) return false;
   if (!in_range(off, len, m.out_cap)) return false;  // (nothing outside [out, out + out_cap) is read)
   if (m.gate != XYWS_NPOS && first >= m.gate) return false;
@@ -90,12 +93,7 @@ XYWS_DEV bool frame_of(const g_u64* rec, const member& m, uint32_t flags, uint32
 // Inclusive scan of v over the workgroup (s_w: one slot per wave); total: the sum.
 XYWS_DEV uint64_t block_scan(uint64_t v, uint32_t tid, uint64_t* s_w, uint64_t& total) {
   const uint32_t lane = tid & (BC_WAVE - 1u), wave = tid / BC_WAVE;
-  uint64_t incl = v;
-#pragma unroll
-  for (uint32_t d = 1; d < BC_WAVE; d <<= 1) {
-    const uint64_t o = shfl_up64(incl, d);
-    if (lane >= d) incl += o;
-  }
+  const uint64_t incl = wave_scan64(v, lane);
   if (lane == BC_WAVE - 1u) s_w[wave] = incl;
   __syncthreads();
   uint64_t before = 0, all = 0;

@@ -1,0 +1,584 @@
+// xyws_rows.h — internal: the rows of the connection sweep's tables
+// (xyws_decode_streams .. xyws_accept_streams), each stated once for every
+// kernel that reads or writes it. include/xyws.h declares the rows as C
+// structs; the kernels move them as 64-bit words, and this header is the one
+// place that says which word and which bits a field is: every index and shift
+// comes from offsetof, none is a literal.
+//
+// The pure part (word indices, pack and unpack of every word that holds more
+// than one field, and the asserts that make "these fields share a word" true)
+// needs nothing of HIP: a plain C++ compiler takes it
+// (tests/cpp/rows_host_check.cpp). The device part (loaders and storers on
+// global pointers) is compiled by hipcc only. A packed value must fit its
+// field: pack does not mask.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "xyws.h"
+
+#if defined(__HIPCC__)
+#define XYWS_HD __host__ __device__ inline __attribute__((always_inline))
+#define XYWS_HD_UNROLL _Pragma("unroll")
+#else
+#define XYWS_HD inline
+#define XYWS_HD_UNROLL
+#endif
+
+// Field f of row type T: its 64-bit word, its first bit in that word, its value
+// taken from / placed into the word.
+#define XYWS_WORD(T, f) (offsetof(T, f) / 8)
+#define XYWS_SHIFT(T, f) (8u * (uint32_t)(offsetof(T, f) % 8))
+#define XYWS_GET(T, f, w) ((uint32_t)(((w) >> XYWS_SHIFT(T, f)) & ::xyws_rows::mask_of(sizeof(((T*)0)->f))))
+#define XYWS_PUT(T, f, v) ((uint64_t)(v) << XYWS_SHIFT(T, f))
+// The fields first..last of T lie in one word, and T is whole words.
+#define XYWS_ONE_WORD(T, first, last)                                                                     \
+  static_assert(XYWS_WORD(T, first) == (offsetof(T, last) + sizeof(((T*)0)->last) - 1) / 8 && sizeof(T) % 8 == 0, \
+                #T ": " #first " .. " #last " share a word")
+
+namespace xyws_rows {
+
+constexpr uint64_t mask_of(size_t bytes) { return bytes >= 8 ? ~0ull : (1ull << (8 * bytes)) - 1ull; }
+
+// ---------------------------------------------------------------- xyws_frame
+struct frame_meta { uint32_t key, flags, hdr_len, status; };  // (key: the wire bytes, little-endian)
+XYWS_ONE_WORD(xyws_frame, key, reserved);
+XYWS_HD uint64_t pack_frame_meta(frame_meta m) {
+  return XYWS_PUT(xyws_frame, key, m.key) | XYWS_PUT(xyws_frame, flags, m.flags) |
+         XYWS_PUT(xyws_frame, hdr_len, m.hdr_len) | XYWS_PUT(xyws_frame, status, m.status);
+}
+XYWS_HD frame_meta unpack_frame_meta(uint64_t w) {
+  return {XYWS_GET(xyws_frame, key, w), XYWS_GET(xyws_frame, flags, w), XYWS_GET(xyws_frame, hdr_len, w),
+          XYWS_GET(xyws_frame, status, w)};
+}
+
+// ---------------------------------------------------------------- xyws_carry
+// key, hdr_len and hdr[14] over three words (w[0] is the word of key); header
+// byte i is byte i of hdr_lo (i < 8) or byte i - 8 of hdr_hi. The reserved
+// bytes behind hdr in w[2] are kept as found.
+struct carry_head { uint32_t key, hdr_len; uint64_t hdr_lo, hdr_hi; };
+constexpr uint32_t CARRY_HDR_SHIFT = XYWS_SHIFT(xyws_carry, hdr);  // hdr[0] in w[0]
+constexpr uint64_t CARRY_HDR_TAIL = mask_of(sizeof(((xyws_carry*)0)->hdr) - 8 - (64 - CARRY_HDR_SHIFT) / 8);  // hdr in w[2]
+XYWS_ONE_WORD(xyws_carry, key, hdr_len);
+static_assert(XYWS_WORD(xyws_carry, hdr) == XYWS_WORD(xyws_carry, key) && CARRY_HDR_SHIFT != 0 &&
+                  (offsetof(xyws_carry, hdr) + sizeof(((xyws_carry*)0)->hdr) - 1) / 8 == XYWS_WORD(xyws_carry, key) + 2,
+              "xyws_carry: hdr begins in the word of key and ends two words on");
+XYWS_HD void pack_carry_head(carry_head h, uint64_t w[3]) {
+  w[0] = XYWS_PUT(xyws_carry, key, h.key) | XYWS_PUT(xyws_carry, hdr_len, h.hdr_len) | (h.hdr_lo << CARRY_HDR_SHIFT);
+  w[1] = (h.hdr_lo >> (64 - CARRY_HDR_SHIFT)) | (h.hdr_hi << CARRY_HDR_SHIFT);
+  w[2] = ((h.hdr_hi >> (64 - CARRY_HDR_SHIFT)) & CARRY_HDR_TAIL) | (w[2] & ~CARRY_HDR_TAIL);
+}
+XYWS_HD carry_head unpack_carry_head(uint64_t w0, uint64_t w1, uint64_t w2) {
+  return {XYWS_GET(xyws_carry, key, w0), XYWS_GET(xyws_carry, hdr_len, w0),
+          (w0 >> CARRY_HDR_SHIFT) | (w1 << (64 - CARRY_HDR_SHIFT)),
+          (w1 >> CARRY_HDR_SHIFT) | ((w2 & CARRY_HDR_TAIL) << (64 - CARRY_HDR_SHIFT))};
+}
+
+// ---------------------------------------------------------------- xyws_verdict
+// (2-byte aligned: four half-words, the reserved bytes zero)
+static_assert(sizeof(xyws_verdict) == 8 && offsetof(xyws_verdict, action) % 2 == 0, "xyws_verdict: four half-words");
+XYWS_HD void pack_verdict(uint32_t close_code, uint32_t peer_code, uint32_t action, uint16_t h[4]) {
+  h[0] = h[1] = h[2] = h[3] = 0;
+  h[offsetof(xyws_verdict, close_code) / 2] = (uint16_t)close_code;
+  h[offsetof(xyws_verdict, peer_code) / 2] = (uint16_t)peer_code;
+  h[offsetof(xyws_verdict, action) / 2] = (uint16_t)action;
+}
+XYWS_HD xyws_verdict unpack_verdict(const uint16_t h[4]) {
+  xyws_verdict v = {h[offsetof(xyws_verdict, close_code) / 2], h[offsetof(xyws_verdict, peer_code) / 2],
+                    (uint8_t)h[offsetof(xyws_verdict, action) / 2], {0, 0, 0}};
+  return v;
+}
+
+// ---------------------------------------------------------------- xyws_reply_carry, xyws_reply_result
+struct reply_state { uint32_t close_code, echoing, status; };  // (the storer keeps the carry's reserved bytes)
+XYWS_ONE_WORD(xyws_reply_carry, close_code, reserved);
+XYWS_HD uint64_t pack_reply_state(reply_state s) {
+  return XYWS_PUT(xyws_reply_carry, close_code, s.close_code) | XYWS_PUT(xyws_reply_carry, echoing, s.echoing) |
+         XYWS_PUT(xyws_reply_carry, status, s.status);
+}
+XYWS_HD reply_state unpack_reply_state(uint64_t w) {
+  return {XYWS_GET(xyws_reply_carry, close_code, w), XYWS_GET(xyws_reply_carry, echoing, w),
+          XYWS_GET(xyws_reply_carry, status, w)};
+}
+constexpr uint64_t REPLY_STATE_BITS = mask_of(offsetof(xyws_reply_carry, reserved) % 8);  // the word without reserved
+
+struct reply_counts { uint32_t answered, close_code, status; };
+XYWS_ONE_WORD(xyws_reply_result, answered, status);
+XYWS_HD uint64_t pack_reply_counts(reply_counts c) {
+  return XYWS_PUT(xyws_reply_result, answered, c.answered) | XYWS_PUT(xyws_reply_result, close_code, c.close_code) |
+         XYWS_PUT(xyws_reply_result, status, c.status);
+}
+XYWS_HD reply_counts unpack_reply_counts(uint64_t w) {
+  return {XYWS_GET(xyws_reply_result, answered, w), XYWS_GET(xyws_reply_result, close_code, w),
+          XYWS_GET(xyws_reply_result, status, w)};
+}
+
+// ---------------------------------------------------------------- xyws_msg_carry, xyws_reasm_result, xyws_message
+// status .. utf8[3] over two words (w[0] is the word of status); utf8: the
+// three bytes, byte i at bits 8i. The reserved bytes behind them are zero.
+struct msg_state { uint32_t status, opcode, frame_member, utf8_len, utf8; };
+constexpr uint32_t MSG_UTF8_SHIFT = XYWS_SHIFT(xyws_msg_carry, utf8);
+XYWS_ONE_WORD(xyws_msg_carry, status, utf8_len);
+static_assert(XYWS_WORD(xyws_msg_carry, utf8) == XYWS_WORD(xyws_msg_carry, status) && MSG_UTF8_SHIFT != 0 &&
+                  XYWS_WORD(xyws_msg_carry, reserved) == XYWS_WORD(xyws_msg_carry, status) + 1,
+              "xyws_msg_carry: utf8 begins in the word of status and ends in the next");
+XYWS_HD void pack_msg_state(msg_state s, uint64_t w[2]) {
+  w[0] = XYWS_PUT(xyws_msg_carry, status, s.status) | XYWS_PUT(xyws_msg_carry, opcode, s.opcode) |
+         XYWS_PUT(xyws_msg_carry, frame_member, s.frame_member) | XYWS_PUT(xyws_msg_carry, utf8_len, s.utf8_len) |
+         ((uint64_t)s.utf8 << MSG_UTF8_SHIFT);
+  w[1] = (uint64_t)s.utf8 >> (64 - MSG_UTF8_SHIFT);
+}
+XYWS_HD msg_state unpack_msg_state(uint64_t w0, uint64_t w1) {
+  return {XYWS_GET(xyws_msg_carry, status, w0), XYWS_GET(xyws_msg_carry, opcode, w0),
+          XYWS_GET(xyws_msg_carry, frame_member, w0), XYWS_GET(xyws_msg_carry, utf8_len, w0),
+          (uint32_t)(((w0 >> MSG_UTF8_SHIFT) | (w1 << (64 - MSG_UTF8_SHIFT))) & mask_of(sizeof(((xyws_msg_carry*)0)->utf8)))};
+}
+
+struct reasm_counts { uint32_t completed, status; };
+XYWS_ONE_WORD(xyws_reasm_result, completed, status);
+XYWS_HD uint64_t pack_reasm_counts(reasm_counts c) {
+  return XYWS_PUT(xyws_reasm_result, completed, c.completed) | XYWS_PUT(xyws_reasm_result, status, c.status);
+}
+XYWS_HD reasm_counts unpack_reasm_counts(uint64_t w) {
+  return {XYWS_GET(xyws_reasm_result, completed, w), XYWS_GET(xyws_reasm_result, status, w)};
+}
+
+struct message_meta { uint32_t status, opcode; };
+XYWS_ONE_WORD(xyws_message, status, reserved);
+XYWS_HD uint64_t pack_message_meta(message_meta m) {
+  return XYWS_PUT(xyws_message, status, m.status) | XYWS_PUT(xyws_message, opcode, m.opcode);
+}
+XYWS_HD message_meta unpack_message_meta(uint64_t w) {
+  return {XYWS_GET(xyws_message, status, w), XYWS_GET(xyws_message, opcode, w)};
+}
+
+// ---------------------------------------------------------------- xyws_hold_carry, xyws_hold_result
+struct hold_state { uint32_t status, opcode; };
+XYWS_ONE_WORD(xyws_hold_carry, status, reserved);
+XYWS_HD uint64_t pack_hold_state(hold_state s) {
+  return XYWS_PUT(xyws_hold_carry, status, s.status) | XYWS_PUT(xyws_hold_carry, opcode, s.opcode);
+}
+XYWS_HD hold_state unpack_hold_state(uint64_t w) {
+  return {XYWS_GET(xyws_hold_carry, status, w), XYWS_GET(xyws_hold_carry, opcode, w)};
+}
+XYWS_ONE_WORD(xyws_hold_result, status, reserved0);
+
+// ---------------------------------------------------------------- xyws_room_result, xyws_bcast_conn, xyws_bcast_result
+struct room_counts { uint32_t nmsgs, skipped; };
+struct room_state { uint32_t receivers, status; };
+XYWS_ONE_WORD(xyws_room_result, nmsgs, skipped);
+XYWS_ONE_WORD(xyws_room_result, receivers, status);
+XYWS_HD uint64_t pack_room_counts(room_counts c) {
+  return XYWS_PUT(xyws_room_result, nmsgs, c.nmsgs) | XYWS_PUT(xyws_room_result, skipped, c.skipped);
+}
+XYWS_HD room_counts unpack_room_counts(uint64_t w) {
+  return {XYWS_GET(xyws_room_result, nmsgs, w), XYWS_GET(xyws_room_result, skipped, w)};
+}
+XYWS_HD uint64_t pack_room_state(room_state s) {
+  return XYWS_PUT(xyws_room_result, receivers, s.receivers) | XYWS_PUT(xyws_room_result, status, s.status);
+}
+XYWS_HD room_state unpack_room_state(uint64_t w) {
+  return {XYWS_GET(xyws_room_result, receivers, w), XYWS_GET(xyws_room_result, status, w)};
+}
+XYWS_ONE_WORD(xyws_bcast_conn, room, reserved0);
+XYWS_ONE_WORD(xyws_bcast_result, status, reserved0);
+
+// ---------------------------------------------------------------- the backlog's rows
+struct backlog_counts { uint32_t count, gaps; };  // xyws_backlog_carry
+XYWS_ONE_WORD(xyws_backlog_carry, count, gaps);
+XYWS_HD uint64_t pack_backlog_counts(backlog_counts c) {
+  return XYWS_PUT(xyws_backlog_carry, count, c.count) | XYWS_PUT(xyws_backlog_carry, gaps, c.gaps);
+}
+XYWS_HD backlog_counts unpack_backlog_counts(uint64_t w) {
+  return {XYWS_GET(xyws_backlog_carry, count, w), XYWS_GET(xyws_backlog_carry, gaps, w)};
+}
+// (the fold keeps a copy of the carry in LDS and writes it back one word per thread)
+constexpr uint32_t BLC_START = XYWS_WORD(xyws_backlog_carry, start), BLC_LEN = XYWS_WORD(xyws_backlog_carry, len),
+                   BLC_COUNTS = XYWS_WORD(xyws_backlog_carry, count), BLC_TOTAL = XYWS_WORD(xyws_backlog_carry, total),
+                   BLC_FLEN = XYWS_WORD(xyws_backlog_carry, flen), BLC_WORDS = sizeof(xyws_backlog_carry) / 8;
+XYWS_ONE_WORD(xyws_backlog_room, keep, reserved0);
+
+struct backlog_taken { uint32_t count, folded; };  // xyws_backlog_room_result
+struct backlog_state { uint32_t dropped, status; };
+XYWS_ONE_WORD(xyws_backlog_room_result, count, folded);
+XYWS_ONE_WORD(xyws_backlog_room_result, dropped, status);
+XYWS_HD uint64_t pack_backlog_taken(backlog_taken t) {
+  return XYWS_PUT(xyws_backlog_room_result, count, t.count) | XYWS_PUT(xyws_backlog_room_result, folded, t.folded);
+}
+XYWS_HD backlog_taken unpack_backlog_taken(uint64_t w) {
+  return {XYWS_GET(xyws_backlog_room_result, count, w), XYWS_GET(xyws_backlog_room_result, folded, w)};
+}
+XYWS_HD uint64_t pack_backlog_state(backlog_state s) {
+  return XYWS_PUT(xyws_backlog_room_result, dropped, s.dropped) | XYWS_PUT(xyws_backlog_room_result, status, s.status);
+}
+XYWS_HD backlog_state unpack_backlog_state(uint64_t w) {
+  return {XYWS_GET(xyws_backlog_room_result, dropped, w), XYWS_GET(xyws_backlog_room_result, status, w)};
+}
+
+struct backlog_join { uint32_t room, flags; };  // xyws_backlog_conn
+XYWS_ONE_WORD(xyws_backlog_conn, room, flags);
+XYWS_HD uint64_t pack_backlog_join(backlog_join j) {
+  return XYWS_PUT(xyws_backlog_conn, room, j.room) | XYWS_PUT(xyws_backlog_conn, flags, j.flags);
+}
+XYWS_HD backlog_join unpack_backlog_join(uint64_t w) {
+  return {XYWS_GET(xyws_backlog_conn, room, w), XYWS_GET(xyws_backlog_conn, flags, w)};
+}
+XYWS_ONE_WORD(xyws_backlog_result, status, reserved0);
+
+// ---------------------------------------------------------------- xyws_accept_result
+// Four words of two or three fields each, w[0] the word of status.
+struct accept_fields { uint32_t status, http_status, reason, consumed, resp_len, path_off, path_len, key_off; };
+XYWS_ONE_WORD(xyws_accept_result, status, reason);
+XYWS_ONE_WORD(xyws_accept_result, consumed, resp_len);
+XYWS_ONE_WORD(xyws_accept_result, path_off, path_len);
+XYWS_ONE_WORD(xyws_accept_result, key_off, reserved);
+static_assert(XYWS_WORD(xyws_accept_result, key_off) == 3 * XYWS_WORD(xyws_accept_result, consumed) &&
+                  XYWS_WORD(xyws_accept_result, path_off) == 2 * XYWS_WORD(xyws_accept_result, consumed) &&
+                  sizeof(xyws_accept_result) == 4 * 8,
+              "xyws_accept_result: four words in the order of pack_accept");
+XYWS_HD void pack_accept(accept_fields a, uint64_t w[4]) {
+  // (http_status and reason joined in 32 bits first: placed apart, k_accept_streams keeps four more scalars spilled)
+  w[XYWS_WORD(xyws_accept_result, status)] =
+      XYWS_PUT(xyws_accept_result, status, a.status) |
+      XYWS_PUT(xyws_accept_result, http_status,
+               a.http_status | (a.reason << (XYWS_SHIFT(xyws_accept_result, reason) - XYWS_SHIFT(xyws_accept_result, http_status))));
+  w[XYWS_WORD(xyws_accept_result, consumed)] =
+      XYWS_PUT(xyws_accept_result, consumed, a.consumed) | XYWS_PUT(xyws_accept_result, resp_len, a.resp_len);
+  w[XYWS_WORD(xyws_accept_result, path_off)] =
+      XYWS_PUT(xyws_accept_result, path_off, a.path_off) | XYWS_PUT(xyws_accept_result, path_len, a.path_len);
+  w[XYWS_WORD(xyws_accept_result, key_off)] = XYWS_PUT(xyws_accept_result, key_off, a.key_off);
+}
+XYWS_HD accept_fields unpack_accept(const uint64_t w[4]) {
+  const uint64_t a = w[XYWS_WORD(xyws_accept_result, status)], b = w[XYWS_WORD(xyws_accept_result, consumed)],
+                 c = w[XYWS_WORD(xyws_accept_result, path_off)], d = w[XYWS_WORD(xyws_accept_result, key_off)];
+  return {XYWS_GET(xyws_accept_result, status, a),   XYWS_GET(xyws_accept_result, http_status, a),
+          XYWS_GET(xyws_accept_result, reason, a),   XYWS_GET(xyws_accept_result, consumed, b),
+          XYWS_GET(xyws_accept_result, resp_len, b), XYWS_GET(xyws_accept_result, path_off, c),
+          XYWS_GET(xyws_accept_result, path_len, c), XYWS_GET(xyws_accept_result, key_off, d)};
+}
+
+}  // namespace xyws_rows
+
+// ================================================================ the device part
+#if defined(__HIPCC__)
+#include "xyws_device.h"
+
+typedef XYWS_GLOBAL uint16_t g_u16;
+
+namespace xyws_rows {
+
+// Field f (a whole word, or the word that holds it) of the row at p: U = true
+// takes it wave-uniform, in scalar registers; U = false is each thread's own load.
+template <bool U>
+XYWS_DEV uint64_t load_word(const void* p, size_t w) {
+  const uint64_t v = ((const g_u64*)p)[w];
+  return U ? uniform64(v) : v;
+}
+#define XYWS_LD(U, T, p, f) ::xyws_rows::load_word<U>(p, XYWS_WORD(T, f))
+#define XYWS_ST(T, p, f, v) (((g_u64*)(p))[XYWS_WORD(T, f)] = (v))
+
+// Row i of the table of T at device address base.
+template <class T>
+XYWS_DEV T* row_at(uint64_t base, uint64_t i) { return (T*)(base + sizeof(T) * i); }
+
+// A whole row copied as it is, one word per lane.
+template <class T>
+XYWS_DEV void copy_row(T* dst, const T* src, uint32_t lane) {
+  if (lane < sizeof(T) / 8) ((g_u64*)dst)[lane] = ((const g_u64*)src)[lane];
+}
+
+// ---- xyws_conn (wave-uniform), xyws_frame (one per thread), xyws_carry, xyws_verdict
+struct conn_row { uint64_t buf, len, frames, cap; };
+XYWS_DEV conn_row load_conn(const xyws_conn* p) {
+  return {XYWS_LD(true, xyws_conn, p, buf), XYWS_LD(true, xyws_conn, p, len), XYWS_LD(true, xyws_conn, p, frames),
+          XYWS_LD(true, xyws_conn, p, cap)};
+}
+
+struct frame_row { uint64_t payload_off, payload_len; uint32_t flags, status; };
+XYWS_DEV frame_row load_frame(const xyws_frame* p) {
+  const frame_meta m = unpack_frame_meta(XYWS_LD(false, xyws_frame, p, key));
+  return {XYWS_LD(false, xyws_frame, p, payload_off), XYWS_LD(false, xyws_frame, p, payload_len), m.flags, m.status};
+}
+XYWS_DEV void store_frame(xyws_frame* p, uint64_t frame_off, uint64_t payload_off, uint64_t payload_len, frame_meta m) {
+  XYWS_ST(xyws_frame, p, frame_off, frame_off);
+  XYWS_ST(xyws_frame, p, payload_off, payload_off);
+  XYWS_ST(xyws_frame, p, payload_len, payload_len);
+  XYWS_ST(xyws_frame, p, key, pack_frame_meta(m));
+}
+
+struct carry_row { uint64_t payload_remaining, phase; carry_head head; };
+XYWS_DEV carry_row load_carry(const xyws_carry* p) {
+  const size_t k = XYWS_WORD(xyws_carry, key);
+  return {XYWS_LD(true, xyws_carry, p, payload_remaining), XYWS_LD(true, xyws_carry, p, phase),
+          unpack_carry_head(load_word<true>(p, k), load_word<true>(p, k + 1), load_word<true>(p, k + 2))};
+}
+// (frames_total grows by nframes; the reserved bytes behind hdr stay)
+XYWS_DEV void store_carry(xyws_carry* p, uint64_t payload_remaining, uint64_t phase, uint64_t nframes, carry_head head) {
+  g_u64* const row = (g_u64*)p;
+  const size_t k = XYWS_WORD(xyws_carry, key);
+  XYWS_ST(xyws_carry, p, payload_remaining, payload_remaining);
+  XYWS_ST(xyws_carry, p, phase, phase);
+  row[XYWS_WORD(xyws_carry, frames_total)] += nframes;
+  uint64_t h[3] = {0, 0, row[k + 2]};
+  pack_carry_head(head, h);
+#pragma unroll
+  for (uint32_t i = 0; i < 3; i++) row[k + i] = h[i];
+}
+
+XYWS_DEV void store_verdict(xyws_verdict* p, const xyws_verdict& v) {
+  uint16_t h[4];
+  pack_verdict(v.close_code, v.peer_code, v.action, h);
+#pragma unroll
+  for (uint32_t i = 0; i < 4; i++) ((g_u16*)p)[i] = h[i];
+}
+
+// ---- xyws_reply_conn, xyws_reply_carry (wave-uniform), xyws_reply_result
+struct reply_conn_row { uint64_t out, out_cap, rc, verdicts; };
+XYWS_DEV reply_conn_row load_reply_conn(const xyws_reply_conn* p) {
+  return {XYWS_LD(true, xyws_reply_conn, p, out), XYWS_LD(true, xyws_reply_conn, p, out_cap),
+          XYWS_LD(true, xyws_reply_conn, p, rc), XYWS_LD(true, xyws_reply_conn, p, verdicts)};
+}
+
+struct reply_carry_row { uint64_t frame_remaining, frames_seen, replies_total, state_word; reply_state state; };
+XYWS_DEV reply_carry_row load_reply_carry(const xyws_reply_carry* p) {
+  const uint64_t w = XYWS_LD(true, xyws_reply_carry, p, close_code);
+  return {XYWS_LD(true, xyws_reply_carry, p, frame_remaining), XYWS_LD(true, xyws_reply_carry, p, frames_seen),
+          XYWS_LD(true, xyws_reply_carry, p, replies_total), w, unpack_reply_state(w)};
+}
+// Status bits set in the word of close_code as loaded (state_word); nothing else is written.
+XYWS_DEV void raise_reply_status(xyws_reply_carry* p, uint64_t state_word, uint32_t bits) {
+  XYWS_ST(xyws_reply_carry, p, close_code, state_word | XYWS_PUT(xyws_reply_carry, status, bits));
+}
+// The whole carry; the reserved bytes stay as state_word has them.
+XYWS_DEV void store_reply_carry(xyws_reply_carry* p, uint64_t frame_remaining, uint64_t frames_seen,
+                                uint64_t replies_total, uint64_t state_word, reply_state s) {
+  XYWS_ST(xyws_reply_carry, p, frame_remaining, frame_remaining);
+  XYWS_ST(xyws_reply_carry, p, frames_seen, frames_seen);
+  XYWS_ST(xyws_reply_carry, p, replies_total, replies_total);
+  XYWS_ST(xyws_reply_carry, p, close_code, (state_word & ~REPLY_STATE_BITS) | pack_reply_state(s));
+}
+
+struct reply_result_row { uint64_t reply_len, first_close; uint32_t status; };
+template <bool U>
+XYWS_DEV reply_result_row load_reply_result(const xyws_reply_result* p) {
+  return {XYWS_LD(U, xyws_reply_result, p, reply_len), XYWS_LD(U, xyws_reply_result, p, first_close),
+          unpack_reply_counts(XYWS_LD(U, xyws_reply_result, p, answered)).status};
+}
+XYWS_DEV void store_reply_result(xyws_reply_result* p, uint64_t reply_len, uint64_t first_close, reply_counts c) {
+  XYWS_ST(xyws_reply_result, p, reply_len, reply_len);
+  XYWS_ST(xyws_reply_result, p, first_close, first_close);
+  XYWS_ST(xyws_reply_result, p, answered, pack_reply_counts(c));
+  XYWS_ST(xyws_reply_result, p, reserved, 0);
+}
+
+// ---- xyws_reasm_conn, xyws_msg_carry (wave-uniform), xyws_reasm_result, xyws_message
+// (out_cap counts as 0 without out, msg_cap without msgs: then neither is loaded)
+struct reasm_conn_row { uint64_t out, out_cap, mc, msgs, msg_cap; };
+template <bool U>
+XYWS_DEV reasm_conn_row load_reasm_conn(const xyws_reasm_conn* p) {
+  reasm_conn_row r;
+  r.out = XYWS_LD(U, xyws_reasm_conn, p, out);
+  r.out_cap = r.out ? XYWS_LD(U, xyws_reasm_conn, p, out_cap) : 0;
+  r.mc = XYWS_LD(U, xyws_reasm_conn, p, mc);
+  r.msgs = XYWS_LD(U, xyws_reasm_conn, p, msgs);
+  r.msg_cap = r.msgs ? XYWS_LD(U, xyws_reasm_conn, p, msg_cap) : 0;
+  return r;
+}
+XYWS_DEV void store_reasm_conn(xyws_reasm_conn* p, const reasm_conn_row& r) {
+  XYWS_ST(xyws_reasm_conn, p, out, r.out);
+  XYWS_ST(xyws_reasm_conn, p, out_cap, r.out_cap);
+  XYWS_ST(xyws_reasm_conn, p, mc, r.mc);
+  XYWS_ST(xyws_reasm_conn, p, msgs, r.msgs);
+  XYWS_ST(xyws_reasm_conn, p, msg_cap, r.msg_cap);
+  for (size_t w = XYWS_WORD(xyws_reasm_conn, reserved); w < sizeof(xyws_reasm_conn) / 8; w++) ((g_u64*)p)[w] = 0;
+}
+
+// (state_word: the word of status as loaded)
+struct msg_carry_row { uint64_t length, nframes, first_frame, frame_remaining, frames_seen, state_word; msg_state state; };
+XYWS_DEV msg_carry_row load_msg_carry(const xyws_msg_carry* p) {
+  const size_t k = XYWS_WORD(xyws_msg_carry, status);
+  const uint64_t w = load_word<true>(p, k);
+  return {XYWS_LD(true, xyws_msg_carry, p, length),      XYWS_LD(true, xyws_msg_carry, p, nframes),
+          XYWS_LD(true, xyws_msg_carry, p, first_frame), XYWS_LD(true, xyws_msg_carry, p, frame_remaining),
+          XYWS_LD(true, xyws_msg_carry, p, frames_seen), w, unpack_msg_state(w, load_word<true>(p, k + 1))};
+}
+// Status bits set in the word of status as loaded; nothing else is written.
+XYWS_DEV void raise_msg_status(xyws_msg_carry* p, uint64_t state_word, uint32_t bits) {
+  XYWS_ST(xyws_msg_carry, p, status, state_word | XYWS_PUT(xyws_msg_carry, status, bits));
+}
+// The whole carry, the reserved bytes zero.
+XYWS_DEV void store_msg_carry(xyws_msg_carry* p, uint64_t length, uint64_t nframes, uint64_t first_frame,
+                              uint64_t frame_remaining, uint64_t frames_seen, msg_state state) {
+  const size_t k = XYWS_WORD(xyws_msg_carry, status);
+  uint64_t w[2];
+  pack_msg_state(state, w);
+  XYWS_ST(xyws_msg_carry, p, length, length);
+  XYWS_ST(xyws_msg_carry, p, nframes, nframes);
+  XYWS_ST(xyws_msg_carry, p, first_frame, first_frame);
+  XYWS_ST(xyws_msg_carry, p, frame_remaining, frame_remaining);
+  XYWS_ST(xyws_msg_carry, p, frames_seen, frames_seen);
+  ((g_u64*)p)[k] = w[0];
+  ((g_u64*)p)[k + 1] = w[1];
+  for (size_t r = k + 2; r < sizeof(xyws_msg_carry) / 8; r++) ((g_u64*)p)[r] = 0;
+}
+
+// (reserved: the view of xyws_hold_streams hands the input's word on)
+struct reasm_result_row { uint64_t out_len, nmsgs; reasm_counts counts; uint64_t reserved; };
+template <bool U>
+XYWS_DEV reasm_result_row load_reasm_result(const xyws_reasm_result* p) {
+  return {XYWS_LD(U, xyws_reasm_result, p, out_len), XYWS_LD(U, xyws_reasm_result, p, nmsgs),
+          unpack_reasm_counts(XYWS_LD(U, xyws_reasm_result, p, completed)), XYWS_LD(U, xyws_reasm_result, p, reserved)};
+}
+XYWS_DEV void store_reasm_result(xyws_reasm_result* p, const reasm_result_row& r) {
+  XYWS_ST(xyws_reasm_result, p, out_len, r.out_len);
+  XYWS_ST(xyws_reasm_result, p, nmsgs, r.nmsgs);
+  XYWS_ST(xyws_reasm_result, p, completed, pack_reasm_counts(r.counts));
+  XYWS_ST(xyws_reasm_result, p, reserved, r.reserved);
+}
+
+// (meta: the word of status and opcode as it is, pack_message_meta's; a copied record keeps it whole)
+struct message_row { uint64_t first_frame, nframes, out_off, length, meta; };
+template <bool U>
+XYWS_DEV message_row load_message(const xyws_message* p) {
+  return {XYWS_LD(U, xyws_message, p, first_frame), XYWS_LD(U, xyws_message, p, nframes),
+          XYWS_LD(U, xyws_message, p, out_off), XYWS_LD(U, xyws_message, p, length), XYWS_LD(U, xyws_message, p, status)};
+}
+XYWS_DEV void store_message(xyws_message* p, const message_row& m) {
+  XYWS_ST(xyws_message, p, first_frame, m.first_frame);
+  XYWS_ST(xyws_message, p, nframes, m.nframes);
+  XYWS_ST(xyws_message, p, out_off, m.out_off);
+  XYWS_ST(xyws_message, p, length, m.length);
+  XYWS_ST(xyws_message, p, status, m.meta);
+}
+
+// ---- xyws_hold_conn, xyws_hold_carry (wave-uniform), xyws_hold_result
+struct hold_conn_row { uint64_t hold_cap, hc, vmsgs, vmsg_cap; };  // (vmsg_cap counts as 0 without vmsgs)
+XYWS_DEV hold_conn_row load_hold_conn(const xyws_hold_conn* p) {
+  hold_conn_row r;
+  r.hold_cap = XYWS_LD(true, xyws_hold_conn, p, hold_cap);
+  r.hc = XYWS_LD(true, xyws_hold_conn, p, hc);
+  r.vmsgs = XYWS_LD(true, xyws_hold_conn, p, vmsgs);
+  r.vmsg_cap = r.vmsgs ? XYWS_LD(true, xyws_hold_conn, p, vmsg_cap) : 0;
+  return r;
+}
+
+struct hold_carry_row { uint64_t start, held, nframes; hold_state state; };
+XYWS_DEV hold_carry_row load_hold_carry(const xyws_hold_carry* p) {
+  return {XYWS_LD(true, xyws_hold_carry, p, start), XYWS_LD(true, xyws_hold_carry, p, held),
+          XYWS_LD(true, xyws_hold_carry, p, nframes), unpack_hold_state(XYWS_LD(true, xyws_hold_carry, p, status))};
+}
+XYWS_DEV void store_hold_carry(xyws_hold_carry* p, const hold_carry_row& c) {
+  XYWS_ST(xyws_hold_carry, p, start, c.start);
+  XYWS_ST(xyws_hold_carry, p, held, c.held);
+  XYWS_ST(xyws_hold_carry, p, nframes, c.nframes);
+  XYWS_ST(xyws_hold_carry, p, status, pack_hold_state(c.state));
+}
+XYWS_DEV void store_hold_result(xyws_hold_result* p, uint64_t held, uint64_t delivered_len, uint32_t status) {
+  XYWS_ST(xyws_hold_result, p, held, held);
+  XYWS_ST(xyws_hold_result, p, delivered_len, delivered_len);
+  XYWS_ST(xyws_hold_result, p, status, status);
+  XYWS_ST(xyws_hold_result, p, reserved, 0);
+}
+// The row {0, 0, status}, one word per lane.
+XYWS_DEV void store_hold_status(xyws_hold_result* p, uint32_t status, uint32_t lane) {
+  if (lane < sizeof(xyws_hold_result) / 8) ((g_u64*)p)[lane] = lane == XYWS_WORD(xyws_hold_result, status) ? (uint64_t)status : 0;
+}
+
+// ---- xyws_room, xyws_room_result (wave-uniform), xyws_bcast_conn, xyws_bcast_result
+// (n_members counts as 0 without members, wire_cap without wire: then neither is loaded)
+struct room_row { uint64_t members, n_members, wire, wire_cap; };
+XYWS_DEV room_row load_room(const xyws_room* p) {
+  room_row r;
+  r.members = XYWS_LD(true, xyws_room, p, members);
+  r.n_members = r.members ? XYWS_LD(true, xyws_room, p, n_members) : 0;
+  r.wire = XYWS_LD(true, xyws_room, p, wire);
+  r.wire_cap = r.wire ? XYWS_LD(true, xyws_room, p, wire_cap) : 0;
+  return r;
+}
+struct room_result_row { uint64_t wire_len; uint32_t nmsgs, status; };
+XYWS_DEV room_result_row load_room_result(const xyws_room_result* p) {
+  return {XYWS_LD(true, xyws_room_result, p, wire_len), unpack_room_counts(XYWS_LD(true, xyws_room_result, p, nmsgs)).nmsgs,
+          unpack_room_state(XYWS_LD(true, xyws_room_result, p, receivers)).status};
+}
+// (counts: pack_room_counts' word, which the wire build sums as one)
+XYWS_DEV void store_room_result(xyws_room_result* p, uint64_t wire_len, uint64_t counts, room_state s) {
+  XYWS_ST(xyws_room_result, p, wire_len, wire_len);
+  XYWS_ST(xyws_room_result, p, nmsgs, counts);
+  XYWS_ST(xyws_room_result, p, receivers, pack_room_state(s));
+  XYWS_ST(xyws_room_result, p, reserved, 0);
+}
+
+// (head_len counts as 0 without head, out_cap without out: then neither is loaded)
+struct bcast_conn_row { uint64_t head, head_len, out, out_cap, reply, room; };
+template <bool U>
+XYWS_DEV bcast_conn_row load_bcast_conn(const xyws_bcast_conn* p) {
+  bcast_conn_row r;
+  r.head = XYWS_LD(U, xyws_bcast_conn, p, head);
+  r.head_len = r.head ? XYWS_LD(U, xyws_bcast_conn, p, head_len) : 0;
+  r.out = XYWS_LD(U, xyws_bcast_conn, p, out);
+  r.out_cap = r.out ? XYWS_LD(U, xyws_bcast_conn, p, out_cap) : 0;
+  r.reply = XYWS_LD(U, xyws_bcast_conn, p, reply);
+  r.room = XYWS_GET(xyws_bcast_conn, room, XYWS_LD(U, xyws_bcast_conn, p, room));
+  return r;
+}
+struct bcast_result_row { uint64_t send_len; uint32_t status; };
+XYWS_DEV bcast_result_row load_bcast_result(const xyws_bcast_result* p) {
+  return {XYWS_LD(true, xyws_bcast_result, p, send_len),
+          XYWS_GET(xyws_bcast_result, status, XYWS_LD(true, xyws_bcast_result, p, status))};
+}
+XYWS_DEV void store_bcast_result(xyws_bcast_result* p, uint64_t send_len, uint64_t bcast_len, uint32_t status) {
+  XYWS_ST(xyws_bcast_result, p, send_len, send_len);
+  XYWS_ST(xyws_bcast_result, p, bcast_len, bcast_len);
+  XYWS_ST(xyws_bcast_result, p, status, status);
+  XYWS_ST(xyws_bcast_result, p, reserved, 0);
+}
+
+// ---- the backlog's rows (wave-uniform)
+struct backlog_room_row { uint64_t log, log_cap, bc; uint32_t keep; };
+XYWS_DEV backlog_room_row load_backlog_room(const xyws_backlog_room* p) {
+  return {XYWS_LD(true, xyws_backlog_room, p, log), XYWS_LD(true, xyws_backlog_room, p, log_cap),
+          XYWS_LD(true, xyws_backlog_room, p, bc),
+          uniform32(XYWS_GET(xyws_backlog_room, keep, XYWS_LD(false, xyws_backlog_room, p, keep)))};
+}
+struct backlog_span { uint64_t start, len; };  // of xyws_backlog_carry, what the delivery reads
+XYWS_DEV backlog_span load_backlog_span(const xyws_backlog_carry* p) {
+  return {XYWS_LD(true, xyws_backlog_carry, p, start), XYWS_LD(true, xyws_backlog_carry, p, len)};
+}
+XYWS_DEV void store_backlog_room_result(xyws_backlog_room_result* p, uint64_t len, backlog_taken t, backlog_state s) {
+  XYWS_ST(xyws_backlog_room_result, p, len, len);
+  XYWS_ST(xyws_backlog_room_result, p, count, pack_backlog_taken(t));
+  XYWS_ST(xyws_backlog_room_result, p, dropped, pack_backlog_state(s));
+  XYWS_ST(xyws_backlog_room_result, p, reserved, 0);
+}
+struct backlog_conn_row { uint64_t out, out_cap, bcast, reply; backlog_join join; };  // (out_cap: 0 without out)
+XYWS_DEV backlog_conn_row load_backlog_conn(const xyws_backlog_conn* p) {
+  backlog_conn_row r;
+  r.out = XYWS_LD(true, xyws_backlog_conn, p, out);
+  r.out_cap = r.out ? XYWS_LD(true, xyws_backlog_conn, p, out_cap) : 0;
+  r.bcast = XYWS_LD(true, xyws_backlog_conn, p, bcast);
+  r.reply = XYWS_LD(true, xyws_backlog_conn, p, reply);
+  r.join = unpack_backlog_join(XYWS_LD(true, xyws_backlog_conn, p, room));
+  return r;
+}
+XYWS_DEV void store_backlog_result(xyws_backlog_result* p, uint64_t send_len, uint64_t backlog_len, uint32_t status) {
+  XYWS_ST(xyws_backlog_result, p, send_len, send_len);
+  XYWS_ST(xyws_backlog_result, p, backlog_len, backlog_len);
+  XYWS_ST(xyws_backlog_result, p, status, status);
+  XYWS_ST(xyws_backlog_result, p, reserved, 0);
+}
+
+// ---- xyws_accept_conn (wave-uniform), xyws_accept_result
+struct accept_conn_row { uint64_t buf, len, out, out_cap; };
+XYWS_DEV accept_conn_row load_accept_conn(const xyws_accept_conn* p) {
+  return {XYWS_LD(true, xyws_accept_conn, p, buf), XYWS_LD(true, xyws_accept_conn, p, len),
+          XYWS_LD(true, xyws_accept_conn, p, out), XYWS_LD(true, xyws_accept_conn, p, out_cap)};
+}
+XYWS_DEV void store_accept_result(xyws_accept_result* p, accept_fields a) {
+  uint64_t w[4];
+  pack_accept(a, w);
+#pragma unroll
+  for (uint32_t i = 0; i < 4; i++) ((g_u64*)p)[i] = w[i];
+}
+
+}  // namespace xyws_rows
+#endif  // __HIPCC__

@@ -33,6 +33,7 @@
 #include "xyws.h"
 #include "xyws_device.h"
 #include "xyws_ctx.h"
+#include "xyws_rows.h"
 
 #define STREAMS_WINDOW 4096u     // bytes of one window (LDS per workgroup, plus one line of slack)
 #define STREAMS_LANES 64u        // lanes per connection: one wave
@@ -85,18 +86,13 @@ __global__ void __launch_bounds__(STREAMS_LANES, 6) k_decode_streams(const xyws_
     uint64_t rem = 0, phase = 0;
     uint32_t key = 0, chl = 0;
     bytes16 hb = {0, 0};
-    g_u64* const cw = (g_u64*)cn.carry;
-    if (cw) {
-      rem = uniform64(cw[0]);
-      phase = uniform64(cw[1]);
-      const uint64_t c3 = uniform64(cw[3]), c4 = uniform64(cw[4]), c5 = uniform64(cw[5]);
-      key = (uint32_t)c3;
-      chl = (uint32_t)(c3 >> 32) & 0xFFu;
-      if (chl > 13) chl = 13;
-      // hdr[] is bytes 29..42: c3 >> 40 holds hdr[0..2], c4 hdr[3..10], c5 hdr[11..13]
-      hb.lo = (c3 >> 40) | (c4 << 24);
-      hb.hi = (c4 >> 40) | ((c5 & 0xFFFFFFull) << 24);
-      hb = low_bytes(hb, chl);
+    if (cn.carry) {
+      const xyws_rows::carry_row c = xyws_rows::load_carry(cn.carry);
+      rem = c.payload_remaining;
+      phase = c.phase;
+      key = c.head.key;
+      chl = c.head.hdr_len > 13 ? 13 : c.head.hdr_len;
+      hb = low_bytes(bytes16{c.head.hdr_lo, c.head.hdr_hi}, chl);
     }
 
     uint64_t pos = lo, nf = 0;
@@ -174,12 +170,8 @@ __global__ void __launch_bounds__(STREAMS_LANES, 6) k_decode_streams(const xyws_
         if (frames && nf < cn.cap && lane == 0) {
           const uint64_t ps = wb + pp;
           const uint32_t st = h.status | (sat_add(ps, h.plen) > hi ? XYWS_ST_PAYLOAD_INCOMPLETE : 0u);
-          // xyws_frame as four words: offsets, length, key | flags | hdr_len | status | reserved
-          g_u64* const f = (g_u64*)(frames + nf);
-          f[0] = (uint64_t)((int64_t)(wb + p - lo) - (int64_t)h0);
-          f[1] = ps - lo;
-          f[2] = h.plen;
-          f[3] = (uint64_t)h.key | ((uint64_t)h.flags << 32) | ((uint64_t)h.hlen << 40) | ((uint64_t)st << 48);
+          xyws_rows::store_frame(frames + nf, (uint64_t)((int64_t)(wb + p - lo) - (int64_t)h0), ps - lo, h.plen,
+                                 {h.key, h.flags, h.hlen, st});
         }
         nf++;
         chl = 0;
@@ -220,14 +212,7 @@ __global__ void __launch_bounds__(STREAMS_LANES, 6) k_decode_streams(const xyws_
     }
 
     if (lane == 0) {
-      if (cw) {
-        cw[0] = rem;
-        cw[1] = phase;
-        cw[2] += nf;
-        cw[3] = (uint64_t)key | ((uint64_t)chl << 32) | (hb.lo << 40);
-        cw[4] = (hb.lo >> 24) | (hb.hi << 40);
-        cw[5] = ((hb.hi >> 24) & 0xFFFFFFull) | (cw[5] & ~0xFFFFFFull);  // (bytes 43..47 are reserved: kept)
-      }
+      if (cn.carry) xyws_rows::store_carry(cn.carry, rem, phase, nf, {key, chl, hb.lo, hb.hi});
       if (nframes_out) ((g_u64*)nframes_out)[ci] = nf;
     }
   }

@@ -210,9 +210,24 @@ def websocket_mask(data, mask, i=0):
 
 def _frames_from_device(frames_t, n):
     import numpy as np
-    raw = frames_t[: n * 32].cpu().numpy().tobytes() if n else b""
-    arr = (Frame * max(n, 1)).from_buffer_copy(raw.ljust(max(n, 1) * 32, b"\0"))
-    return [arr[k] for k in range(n)], np
+    return _lib.read_rows(Frame, frames_t, n), np
+
+
+class _Rows:
+    """The first n rows (ctypes structure `struct`) of a device uint8 tensor
+    as host copies: the tensor is copied once, when a row is first asked for;
+    an index outside the call's items is an IndexError."""
+
+    def __init__(self, struct, t, n):
+        self.struct, self.t, self.n, self._raw = struct, t, n, None
+
+    def __getitem__(self, k):
+        if not 0 <= k < self.n:
+            raise IndexError(k)
+        size = C.sizeof(self.struct)
+        if self._raw is None:
+            self._raw = self.t[:size * max(self.n, 1)].cpu().numpy().tobytes()
+        return self.struct.from_buffer_copy(self._raw, size * k)
 
 
 class DecodeResult:
@@ -329,15 +344,11 @@ class GroupReply:
 
     def __init__(self, group, decoded):
         self.group, self.decoded = group, decoded
-        self._rows = None
+        self._rows = _Rows(_lib.ReplyResult, group.results_t, len(decoded.ids))
 
     def result(self, k):
         """xyws_reply_result of item k."""
-        if self._rows is None:
-            self._rows = self.group.results_t[:32 * max(len(self.decoded.ids), 1)].cpu().numpy().tobytes()
-        if not 0 <= k < len(self.decoded.ids):
-            raise IndexError(k)
-        return _lib.ReplyResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+        return self._rows[k]
 
     def verdicts(self, k):
         """The verdicts of item k's frames (empty when its reply overflowed or the connection was closed)."""
@@ -345,10 +356,7 @@ class GroupReply:
         if res.status & _lib.RPL_OVERFLOW or (res.status & _lib.RPL_CLOSED and res.first_close == _lib.NPOS):
             return []
         n = min(self.decoded.nframes(k), g.cap)
-        i = self.decoded.ids[k]
-        raw = g.verdicts_t[8 * g.cap * i:8 * (g.cap * i + n)].cpu().numpy().tobytes() if n else b""
-        arr = (_lib.Verdict * max(n, 1)).from_buffer_copy(raw.ljust(8 * max(n, 1), b"\0"))
-        return [arr[j] for j in range(n)]
+        return _lib.read_rows(_lib.Verdict, g.verdicts_t, n, g.cap * self.decoded.ids[k])
 
 
 class GroupAccept:
@@ -360,15 +368,11 @@ class GroupAccept:
     def __init__(self, group, ids, outs, table_t, results_t):
         self.group, self.ids, self.outs = group, ids, outs
         self._table_t, self.results_t = table_t, results_t  # (the table stays alive until the call has run)
-        self._rows = None
+        self._rows = _Rows(_lib.AcceptResult, results_t, len(outs))
 
     def result(self, k):
         """xyws_accept_result of item k."""
-        if self._rows is None:
-            self._rows = self.results_t.cpu().numpy().tobytes()
-        if not 0 <= k < len(self.outs):
-            raise IndexError(k)
-        return _lib.AcceptResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+        return self._rows[k]
 
     def response(self, k):
         """The response bytes written to item k's send buffer (empty while its request is incomplete)."""
@@ -384,24 +388,17 @@ class GroupMessages:
 
     def __init__(self, group, decoded, msg_cap):
         self.group, self.decoded, self.msg_cap = group, decoded, msg_cap
-        self._rows = None
+        self._rows = _Rows(_lib.ReasmResult, group.mresults_t, len(decoded.ids))
 
     def result(self, k):
         """xyws_reasm_result of item k."""
-        if self._rows is None:
-            self._rows = self.group.mresults_t[:32 * max(len(self.decoded.ids), 1)].cpu().numpy().tobytes()
-        if not 0 <= k < len(self.decoded.ids):
-            raise IndexError(k)
-        return _lib.ReasmResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+        return self._rows[k]
 
     def messages(self, k):
         """The stored records of item k (xyws_message; out_off counts from its out buffer's start)."""
         g = self.group
         n = min(self.result(k).nmsgs, self.msg_cap)
-        row = 40 * (g.cap + 1) * self.decoded.ids[k]
-        raw = g.msgs_t[row:row + 40 * n].cpu().numpy().tobytes() if n else b""
-        arr = (_lib.Message * max(n, 1)).from_buffer_copy(raw.ljust(40 * max(n, 1), b"\0"))
-        return [arr[j] for j in range(n)]
+        return _lib.read_rows(_lib.Message, g.msgs_t, n, (g.cap + 1) * self.decoded.ids[k])
 
 
 class GroupHold:
@@ -416,7 +413,8 @@ class GroupHold:
         self._tensors, self.hold_cap = tensors, hold_cap
         self.msg_cap = messages.msg_cap
         self.out_caps = [c + hold_cap for c in messages.out_caps]  # (broadcast() sizes the wires by them)
-        self._rows = self._vrows = None
+        self._rows = _Rows(_lib.HoldResult, tensors["results"], len(self.decoded.ids))
+        self._vrows = _Rows(_lib.ReasmResult, tensors["view_results"], len(self.decoded.ids))
 
     def _tables(self):
         """The device addresses broadcast() reads instead of the reassembly's."""
@@ -424,28 +422,17 @@ class GroupHold:
 
     def result(self, k):
         """xyws_hold_result of item k."""
-        if self._rows is None:
-            self._rows = self._tensors["results"].cpu().numpy().tobytes()
-        if not 0 <= k < len(self.decoded.ids):
-            raise IndexError(k)
-        return _lib.HoldResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+        return self._rows[k]
 
     def view_result(self, k):
         """Item k's row of the view (xyws_reasm_result)."""
-        if self._vrows is None:
-            self._vrows = self._tensors["view_results"].cpu().numpy().tobytes()
-        if not 0 <= k < len(self.decoded.ids):
-            raise IndexError(k)
-        return _lib.ReasmResult.from_buffer_copy(self._vrows[32 * k:32 * k + 32])
+        return self._vrows[k]
 
     def messages(self, k):
         """The view's stored records of item k (out_off counts from the hold's
         start, hold_cap bytes in front of its out buffer)."""
         n = min(self.view_result(k).nmsgs, self.msg_cap)
-        row = 40 * (self.group.cap + 1) * k
-        raw = self._tensors["vmsgs"][row:row + 40 * n].cpu().numpy().tobytes() if n else b""
-        arr = (_lib.Message * max(n, 1)).from_buffer_copy(raw.ljust(40 * max(n, 1), b"\0"))
-        return [arr[j] for j in range(n)]
+        return _lib.read_rows(_lib.Message, self._tensors["vmsgs"], n, (self.group.cap + 1) * k)
 
 
 class GroupBroadcast:
@@ -456,23 +443,16 @@ class GroupBroadcast:
 
     def __init__(self, group, decoded, tensors, wires):
         self.group, self.decoded, self._tensors, self._wires = group, decoded, tensors, wires
-        self._rows = self._rrows = None
+        self._rows = _Rows(_lib.BcastResult, tensors["results"], len(decoded.ids))
+        self._rrows = _Rows(_lib.RoomResult, tensors["room_results"], len(wires))
 
     def result(self, k):
         """xyws_bcast_result of item k."""
-        if self._rows is None:
-            self._rows = self._tensors["results"].cpu().numpy().tobytes()
-        if not 0 <= k < len(self.decoded.ids):
-            raise IndexError(k)
-        return _lib.BcastResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+        return self._rows[k]
 
     def room_result(self, r):
         """xyws_room_result of room r."""
-        if self._rrows is None:
-            self._rrows = self._tensors["room_results"].cpu().numpy().tobytes()
-        if not 0 <= r < len(self._wires):
-            raise IndexError(r)
-        return _lib.RoomResult.from_buffer_copy(self._rrows[32 * r:32 * r + 32])
+        return self._rrows[r]
 
     def wire(self, r):
         """Room r's outbound bytes of this sweep (a device tensor: the first
@@ -488,23 +468,16 @@ class GroupBacklog:
 
     def __init__(self, group, decoded, tensors, nr):
         self.group, self.decoded, self._tensors, self.nr = group, decoded, tensors, nr
-        self._rows = self._rrows = None
+        self._rows = _Rows(_lib.BacklogResult, tensors["results"], len(decoded.ids))
+        self._rrows = _Rows(_lib.BacklogRoomResult, tensors["room_results"], nr)
 
     def result(self, k):
         """xyws_backlog_result of item k."""
-        if not 0 <= k < len(self.decoded.ids):
-            raise IndexError(k)
-        if self._rows is None:
-            self._rows = self._tensors["results"].cpu().numpy().tobytes()
-        return _lib.BacklogResult.from_buffer_copy(self._rows[32 * k:32 * k + 32])
+        return self._rows[k]
 
     def room_result(self, r):
         """xyws_backlog_room_result of room r."""
-        if not 0 <= r < self.nr:
-            raise IndexError(r)
-        if self._rrows is None:
-            self._rrows = self._tensors["room_results"].cpu().numpy().tobytes()
-        return _lib.BacklogRoomResult.from_buffer_copy(self._rrows[32 * r:32 * r + 32])
+        return self._rrows[r]
 
 
 class connection_group:
@@ -593,15 +566,15 @@ class connection_group:
         self._turn = (k + 1) % self.RING
         if self._done[k] is not None:
             self._done[k].synchronize()
-        tab = self._host[k].numpy().reshape(-1, 8)  # xyws_conn: buf, len, carry, frames, cap, reserved[3]
-        cbase, fbase = self.carry_t.data_ptr(), self.frames_t.data_ptr()
-        for row, (i, t) in zip(tab, items):
-            row[0], row[1], row[2] = t.data_ptr(), t.numel(), cbase + 64 * i
-            row[3], row[4] = (fbase + 32 * self.cap * i, self.cap) if self.cap else (0, 0)
         m = len(items)
+        tab = _lib.Table(_lib.Conn, m, self._host[k])
+        cbase, fbase = self.carry_t.data_ptr(), self.frames_t.data_ptr()
+        for row, (i, t) in zip(tab.rows, items):
+            row.buf, row.len, row.carry = t.data_ptr(), t.numel(), cbase + 64 * i
+            row.frames, row.cap = (fbase + 32 * self.cap * i, self.cap) if self.cap else (0, 0)
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
-            self._dev[k][:8 * m].copy_(self._host[k][:8 * m], non_blocking=True)
+            tab.upload(self._dev[k])
             check(self.ctx.L.xyws_decode_streams(self.ctx.h, C.c_void_p(self._dev[k].data_ptr()), m,
                                                  C.c_void_p(self.counts_t.data_ptr()), self.opts,
                                                  C.c_void_p(stream.cuda_stream)), "xyws_decode_streams")
@@ -629,13 +602,12 @@ class connection_group:
         if len(outs) != len(bufs) or any(t.device != self.device for t in bufs + outs):
             raise XywsError(-1, "one request and one send buffer on the group's device per item")
         m = len(bufs)
-        host = torch.zeros(max(m, 1) * 4, dtype=torch.int64)
-        tab = host.numpy().reshape(-1, 4)  # xyws_accept_conn: buf, len, out, out_cap
-        for row, b, o in zip(tab, bufs, outs):
-            row[0], row[1], row[2], row[3] = b.data_ptr(), b.numel(), o.data_ptr(), o.numel()
+        tab = _lib.Table(_lib.AcceptConn, m)
+        for row, b, o in zip(tab.rows, bufs, outs):
+            row.buf, row.len, row.out, row.out_cap = b.data_ptr(), b.numel(), o.data_ptr(), o.numel()
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
-            table_t = host.to(self.device)
+            table_t = tab.upload(self.device)
             results_t = torch.zeros(max(m, 1) * 32, dtype=torch.uint8, device=self.device)
             check(self.ctx.L.xyws_accept_streams(self.ctx.h, C.c_void_p(table_t.data_ptr()), m, int(max_request),
                                                  int(policy), C.c_void_p(results_t.data_ptr()),
@@ -669,14 +641,14 @@ class connection_group:
         if result._replied and self._done[k] is not None:
             self._done[k].synchronize()  # (the slot's reply table is rewritten)
         result._replied = True
-        tab = self._rhost[k].numpy().reshape(-1, 4)  # xyws_reply_conn: out, out_cap, rc, verdicts
-        rbase, vbase = self.rcarry_t.data_ptr(), self.verdicts_t.data_ptr()
-        for row, i, t in zip(tab, result.ids, outs):
-            row[0], row[1], row[2], row[3] = t.data_ptr(), t.numel(), rbase + 32 * i, vbase + 8 * self.cap * i
         m = len(outs)
+        tab = _lib.Table(_lib.ReplyConn, m, self._rhost[k])
+        rbase, vbase = self.rcarry_t.data_ptr(), self.verdicts_t.data_ptr()
+        for row, i, t in zip(tab.rows, result.ids, outs):
+            row.out, row.out_cap, row.rc, row.verdicts = t.data_ptr(), t.numel(), rbase + 32 * i, vbase + 8 * self.cap * i
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
-            self._rdev[k][:4 * m].copy_(self._rhost[k][:4 * m], non_blocking=True)
+            tab.upload(self._rdev[k])
             check(self.ctx.L.xyws_reply_streams(
                 self.ctx.h, C.c_void_p(self._dev[k].data_ptr()), C.c_void_p(self.counts_t.data_ptr()),
                 C.c_void_p(self._rdev[k].data_ptr()), m, int(max_payload), policy, flags, enc_opts, action_mask,
@@ -708,15 +680,15 @@ class connection_group:
         if result._reassembled and self._done[k] is not None:
             self._done[k].synchronize()  # (the slot's table is rewritten)
         result._reassembled = True
-        tab = self._mhost[k].numpy().reshape(-1, 8)  # xyws_reasm_conn: out, out_cap, mc, msgs, msg_cap, reserved[3]
-        cbase, mbase = self.mcarry_t.data_ptr(), self.msgs_t.data_ptr()
-        for row, i, t in zip(tab, result.ids, outs):
-            row[0], row[1], row[2] = t.data_ptr(), t.numel(), cbase + 64 * i
-            row[3], row[4] = mbase + 40 * (self.cap + 1) * i, mcap
         m = len(outs)
+        tab = _lib.Table(_lib.ReasmConn, m, self._mhost[k])
+        cbase, mbase = self.mcarry_t.data_ptr(), self.msgs_t.data_ptr()
+        for row, i, t in zip(tab.rows, result.ids, outs):
+            row.out, row.out_cap, row.mc = t.data_ptr(), t.numel(), cbase + 64 * i
+            row.msgs, row.msg_cap = mbase + 40 * (self.cap + 1) * i, mcap
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
-            self._mdev[k][:8 * m].copy_(self._mhost[k][:8 * m], non_blocking=True)
+            tab.upload(self._mdev[k])
             check(self.ctx.L.xyws_reassemble_streams(
                 self.ctx.h, C.c_void_p(self._dev[k].data_ptr()), C.c_void_p(self.counts_t.data_ptr()),
                 C.c_void_p(self._mdev[k].data_ptr()), m, opts, C.c_void_p(self.mresults_t.data_ptr()),
@@ -745,7 +717,6 @@ class connection_group:
         suffices. The group owns the hold carries. Returns a GroupHold, which
         broadcast() takes in place of `messages`. Call it before the group's
         next decode(), reply() or reassemble()."""
-        import numpy as np
         import torch
         dec = messages.decoded
         if messages.group is not self or dec._slot is None or not hasattr(messages, "outs"):
@@ -758,7 +729,7 @@ class connection_group:
                 raise ValueError(f"item {k}: the out tensor needs hold_cap = {hold_cap} bytes of its storage in front "
                                  f"of it, has {t.storage_offset() * t.element_size()}")
         m = len(dec.ids)
-        htab = np.zeros((max(m, 1), 4), np.uint64)  # xyws_hold_conn: hold_cap, hc, vmsgs, vmsg_cap
+        htab = _lib.Table(_lib.HoldConn, m)
         with torch.cuda.device(self.device):
             tensors = dict(vmsgs=torch.empty(max(m, 1) * (self.cap + 1) * 40, dtype=torch.uint8, device=self.device),
                            view=torch.zeros(64 * max(m, 1), dtype=torch.uint8, device=self.device),
@@ -766,9 +737,10 @@ class connection_group:
                            results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
                            outs=messages.outs)
             hbase, vbase = self.hcarry_t.data_ptr(), tensors["vmsgs"].data_ptr()
-            for k, i in enumerate(dec.ids):
-                htab[k] = [hold_cap, hbase + 32 * i, vbase + 40 * (self.cap + 1) * k, messages.msg_cap]
-            tensors["hold"] = torch.from_numpy(htab.reshape(-1).view(np.uint8)).to(self.device)
+            for k, (row, i) in enumerate(zip(htab.rows, dec.ids)):
+                row.hold_cap, row.hc = hold_cap, hbase + 32 * i
+                row.vmsgs, row.vmsg_cap = vbase + 40 * (self.cap + 1) * k, messages.msg_cap
+            tensors["hold"] = htab.upload(self.device)
             stream = torch.cuda.current_stream(self.device)
             check(self.ctx.L.xyws_hold_streams(
                 self.ctx.h, C.c_void_p(self._mdev[dec._slot].data_ptr()), C.c_void_p(self.mresults_t.data_ptr()),
@@ -828,23 +800,23 @@ class connection_group:
             need = sum(messages.out_caps[item[int(i)]] + messages.msg_cap * (10 + hlen[item[int(i)]]) for i in ids)
             wires.append(torch.empty(max(need if wire_caps is None else int(wire_caps[r]), 1), dtype=torch.uint8,
                                      device=self.device))
-        btab = np.zeros((max(m, 1), 8), np.uint64)  # xyws_bcast_conn: head, head_len, out, out_cap, reply, room, reserved[2]
+        btab = _lib.Table(_lib.BcastConn, m)
         rbase = self.results_t.data_ptr()
-        for k, (i, t, h) in enumerate(zip(dec.ids, outs, hds)):
-            btab[k, 0], btab[k, 1] = (h.data_ptr(), h.numel()) if h is not None and h.numel() else (0, 0)
-            btab[k, 2], btab[k, 3] = t.data_ptr(), t.numel()
-            btab[k, 4] = rbase + 32 * k if reply is not None else 0
-            btab[k, 5] = room_of.get(i, _lib.ROOM_NONE)
+        for k, (row, i, t, h) in enumerate(zip(btab.rows, dec.ids, outs, hds)):
+            row.head, row.head_len = (h.data_ptr(), h.numel()) if h is not None and h.numel() else (0, 0)
+            row.out, row.out_cap = t.data_ptr(), t.numel()
+            row.reply = rbase + 32 * k if reply is not None else 0
+            row.room = room_of.get(i, _lib.ROOM_NONE)
         with torch.cuda.device(self.device):
             members_t = torch.from_numpy(np.asarray(flat + [0], np.uint32).view(np.uint8)).to(self.device)
-            rtab = np.zeros((max(nr, 1), 4), np.uint64)  # xyws_room: members, n_members, wire, wire_cap
+            rtab = _lib.Table(_lib.Room, nr)
             pos = 0
-            for r, ids in enumerate(rooms):
+            for r, (row, ids) in enumerate(zip(rtab.rows, rooms)):
                 cap = wires[r].numel() if wire_caps is None else int(wire_caps[r])
-                rtab[r] = [members_t.data_ptr() + 4 * pos, len(ids), wires[r].data_ptr() if cap else 0, cap]
+                row.members, row.n_members = members_t.data_ptr() + 4 * pos, len(ids)
+                row.wire, row.wire_cap = wires[r].data_ptr() if cap else 0, cap
                 pos += len(ids)
-            tensors = dict(members=members_t, rooms=torch.from_numpy(rtab.reshape(-1).view(np.uint8)).to(self.device),
-                           bconns=torch.from_numpy(btab.reshape(-1).view(np.uint8)).to(self.device),
+            tensors = dict(members=members_t, rooms=rtab.upload(self.device), bconns=btab.upload(self.device),
                            room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
                            results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
                            outs=outs, heads=hds, messages=messages, replied=reply is not None)
@@ -884,7 +856,6 @@ class connection_group:
         broadcast() was given the sweep's reply, a joiner whose reply closed
         or overflowed is sent nothing (XYWS_BLC_NOT_RECEIVER). Returns a
         GroupBacklog. Call it before the group's next decode()."""
-        import numpy as np
         import torch
         if not isinstance(bcast, GroupBroadcast) or bcast.group is not self:
             raise XywsError(-1, "backlog() takes the result of this group's broadcast()")
@@ -910,18 +881,18 @@ class connection_group:
             while len(self._blogs) < nr:
                 self._blogs.append((torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device), cap))
                 self._bcarries.append(torch.zeros(192, dtype=torch.uint8, device=self.device))
-            rtab = np.zeros((max(nr, 1), 4), np.uint64)  # xyws_backlog_room: log, log_cap, bc, keep
+            rtab = _lib.Table(_lib.BacklogRoom, nr)
             for r in range(nr):
-                log, lcap = self._blogs[r]
-                rtab[r] = [log.data_ptr(), lcap, self._bcarries[r].data_ptr(), keep]
-            jtab = np.zeros((max(m, 1), 8), np.uint64)  # xyws_backlog_conn: out, out_cap, bcast, reply, room | flags
+                row, (log, lcap) = rtab[r], self._blogs[r]
+                row.log, row.log_cap, row.bc, row.keep = log.data_ptr(), lcap, self._bcarries[r].data_ptr(), keep
+            jtab = _lib.Table(_lib.BacklogConn, m)
             bbase, rbase = bt["results"].data_ptr(), self.results_t.data_ptr()
-            for k, (i, t) in enumerate(zip(dec.ids, bt["outs"])):
+            for k, (row, i, t) in enumerate(zip(jtab.rows, dec.ids, bt["outs"])):
                 # (the reply row broadcast() named: only it says that a joiner, not yet a member, closed or overflowed)
-                jtab[k, :4] = [t.data_ptr(), t.numel(), bbase + 32 * k, rbase + 32 * k if bt["replied"] else 0]
-                jtab[k, 4] = joined[i] | (_lib.BL_JOIN << 32) if i in joined else _lib.ROOM_NONE
-            tensors = dict(brooms=torch.from_numpy(rtab.reshape(-1).view(np.uint8)).to(self.device),
-                           jconns=torch.from_numpy(jtab.reshape(-1).view(np.uint8)).to(self.device),
+                row.out, row.out_cap, row.bcast = t.data_ptr(), t.numel(), bbase + 32 * k
+                row.reply = rbase + 32 * k if bt["replied"] else 0
+                row.room, row.flags = (joined[i], _lib.BL_JOIN) if i in joined else (_lib.ROOM_NONE, 0)
+            tensors = dict(brooms=rtab.upload(self.device), jconns=jtab.upload(self.device),
                            room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
                            results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device), bcast=bcast)
             stream = torch.cuda.current_stream(self.device)
