@@ -1035,8 +1035,9 @@ int xyws_hold_streams(xyws_ctx* ctx,
  * backlog on the device and copies the backlog behind the send bytes of every
  * connection marked as joining: decode, reassemble, hold, reply, broadcast,
  * backlog, still with no host read of device state. The welcome and farewell
- * lines of the reference's room (:49-87) are server-authored text and are not
- * part of this call.
+ * lines of the reference's room (:49-87) are server-authored text:
+ * xyws_roster_streams (below), called between the broadcast and this call,
+ * frames and delivers them, and this call appends behind them.
  *
  * dev_reasm, dev_reasm_results, dev_bconns, n, dev_rooms and n_rooms are what
  * this sweep's xyws_broadcast_streams call was given (the hold's view when
@@ -1304,6 +1305,197 @@ int xyws_accept_streams(xyws_ctx* ctx, const xyws_accept_conn* dev_conns, uint64
                         xyws_accept_result* dev_results /* n, nullable */, void* stream);
 int xyws_accept_request(const void* host_req, uint64_t len, uint32_t max_request, uint32_t policy,
                         void* host_out, uint64_t out_cap, xyws_accept_result* res /* nullable */);
+
+/* ---- many rooms, one roster call ---------------------------------------------
+ * Who is in the room: chat_room::m_participants with join and leave, and the
+ * welcome and farewell lines the room says on each (example/websocket/
+ * websocket_chat.cpp:34-39, 49-87). This call, between xyws_broadcast_streams
+ * and xyws_backlog_streams, keeps every room's member list on the device. It
+ * takes the sweep's joins and leaves from the sweep's own result rows, rewrites
+ * the lists the next sweep's broadcast reads, frames one notice per event into
+ * the room's notice wire, delivers that wire as the broadcast delivers the
+ * room's wire, and marks the joiners for the backlog call: accept, decode,
+ * reassemble, hold, reply, broadcast, roster, backlog, with no host read of
+ * device state. A connection whose handshake completes in a sweep is sent
+ * `101 | welcome | recent messages` in that sweep.
+ *
+ * dev_bconns, n, dev_rooms and n_rooms are the broadcast's tables;
+ * dev_rconns[i] goes with dev_bconns[i], dev_rrooms[r] with dev_rooms[r]. The
+ * member arrays dev_rooms[r].members names must be writable and hold
+ * member_cap entries. text is a host pointer, copied into the launches; NULL
+ * means the reference's three strings. flags are a notice's frame flags, as
+ * xyws_broadcast_streams takes them.
+ *
+ *  1. Events. With rc = dev_rconns[i]: connection i leaves when rc.flags has
+ *     XYWS_RS_LEAVE, or has XYWS_RS_LEAVE_ON_CLOSE while rc.reply is given and
+ *     has XYWS_RPL_CLOSED. A leave has an effect only where a room's list holds
+ *     i. Connection i wants to join rc.room when it does not leave, rc.room <
+ *     n_rooms, and rc.flags has XYWS_RS_JOIN, or has XYWS_RS_JOIN_ON_ACCEPT
+ *     while rc.accept is given and has XYWS_ACC_ACCEPTED. A connection with
+ *     dev_bconns[i].room < n_rooms counts as a member of that room: its join is
+ *     refused with XYWS_RSC_ALREADY and nothing changes. Leave wins over join.
+ *     A null name has length 0 whatever name_len says; a name_len above
+ *     XYWS_ROSTER_NAME_MAX counts as 0 and sets XYWS_RSC_BAD_NAME. The event
+ *     still happens: no member gets stuck in a list because of its name.
+ *  2. The list, per room r. First the leavers and the entries >= n
+ *     (XYWS_RS_BAD_MEMBER: dropped, never dereferenced) are removed, the
+ *     others keeping their order. Then the room's joiners are appended in
+ *     ascending table index while n_members < member_cap (0 for a null
+ *     members); the others get XYWS_RSC_FULL, no welcome and no table change
+ *     (the room row gets XYWS_RS_FULL; the caller raises XYWS_RS_JOIN again or
+ *     closes them). dev_rooms[r].n_members is rewritten. dev_bconns[i].room
+ *     becomes r for an admitted joiner and XYWS_ROOM_NONE for a leaver that was
+ *     listed; of both rows only these fields are written. The new list is what
+ *     the next sweep's broadcast reads: the join protocol of
+ *     xyws_backlog_streams 10.
+ *  3. The notice wire of room r: the farewells of its leavers in the order
+ *     members[] had them, then the welcomes of its admitted joiners in joining
+ *     order. A notice is header(flags, L) | head | name_i | joined-or-left with
+ *     L = head_len + name_len_i + the tail's length, the header as
+ *     xyws_broadcast_streams builds it (2 bytes for L < 126, else 4). Positions
+ *     >= notes_cap (0 for a null notes) are not written; notes_len,
+ *     welcome_off = the farewells' length, joined, left and n_members are exact
+ *     whatever notes_cap; XYWS_RS_TRUNCATED is set when notes_len > notes_cap.
+ *     No byte outside [notes, notes + min(notes_len, notes_cap)) is written.
+ *  4. Delivery. base = bcast ? bcast->send_len : reply ? reply->reply_len :
+ *     accept ? (ACCEPTED or REJECTED ? resp_len : 0) : 0. Not a receiver:
+ *     reply has CLOSED or OVERFLOW; bcast has XYWS_BC_NOT_RECEIVER; every
+ *     leaver; a connection with XYWS_RS_JOIN_ON_ACCEPT whose accept row is
+ *     given and not ACCEPTED. Its row is {base, 0, XYWS_RSC_NOT_RECEIVER | the
+ *     event bits}. Otherwise, with w = min(notes_len, notes_cap) of its room: a
+ *     member that stays (XYWS_RSC_MEMBER) receives notes[0 .. w), note_off 0;
+ *     an admitted joiner (XYWS_RSC_JOINED) the suffix that begins at its own
+ *     welcome: note_off is that offset, note_len = max(w - note_off, 0). That
+ *     is what the reference's sequential leave.., join.. sends each
+ *     participant when the sweep's leaves are placed before its joins: whoever
+ *     is present hears every farewell and every welcome, a newcomer its own
+ *     welcome and the later ones. Everyone else gets {base, 0,
+ *     XYWS_RSC_NO_ROOM | the event bits}. The bytes go to out + base; positions
+ *     >= out_cap (0 for a null out) are not written; send_len = base +
+ *     note_len, XYWS_RSC_TRUNCATED whenever send_len > out_cap. room
+ *     is the room the connection is in after the call, for a listed leaver the
+ *     room it left, else XYWS_ROOM_NONE. No byte outside
+ *     [out + min(base, out_cap), out + min(send_len, out_cap)) is written:
+ *     send-slab neighbours share 16-byte lines, and out, notes and name may
+ *     have any alignment.
+ *  5. Hand-over to the backlog. With dev_jconns given, room and flags of entry
+ *     i become {r, XYWS_BL_JOIN} for an admitted joiner and {XYWS_ROOM_NONE, 0}
+ *     for every other connection; nothing else of the row is written. A roster
+ *     row has send_len, note_len and status where xyws_bcast_result has
+ *     send_len, bcast_len and status, and XYWS_RSC_TRUNCATED, _NOT_RECEIVER and
+ *     _NO_ROOM have the XYWS_BC_ values: the caller sets dev_jconns[i].bcast =
+ *     &dev_results[i] once and the backlog appends behind the notices,
+ *     unchanged. Notices are not folded into the backlog (welcome and farewell
+ *     bypass m_recent_messages too).
+ *     The lists this sweep's backlog folds. xyws_backlog_streams recounts the
+ *     room's frames from the list the broadcast read and clears the backlog
+ *     (XYWS_BL_MISMATCH | XYWS_BL_GAP) when the count differs from the room row:
+ *     after this call dev_rooms no longer is that list wherever a member that
+ *     spoke left (it said something and closed in the same sweep) or a joiner
+ *     had messages of its own in the sweep's tables. So this sweep's backlog
+ *     call is given the `seen` rows in place of dev_rooms: with
+ *     dev_rrooms[r].seen set, seen->members[0 .. c) receives members[0 .. c)
+ *     as this call found them, c = min(n_members, member_cap), bad entries
+ *     included, and seen->n_members = c, before anything is rewritten; wire
+ *     and wire_cap of the seen row are the caller's (the same as
+ *     dev_rooms[r]'s) and are not touched. The seen rows of all rooms form one
+ *     table, entry r for room r; their member arrays are not the rooms' own.
+ *     A caller that passes dev_rooms itself to the backlog after this call
+ *     loses the backlog of every room in which one of the two cases occurs.
+ *  6. The caller's duties. A member keeps its table index for as long as it is
+ *     listed (an idle connection is an entry with len = 0); a slot is free
+ *     again in the sweep after its leave. dev_rooms, dev_bconns and the member
+ *     arrays stay resident on the device and are not uploaded again over this
+ *     call's writes. A connection is listed at most once and
+ *     dev_bconns[i].room names the room that lists it. notes, the wires, the
+ *     logs and the send buffers must not overlap. When the caller breaks these
+ *     the results are unspecified; nothing outside the named ranges is touched.
+ *  7. Properties. At most three launches on `stream`: the events (one thread
+ *     per connection: fills dev_want and initialises every result row; omitted
+ *     when n == 0), the room pass (one workgroup per room: 2. and 3.; omitted
+ *     when n_rooms == 0) and the delivery (omitted when n == 0); dev_want and
+ *     dev_results are the hand-over between them. No context scratch, no
+ *     atomics, nothing spins; the device error word is untouched; no device
+ *     state is read on the host; no reserve is needed; the call can be captured
+ *     into a hipGraph at once and runs concurrently on different streams.
+ *     n == 0 && n_rooms == 0 returns XYWS_OK and launches nothing.
+ *     XYWS_ERR_INVALID, decided on the arguments alone before the context is
+ *     used: a null ctx; null dev_bconns, dev_rconns, dev_want or dev_results
+ *     with n > 0; null dev_rooms, dev_rrooms or dev_room_results with n_rooms >
+ *     0; n >= UINT32_MAX or n_rooms >= UINT32_MAX (indices are 32 bits); flags
+ *     with XYWS_FLAG_HAS_MASK; a text length above 32. */
+#define XYWS_ROSTER_NAME_MAX 256u
+#define XYWS_ROSTER_TEXT_MAX 32u
+
+typedef struct xyws_roster_conn {        /* 64 bytes; entry i goes with dev_bconns[i] */
+  const void* name;      /* device, nullable: the peer's address text (socket_address::to_str()) */
+  uint64_t    name_len;  /* <= XYWS_ROSTER_NAME_MAX */
+  void*       out;       /* device: the connection's send buffer */
+  uint64_t    out_cap;
+  const xyws_bcast_result*  bcast;  /* device, nullable: this sweep's rows */
+  const xyws_reply_result*  reply;
+  const xyws_accept_result* accept;
+  uint32_t    room;      /* the room to join */
+  uint32_t    flags;     /* XYWS_RS_JOIN | _LEAVE | _JOIN_ON_ACCEPT | _LEAVE_ON_CLOSE */
+} xyws_roster_conn;
+#define XYWS_RS_JOIN           0x1u
+#define XYWS_RS_LEAVE          0x2u
+#define XYWS_RS_JOIN_ON_ACCEPT 0x4u
+#define XYWS_RS_LEAVE_ON_CLOSE 0x8u
+
+typedef struct xyws_roster_room {        /* 32 bytes; entry r goes with dev_rooms[r] */
+  uint64_t member_cap;   /* entries of the writable array dev_rooms[r].members names */
+  void*    notes;        /* device, nullable (then notes_cap counts as 0): the room's notice wire of this sweep */
+  uint64_t notes_cap;
+  xyws_room* seen;       /* device, nullable: a second room row, with a member array of member_cap entries of
+                            its own, that receives the list as this call found it (5.) */
+} xyws_roster_room;
+
+typedef struct xyws_roster_room_result { /* 32 bytes */
+  uint64_t notes_len;    /* full length of the notice wire (may exceed notes_cap) */
+  uint64_t welcome_off;  /* where the welcomes begin in it */
+  uint32_t joined;       /* joiners admitted */
+  uint32_t left;         /* leavers removed */
+  uint32_t n_members;    /* the list's length after the call */
+  uint32_t status;       /* XYWS_RS_TRUNCATED | _FULL | _BAD_MEMBER */
+} xyws_roster_room_result;
+#define XYWS_RS_TRUNCATED  0x10u /* notes_len > notes_cap */
+#define XYWS_RS_FULL       0x20u /* a joiner was refused for member_cap */
+#define XYWS_RS_BAD_MEMBER 0x40u /* a members[] entry >= n: dropped from the list, never dereferenced */
+
+typedef struct xyws_roster_result {      /* 32 bytes; the first three fields lie as xyws_bcast_result's */
+  uint64_t send_len;     /* base + note_len: the caller sends out[0 .. min(send_len, out_cap)) */
+  uint64_t note_len;     /* bytes of the room's notice wire appended for this connection */
+  uint32_t status;       /* XYWS_RSC_* */
+  uint32_t room;         /* the room it is in after the call (a listed leaver: the room left), else XYWS_ROOM_NONE */
+  uint64_t note_off;     /* where its bytes begin in the notice wire */
+} xyws_roster_result;
+#define XYWS_RSC_TRUNCATED    0x1u   /* send_len > out_cap */
+#define XYWS_RSC_NOT_RECEIVER 0x2u   /* closed, overflowed, leaving or not accepted: nothing appended */
+#define XYWS_RSC_NO_ROOM      0x4u
+#define XYWS_RSC_MEMBER       0x8u   /* was a member and stays one */
+#define XYWS_RSC_JOINED       0x10u
+#define XYWS_RSC_LEFT         0x20u
+#define XYWS_RSC_FULL         0x40u  /* the join was refused for member_cap */
+#define XYWS_RSC_ALREADY      0x80u  /* the join was refused: a member already */
+#define XYWS_RSC_BAD_NAME     0x100u /* name_len > XYWS_ROSTER_NAME_MAX: counted as 0 */
+
+typedef struct xyws_roster_text {        /* host; passed to the launches by value */
+  uint8_t head[XYWS_ROSTER_TEXT_MAX];    /* before the name */
+  uint8_t joined[XYWS_ROSTER_TEXT_MAX];  /* behind it in a welcome */
+  uint8_t left[XYWS_ROSTER_TEXT_MAX];    /* behind it in a farewell */
+  uint8_t head_len, joined_len, left_len; /* each <= XYWS_ROSTER_TEXT_MAX */
+  uint8_t reserved[5];
+} xyws_roster_text;
+
+int xyws_roster_streams(xyws_ctx* ctx,
+                        xyws_bcast_conn* dev_bconns, const xyws_roster_conn* dev_rconns, uint64_t n,
+                        xyws_room* dev_rooms, const xyws_roster_room* dev_rrooms,
+                        xyws_roster_room_result* dev_room_results, uint64_t n_rooms,
+                        const xyws_roster_text* text /* host, nullable */, uint8_t flags,
+                        xyws_backlog_conn* dev_jconns /* n, nullable */,
+                        uint32_t* dev_want /* n words of caller scratch */,
+                        xyws_roster_result* dev_results /* n */, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

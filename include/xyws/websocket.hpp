@@ -405,6 +405,31 @@ inline void backlog_streams(context& ctx, const xyws_reasm_conn* dev_reasm, cons
         "xyws_backlog_streams");
 }
 
+// Who is in the room, between broadcast_streams and backlog_streams of the same
+// sweep, in at most three launches (xyws_roster_streams; the reference's
+// m_participants, join, leave, welcome and farewell). dev_bconns and dev_rooms
+// are the broadcast's tables, resident on the device: the member lists, their
+// counts and each connection's room are rewritten here for the next sweep.
+// dev_rconns[i] names connection i's address text, its send buffer, this
+// sweep's broadcast, reply and accept rows and what it asks (XYWS_RS_*);
+// dev_rrooms[r] the capacity of room r's member array, its notice wire and its
+// `seen` row, which receives the list as the broadcast read it: this sweep's
+// backlog_streams is given the seen rows in place of dev_rooms.
+// The leavers' farewells and the joiners' welcomes are framed with `flags`
+// and appended behind every participant's send bytes. dev_jconns (nullable)
+// is the backlog call's table: the joiners are marked in it. text (host,
+// nullable) replaces the reference's three strings.
+inline void roster_streams(context& ctx, xyws_bcast_conn* dev_bconns, const xyws_roster_conn* dev_rconns,
+                           std::uint64_t n, xyws_room* dev_rooms, const xyws_roster_room* dev_rrooms,
+                           xyws_roster_room_result* dev_room_results, std::uint64_t n_rooms, std::uint32_t* dev_want,
+                           xyws_roster_result* dev_results, xyws_backlog_conn* dev_jconns = nullptr,
+                           std::uint8_t flags = XYWS_FLAG_FIN | XYWS_FLAG_OP_TEXT, const xyws_roster_text* text = nullptr,
+                           void* stream = nullptr) {
+  check(xyws_roster_streams(ctx.native(), dev_bconns, dev_rconns, n, dev_rooms, dev_rrooms, dev_room_results, n_rooms,
+                            text, flags, dev_jconns, dev_want, dev_results, stream),
+        "xyws_roster_streams");
+}
+
 // The opening handshakes of the connections still in HTTP state, in one launch
 // (xyws_accept_streams), before any of the calls above sees them: dev_conns[i]
 // names every byte connection i has sent so far and its send buffer. A whole

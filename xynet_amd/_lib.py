@@ -260,6 +260,46 @@ assert C.sizeof(BacklogConn) == 64 and C.sizeof(BacklogResult) == 32
 BL_PASSTHROUGH, BL_BAD_CARRY, BL_MISMATCH, BL_GAP, BL_EVICTED, BL_TOO_LONG = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 BL_JOIN = 0x1  # xyws_backlog_conn.flags
 BLC_JOINED, BLC_TRUNCATED, BLC_NO_ROOM, BLC_NOT_RECEIVER = 0x1, 0x2, 0x4, 0x8  # xyws_backlog_result.status
+ROSTER_NAME_MAX, ROSTER_TEXT_MAX = 256, 32
+
+
+class RosterConn(C.Structure):
+    """xyws_roster_conn (include/xyws.h), 64 bytes: entry i goes with entry i of the xyws_bcast_conn table."""
+    _fields_ = [("name", C.c_void_p), ("name_len", C.c_uint64), ("out", C.c_void_p), ("out_cap", C.c_uint64),
+                ("bcast", C.c_void_p), ("reply", C.c_void_p), ("accept", C.c_void_p), ("room", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class RosterRoom(C.Structure):
+    """xyws_roster_room (include/xyws.h), 32 bytes: entry r goes with entry r of the xyws_room table."""
+    _fields_ = [("member_cap", C.c_uint64), ("notes", C.c_void_p), ("notes_cap", C.c_uint64), ("seen", C.c_void_p)]
+
+
+class RosterRoomResult(C.Structure):
+    """xyws_roster_room_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("notes_len", C.c_uint64), ("welcome_off", C.c_uint64), ("joined", C.c_uint32), ("left", C.c_uint32),
+                ("n_members", C.c_uint32), ("status", C.c_uint32)]
+
+
+class RosterResult(C.Structure):
+    """xyws_roster_result (include/xyws.h), 32 bytes: readable as an xyws_bcast_result."""
+    _fields_ = [("send_len", C.c_uint64), ("note_len", C.c_uint64), ("status", C.c_uint32), ("room", C.c_uint32),
+                ("note_off", C.c_uint64)]
+
+
+class RosterText(C.Structure):
+    """xyws_roster_text (include/xyws.h), 104 bytes, host memory: the strings of a notice."""
+    _fields_ = [("head", C.c_uint8 * ROSTER_TEXT_MAX), ("joined", C.c_uint8 * ROSTER_TEXT_MAX),
+                ("left", C.c_uint8 * ROSTER_TEXT_MAX), ("head_len", C.c_uint8), ("joined_len", C.c_uint8),
+                ("left_len", C.c_uint8), ("reserved", C.c_uint8 * 5)]
+
+
+assert C.sizeof(RosterConn) == 64 and C.sizeof(RosterRoom) == 32 and C.sizeof(RosterRoomResult) == 32
+assert C.sizeof(RosterResult) == 32 and C.sizeof(RosterText) == 104
+RS_JOIN, RS_LEAVE, RS_JOIN_ON_ACCEPT, RS_LEAVE_ON_CLOSE = 0x1, 0x2, 0x4, 0x8  # xyws_roster_conn.flags
+RS_TRUNCATED, RS_FULL, RS_BAD_MEMBER = 0x10, 0x20, 0x40  # xyws_roster_room_result.status
+(RSC_TRUNCATED, RSC_NOT_RECEIVER, RSC_NO_ROOM, RSC_MEMBER, RSC_JOINED, RSC_LEFT, RSC_FULL, RSC_ALREADY,
+ RSC_BAD_NAME) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40, 0x80, 0x100  # xyws_roster_result.status
 assert C.sizeof(ArenaResult) == 104
 XYWS_ERR_AGAIN = -6
 ARENA_SLOTS = 8
@@ -428,6 +468,11 @@ def load():
     # (no HIP call: members per tile of the fold, bytes per delivery step, grid cap, wave size)
     L.xyws_debug_backlog_geometry.restype = i32
     L.xyws_debug_backlog_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_roster_streams.restype = i32
+    L.xyws_roster_streams.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(RosterText), u8, vp, vp, vp, vp]
+    # (no HIP call: members per tile of the room pass, words per step of the joiner scan, bytes per delivery step, grid cap)
+    L.xyws_debug_roster_geometry.restype = i32
+    L.xyws_debug_roster_geometry.argtypes = [C.POINTER(u64)]
     L.xyws_accept_streams.restype = i32
     L.xyws_accept_streams.argtypes = [vp, vp, u64, u32, u32, vp, vp]
     # (host only: no context, no HIP call)

@@ -1,5 +1,5 @@
 // xyws_rows.h — internal: the rows of the connection sweep's tables
-// (xyws_decode_streams .. xyws_accept_streams), each stated once for every
+// (xyws_decode_streams .. xyws_roster_streams), each stated once for every
 // kernel that reads or writes it. include/xyws.h declares the rows as C
 // structs; the kernels move them as 64-bit words, and this header is the one
 // place that says which word and which bits a field is: every index and shift
@@ -224,6 +224,79 @@ XYWS_HD backlog_join unpack_backlog_join(uint64_t w) {
   return {XYWS_GET(xyws_backlog_conn, room, w), XYWS_GET(xyws_backlog_conn, flags, w)};
 }
 XYWS_ONE_WORD(xyws_backlog_result, status, reserved0);
+
+// ---------------------------------------------------------------- the roster's rows
+struct roster_ask { uint32_t room, flags; };  // xyws_roster_conn
+XYWS_ONE_WORD(xyws_roster_conn, room, flags);
+XYWS_HD uint64_t pack_roster_ask(roster_ask a) {
+  return XYWS_PUT(xyws_roster_conn, room, a.room) | XYWS_PUT(xyws_roster_conn, flags, a.flags);
+}
+XYWS_HD roster_ask unpack_roster_ask(uint64_t w) {
+  return {XYWS_GET(xyws_roster_conn, room, w), XYWS_GET(xyws_roster_conn, flags, w)};
+}
+
+struct roster_counts { uint32_t joined, left; };  // xyws_roster_room_result
+struct roster_state { uint32_t n_members, status; };
+XYWS_ONE_WORD(xyws_roster_room_result, joined, left);
+XYWS_ONE_WORD(xyws_roster_room_result, n_members, status);
+XYWS_HD uint64_t pack_roster_counts(roster_counts c) {
+  return XYWS_PUT(xyws_roster_room_result, joined, c.joined) | XYWS_PUT(xyws_roster_room_result, left, c.left);
+}
+XYWS_HD roster_counts unpack_roster_counts(uint64_t w) {
+  return {XYWS_GET(xyws_roster_room_result, joined, w), XYWS_GET(xyws_roster_room_result, left, w)};
+}
+XYWS_HD uint64_t pack_roster_state(roster_state s) {
+  return XYWS_PUT(xyws_roster_room_result, n_members, s.n_members) | XYWS_PUT(xyws_roster_room_result, status, s.status);
+}
+XYWS_HD roster_state unpack_roster_state(uint64_t w) {
+  return {XYWS_GET(xyws_roster_room_result, n_members, w), XYWS_GET(xyws_roster_room_result, status, w)};
+}
+
+struct roster_place { uint32_t status, room; };  // xyws_roster_result
+XYWS_ONE_WORD(xyws_roster_result, status, room);
+XYWS_HD uint64_t pack_roster_place(roster_place p) {
+  return XYWS_PUT(xyws_roster_result, status, p.status) | XYWS_PUT(xyws_roster_result, room, p.room);
+}
+XYWS_HD roster_place unpack_roster_place(uint64_t w) {
+  return {XYWS_GET(xyws_roster_result, status, w), XYWS_GET(xyws_roster_result, room, w)};
+}
+// A roster row read as a broadcast row (xyws_backlog_conn.bcast may name one): the
+// words and the status field's place agree, and so do the bits the backlog tests.
+static_assert(XYWS_WORD(xyws_roster_result, send_len) == XYWS_WORD(xyws_bcast_result, send_len) &&
+                  XYWS_WORD(xyws_roster_result, note_len) == XYWS_WORD(xyws_bcast_result, bcast_len) &&
+                  offsetof(xyws_roster_result, status) == offsetof(xyws_bcast_result, status) &&
+                  sizeof(((xyws_roster_result*)0)->status) == sizeof(((xyws_bcast_result*)0)->status) &&
+                  sizeof(xyws_roster_result) == sizeof(xyws_bcast_result),
+              "xyws_roster_result: send_len, note_len and status lie as xyws_bcast_result's send_len, bcast_len and status");
+static_assert(XYWS_RSC_TRUNCATED == XYWS_BC_TRUNCATED && XYWS_RSC_NOT_RECEIVER == XYWS_BC_NOT_RECEIVER &&
+                  XYWS_RSC_NO_ROOM == XYWS_BC_NO_ROOM,
+              "xyws_roster_result: the first three status bits are xyws_bcast_result's");
+
+// xyws_roster_text as the kernels take it: the three strings as 64-bit words
+// (byte i of a string = byte i % 8 of its word i / 8), then the lengths.
+constexpr uint32_t ROSTER_TEXT_WORDS = XYWS_ROSTER_TEXT_MAX / 8;
+static_assert(XYWS_ROSTER_TEXT_MAX % 8 == 0 && offsetof(xyws_roster_text, head) == 0 &&
+                  offsetof(xyws_roster_text, joined) == XYWS_ROSTER_TEXT_MAX &&
+                  offsetof(xyws_roster_text, left) == 2 * XYWS_ROSTER_TEXT_MAX &&
+                  offsetof(xyws_roster_text, head_len) == 3 * XYWS_ROSTER_TEXT_MAX,
+              "xyws_roster_text: three strings of whole words, then the lengths");
+struct roster_words {
+  uint64_t w[3 * ROSTER_TEXT_WORDS];  // head, joined, left
+  uint32_t head_len, joined_len, left_len;
+};
+XYWS_HD roster_words pack_roster_text(const xyws_roster_text& t) {
+  roster_words r;
+  const uint8_t* const b = reinterpret_cast<const uint8_t*>(&t);  // (the strings come first: the assert above)
+  for (uint32_t k = 0; k < 3 * ROSTER_TEXT_WORDS; k++) {
+    uint64_t v = 0;
+    for (uint32_t i = 0; i < 8; i++) v |= (uint64_t)b[8 * k + i] << (8 * i);
+    r.w[k] = v;
+  }
+  r.head_len = t.head_len;
+  r.joined_len = t.joined_len;
+  r.left_len = t.left_len;
+  return r;
+}
 
 // ---------------------------------------------------------------- xyws_accept_result
 // Four words of two or three fields each, w[0] the word of status.
@@ -565,6 +638,100 @@ XYWS_DEV void store_backlog_result(xyws_backlog_result* p, uint64_t send_len, ui
   XYWS_ST(xyws_backlog_result, p, backlog_len, backlog_len);
   XYWS_ST(xyws_backlog_result, p, status, status);
   XYWS_ST(xyws_backlog_result, p, reserved, 0);
+}
+
+// ---- the roster's rows, and the words of other rows that xyws_roster_streams rewrites
+// (name_len counts as 0 without name, out_cap without out: then neither is loaded)
+struct roster_conn_row { uint64_t name, name_len, out, out_cap, bcast, reply, accept; roster_ask ask; };
+template <bool U>
+XYWS_DEV roster_conn_row load_roster_conn(const xyws_roster_conn* p) {
+  roster_conn_row r;
+  r.name = XYWS_LD(U, xyws_roster_conn, p, name);
+  r.name_len = r.name ? XYWS_LD(U, xyws_roster_conn, p, name_len) : 0;
+  r.out = XYWS_LD(U, xyws_roster_conn, p, out);
+  r.out_cap = r.out ? XYWS_LD(U, xyws_roster_conn, p, out_cap) : 0;
+  r.bcast = XYWS_LD(U, xyws_roster_conn, p, bcast);
+  r.reply = XYWS_LD(U, xyws_roster_conn, p, reply);
+  r.accept = XYWS_LD(U, xyws_roster_conn, p, accept);
+  r.ask = unpack_roster_ask(XYWS_LD(U, xyws_roster_conn, p, room));
+  return r;
+}
+// What the notices take of a connection: its name (each thread's own load).
+struct roster_name { uint64_t name, name_len; };
+XYWS_DEV roster_name load_roster_name(const xyws_roster_conn* p) {
+  return {XYWS_LD(false, xyws_roster_conn, p, name), XYWS_LD(false, xyws_roster_conn, p, name_len)};
+}
+// (member_cap counts as 0 without the room's members, notes_cap without notes)
+struct roster_room_row { uint64_t member_cap, notes, notes_cap, seen; };
+XYWS_DEV roster_room_row load_roster_room(const xyws_roster_room* p, bool has_members) {
+  roster_room_row r;
+  r.member_cap = has_members ? XYWS_LD(true, xyws_roster_room, p, member_cap) : 0;
+  r.notes = XYWS_LD(true, xyws_roster_room, p, notes);
+  r.notes_cap = r.notes ? XYWS_LD(true, xyws_roster_room, p, notes_cap) : 0;
+  r.seen = XYWS_LD(true, xyws_roster_room, p, seen);
+  return r;
+}
+// The member array an xyws_room row names (the roster's `seen` row: only this and the count are touched).
+XYWS_DEV uint64_t load_room_members(const xyws_room* p) { return XYWS_LD(true, xyws_room, p, members); }
+// A broadcast row as each thread's own load (load_bcast_result takes it wave-uniform).
+XYWS_DEV bcast_result_row load_bcast_result_own(const xyws_bcast_result* p) {
+  return {XYWS_LD(false, xyws_bcast_result, p, send_len),
+          XYWS_GET(xyws_bcast_result, status, XYWS_LD(false, xyws_bcast_result, p, status))};
+}
+XYWS_DEV uint64_t load_roster_notes_len(const xyws_roster_room_result* p) {
+  return XYWS_LD(true, xyws_roster_room_result, p, notes_len);
+}
+XYWS_DEV void store_roster_room_result(xyws_roster_room_result* p, uint64_t notes_len, uint64_t welcome_off,
+                                       roster_counts c, roster_state s) {
+  XYWS_ST(xyws_roster_room_result, p, notes_len, notes_len);
+  XYWS_ST(xyws_roster_room_result, p, welcome_off, welcome_off);
+  XYWS_ST(xyws_roster_room_result, p, joined, pack_roster_counts(c));
+  XYWS_ST(xyws_roster_room_result, p, n_members, pack_roster_state(s));
+}
+struct roster_result_row { uint64_t note_off; roster_place place; };  // what the later launches read of a row
+template <bool U>
+XYWS_DEV roster_result_row load_roster_result(const xyws_roster_result* p) {
+  return {XYWS_LD(U, xyws_roster_result, p, note_off), unpack_roster_place(XYWS_LD(U, xyws_roster_result, p, status))};
+}
+XYWS_DEV void store_roster_result(xyws_roster_result* p, uint64_t send_len, uint64_t note_len, roster_place pl,
+                                  uint64_t note_off) {
+  XYWS_ST(xyws_roster_result, p, send_len, send_len);
+  XYWS_ST(xyws_roster_result, p, note_len, note_len);
+  XYWS_ST(xyws_roster_result, p, status, pack_roster_place(pl));
+  XYWS_ST(xyws_roster_result, p, note_off, note_off);
+}
+// The room pass's part of a row: its place, and for a joiner where its welcome begins.
+XYWS_DEV void store_roster_place(xyws_roster_result* p, roster_place pl) {
+  XYWS_ST(xyws_roster_result, p, status, pack_roster_place(pl));
+}
+XYWS_DEV void store_roster_note_off(xyws_roster_result* p, uint64_t note_off) {
+  XYWS_ST(xyws_roster_result, p, note_off, note_off);
+}
+// The delivery's part: the lengths, and the row's place again with the bits it adds.
+XYWS_DEV void store_roster_lengths(xyws_roster_result* p, uint64_t send_len, uint64_t note_len, roster_place pl) {
+  XYWS_ST(xyws_roster_result, p, send_len, send_len);
+  XYWS_ST(xyws_roster_result, p, note_len, note_len);
+  XYWS_ST(xyws_roster_result, p, status, pack_roster_place(pl));
+}
+// xyws_bcast_conn.room alone (each thread's own): the other half of its word stays as found.
+XYWS_DEV uint32_t load_bcast_room(const xyws_bcast_conn* p) {
+  return XYWS_GET(xyws_bcast_conn, room, XYWS_LD(false, xyws_bcast_conn, p, room));
+}
+XYWS_DEV void store_bcast_room(xyws_bcast_conn* p, uint32_t room) {
+  const uint64_t field = XYWS_PUT(xyws_bcast_conn, room, mask_of(sizeof(((xyws_bcast_conn*)0)->room)));
+  XYWS_ST(xyws_bcast_conn, p, room, (XYWS_LD(false, xyws_bcast_conn, p, room) & ~field) | XYWS_PUT(xyws_bcast_conn, room, room));
+}
+// xyws_room.n_members alone, and the word of xyws_backlog_conn's room and flags.
+XYWS_DEV void store_room_count(xyws_room* p, uint64_t n_members) { XYWS_ST(xyws_room, p, n_members, n_members); }
+XYWS_DEV void store_backlog_join(xyws_backlog_conn* p, backlog_join j) {
+  XYWS_ST(xyws_backlog_conn, p, room, pack_backlog_join(j));
+}
+// What the roster reads of an accept row: status and resp_len.
+struct accept_brief { uint32_t status, resp_len; };
+template <bool U>
+XYWS_DEV accept_brief load_accept_brief(const xyws_accept_result* p) {
+  return {XYWS_GET(xyws_accept_result, status, XYWS_LD(U, xyws_accept_result, p, status)),
+          XYWS_GET(xyws_accept_result, resp_len, XYWS_LD(U, xyws_accept_result, p, resp_len))};
 }
 
 // ---- xyws_accept_conn (wave-uniform), xyws_accept_result

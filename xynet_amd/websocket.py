@@ -18,7 +18,10 @@ Names, argument meaning and error behaviour follow the reference headers
   connection_group.accept          websocket_handshake (example/include/common/websocket.h:40-68) for many
                                    connections at once: the HTTP upgrade parsed, checked and answered
                                    (xyws_accept_streams, one launch)
-  websocket_request_handler        include/xynet/http/websocket_request_handler.h:66-264, one request on
+  connection_group.rooms / roster  chat_room's participants, join, leave, welcome and farewell
+                                   (example/websocket/websocket_chat.cpp:34-39, 49-87) for many rooms at
+                                   once, the lists kept on the device (xyws_roster_streams)
+  websocket_request_handler       include/xynet/http/websocket_request_handler.h:66-264, one request on
                                    the host (xyws_accept_request: the kernel's grammar compiled for the host)
   encode_frames                    echo_once's replies, batched on the device
                                    (example/websocket/websocket_echo.cpp:18-27)
@@ -480,6 +483,99 @@ class GroupBacklog:
         return self._rrows[r]
 
 
+class RoomSet:
+    """The rooms of a connection_group kept on the device
+    (connection_group.rooms): the xyws_room table, every room's member array
+    of member_cap entries, its wire and its notice buffer, and the group's
+    xyws_bcast_conn table, whose room column says where each connection is.
+    roster() rewrites the lists, the counts and that column on the device;
+    broadcast() reads them. A second table of the same shape (the `seen`
+    rows) receives each sweep's lists as its broadcast read them: backlog()
+    behind a roster() folds from those, so a member that talks and closes in
+    one sweep, or a joiner that spoke, does not cost the room its recent
+    messages. Connection k is item k of every sweep."""
+
+    def __init__(self, group, n_rooms, member_cap, wire_cap, notes_cap):
+        import torch
+        self.group, self.nr, self.member_cap = group, int(n_rooms), int(member_cap)
+        if self.nr < 0 or self.member_cap < 0 or wire_cap < 1 or notes_cap < 1:
+            raise ValueError("n_rooms and member_cap must not be negative, the buffers not empty")
+        dev, n = group.device, group.n
+        with torch.cuda.device(dev):
+            self.members_t = torch.zeros(max(self.nr * self.member_cap, 1), dtype=torch.int32, device=dev)
+            self.wires = [torch.empty(int(wire_cap), dtype=torch.uint8, device=dev) for _ in range(self.nr)]
+            self.notes = [torch.empty(int(notes_cap), dtype=torch.uint8, device=dev) for _ in range(self.nr)]
+            # the `seen` rows: each sweep's lists as its broadcast read them, for that sweep's backlog fold
+            self.seen_members_t = torch.zeros(max(self.nr * self.member_cap, 1), dtype=torch.int32, device=dev)
+            rtab, stab = _lib.Table(_lib.Room, self.nr), _lib.Table(_lib.Room, self.nr)
+            self.seen_rooms_t = torch.zeros(32 * max(self.nr, 1), dtype=torch.uint8, device=dev)
+            rrtab = _lib.Table(_lib.RosterRoom, self.nr)
+            for r in range(self.nr):
+                rtab[r].members, rtab[r].n_members = self.members_t.data_ptr() + 4 * self.member_cap * r, 0
+                stab[r].members, stab[r].n_members = self.seen_members_t.data_ptr() + 4 * self.member_cap * r, 0
+                for row in (rtab[r], stab[r]):
+                    row.wire, row.wire_cap = self.wires[r].data_ptr(), self.wires[r].numel()
+                rrtab[r].member_cap = self.member_cap
+                rrtab[r].notes, rrtab[r].notes_cap = self.notes[r].data_ptr(), self.notes[r].numel()
+                rrtab[r].seen = self.seen_rooms_t.data_ptr() + 32 * r
+            self.seen_rooms_t.copy_(stab.upload(dev)[:32 * max(self.nr, 1)])
+            self.rooms_t, self.rrooms_t = rtab.upload(dev), rrtab.upload(dev)
+            btab = _lib.Table(_lib.BcastConn, n)
+            for k in range(n):
+                btab[k].room = _lib.ROOM_NONE
+            self.bconns_t = btab.upload(dev)
+
+    def stage_bconns(self, table):
+        """The caller's fields of the bconns rows (head .. reply) from a
+        host-built table, on the device; the room column stays the roster's."""
+        import torch
+        n, words = self.group.n, _lib.BcastConn.room.offset // 8
+        with torch.cuda.device(self.group.device):
+            fresh = table.upload(self.group.device).view(torch.int64).view(max(n, 1), -1)
+            self.bconns_t.view(torch.int64).view(max(n, 1), -1)[:n, :words].copy_(fresh[:n, :words])
+
+    def members(self, r):
+        """Host copy of room r's list (synchronizes)."""
+        if not 0 <= r < self.nr:
+            raise IndexError("no such room")
+        count = _lib.read_rows(_lib.Room, self.rooms_t, 1, r)[0].n_members
+        lo = self.member_cap * r
+        return [int(x) & 0xFFFFFFFF for x in self.members_t[lo:lo + count].cpu().numpy()]
+
+    def state_tensors(self):
+        """The tensors roster() rewrites from sweep to sweep."""
+        return [self.members_t, self.rooms_t, self.bconns_t]
+
+
+class GroupRoster:
+    """Results of one connection_group.roster call: item k as in the decode
+    result of its sweep, room r as in the room set (host copies on demand). It
+    owns the call's tables and rows; the lists belong to the room set."""
+
+    def __init__(self, group, bcast, room_set, tensors):
+        self.group, self.bcast, self.room_set, self._tensors = group, bcast, room_set, tensors
+        self.decoded = bcast.decoded
+        self._rows = _Rows(_lib.RosterResult, tensors["results"], len(self.decoded.ids))
+        self._rrows = _Rows(_lib.RosterRoomResult, tensors["room_results"], room_set.nr)
+
+    def result(self, k):
+        """xyws_roster_result of item k."""
+        return self._rows[k]
+
+    def room_result(self, r):
+        """xyws_roster_room_result of room r."""
+        return self._rrows[r]
+
+    def notes(self, r):
+        """Room r's notice wire of this sweep (a device tensor: the first min(notes_len, notes_cap) bytes)."""
+        t = self.room_set.notes[r]
+        return t[:min(self.room_result(r).notes_len, t.numel())]
+
+    def members(self, r):
+        """Room r's list after the call (host copy)."""
+        return self.room_set.members(r)
+
+
 class connection_group:
     """The decoder states of n connections and one xyws_decode_streams call
     for whatever a sweep of the completion queue brought: decode() takes the
@@ -497,7 +593,11 @@ class connection_group:
     (xyws_hold_streams) and hands broadcast() the whole message in the sweep
     that completes it. backlog(), after broadcast(), keeps each room's recent
     messages on the device (xyws_backlog_streams) and sends them to the
-    connections that join."""
+    connections that join. rooms() makes a room set that lives on the device;
+    with it broadcast() reads the lists where roster(), between broadcast()
+    and backlog(), keeps them (xyws_roster_streams): joins and leaves taken
+    from the sweep's own rows, each said to the room as the reference's
+    welcome and farewell lines."""
     RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
 
     def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
@@ -765,8 +865,12 @@ class connection_group:
         behind its reply when `reply` is the GroupReply of the same sweep
         (out_items are then the tensors reply() wrote), from the start
         otherwise. wire_caps[r]: room r's wire capacity (default: the bound
-        that always suffices). Returns a GroupBroadcast. Call it before the
-        group's next decode(), reply() or reassemble()."""
+        that always suffices). rooms may be the RoomSet of rooms() instead:
+        the lists are then the ones roster() keeps on the device, every
+        connection of the group is an item of the sweep (item k is connection
+        k: XywsError otherwise), and the wires are the room set's. Returns a
+        GroupBroadcast. Call it before the group's next decode(), reply() or
+        reassemble()."""
         import numpy as np
         import torch
         dec = messages.decoded
@@ -783,6 +887,8 @@ class connection_group:
         hds = [None] * m if heads is None else [None if h is None else _dev_u8(h) for h in heads]
         if len(hds) != m or any(h is not None and h.device != self.device for h in hds):
             raise XywsError(-1, "one head (or None) on the group's device per decoded item")
+        if isinstance(rooms, RoomSet):
+            return self._broadcast_resident(messages, rooms, outs, hds, reply, flags, enc_opts, reasm_p, rres_p)
         item = {i: k for k, i in enumerate(dec.ids)}
         room_of, flat = {}, []
         for r, ids in enumerate(rooms):
@@ -829,6 +935,127 @@ class connection_group:
             self._done[dec._slot].record(stream)
         return GroupBroadcast(self, dec, tensors, wires)
 
+    def rooms(self, n_rooms, member_cap, wire_cap=65536, notes_cap=65536):
+        """A room set on the device: n_rooms rooms of at most member_cap
+        members, each with a wire of wire_cap and a notice buffer of notes_cap
+        bytes, all empty. broadcast(..., rooms=room_set) reads it, roster()
+        keeps it. Returns a RoomSet."""
+        return RoomSet(self, n_rooms, member_cap, int(wire_cap), int(notes_cap))
+
+    def _broadcast_resident(self, messages, room_set, outs, hds, reply, flags, enc_opts, reasm_p, rres_p):
+        """broadcast() over a room set: the lists, the counts and every
+        connection's room are the device's; only the caller's fields of the
+        bconns rows are staged."""
+        import torch
+        dec = messages.decoded
+        m = len(dec.ids)
+        if room_set.group is not self or list(dec.ids) != list(range(self.n)):
+            raise XywsError(-1, "a room set needs slot-stable sweeps: item k is connection k, every connection an item")
+        btab = _lib.Table(_lib.BcastConn, m)
+        rbase = self.results_t.data_ptr()
+        for k, (row, t, h) in enumerate(zip(btab.rows, outs, hds)):
+            row.head, row.head_len = (h.data_ptr(), h.numel()) if h is not None and h.numel() else (0, 0)
+            row.out, row.out_cap = t.data_ptr(), t.numel()
+            row.reply = rbase + 32 * k if reply is not None else 0
+        with torch.cuda.device(self.device):
+            room_set.stage_bconns(btab)
+            nr = room_set.nr
+            tensors = dict(members=room_set.members_t, rooms=room_set.rooms_t, bconns=room_set.bconns_t,
+                           room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
+                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
+                           outs=outs, heads=hds, messages=messages, replied=reply is not None, room_set=room_set)
+            stream = torch.cuda.current_stream(self.device)
+            check(self.ctx.L.xyws_broadcast_streams(
+                self.ctx.h, C.c_void_p(reasm_p), C.c_void_p(rres_p), C.c_void_p(room_set.bconns_t.data_ptr()), m,
+                C.c_void_p(room_set.rooms_t.data_ptr()), C.c_void_p(tensors["room_results"].data_ptr()), nr, flags,
+                enc_opts, C.c_void_p(tensors["results"].data_ptr()), C.c_void_p(stream.cuda_stream)),
+                "xyws_broadcast_streams")
+            self._done[dec._slot] = torch.cuda.Event()
+            self._done[dec._slot].record(stream)
+        return GroupBroadcast(self, dec, tensors, room_set.wires)
+
+    def roster(self, bcast, room_set, names=None, joins=(), leaves=(), accept=None, on_accept=None,
+               leave_on_close=True, flags=0x11, text=None):
+        """Who is in the room (xyws_roster_streams, at most three launches),
+        after broadcast(..., rooms=room_set) of the same sweep and before
+        backlog(): the room set's lists are updated on the device from the
+        sweep's own rows, and every event is said to the room as the
+        reference's chat_room says it: a welcome or farewell line framed with
+        `flags`, appended behind what broadcast() left in every participant's
+        send tensor. names[k]: item k's address text (a device uint8 tensor or
+        None); joins: (conn_id, room) pairs; leaves: conn ids; accept with
+        on_accept = {conn_id: room}: the GroupAccept of this sweep, whose
+        accepted connections join that room behind their 101 in the same send
+        tensor; leave_on_close: a member whose reply closed leaves. text: a
+        _lib.RosterText in place of the reference's strings. Nothing is read
+        back: the next sweep's broadcast() finds the new lists on the device.
+        Returns a GroupRoster, which backlog() takes in place of `bcast`."""
+        import torch
+        if not isinstance(bcast, GroupBroadcast) or bcast.group is not self or \
+                bcast._tensors.get("room_set") is not room_set:
+            raise XywsError(-1, "roster() takes the result of this group's broadcast() over the same room set")
+        dec, bt = bcast.decoded, bcast._tensors
+        m, nr = len(dec.ids), room_set.nr
+        nms = [None] * m if names is None else [None if t is None else _dev_u8(t) for t in names]
+        if len(nms) != m or any(t is not None and (t.device != self.device or t.numel() > _lib.ROSTER_NAME_MAX)
+                                for t in nms):
+            raise XywsError(-1, "one name (or None) of at most 256 bytes on the group's device per item")
+        ask = {}
+        for i, r in list(joins.items() if isinstance(joins, dict) else joins):
+            ask[int(i)] = [int(r), _lib.RS_JOIN]
+        acc_row = {}
+        if on_accept:
+            if accept is None or accept.group is not self:
+                raise XywsError(-1, "on_accept needs the accept() result of this sweep")
+            acc_row = {i: k for k, i in enumerate(accept.ids)}
+            for i, r in on_accept.items():
+                if int(i) not in acc_row or int(i) in ask:
+                    raise XywsError(-1, "an on_accept connection must be an item of the accept() call and join once")
+                ask[int(i)] = [int(r), _lib.RS_JOIN_ON_ACCEPT]
+        if any(not 0 <= i < m or not 0 <= r < nr for i, (r, _) in ask.items()) or any(not 0 <= int(i) < m for i in leaves):
+            raise XywsError(-1, "joins and leaves name connections of the group and rooms of the room set")
+        gone = {int(i) for i in leaves}
+        if text is not None and max(text.head_len, text.joined_len, text.left_len) > _lib.ROSTER_TEXT_MAX:
+            raise XywsError(-1, "a text length above 32")
+        rtab, jtab = _lib.Table(_lib.RosterConn, m), _lib.Table(_lib.BacklogConn, m)
+        with torch.cuda.device(self.device):
+            results_t = torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device)
+            bbase, pbase = bt["results"].data_ptr(), self.results_t.data_ptr()
+            abase = accept.results_t.data_ptr() if acc_row else 0
+            for k, (row, jrow, t, nm) in enumerate(zip(rtab.rows, jtab.rows, bt["outs"], nms)):
+                row.name, row.name_len = (nm.data_ptr(), nm.numel()) if nm is not None and nm.numel() else (0, 0)
+                row.out, row.out_cap = t.data_ptr(), t.numel()
+                room, fl = ask.get(k, (_lib.ROOM_NONE, 0))
+                if k in acc_row and fl & _lib.RS_JOIN_ON_ACCEPT:
+                    row.accept = abase + 32 * acc_row[k]  # (the 101 is all this sweep wrote for it)
+                else:
+                    row.bcast, row.reply = bbase + 32 * k, pbase + 32 * k if bt["replied"] else 0
+                fl |= (_lib.RS_LEAVE if k in gone else 0) | (_lib.RS_LEAVE_ON_CLOSE if leave_on_close else 0)
+                row.room, row.flags = room, fl
+                jrow.out, jrow.out_cap, jrow.bcast = t.data_ptr(), t.numel(), results_t.data_ptr() + 32 * k
+                jrow.reply = pbase + 32 * k if bt["replied"] and not row.accept else 0
+                jrow.room, jrow.flags = _lib.ROOM_NONE, 0
+            tensors = dict(rconns=rtab.upload(self.device), jconns=jtab.upload(self.device), results=results_t,
+                           room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
+                           want=torch.zeros(max(m, 1), dtype=torch.int32, device=self.device), names=nms, accept=accept,
+                           text=text)
+            stream = torch.cuda.current_stream(self.device)
+            check(self.ctx.L.xyws_roster_streams(
+                self.ctx.h, C.c_void_p(room_set.bconns_t.data_ptr()), C.c_void_p(tensors["rconns"].data_ptr()), m,
+                C.c_void_p(room_set.rooms_t.data_ptr()), C.c_void_p(room_set.rrooms_t.data_ptr()),
+                C.c_void_p(tensors["room_results"].data_ptr()), nr, C.byref(text) if text is not None else None, flags,
+                C.c_void_p(tensors["jconns"].data_ptr()), C.c_void_p(tensors["want"].data_ptr()),
+                C.c_void_p(results_t.data_ptr()), C.c_void_p(stream.cuda_stream)), "xyws_roster_streams")
+            self._done[dec._slot] = torch.cuda.Event()
+            self._done[dec._slot].record(stream)
+        return GroupRoster(self, bcast, room_set, tensors)
+
+    def state_tensors(self):
+        """Every tensor of the group that carries state from one sweep to the
+        next (the carries, the counts, the backlog's logs and carries)."""
+        return [self.carry_t, self.rcarry_t, self.mcarry_t, self.hcarry_t, self.counts_t] + \
+            [log for log, _ in self._blogs] + list(self._bcarries)
+
     def backlog_carry(self, room):
         """Host copy of a room's backlog carry (synchronizes)."""
         if not 0 <= room < len(self._bcarries):
@@ -854,11 +1081,19 @@ class connection_group:
         them across sweeps: room r is the same room in every call, and a
         log_cap other than the one its log was made with is refused. When
         broadcast() was given the sweep's reply, a joiner whose reply closed
-        or overflowed is sent nothing (XYWS_BLC_NOT_RECEIVER). Returns a
-        GroupBacklog. Call it before the group's next decode()."""
+        or overflowed is sent nothing (XYWS_BLC_NOT_RECEIVER). Given the
+        GroupRoster of the sweep in place of `bcast`, the joiners are the ones
+        roster() admitted (marked on the device: pass none) and the backlog
+        goes behind the notices. Returns a GroupBacklog. Call it before the
+        group's next decode()."""
         import torch
+        roster = bcast if isinstance(bcast, GroupRoster) else None
+        if roster is not None:  # the joiners are the ones roster() admitted: its jconns table names them on the device
+            if joiners:
+                raise XywsError(-1, "after roster() the joiners are the roster's: pass none")
+            bcast = roster.bcast
         if not isinstance(bcast, GroupBroadcast) or bcast.group is not self:
-            raise XywsError(-1, "backlog() takes the result of this group's broadcast()")
+            raise XywsError(-1, "backlog() takes the result of this group's broadcast() or roster()")
         dec, bt = bcast.decoded, bcast._tensors
         messages = bt["messages"]
         reasm_p, rres_p = messages._tables() if isinstance(messages, GroupHold) else \
@@ -892,13 +1127,18 @@ class connection_group:
                 row.out, row.out_cap, row.bcast = t.data_ptr(), t.numel(), bbase + 32 * k
                 row.reply = rbase + 32 * k if bt["replied"] else 0
                 row.room, row.flags = (joined[i], _lib.BL_JOIN) if i in joined else (_lib.ROOM_NONE, 0)
-            tensors = dict(brooms=rtab.upload(self.device), jconns=jtab.upload(self.device),
+            tensors = dict(brooms=rtab.upload(self.device),
+                           jconns=jtab.upload(self.device) if roster is None else roster._tensors["jconns"],
                            room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
-                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device), bcast=bcast)
+                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device), bcast=bcast,
+                           roster=roster)
             stream = torch.cuda.current_stream(self.device)
+            # (after roster() the room table holds the next sweep's lists: the fold walks the ones this sweep's
+            # broadcast read, which roster() left in the room set's `seen` rows)
+            rooms_t = bt["rooms"] if roster is None else roster.room_set.seen_rooms_t
             check(self.ctx.L.xyws_backlog_streams(
                 self.ctx.h, C.c_void_p(reasm_p), C.c_void_p(rres_p), C.c_void_p(bt["bconns"].data_ptr()), m,
-                C.c_void_p(bt["rooms"].data_ptr()), C.c_void_p(bt["room_results"].data_ptr()),
+                C.c_void_p(rooms_t.data_ptr()), C.c_void_p(bt["room_results"].data_ptr()),
                 C.c_void_p(tensors["brooms"].data_ptr()), C.c_void_p(tensors["room_results"].data_ptr()), nr,
                 C.c_void_p(tensors["jconns"].data_ptr()), C.c_void_p(tensors["results"].data_ptr()),
                 C.c_void_p(stream.cuda_stream)), "xyws_backlog_streams")
