@@ -50,6 +50,9 @@
  *     include/xynet/http/websocket_request_handler.h           handshakes of many connections, one
  *     as websocket_handshake runs it, once per coroutine       launch), xyws_accept_request (one
  *     example/include/common/websocket.h:40-68                 request in host memory)
+ *   websocket_request_handler::get_path, which a server      xyws_route_streams (each accepted
+ *     with several rooms looks up on the host                  connection's room from its request
+ *     include/xynet/http/websocket_request_handler.h           target, one launch), xyws_route_lookup
  *   recv_all / io_service remote-queue eventfd               xyws_arena_* (pinned recv arena,
  *     include/xynet/socket/impl/recv_all.h:86-121              H2D -> decode -> D2H, completion
  *     include/xynet/io_service.h:362-381                       written to an eventfd)
@@ -1496,6 +1499,136 @@ int xyws_roster_streams(xyws_ctx* ctx,
                         xyws_backlog_conn* dev_jconns /* n, nullable */,
                         uint32_t* dev_want /* n words of caller scratch */,
                         xyws_roster_result* dev_results /* n */, void* stream);
+
+/* ---- many handshakes, one routing call ----------------------------------------
+ * Which room a joiner goes to, decided on the device from the request target
+ * (the reference's websocket_request_handler::get_path, which its examples look
+ * at on the host). xyws_route_streams runs between xyws_accept_streams and
+ * xyws_roster_streams: for every accepted connection it takes the request
+ * target out of the request bytes, looks it up in a route table that lives on
+ * the device, and writes the room into that connection's roster row, which
+ * XYWS_RS_JOIN_ON_ACCEPT then joins: `101 | welcome | recent messages` in the
+ * sweep that accepts, whatever the room, with no host read of device state.
+ *
+ * The table. xyws_route_build makes it on the host as one opaque blob (it begins
+ * with a magic and a version word; the hash and the slot layout are private to
+ * the library); the caller copies the blob to 4-byte-aligned device memory and
+ * passes it to every call. xyws_route_lookup is the same lookup over host
+ * memory: the same source compiled for the host, no context and no HIP call.
+ *   Normal form: a key loses one trailing `/` when it is longer than one byte.
+ *   Bytes are compared as they are: no percent decoding, no case folding, no
+ *   dot-segment handling. xyws_route_build refuses with XYWS_ERR_INVALID: a key
+ *   of length 0 or above XYWS_ROUTE_KEY_MAX (as given); a key that contains `?`
+ *   or `#`; two keys equal in normal form; unknown flags; a non-zero `slots`
+ *   that is not a power of two or is <= n_routes (0: the library chooses; the
+ *   smallest legal value gives the longest probe chains); null routes with
+ *   n_routes > 0, a null key, or a null host_table with cap >= the size needed.
+ *   *need receives the blob's size whenever the routes are valid (0 when they
+ *   are refused); XYWS_ERR_CAPACITY when cap < *need, and nothing is written.
+ *   The key P of a request target T is T up to its first `?` or `#`, in normal
+ *   form. Route K matches P when P equals K; a route with XYWS_ROUTE_PREFIX also
+ *   when P begins with K and the next byte of P is `/` (for K = `/` it is
+ *   enough that P begins with `/`). The longest matching K wins; it is unique.
+ *   Only the first XYWS_ROUTE_KEY_MAX bytes of P take part: a longer P has no
+ *   exact match, and its prefix candidates are those that end within that
+ *   window. `?` and `#` are looked for in the first XYWS_ROUTE_KEY_MAX + 1 bytes
+ *   of T only; a target without one there has P = T as it is (its last byte is
+ *   not looked at, so key_len is then the target's length).
+ *   A damaged blob may misroute, but nothing outside [table, table + table_len)
+ *   is ever read: every offset taken from the blob is bounds-checked, on the
+ *   host and on the device, and a probe ends after `slots` steps. A blob whose
+ *   magic, version or size is wrong (or that is not 4-byte aligned) matches
+ *   nothing: every row gets XYWS_RT_BAD_TABLE and is handled as a miss.
+ *   table_len == 0 is a table without routes: everything misses.
+ *
+ * Entry k of dev_rtconns goes with dev_aconns[k] and dev_aresults[k] (the
+ * tables of this sweep's xyws_accept_streams call) and names the roster row of
+ * that connection.
+ *
+ *  1. A row whose accept row lacks XYWS_ACC_ACCEPTED is {XYWS_RT_NOT_ACCEPTED,
+ *     XYWS_ROOM_NONE, UINT32_MAX, 0, 0}. Nothing else is written for it, not
+ *     even its roster row.
+ *  2. An accepted row has the key P of buf[path_off, path_off + path_len);
+ *     key_off and key_len name P in buf. On a match the status is
+ *     XYWS_RT_MATCHED, with XYWS_RT_BY_PREFIX when K is shorter than P; room and
+ *     route are the route's room and its index as given to xyws_route_build. On
+ *     a miss with policy 0 the status is XYWS_RT_MISS, route UINT32_MAX and
+ *     room = default_room, which may be XYWS_ROOM_NONE: accepted, but in no
+ *     room. With rconn < n_rconns, dev_rconns[rconn].room = room by one 32-bit
+ *     store; no other byte of that row is written. rconn == XYWS_ROUTE_NO_ROW:
+ *     only the result row is wanted. Any other rconn >= n_rconns sets
+ *     XYWS_RT_BAD_ROW and is never dereferenced. Two entries must not name the
+ *     same roster row.
+ *  3. A miss under XYWS_RT_MISS_404. The connection's accept row is rewritten to
+ *     what xyws_accept_streams writes for a whole request that a check refused:
+ *     status XYWS_ACC_REJECTED (| XYWS_ACC_TRUNCATED when out_cap < 64),
+ *     http_status 404, reason XYWS_ACR_NOT_FOUND, consumed kept, resp_len 64,
+ *     path_off and path_len 0, key_off UINT32_MAX. The 64 bytes `HTTP/1.1 404
+ *     Not Found`, `Connection: close`, `Content-Length: 0`, blank line go to
+ *     out[0 .. min(64, out_cap)) over the 101; no other byte of out is written
+ *     (neighbouring ranges share 16-byte lines). The route row is XYWS_RT_MISS |
+ *     XYWS_RT_NOT_FOUND with room XYWS_ROOM_NONE, which is also stored to the
+ *     roster row: xyws_roster_streams then treats the connection as a rejected
+ *     handshake by its rules 1 and 4, which is why this call runs before it.
+ *  4. Reads. Nothing outside buf[path_off, path_off + min(path_len,
+ *     XYWS_ROUTE_KEY_MAX + 1)) is read from the request but the whole 16-byte
+ *     lines that hold those bytes. The accept row is trusted only as far as
+ *     path_off + path_len <= min(len, XYWS_ACCEPT_MAX_REQUEST): a row for which
+ *     that does not hold gets XYWS_RT_BAD_ROW and a miss's status, room and
+ *     route; nothing is read from its request, and since its tables cannot be
+ *     believed nothing but the route row is written for it.
+ *  5. One launch, no context scratch, no atomics, no host read of device
+ *     state; the device error word is untouched; no reserve is needed, the call
+ *     can be captured into a hipGraph at once and runs concurrently on
+ *     different streams. n == 0 returns XYWS_OK and launches nothing.
+ *     XYWS_ERR_INVALID, decided on the arguments alone: a null ctx; null
+ *     dev_aconns, dev_aresults or dev_rtconns with n > 0; a null table with
+ *     table_len > 0; null dev_rconns with n_rconns > 0; unknown policy bits. */
+#define XYWS_ROUTE_KEY_MAX 256u
+#define XYWS_ROUTE_PREFIX  0x1u        /* xyws_route.flags */
+#define XYWS_ROUTE_NO_ROW  UINT32_MAX  /* xyws_route_conn.rconn */
+#define XYWS_RT_MISS_404   0x1u        /* policy bit */
+#define XYWS_RT_MATCHED      0x1u      /* xyws_route_result.status */
+#define XYWS_RT_BY_PREFIX    0x2u
+#define XYWS_RT_MISS         0x4u
+#define XYWS_RT_NOT_FOUND    0x8u      /* the miss was answered with the 404 */
+#define XYWS_RT_NOT_ACCEPTED 0x10u
+#define XYWS_RT_BAD_ROW      0x20u     /* rconn out of range, or an accept row that names bytes outside the request */
+#define XYWS_RT_BAD_TABLE    0x40u
+#define XYWS_ACR_NOT_FOUND 11          /* xyws_accept_result.reason after xyws_route_streams' 404 */
+
+typedef struct xyws_route {            /* host; 24 bytes */
+  const void* key;
+  uint32_t    key_len;   /* 1 .. XYWS_ROUTE_KEY_MAX */
+  uint32_t    room;
+  uint32_t    flags;     /* XYWS_ROUTE_PREFIX */
+  uint32_t    reserved;
+} xyws_route;
+
+typedef struct xyws_route_conn {       /* 8 bytes; entry k goes with dev_aconns[k], dev_aresults[k] */
+  uint32_t rconn;        /* index into dev_rconns, or XYWS_ROUTE_NO_ROW */
+  uint32_t reserved;
+} xyws_route_conn;
+
+typedef struct xyws_route_result {     /* 32 bytes */
+  uint32_t status;       /* XYWS_RT_* */
+  uint32_t room;
+  uint32_t route;        /* index given to xyws_route_build, or UINT32_MAX */
+  uint32_t key_off;      /* P in buf (in the target for xyws_route_lookup) */
+  uint32_t key_len;
+  uint32_t reserved[3];
+} xyws_route_result;
+
+int xyws_route_build(const xyws_route* routes, uint32_t n_routes, uint32_t slots /* 0: the library chooses */,
+                     void* host_table, uint64_t cap, uint64_t* need /* always written when non-null */);
+int xyws_route_lookup(const void* host_table, uint64_t table_len, const void* target, uint64_t len,
+                      xyws_route_result* res);
+int xyws_route_streams(xyws_ctx* ctx, const xyws_accept_conn* dev_aconns, xyws_accept_result* dev_aresults,
+                       const xyws_route_conn* dev_rtconns, uint64_t n,
+                       const void* dev_table, uint64_t table_len,
+                       xyws_roster_conn* dev_rconns, uint64_t n_rconns,
+                       uint32_t default_room, uint32_t policy /* XYWS_RT_MISS_404 */,
+                       xyws_route_result* dev_results /* n, nullable */, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

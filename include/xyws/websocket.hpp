@@ -445,6 +445,39 @@ inline void accept_streams(context& ctx, const xyws_accept_conn* dev_conns, std:
         "xyws_accept_streams");
 }
 
+// The route table of xyws_route_streams, built on the host (xyws_route_build):
+// one opaque blob, to be copied to 4-byte-aligned device memory as it is.
+// slots = 0 lets the library choose the table's size. Throws xyws::error for
+// what the build refuses (an empty or too long key, `?` or `#` in a key, two
+// keys equal once a trailing `/` is dropped, unknown flags, a bad slot count).
+inline std::vector<std::byte> route_table(std::span<const xyws_route> routes, std::uint32_t slots = 0) {
+  std::uint64_t need = 0;
+  const int rc = xyws_route_build(routes.data(), static_cast<std::uint32_t>(routes.size()), slots, nullptr, 0, &need);
+  if (rc != XYWS_ERR_CAPACITY) check(rc ? rc : XYWS_ERR_INVALID, "xyws_route_build");
+  std::vector<std::byte> blob(need);
+  check(xyws_route_build(routes.data(), static_cast<std::uint32_t>(routes.size()), slots, blob.data(), need, &need),
+        "xyws_route_build");
+  return blob;
+}
+
+// Which room every accepted connection goes to, in one launch between
+// accept_streams and roster_streams (xyws_route_streams): the request target of
+// dev_aconns[k] / dev_aresults[k] is looked up in the device copy of a
+// route_table() blob and the room is stored into dev_rconns[dev_rtconns[k].rconn],
+// which XYWS_RS_JOIN_ON_ACCEPT then joins. A target no route matches goes to
+// default_room (XYWS_ROOM_NONE: accepted, in no room) or, under
+// XYWS_RT_MISS_404, gets `404 Not Found` over its 101 and a rejected accept
+// row. dev_results (nullable device pointer, n entries) receives the route rows.
+inline void route_streams(context& ctx, const xyws_accept_conn* dev_aconns, xyws_accept_result* dev_aresults,
+                          const xyws_route_conn* dev_rtconns, std::uint64_t n, const void* dev_table,
+                          std::uint64_t table_len, xyws_roster_conn* dev_rconns, std::uint64_t n_rconns,
+                          xyws_route_result* dev_results = nullptr, std::uint32_t default_room = XYWS_ROOM_NONE,
+                          std::uint32_t policy = 0, void* stream = nullptr) {
+  check(xyws_route_streams(ctx.native(), dev_aconns, dev_aresults, dev_rtconns, n, dev_table, table_len, dev_rconns,
+                           n_rconns, default_room, policy, dev_results, stream),
+        "xyws_route_streams");
+}
+
 // class websocket_request_handler (websocket_request_handler.h:66-264) over
 // xyws_accept_request: host memory only, no context, no device. parse() takes
 // the accumulated request and returns what the reference's does: the bytes

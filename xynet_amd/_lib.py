@@ -335,6 +335,31 @@ ACC_ACCEPTED, ACC_REJECTED, ACC_TRUNCATED = 0x1, 0x2, 0x4  # xyws_accept_result.
 ACC_REFERENCE = 0x100  # xyws_accept_streams policy
 (ACR_NONE, ACR_PARSE, ACR_TOO_LONG, ACR_METHOD, ACR_VERSION, ACR_FOLDED, ACR_HOST, ACR_UPGRADE, ACR_CONNECTION,
  ACR_KEY, ACR_WS_VERSION) = range(11)  # xyws_accept_result.reason
+ACR_NOT_FOUND = 11  # after xyws_route_streams' 404
+
+
+class Route(C.Structure):
+    """xyws_route (include/xyws.h), 24 bytes, host memory: one route given to xyws_route_build."""
+    _fields_ = [("key", C.c_void_p), ("key_len", C.c_uint32), ("room", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class RouteConn(C.Structure):
+    """xyws_route_conn (include/xyws.h), 8 bytes: entry k goes with entry k of the accept tables."""
+    _fields_ = [("rconn", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RouteResult(C.Structure):
+    """xyws_route_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("status", C.c_uint32), ("room", C.c_uint32), ("route", C.c_uint32), ("key_off", C.c_uint32),
+                ("key_len", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(Route) == 24 and C.sizeof(RouteConn) == 8 and C.sizeof(RouteResult) == 32
+ROUTE_KEY_MAX, ROUTE_PREFIX, ROUTE_NO_ROW = 256, 0x1, 0xFFFFFFFF
+RT_MISS_404 = 0x1  # xyws_route_streams policy
+(RT_MATCHED, RT_BY_PREFIX, RT_MISS, RT_NOT_FOUND, RT_NOT_ACCEPTED, RT_BAD_ROW,
+ RT_BAD_TABLE) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40  # xyws_route_result.status
 
 
 
@@ -484,6 +509,22 @@ def load():
     # (no HIP call: xyws_accept_request over a host slab of n requests, on the calling thread)
     L.xyws_debug_accept_host.restype = i32
     L.xyws_debug_accept_host.argtypes = [vp, u64, u64, u64, u32, u32, vp, u64, u64, vp]
+    L.xyws_route_build.restype = i32
+    L.xyws_route_build.argtypes = [C.POINTER(Route), u32, u32, vp, u64, C.POINTER(u64)]
+    # (host only: no context, no HIP call)
+    L.xyws_route_lookup.restype = i32
+    L.xyws_route_lookup.argtypes = [vp, u64, vp, u64, C.POINTER(RouteResult)]
+    L.xyws_route_streams.restype = i32
+    L.xyws_route_streams.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, u32, u32, vp, vp]
+    # (no HIP call: lanes per connection, target bytes per lane, staged bytes per wave, grid cap)
+    L.xyws_debug_route_geometry.restype = i32
+    L.xyws_debug_route_geometry.argtypes = [C.POINTER(u64)]
+    # (no HIP call: the slot at which the chain of a key in normal form begins among `slots`)
+    L.xyws_debug_route_home.restype = u32
+    L.xyws_debug_route_home.argtypes = [vp, u32, u32]
+    # (no HIP call: xyws_route_lookup over the targets of a host slab of n requests, on the calling thread)
+    L.xyws_debug_route_host.restype = i32
+    L.xyws_debug_route_host.argtypes = [vp, u64, vp, u64, vp, u64, u32, vp]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]
@@ -555,6 +596,31 @@ def load_tools():
     T.xyws_tools_digest.argtypes = [vp, u64, vp, vp, vp]
     _tools = T
     return T
+
+
+def route_table(exact=None, prefix=None, slots=0):
+    """The blob xyws_route_build makes of {key bytes: room} for exact and for
+    XYWS_ROUTE_PREFIX routes (host bytes). Route indices count the exact routes
+    first, each dict in its own order."""
+    routes = [(bytes(k), int(r), 0) for k, r in (exact or {}).items()] + \
+             [(bytes(k), int(r), ROUTE_PREFIX) for k, r in (prefix or {}).items()]
+    return route_table_of(routes, slots)
+
+
+def route_table_of(routes, slots=0):
+    """xyws_route_build over (key bytes, room, flags) triples (host bytes)."""
+    lib = load()
+    rows = (Route * max(len(routes), 1))()
+    keep = [C.create_string_buffer(k, max(len(k), 1)) for k, _, _ in routes]
+    for row, buf, (k, room, flags) in zip(rows, keep, routes):
+        row.key, row.key_len, row.room, row.flags = C.addressof(buf), len(k), room, flags
+    need = C.c_uint64()
+    rc = lib.xyws_route_build(rows, len(routes), slots, None, 0, C.byref(need))
+    if rc != -4:
+        raise XywsError(rc if rc else -1, "xyws_route_build")
+    blob = C.create_string_buffer(need.value)
+    check(lib.xyws_route_build(rows, len(routes), slots, blob, need.value, C.byref(need)), "xyws_route_build")
+    return blob.raw
 
 
 def check(rc, what=""):

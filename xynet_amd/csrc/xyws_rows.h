@@ -330,6 +330,32 @@ XYWS_HD accept_fields unpack_accept(const uint64_t w[4]) {
           XYWS_GET(xyws_accept_result, path_len, c), XYWS_GET(xyws_accept_result, key_off, d)};
 }
 
+// ---------------------------------------------------------------- xyws_route_conn, xyws_route_result
+// Three words of two fields each (key_len with reserved[0], which is zero), then a reserved word.
+struct route_place { uint32_t status, room; };
+struct route_key { uint32_t route, key_off; };
+XYWS_ONE_WORD(xyws_route_conn, rconn, reserved);
+XYWS_ONE_WORD(xyws_route_result, status, room);
+XYWS_ONE_WORD(xyws_route_result, route, key_off);
+static_assert(XYWS_SHIFT(xyws_route_result, key_len) == 0 && XYWS_WORD(xyws_route_result, key_len) + 2 == sizeof(xyws_route_result) / 8,
+              "xyws_route_result: key_len begins the third of four words");
+XYWS_HD uint64_t pack_route_place(route_place p) {
+  return XYWS_PUT(xyws_route_result, status, p.status) | XYWS_PUT(xyws_route_result, room, p.room);
+}
+XYWS_HD route_place unpack_route_place(uint64_t w) {
+  return {XYWS_GET(xyws_route_result, status, w), XYWS_GET(xyws_route_result, room, w)};
+}
+XYWS_HD uint64_t pack_route_key(route_key k) {
+  return XYWS_PUT(xyws_route_result, route, k.route) | XYWS_PUT(xyws_route_result, key_off, k.key_off);
+}
+XYWS_HD route_key unpack_route_key(uint64_t w) {
+  return {XYWS_GET(xyws_route_result, route, w), XYWS_GET(xyws_route_result, key_off, w)};
+}
+// xyws_roster_conn.room as a 32-bit word of its row: what xyws_route_streams stores alone.
+constexpr uint32_t ROSTER_ROOM_HALF = offsetof(xyws_roster_conn, room) / 4;
+static_assert(offsetof(xyws_roster_conn, room) % 4 == 0 && sizeof(((xyws_roster_conn*)0)->room) == 4,
+              "xyws_roster_conn: room is one aligned 32-bit word");
+
 }  // namespace xyws_rows
 
 // ================================================================ the device part
@@ -746,6 +772,28 @@ XYWS_DEV void store_accept_result(xyws_accept_result* p, accept_fields a) {
 #pragma unroll
   for (uint32_t i = 0; i < 4; i++) ((g_u64*)p)[i] = w[i];
 }
+
+// ---- xyws_route_conn, xyws_route_result (wave-uniform), and what xyws_route_streams takes of other rows
+typedef XYWS_GLOBAL uint32_t g_u32;
+XYWS_DEV uint32_t load_route_conn(const xyws_route_conn* p) {
+  return XYWS_GET(xyws_route_conn, rconn, XYWS_LD(true, xyws_route_conn, p, rconn));
+}
+// What the route call reads of an accept row: whether it was accepted, where its request ends and its target lies.
+struct accept_target { uint32_t status, consumed, path_off, path_len; };
+XYWS_DEV accept_target load_accept_target(const xyws_accept_result* p) {
+  const uint64_t c = XYWS_LD(true, xyws_accept_result, p, path_off);
+  return {XYWS_GET(xyws_accept_result, status, XYWS_LD(true, xyws_accept_result, p, status)),
+          XYWS_GET(xyws_accept_result, consumed, XYWS_LD(true, xyws_accept_result, p, consumed)),
+          XYWS_GET(xyws_accept_result, path_off, c), XYWS_GET(xyws_accept_result, path_len, c)};
+}
+XYWS_DEV void store_route_result(xyws_route_result* p, route_place pl, route_key k, uint32_t key_len) {
+  XYWS_ST(xyws_route_result, p, status, pack_route_place(pl));
+  XYWS_ST(xyws_route_result, p, route, pack_route_key(k));
+  XYWS_ST(xyws_route_result, p, key_len, (uint64_t)key_len);
+  ((g_u64*)p)[XYWS_WORD(xyws_route_result, key_len) + 1] = 0;
+}
+// xyws_roster_conn.room alone, by one 32-bit store: no other byte of the row is written.
+XYWS_DEV void store_roster_room(xyws_roster_conn* p, uint32_t room) { ((g_u32*)p)[ROSTER_ROOM_HALF] = room; }
 
 }  // namespace xyws_rows
 #endif  // __HIPCC__

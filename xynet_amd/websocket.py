@@ -384,6 +384,58 @@ class GroupAccept:
         return self.outs[k][:n].cpu().numpy().tobytes() if n else b""
 
 
+class RouteTable:
+    """A route table on the device (connection_group.routes): the blob
+    xyws_route_build makes of the exact and the prefix routes, kept resident
+    and passed to every route() call; update() replaces it."""
+
+    def __init__(self, group, exact=None, prefix=None, slots=0):
+        self.group, self.blob_t, self.nbytes, self.host = group, None, 0, b""
+        self.update(exact, prefix, slots)
+
+    def update(self, exact=None, prefix=None, slots=0):
+        """Replace the routes (the calls already queued keep reading the old blob's storage in stream order)."""
+        import numpy as np
+        import torch
+        self.host = _lib.route_table(exact, prefix, slots)
+        fresh = torch.from_numpy(np.frombuffer(self.host, np.uint8).copy())
+        if self.blob_t is None or self.blob_t.numel() < len(self.host):
+            self.blob_t = fresh.to(self.group.device)
+        else:
+            self.blob_t[:len(self.host)].copy_(fresh)
+        self.nbytes = len(self.host)
+        return self
+
+
+class GroupRoute:
+    """Results of one connection_group.route call, item k being item k of
+    the accept() call it took (host copies on demand). It owns the
+    xyws_roster_conn rows the call wrote the rooms into, which
+    roster(route=...) completes and hands to xyws_roster_streams."""
+
+    def __init__(self, group, accept, table, rconn_of, tensors):
+        self.group, self.accept, self.table, self.rconn_of, self._tensors = group, accept, table, rconn_of, tensors
+        self.rconns_t = tensors["rconns"]
+        self._rows = _Rows(_lib.RouteResult, tensors["results"], len(accept.ids))
+
+    def result(self, k):
+        """xyws_route_result of item k."""
+        return self._rows[k]
+
+    def _complete(self, fresh, keep_rows):
+        """The host-built roster rows `fresh` over this call's rows, the room
+        words of keep_rows excepted: those are the ones the device wrote."""
+        import torch
+        col = _lib.RosterConn.room.offset // 4
+        dst = self.rconns_t.view(torch.int32).view(-1, C.sizeof(_lib.RosterConn) // 4)
+        src = fresh.view(torch.int32).view(-1, C.sizeof(_lib.RosterConn) // 4)
+        idx = torch.tensor(sorted(keep_rows), dtype=torch.long).to(self.group.device)
+        kept = dst[idx, col].clone()
+        dst.copy_(src[:dst.shape[0]])
+        dst[idx, col] = kept
+        return self.rconns_t
+
+
 class GroupMessages:
     """Results and message records of one connection_group.reassemble call,
     item k as in the decode result it took (host copies on demand; valid until
@@ -714,6 +766,54 @@ class connection_group:
                                                  C.c_void_p(stream.cuda_stream)), "xyws_accept_streams")
         return GroupAccept(self, ids, outs, table_t, results_t)
 
+    def routes(self, exact=None, prefix=None, slots=0):
+        """A route table on the device: exact = {key bytes: room} matches a
+        request target's key (the target up to its first `?` or `#`, one
+        trailing `/` dropped) byte for byte, prefix = {key bytes: room} also
+        every key below it (`/rooms` matches `/rooms/a`, `/` everything that
+        begins with `/`); the longest key wins. Returns a RouteTable."""
+        return RouteTable(self, exact, prefix, slots)
+
+    def route(self, accept, table, rconn_of=None, default_room=_lib.ROOM_NONE, miss_404=False):
+        """Send every connection that accept() accepted to the room its
+        request target names (xyws_route_streams, one launch), between
+        accept() and roster(): rconn_of[k] is the roster row (the connection
+        id of the sweep) of accept item k, None for none; by default the ids
+        given to accept(). A target no route matches goes to default_room, or
+        with miss_404 gets `404 Not Found` over its 101 and counts as a
+        rejected handshake from then on. Returns a GroupRoute, which
+        roster(route=...) takes."""
+        import torch
+        if not isinstance(accept, GroupAccept) or accept.group is not self or not isinstance(table, RouteTable) or \
+                table.group is not self:
+            raise XywsError(-1, "route() takes this group's accept() result and one of its route tables")
+        m = len(accept.ids)
+        if rconn_of is None:
+            rconn_of = dict(enumerate(accept.ids))
+        elif not isinstance(rconn_of, dict):
+            rconn_of = dict(enumerate(rconn_of))
+        rconn_of = {int(k): int(r) for k, r in rconn_of.items() if r is not None}
+        rows = list(rconn_of.values())
+        if any(not 0 <= k < m for k in rconn_of) or any(not 0 <= r < self.n for r in rows) or len(set(rows)) != len(rows):
+            raise XywsError(-1, "rconn_of names accept items and distinct connections of the group")
+        tab = _lib.Table(_lib.RouteConn, m)
+        for k in range(m):
+            tab[k].rconn = rconn_of.get(k, _lib.ROUTE_NO_ROW)
+        rtab = _lib.Table(_lib.RosterConn, self.n)
+        for i in range(self.n):
+            rtab[i].room = _lib.ROOM_NONE
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            tensors = dict(rtconns=tab.upload(self.device), rconns=rtab.upload(self.device),
+                           results=torch.zeros(max(m, 1) * 32, dtype=torch.uint8, device=self.device))
+            check(self.ctx.L.xyws_route_streams(
+                self.ctx.h, C.c_void_p(accept._table_t.data_ptr()), C.c_void_p(accept.results_t.data_ptr()),
+                C.c_void_p(tensors["rtconns"].data_ptr()), m, C.c_void_p(table.blob_t.data_ptr()), table.nbytes,
+                C.c_void_p(tensors["rconns"].data_ptr()), self.n, int(default_room),
+                _lib.RT_MISS_404 if miss_404 else 0, C.c_void_p(tensors["results"].data_ptr()),
+                C.c_void_p(stream.cuda_stream)), "xyws_route_streams")
+        return GroupRoute(self, accept, table, rconn_of, tensors)
+
     def reply_carry(self, conn_id):
         """Host copy of a connection's reply carry (synchronizes)."""
         if not 0 <= conn_id < self.n:
@@ -975,7 +1075,7 @@ class connection_group:
         return GroupBroadcast(self, dec, tensors, room_set.wires)
 
     def roster(self, bcast, room_set, names=None, joins=(), leaves=(), accept=None, on_accept=None,
-               leave_on_close=True, flags=0x11, text=None):
+               leave_on_close=True, flags=0x11, text=None, route=None):
         """Who is in the room (xyws_roster_streams, at most three launches),
         after broadcast(..., rooms=room_set) of the same sweep and before
         backlog(): the room set's lists are updated on the device from the
@@ -986,7 +1086,10 @@ class connection_group:
         None); joins: (conn_id, room) pairs; leaves: conn ids; accept with
         on_accept = {conn_id: room}: the GroupAccept of this sweep, whose
         accepted connections join that room behind their 101 in the same send
-        tensor; leave_on_close: a member whose reply closed leaves. text: a
+        tensor; with route, the GroupRoute of this sweep, on_accept may be a
+        plain collection of conn ids (and accept is the route's): each joins
+        the room route() wrote into its row on the device; leave_on_close: a
+        member whose reply closed leaves. text: a
         _lib.RosterText in place of the reference's strings. Nothing is read
         back: the next sweep's broadcast() finds the new lists on the device.
         Returns a GroupRoster, which backlog() takes in place of `bcast`."""
@@ -1003,16 +1106,25 @@ class connection_group:
         ask = {}
         for i, r in list(joins.items() if isinstance(joins, dict) else joins):
             ask[int(i)] = [int(r), _lib.RS_JOIN]
-        acc_row = {}
+        acc_row, routed = {}, set()
+        if route is not None:
+            if not isinstance(route, GroupRoute) or route.group is not self or accept not in (None, route.accept):
+                raise XywsError(-1, "route is this group's route() result over the accept() result of this sweep")
+            accept = route.accept
         if on_accept:
             if accept is None or accept.group is not self:
                 raise XywsError(-1, "on_accept needs the accept() result of this sweep")
             acc_row = {i: k for k, i in enumerate(accept.ids)}
-            for i, r in on_accept.items():
+            for i, r in (on_accept.items() if isinstance(on_accept, dict) else [(i, None) for i in on_accept]):
                 if int(i) not in acc_row or int(i) in ask:
                     raise XywsError(-1, "an on_accept connection must be an item of the accept() call and join once")
-                ask[int(i)] = [int(r), _lib.RS_JOIN_ON_ACCEPT]
-        if any(not 0 <= i < m or not 0 <= r < nr for i, (r, _) in ask.items()) or any(not 0 <= int(i) < m for i in leaves):
+                if r is None:  # the room is the one route() wrote into this connection's row
+                    if route is None or route.rconn_of.get(acc_row[int(i)]) != int(i):
+                        raise XywsError(-1, "an on_accept connection without a room needs the route() result that wrote its row")
+                    routed.add(int(i))
+                ask[int(i)] = [0 if r is None else int(r), _lib.RS_JOIN_ON_ACCEPT]
+        if any(not 0 <= i < m or (i not in routed and not 0 <= r < nr) for i, (r, _) in ask.items()) or \
+                any(not 0 <= int(i) < m for i in leaves):
             raise XywsError(-1, "joins and leaves name connections of the group and rooms of the room set")
         gone = {int(i) for i in leaves}
         if text is not None and max(text.head_len, text.joined_len, text.left_len) > _lib.ROSTER_TEXT_MAX:
@@ -1035,10 +1147,13 @@ class connection_group:
                 jrow.out, jrow.out_cap, jrow.bcast = t.data_ptr(), t.numel(), results_t.data_ptr() + 32 * k
                 jrow.reply = pbase + 32 * k if bt["replied"] and not row.accept else 0
                 jrow.room, jrow.flags = _lib.ROOM_NONE, 0
-            tensors = dict(rconns=rtab.upload(self.device), jconns=jtab.upload(self.device), results=results_t,
+            rconns_t = rtab.upload(self.device)
+            if routed:
+                rconns_t = route._complete(rconns_t, routed)
+            tensors = dict(rconns=rconns_t, jconns=jtab.upload(self.device), results=results_t,
                            room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
                            want=torch.zeros(max(m, 1), dtype=torch.int32, device=self.device), names=nms, accept=accept,
-                           text=text)
+                           text=text, route=route)
             stream = torch.cuda.current_stream(self.device)
             check(self.ctx.L.xyws_roster_streams(
                 self.ctx.h, C.c_void_p(room_set.bconns_t.data_ptr()), C.c_void_p(tensors["rconns"].data_ptr()), m,
@@ -1279,6 +1394,14 @@ class websocket_request_handler:
 
     def get_path(self):
         return self._req[self._res.path_off:self._res.path_off + self._res.path_len]
+
+    def get_room(self, table_bytes):
+        """The room the request target goes to by the route table
+        `table_bytes` (_lib.route_table's blob), None when no route matches
+        (xyws_route_lookup: the kernel's lookup compiled for the host)."""
+        path, res = self.get_path(), _lib.RouteResult()
+        check(self.L.xyws_route_lookup(table_bytes, len(table_bytes), path, len(path), C.byref(res)), "xyws_route_lookup")
+        return res.room if res.status & _lib.RT_MATCHED else None
 
     def result(self):
         return self._res
