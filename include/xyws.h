@@ -532,6 +532,14 @@ int xyws_notifier_create(int eventfd, xyws_notifier** out);
 int xyws_notifier_destroy(xyws_notifier* n);
 int xyws_notifier_signal(xyws_notifier* n, uint64_t seq); /* marks seq complete, writes the fd */
 uint64_t xyws_notifier_completed(const xyws_notifier* n); /* highest completed seq + 1 */
+/* xyws_notifier_signal(n, seq) run by `stream` itself, once it has passed
+ * everything enqueued before: a hipLaunchHostFunc callback, so that the ring
+ * learns through the eventfd that a sweep's outbox (xyws_outbox_streams) is
+ * ready as it does for an arena submission. Not for a capturing stream. The
+ * callback's block lives in the notifier, in a ring of 64: XYWS_ERR_AGAIN when
+ * the callback that last used this one's slot has not run yet. The notifier is
+ * destroyed only after every callback ran. */
+int xyws_notifier_enqueue(xyws_notifier* n, uint64_t seq, void* stream);
 
 /* ---- one batch across several devices -----------------
  * Frames are independent, so a batch of back-to-back frames splits across
@@ -1629,6 +1637,111 @@ int xyws_route_streams(xyws_ctx* ctx, const xyws_accept_conn* dev_aconns, xyws_a
                        xyws_roster_conn* dev_rconns, uint64_t n_rconns,
                        uint32_t default_room, uint32_t policy /* XYWS_RT_MISS_404 */,
                        xyws_route_result* dev_results /* n, nullable */, void* stream);
+
+/* ---- a sweep's send bytes in one buffer ------------------------------------------
+ * The last call of a sweep (the reference's chat_session::writer draining
+ * m_write_msgs into m_socket.send, and websocket_send_close, once per
+ * connection: here for every connection of the sweep at once). The calls before
+ * it leave each connection's bytes in its own send range and say how many in a
+ * result row; xyws_outbox_streams turns those rows and scattered ranges into
+ * three things the host takes with one copy, or reads in place from pinned
+ * memory: a dense pack of the send bytes, an ordered send list with one entry
+ * per connection that has something to send or must be closed, and a 64-byte
+ * summary.
+ *
+ *  1. Length. For connection i, full_len is the send_len of its backlog row when
+ *     one is given, else of its bcast row (a roster row is taken as well: its
+ *     first three fields lie alike), else the reply_len of its reply row, else
+ *     the resp_len of its accept row when that has XYWS_ACC_ACCEPTED or
+ *     XYWS_ACC_REJECTED, else 0: rule 4 of xyws_roster_streams with the backlog
+ *     row in front. len = min(full_len, out_cap); out_cap counts as 0 for a null
+ *     out.
+ *  2. Flags. XYWS_OB_CLOSE: a reply row is given and has XYWS_RPL_CLOSED, or an
+ *     accept row is given and has XYWS_ACC_REJECTED. XYWS_OB_OVERFLOW: a reply
+ *     row is given and has XYWS_RPL_OVERFLOW. XYWS_OB_TRUNCATED: full_len >
+ *     out_cap. XYWS_RPL_CLOSED is sticky: a connection that an earlier sweep
+ *     closed is listed with XYWS_OB_CLOSE and len 0 in every sweep until the
+ *     caller clears its slot (every row pointer null). A slot with every pointer
+ *     null is never listed.
+ *  3. The list. Connection i is listed when len > 0 or it has a flag. Entries
+ *     are written in ascending i, entry k to entries[k]; entries at and beyond
+ *     n_entries are not written. `off` of an entry is the sum of align16(len)
+ *     over the listed connections before it.
+ *  4. The pack. pack_cap is rounded down to a multiple of 16; a null pack counts
+ *     as capacity 0: a plan-only call, whose list and sizes are exact and in
+ *     which everything with bytes is deferred. An entry with len > 0 whose slot
+ *     [off, off + align16(len)) ends at or below the capacity is packed:
+ *     pack[off .. off + len) = out[0 .. len), the remaining bytes of the slot
+ *     zero. Otherwise the entry gets XYWS_OB_DEFERRED and no byte of its slot is
+ *     written: the caller sends it from `out` itself. Offsets never depend on
+ *     the capacity. No byte of the pack outside packed slots is written, and no
+ *     destination byte (pack, entries, summary) is read, or written twice: they
+ *     may lie across PCIe.
+ *  5. Reads. Of `out` only whole 16-byte lines that hold one of out[0 .. len)
+ *     are loaded; `out` has any alignment, and neighbours share lines. The rows
+ *     and the send ranges are only read, and the call is idempotent: a second
+ *     call over the same inputs writes the same bytes.
+ *  6. The summary is written once per call, every field exact whatever the
+ *     capacity.
+ *  7. Properties. Three launches on `stream`: a plan pass, the scan of its tile
+ *     sums by one workgroup, and the pack pass; dev_scratch (8-byte aligned,
+ *     xyws_outbox_scratch_bytes(n) bytes, the call's alone until the stream has
+ *     passed it) is the only hand-over between them. No context scratch, no
+ *     atomics, nothing spins; the device error word is untouched, no device
+ *     state is read on the host and no reserve is needed: the call can be
+ *     captured into a hipGraph at once and runs concurrently on different
+ *     streams. n == 0 returns XYWS_OK, launches nothing and leaves the summary
+ *     alone. XYWS_ERR_INVALID, decided on the arguments alone, before the
+ *     context is used: a null ctx; null dev_conns, entries, summary or
+ *     dev_scratch with n > 0; scratch_bytes below xyws_outbox_scratch_bytes(n);
+ *     a pack that is not 16-byte aligned; n >= UINT32_MAX.
+ *  8. Where the outputs may live. pack, entries and summary are device memory,
+ *     or pinned host memory addressed by its device pointer:
+ *     xyws_outbox_map(pinned_host, &dev_ptr), called at set-up time, wraps
+ *     hipHostGetDevicePointer and returns XYWS_ERR_INVALID with *dev_ptr = NULL
+ *     when the memory is not mapped for the device, so that no kernel is ever
+ *     handed a host address that was not checked. The host reads such memory
+ *     only after the stream has passed the call. */
+typedef struct xyws_outbox_conn {     /* 64 bytes; entry i is connection i of the sweep's slot-stable tables */
+  const void* out;                    /* device: the connection's send buffer (only read) */
+  uint64_t    out_cap;                /* counts as 0 for a null out */
+  const xyws_backlog_result* backlog; /* device, nullable: this sweep's rows, as the earlier calls wrote them */
+  const xyws_bcast_result*   bcast;   /* ... a roster row is taken as well */
+  const xyws_reply_result*   reply;
+  const xyws_accept_result*  accept;
+  uint64_t    reserved[2];            /* zero */
+} xyws_outbox_conn;
+
+typedef struct xyws_outbox_entry {    /* 32 bytes */
+  uint32_t conn;      /* table index */
+  uint32_t flags;     /* XYWS_OB_* */
+  uint64_t off;       /* its slot in the pack: a multiple of 16, exact whatever pack_cap */
+  uint64_t len;       /* bytes to send: min(full_len, out_cap) */
+  uint64_t full_len;  /* what the sweep produced for it (> len: XYWS_OB_TRUNCATED) */
+} xyws_outbox_entry;
+#define XYWS_OB_CLOSE     0x1u /* close the socket after these bytes */
+#define XYWS_OB_OVERFLOW  0x2u /* reply row has XYWS_RPL_OVERFLOW: the caller closes */
+#define XYWS_OB_TRUNCATED 0x4u /* full_len > out_cap: bytes were lost in the send range: the caller closes */
+#define XYWS_OB_DEFERRED  0x8u /* its slot does not fit the pack: nothing of it was packed */
+
+typedef struct xyws_outbox_summary {  /* 64 bytes */
+  uint64_t n_entries;   /* entries written */
+  uint64_t pack_len;    /* sum of all slots, whatever pack_cap */
+  uint64_t packed_len;  /* end of the last slot that was packed: the bytes of the pack the host needs */
+  uint64_t send_bytes;  /* sum of len */
+  uint32_t n_close, n_truncated, n_deferred;
+  uint32_t status;      /* XYWS_OBS_* */
+  uint64_t reserved[2];
+} xyws_outbox_summary;
+#define XYWS_OBS_DEFERRED  0x1u /* n_deferred > 0 */
+#define XYWS_OBS_TRUNCATED 0x2u /* n_truncated > 0 */
+
+uint64_t xyws_outbox_scratch_bytes(uint64_t n);   /* host; what dev_scratch must hold for n connections */
+int xyws_outbox_map(void* pinned_host, void** dev_ptr);
+int xyws_outbox_streams(xyws_ctx* ctx, const xyws_outbox_conn* dev_conns, uint64_t n,
+                        void* pack, uint64_t pack_cap,
+                        xyws_outbox_entry* entries /* room for n */, xyws_outbox_summary* summary,
+                        void* dev_scratch, uint64_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

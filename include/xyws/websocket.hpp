@@ -478,6 +478,32 @@ inline void route_streams(context& ctx, const xyws_accept_conn* dev_aconns, xyws
         "xyws_route_streams");
 }
 
+// What a sweep left to send, packed into one buffer by its last call
+// (xyws_outbox_streams, three launches): dev_conns[i] names connection i's send
+// buffer and the rows the sweep's calls wrote for it. `pack` (16-byte aligned,
+// pack_cap bytes; null: a plan-only call) receives the send bytes in slots that
+// begin at multiples of 16, `entries` (room for n) one entry per connection
+// that sends or must be closed, in table order, `summary` the counts and
+// sizes. The three may be device memory or pinned host memory addressed by its
+// device pointer (outbox_map). dev_scratch: outbox_scratch_bytes(n) bytes of
+// device memory, the call's own until the stream has passed it.
+inline std::uint64_t outbox_scratch_bytes(std::uint64_t n) { return xyws_outbox_scratch_bytes(n); }
+inline void outbox_streams(context& ctx, const xyws_outbox_conn* dev_conns, std::uint64_t n, void* pack,
+                           std::uint64_t pack_cap, xyws_outbox_entry* entries, xyws_outbox_summary* summary,
+                           void* dev_scratch, std::uint64_t scratch_bytes, void* stream = nullptr) {
+  check(xyws_outbox_streams(ctx.native(), dev_conns, n, pack, pack_cap, entries, summary, dev_scratch, scratch_bytes,
+                            stream),
+        "xyws_outbox_streams");
+}
+// The device pointer of pinned host memory for outbox_streams' outputs, checked
+// once at set-up time. Throws xyws::error when the memory is not mapped for the
+// device.
+inline void* outbox_map(void* pinned_host) {
+  void* dev = nullptr;
+  check(xyws_outbox_map(pinned_host, &dev), "xyws_outbox_map");
+  return dev;
+}
+
 // class websocket_request_handler (websocket_request_handler.h:66-264) over
 // xyws_accept_request: host memory only, no context, no device. parse() takes
 // the accumulated request and returns what the reference's does: the bytes

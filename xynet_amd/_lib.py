@@ -362,6 +362,30 @@ RT_MISS_404 = 0x1  # xyws_route_streams policy
  RT_BAD_TABLE) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40  # xyws_route_result.status
 
 
+class OutboxConn(C.Structure):
+    """xyws_outbox_conn (include/xyws.h), 64 bytes: entry i is connection i of the sweep's tables."""
+    _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("backlog", C.c_void_p), ("bcast", C.c_void_p),
+                ("reply", C.c_void_p), ("accept", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class OutboxEntry(C.Structure):
+    """xyws_outbox_entry (include/xyws.h), 32 bytes: one connection that sends or is closed."""
+    _fields_ = [("conn", C.c_uint32), ("flags", C.c_uint32), ("off", C.c_uint64), ("len", C.c_uint64),
+                ("full_len", C.c_uint64)]
+
+
+class OutboxSummary(C.Structure):
+    """xyws_outbox_summary (include/xyws.h), 64 bytes."""
+    _fields_ = [("n_entries", C.c_uint64), ("pack_len", C.c_uint64), ("packed_len", C.c_uint64),
+                ("send_bytes", C.c_uint64), ("n_close", C.c_uint32), ("n_truncated", C.c_uint32),
+                ("n_deferred", C.c_uint32), ("status", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(OutboxConn) == 64 and C.sizeof(OutboxEntry) == 32 and C.sizeof(OutboxSummary) == 64
+OB_CLOSE, OB_OVERFLOW, OB_TRUNCATED, OB_DEFERRED = 0x1, 0x2, 0x4, 0x8  # xyws_outbox_entry.flags
+OBS_DEFERRED, OBS_TRUNCATED = 0x1, 0x2  # xyws_outbox_summary.status
+
+
 
 class Table:
     """n rows of the ctypes structure `struct` (one of the row types above),
@@ -525,6 +549,18 @@ def load():
     # (no HIP call: xyws_route_lookup over the targets of a host slab of n requests, on the calling thread)
     L.xyws_debug_route_host.restype = i32
     L.xyws_debug_route_host.argtypes = [vp, u64, vp, u64, vp, u64, u32, vp]
+    L.xyws_outbox_scratch_bytes.restype = u64
+    L.xyws_outbox_scratch_bytes.argtypes = [u64]
+    L.xyws_outbox_map.restype = i32
+    L.xyws_outbox_map.argtypes = [vp, C.POINTER(vp)]
+    L.xyws_outbox_streams.restype = i32
+    L.xyws_outbox_streams.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, vp]
+    # (no HIP call: connections per tile of the plan pass, bytes per step of the pack pass, its largest grid x and y)
+    L.xyws_debug_outbox_geometry.restype = i32
+    L.xyws_debug_outbox_geometry.argtypes = [C.POINTER(u64)]
+    # (measurements: one device-to-host copy per sender, issued from C by the calling thread)
+    L.xyws_debug_outbox_host_fetch.restype = i32
+    L.xyws_debug_outbox_host_fetch.argtypes = [vp, vp, u64, vp, u64, vp]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]
@@ -569,6 +605,8 @@ def load():
     L.xyws_notifier_signal.argtypes = [vp, u64]
     L.xyws_notifier_completed.restype = u64
     L.xyws_notifier_completed.argtypes = [vp]
+    L.xyws_notifier_enqueue.restype = i32
+    L.xyws_notifier_enqueue.argtypes = [vp, u64, vp]
     L.xyws_shard_plan.restype = i32
     L.xyws_shard_plan.argtypes = [vp, u64, vp, u32, C.POINTER(u64)]
     L.xyws_shard_plan_frames.restype = i32

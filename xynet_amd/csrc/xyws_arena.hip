@@ -26,9 +26,22 @@
 
 using namespace xyws_internal;
 
+// A completion a stream reports by itself (xyws_notifier_enqueue): the block its
+// hipLaunchHostFunc callback reads, in a small ring of the notifier's own. A
+// slot is taken again only after its callback ran.
+#define XYWS_NOTIFIER_SLOTS 64
+struct xyws_notifier;
+struct notifier_cb {
+  xyws_notifier* n;
+  uint64_t seq;
+  std::atomic<bool> busy;
+};
+
 struct xyws_notifier {
   int fd;
   std::atomic<uint64_t> completed;  // highest completed seq + 1 (in-order completion)
+  std::atomic<uint64_t> next_cb;    // enqueues so far: the next one takes slot next_cb % XYWS_NOTIFIER_SLOTS
+  notifier_cb cb[XYWS_NOTIFIER_SLOTS];
 };
 
 namespace {
@@ -85,6 +98,12 @@ void on_complete(void* p) {
   notify(c->n, c->seq);
 }
 
+void on_enqueued(void* p) {
+  notifier_cb* c = static_cast<notifier_cb*>(p);
+  notify(c->n, c->seq);
+  c->busy.store(false, std::memory_order_release);
+}
+
 void arena_free(xyws_arena* a) {
   if (a->stream) (void)hipStreamSynchronize(a->stream);
   for (auto& s : a->slot) {
@@ -124,6 +143,8 @@ int xyws_notifier_create(int eventfd, xyws_notifier** out) {
   if (!n) return XYWS_ERR_NOMEM;
   n->fd = eventfd;
   n->completed.store(0);
+  n->next_cb.store(0);
+  for (auto& c : n->cb) c.busy.store(false);
   *out = n;
   return XYWS_OK;
 }
@@ -142,6 +163,20 @@ int xyws_notifier_signal(xyws_notifier* n, uint64_t seq) {
 
 uint64_t xyws_notifier_completed(const xyws_notifier* n) {
   return n ? n->completed.load(std::memory_order_acquire) : 0;
+}
+
+int xyws_notifier_enqueue(xyws_notifier* n, uint64_t seq, void* stream) {
+  if (!n) return XYWS_ERR_INVALID;
+  notifier_cb* const c = &n->cb[n->next_cb.fetch_add(1, std::memory_order_relaxed) % XYWS_NOTIFIER_SLOTS];
+  bool idle = false;
+  if (!c->busy.compare_exchange_strong(idle, true, std::memory_order_acquire)) return XYWS_ERR_AGAIN;
+  c->n = n;
+  c->seq = seq;
+  if (hipLaunchHostFunc((hipStream_t)stream, on_enqueued, c) != hipSuccess) {
+    c->busy.store(false, std::memory_order_release);
+    return XYWS_ERR_HIP;
+  }
+  return XYWS_OK;
 }
 
 int xyws_arena_create(xyws_ctx* ctx, void* host, uint64_t bytes, uint64_t max_frames, int eventfd,

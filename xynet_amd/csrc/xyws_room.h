@@ -90,7 +90,8 @@ XYWS_DEV bool frame_of(const xyws_message* rec, const member& m, uint32_t flags,
   return true;
 }
 
-// Inclusive scan of v over the workgroup (s_w: one slot per wave); total: the sum.
+// Inclusive scan of v over a workgroup of WAVES waves (s_w: one slot per wave); total: the sum.
+template <uint32_t WAVES = BC_WIRE_THREADS / BC_WAVE>
 XYWS_DEV uint64_t block_scan(uint64_t v, uint32_t tid, uint64_t* s_w, uint64_t& total) {
   const uint32_t lane = tid & (BC_WAVE - 1u), wave = tid / BC_WAVE;
   const uint64_t incl = wave_scan64(v, lane);
@@ -98,7 +99,7 @@ XYWS_DEV uint64_t block_scan(uint64_t v, uint32_t tid, uint64_t* s_w, uint64_t& 
   __syncthreads();
   uint64_t before = 0, all = 0;
 #pragma unroll
-  for (uint32_t w = 0; w < BC_WIRE_THREADS / BC_WAVE; w++) {
+  for (uint32_t w = 0; w < WAVES; w++) {
     const uint64_t x = s_w[w];
     if (w < wave) before += x;
     all += x;

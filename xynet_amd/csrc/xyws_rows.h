@@ -356,6 +356,57 @@ constexpr uint32_t ROSTER_ROOM_HALF = offsetof(xyws_roster_conn, room) / 4;
 static_assert(offsetof(xyws_roster_conn, room) % 4 == 0 && sizeof(((xyws_roster_conn*)0)->room) == 4,
               "xyws_roster_conn: room is one aligned 32-bit word");
 
+// ---------------------------------------------------------------- xyws_outbox_conn, xyws_outbox_entry, xyws_outbox_summary
+// The conn row is six whole words. An entry is four words, the first of them
+// conn and flags; the summary's counts are two words of two fields each.
+struct outbox_tag { uint32_t conn, flags; };             // xyws_outbox_entry
+struct outbox_counts { uint32_t n_close, n_truncated; };  // xyws_outbox_summary
+struct outbox_state { uint32_t n_deferred, status; };
+XYWS_ONE_WORD(xyws_outbox_entry, conn, flags);
+XYWS_ONE_WORD(xyws_outbox_summary, n_close, n_truncated);
+XYWS_ONE_WORD(xyws_outbox_summary, n_deferred, status);
+constexpr uint32_t OBE_WORDS = sizeof(xyws_outbox_entry) / 8, OBS_WORDS = sizeof(xyws_outbox_summary) / 8;
+static_assert(XYWS_WORD(xyws_outbox_conn, reserved) == 6 * XYWS_WORD(xyws_outbox_conn, out_cap) &&
+                  sizeof(xyws_outbox_conn) == 8 * 8 && XYWS_WORD(xyws_outbox_summary, reserved) + 2 == OBS_WORDS,
+              "xyws_outbox_conn: six words and two reserved; xyws_outbox_summary: two reserved words end it");
+XYWS_HD uint64_t pack_outbox_tag(outbox_tag t) {
+  return XYWS_PUT(xyws_outbox_entry, conn, t.conn) | XYWS_PUT(xyws_outbox_entry, flags, t.flags);
+}
+XYWS_HD outbox_tag unpack_outbox_tag(uint64_t w) {
+  return {XYWS_GET(xyws_outbox_entry, conn, w), XYWS_GET(xyws_outbox_entry, flags, w)};
+}
+XYWS_HD uint64_t pack_outbox_counts(outbox_counts c) {
+  return XYWS_PUT(xyws_outbox_summary, n_close, c.n_close) | XYWS_PUT(xyws_outbox_summary, n_truncated, c.n_truncated);
+}
+XYWS_HD outbox_counts unpack_outbox_counts(uint64_t w) {
+  return {XYWS_GET(xyws_outbox_summary, n_close, w), XYWS_GET(xyws_outbox_summary, n_truncated, w)};
+}
+XYWS_HD uint64_t pack_outbox_state(outbox_state s) {
+  return XYWS_PUT(xyws_outbox_summary, n_deferred, s.n_deferred) | XYWS_PUT(xyws_outbox_summary, status, s.status);
+}
+XYWS_HD outbox_state unpack_outbox_state(uint64_t w) {
+  return {XYWS_GET(xyws_outbox_summary, n_deferred, w), XYWS_GET(xyws_outbox_summary, status, w)};
+}
+// A whole entry and a whole summary as the words the kernels store, one word per thread.
+struct outbox_entry_fields { outbox_tag tag; uint64_t off, len, full_len; };
+XYWS_HD void pack_outbox_entry(const outbox_entry_fields& e, uint64_t w[OBE_WORDS]) {
+  w[XYWS_WORD(xyws_outbox_entry, conn)] = pack_outbox_tag(e.tag);
+  w[XYWS_WORD(xyws_outbox_entry, off)] = e.off;
+  w[XYWS_WORD(xyws_outbox_entry, len)] = e.len;
+  w[XYWS_WORD(xyws_outbox_entry, full_len)] = e.full_len;
+}
+struct outbox_summary_fields { uint64_t n_entries, pack_len, packed_len, send_bytes; outbox_counts counts; outbox_state state; };
+XYWS_HD void pack_outbox_summary(const outbox_summary_fields& s, uint64_t w[OBS_WORDS]) {
+  XYWS_HD_UNROLL
+  for (uint32_t i = 0; i < OBS_WORDS; i++) w[i] = 0;  // (the reserved words)
+  w[XYWS_WORD(xyws_outbox_summary, n_entries)] = s.n_entries;
+  w[XYWS_WORD(xyws_outbox_summary, pack_len)] = s.pack_len;
+  w[XYWS_WORD(xyws_outbox_summary, packed_len)] = s.packed_len;
+  w[XYWS_WORD(xyws_outbox_summary, send_bytes)] = s.send_bytes;
+  w[XYWS_WORD(xyws_outbox_summary, n_close)] = pack_outbox_counts(s.counts);
+  w[XYWS_WORD(xyws_outbox_summary, n_deferred)] = pack_outbox_state(s.state);
+}
+
 }  // namespace xyws_rows
 
 // ================================================================ the device part
@@ -794,6 +845,30 @@ XYWS_DEV void store_route_result(xyws_route_result* p, route_place pl, route_key
 }
 // xyws_roster_conn.room alone, by one 32-bit store: no other byte of the row is written.
 XYWS_DEV void store_roster_room(xyws_roster_conn* p, uint32_t room) { ((g_u32*)p)[ROSTER_ROOM_HALF] = room; }
+
+// ---- xyws_outbox_conn, and what xyws_outbox_streams takes of the sweep's result rows
+// (out_cap counts as 0 without out: then it is not loaded)
+struct outbox_conn_row { uint64_t out, out_cap, backlog, bcast, reply, accept; };
+template <bool U>
+XYWS_DEV outbox_conn_row load_outbox_conn(const xyws_outbox_conn* p) {
+  outbox_conn_row r;
+  r.out = XYWS_LD(U, xyws_outbox_conn, p, out);
+  r.out_cap = r.out ? XYWS_LD(U, xyws_outbox_conn, p, out_cap) : 0;
+  r.backlog = XYWS_LD(U, xyws_outbox_conn, p, backlog);
+  r.bcast = XYWS_LD(U, xyws_outbox_conn, p, bcast);
+  r.reply = XYWS_LD(U, xyws_outbox_conn, p, reply);
+  r.accept = XYWS_LD(U, xyws_outbox_conn, p, accept);
+  return r;
+}
+// The send buffer alone (wave-uniform): what the pack pass reads of a row.
+XYWS_DEV uint64_t load_outbox_out(const xyws_outbox_conn* p) { return XYWS_LD(true, xyws_outbox_conn, p, out); }
+// A backlog row's send_len (each thread's own load).
+XYWS_DEV uint64_t load_backlog_send_len(const xyws_backlog_result* p) {
+  return XYWS_LD(false, xyws_backlog_result, p, send_len);
+}
+// Word w of the entry at p / of the summary at p, one word per thread that calls it.
+XYWS_DEV void store_outbox_entry_word(xyws_outbox_entry* p, uint32_t w, uint64_t v) { ((g_u64*)p)[w] = v; }
+XYWS_DEV void store_outbox_summary_word(xyws_outbox_summary* p, uint32_t w, uint64_t v) { ((g_u64*)p)[w] = v; }
 
 }  // namespace xyws_rows
 #endif  // __HIPCC__

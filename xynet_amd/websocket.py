@@ -628,6 +628,53 @@ class GroupRoster:
         return self.room_set.members(r)
 
 
+class GroupOutbox:
+    """The pack, send list and summary of one connection_group.outbox call
+    (host copies on demand; every accessor waits for the call). Table row i is
+    item i of the sweep; the rows behind the sweep's items are the accept()
+    items that are no item of the sweep. conn_ids[i] is row i's connection id.
+    It owns the call's table, outputs and scratch."""
+
+    def __init__(self, group, conn_ids, outs, tensors, pack_cap, host):
+        self.group, self.conn_ids, self.outs, self._tensors = group, conn_ids, outs, tensors
+        self.pack_cap, self.host = pack_cap, host
+        self._summary = self._entries = self._pack = None
+
+    def _wait(self):
+        self._tensors["done"].synchronize()
+
+    def summary(self):
+        """xyws_outbox_summary of the call."""
+        if self._summary is None:
+            self._wait()
+            raw = self._tensors["summary"].cpu().numpy().tobytes()
+            self._summary = _lib.OutboxSummary.from_buffer_copy(raw)
+        return self._summary
+
+    def entries(self):
+        """The send list: the n_entries xyws_outbox_entry rows, in table order."""
+        if self._entries is None:
+            n, size = self.summary().n_entries, C.sizeof(_lib.OutboxEntry)
+            raw = self._tensors["entries"][:size * n].cpu().numpy().tobytes() if n else b""
+            self._entries = [_lib.OutboxEntry.from_buffer_copy(raw, size * k) for k in range(n)]
+        return self._entries
+
+    def pack(self):
+        """The first packed_len bytes of the pack (host bytes)."""
+        if self._pack is None:
+            n = self.summary().packed_len
+            self._pack = self._tensors["pack"][:n].cpu().numpy().tobytes() if n else b""
+        return self._pack
+
+    def bytes(self, k):
+        """The bytes entry k sends: its slot of the pack, or for a deferred
+        entry the first len bytes of its send tensor."""
+        e = self.entries()[k]
+        if e.flags & _lib.OB_DEFERRED:
+            return self.outs[e.conn][:e.len].cpu().numpy().tobytes()
+        return self.pack()[e.off:e.off + e.len]
+
+
 class connection_group:
     """The decoder states of n connections and one xyws_decode_streams call
     for whatever a sweep of the completion queue brought: decode() takes the
@@ -649,7 +696,9 @@ class connection_group:
     with it broadcast() reads the lists where roster(), between broadcast()
     and backlog(), keeps them (xyws_roster_streams): joins and leaves taken
     from the sweep's own rows, each said to the room as the reference's
-    welcome and farewell lines."""
+    welcome and farewell lines. outbox() ends the sweep (xyws_outbox_streams):
+    every connection's send bytes in one pack, with the list of who sends and
+    who is closed, in device or pinned host memory."""
     RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
 
     def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
@@ -855,7 +904,9 @@ class connection_group:
                 C.c_void_p(self.results_t.data_ptr()), C.c_void_p(stream.cuda_stream)), "xyws_reply_streams")
             self._done[k] = torch.cuda.Event()
             self._done[k].record(stream)
-        return GroupReply(self, result)
+        rep = GroupReply(self, result)
+        rep.outs = outs  # (outbox() packs them)
+        return rep
 
     def reassemble(self, result, out_items, opts=_lib.REASM_UTF8, msg_cap=None):
         """Gather and validate the messages of the decode() call that returned
@@ -1260,6 +1311,88 @@ class connection_group:
             self._done[dec._slot] = torch.cuda.Event()
             self._done[dec._slot].record(stream)
         return GroupBacklog(self, dec, tensors, nr)
+
+    def outbox(self, last, accept=None, pack_cap=None, host=False):
+        """Pack what a sweep left to send (xyws_outbox_streams, three
+        launches, the sweep's last call): `last` is the sweep's last result
+        object, a GroupBacklog, GroupRoster, GroupBroadcast or GroupReply (None
+        for a sweep of handshakes alone); accept, the GroupAccept of the sweep
+        for the connections still in HTTP state. Row i of the table is item i
+        of `last`, named by the rows the sweep's calls wrote for it; an
+        accept() item that is an item of the sweep gives its row the accept
+        row, any other gets a row of its own behind them. pack_cap: the pack's
+        capacity (default: what always suffices). host=True puts the pack, the
+        list and the summary into pinned host memory, which the kernels write
+        through its device pointer (xyws_outbox_map). Returns a GroupOutbox."""
+        import torch
+        roster = bcast = reply = None
+        backlog = last if isinstance(last, GroupBacklog) else None
+        if backlog is not None:
+            roster, bcast = backlog._tensors["roster"], backlog._tensors["bcast"]
+        elif isinstance(last, GroupRoster):
+            roster, bcast = last, last.bcast
+        elif isinstance(last, GroupBroadcast):
+            bcast = last
+        elif isinstance(last, GroupReply):
+            reply = last
+        elif last is not None or accept is None:
+            raise XywsError(-1, "outbox() takes the result of this group's backlog(), roster(), broadcast() or reply()")
+        if (last is not None and last.group is not self) or (accept is not None and accept.group is not self):
+            raise XywsError(-1, "outbox() takes results of this group")
+        if pack_cap is not None and int(pack_cap) < 0:
+            raise ValueError("pack_cap must not be negative")
+        ids = [] if last is None else list(last.decoded.ids)
+        if bcast is not None:
+            outs, replied = list(bcast._tensors["outs"]), bcast._tensors["replied"]
+        else:
+            outs, replied = (list(reply.outs), True) if reply is not None else ([], False)
+        m = len(ids)
+        item = {i: k for k, i in enumerate(ids)}
+        acc_of = {}
+        for j, i in enumerate(accept.ids if accept is not None else []):
+            if i in item:
+                acc_of[item[i]] = j
+            else:
+                acc_of[len(ids)] = j
+                ids.append(i)
+                outs.append(accept.outs[j])
+        n = len(ids)
+        tab = _lib.Table(_lib.OutboxConn, n)
+        jbase = backlog._tensors["results"].data_ptr() if backlog is not None else 0
+        bbase = (roster or bcast)._tensors["results"].data_ptr() if bcast is not None else 0
+        pbase, abase = self.results_t.data_ptr(), accept.results_t.data_ptr() if accept is not None else 0
+        for k, (row, t) in enumerate(zip(tab.rows, outs)):
+            row.out, row.out_cap = (t.data_ptr(), t.numel()) if t.numel() else (0, 0)
+            if k < m:
+                row.backlog, row.bcast = jbase and jbase + 32 * k, bbase and bbase + 32 * k
+                # (as roster(): a connection still in HTTP state has no reply row of this sweep)
+                row.reply = pbase + 32 * k if replied and k not in acc_of else 0
+            row.accept = abase + 32 * acc_of[k] if k in acc_of else 0
+        cap = sum((t.numel() + 15) & ~15 for t in outs) if pack_cap is None else int(pack_cap)
+        L = self.ctx.L
+        need = L.xyws_outbox_scratch_bytes(n)
+        with torch.cuda.device(self.device):
+            sizes = dict(pack=max(cap, 16), entries=32 * max(n, 1), summary=64)
+            if host:
+                keep = {k: torch.zeros(v, dtype=torch.uint8).pin_memory() for k, v in sizes.items()}
+                ptr = {}
+                for k, t in keep.items():
+                    d = C.c_void_p()
+                    check(L.xyws_outbox_map(C.c_void_p(t.data_ptr()), C.byref(d)), "xyws_outbox_map")
+                    ptr[k] = d.value
+            else:
+                keep = {k: torch.zeros(v, dtype=torch.uint8, device=self.device) for k, v in sizes.items()}
+                ptr = {k: t.data_ptr() for k, t in keep.items()}
+            tensors = dict(keep, conns=tab.upload(self.device), last=last, accept=accept,
+                           scratch=torch.empty(max(need, 8), dtype=torch.uint8, device=self.device))
+            stream = torch.cuda.current_stream(self.device)
+            check(L.xyws_outbox_streams(
+                self.ctx.h, C.c_void_p(tensors["conns"].data_ptr()), n, C.c_void_p(ptr["pack"]) if cap else None, cap,
+                C.c_void_p(ptr["entries"]), C.c_void_p(ptr["summary"]), C.c_void_p(tensors["scratch"].data_ptr()),
+                tensors["scratch"].numel(), C.c_void_p(stream.cuda_stream)), "xyws_outbox_streams")
+            tensors["done"] = torch.cuda.Event()
+            tensors["done"].record(stream)
+        return GroupOutbox(self, ids, outs, tensors, cap, host)
 
     def msg_carry(self, conn_id):
         """Host copy of a connection's message carry (synchronizes)."""
