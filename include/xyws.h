@@ -1743,6 +1743,196 @@ int xyws_outbox_streams(xyws_ctx* ctx, const xyws_outbox_conn* dev_conns, uint64
                         xyws_outbox_entry* entries /* room for n */, xyws_outbox_summary* summary,
                         void* dev_scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- a sweep's received bytes to the connections ----------------------------------
+ * The first call of a sweep, the mirror of xyws_outbox_streams (the reference
+ * hands every socket its own recv buffer, recv_all.h:86-121; an io_uring
+ * service drains its completion queue instead). While it drains, the host
+ * fills three things: a dense pack of the received bytes, an entry list with
+ * one 32-byte entry per completed recv in arrival order (any number per
+ * connection), and a 32-byte head that says how many entries there are.
+ * xyws_inbox_streams scatters the bytes into the connections' receive ranges,
+ * keeps a small per-connection carry (HTTP, open or dead, and the bytes of an
+ * unfinished request) and writes the buf and len words of the slot-stable,
+ * resident xyws_conn and xyws_accept_conn rows, so that xyws_accept_streams,
+ * xyws_decode_streams and the calls behind them run over tables the host
+ * never touches again. The entry count comes from the head, not from an
+ * argument: one captured graph serves sweeps of any shape.
+ *
+ *  1. Entries. M = min(head.m, m_cap); entries from M on are never read
+ *     (head.m > m_cap: XYWS_IBM_CLIPPED). With P = min(head.pack_len,
+ *     pack_cap) an entry is valid when conn < n and off <= P and
+ *     len <= P - off. An entry with conn >= n is ignored and counted in
+ *     n_bad_entries; one with conn < n and a bad range is counted there too
+ *     and breaks its connection (rule 4). `at` is the host's running count of
+ *     the connection's bytes in this sweep before this entry: with it the
+ *     order of a connection's bytes does not depend on where its entries
+ *     stand in the list.
+ *  2. Per connection i, over its valid entries: T = max(at + len), 0 when
+ *     there are none; S = the sum of len; eof = any entry of the connection
+ *     (bad ranges included) has XYWS_IBE_EOF. n_entries of its result row
+ *     counts every entry with conn == i.
+ *  3. State step, before anything is placed; s = carry.state.
+ *     - s is XYWS_IB_DEAD (or any value above it): the entries are dropped,
+ *       XYWS_IBR_DROPPED when there were any, every length written is 0.
+ *     - s is HTTP and XYWS_IBC_NO_HANDSHAKE is set: s becomes open (kept and
+ *       lead 0, not counted in n_opened).
+ *     - s is HTTP and aresult has XYWS_ACC_REJECTED: s becomes dead, the
+ *       carry gets the sticky XYWS_IBR_REFUSED, the entries are dropped.
+ *     - s is HTTP and aresult has XYWS_ACC_ACCEPTED: the connection opens.
+ *       consumed <= http_len is required, otherwise it is broken
+ *       (XYWS_IBR_BAD_CONSUMED). kept = http_len - consumed: the frame bytes
+ *       that arrived behind the request in an earlier sweep and already lie
+ *       in the range. lead = consumed when kept > 0, else 0. The result row
+ *       gets XYWS_IBR_OPENED and n_opened counts it, unless rule 4 breaks it.
+ *     - otherwise (no aresult, or neither bit) s stays HTTP.
+ *     The verdict is the slot's accept row, whoever's request left it:
+ *     xyws_accept_streams overwrites it with "incomplete" only in the sweep
+ *     after the verdict, when it sees len 0. A slot that changes hands
+ *     therefore needs both its carry and its xyws_accept_result row zeroed
+ *     before the new connection's first sweep; otherwise the new connection
+ *     is refused, or broken by the old `consumed`, on the old one's row.
+ *  4. Placement. Base A = http_len while s is HTTP, and in the opening sweep
+ *     when kept > 0; otherwise A = 0. The connection is broken when S != T
+ *     (XYWS_IBR_BAD_TILING), when A + T > cap (XYWS_IBR_OVERFLOW) or when an
+ *     entry of it has a bad range (XYWS_IBR_BAD_RANGE); every bit that
+ *     applies is set. Broken: no byte of its range is written, every length
+ *     written is 0, lead is 0, the state becomes dead and the bits stay in
+ *     the carry until the caller resets it; n_broken counts it. Otherwise
+ *     range[A + at, A + at + len) = pack[off, off + len) for every entry.
+ *     Entries of one connection that overlap while S == T are the caller's
+ *     fault: the bytes inside that connection's own [A, A + T) are then
+ *     unspecified, nothing else is touched.
+ *  5. Rows. Only the buf and len words are written; carry, frames, cap, out
+ *     and out_cap stay the caller's.
+ *     - open: conn->buf = buf + lead, conn->len = kept + T (kept only in the
+ *       opening sweep), aconn->buf = buf, aconn->len = 0, http_len = 0.
+ *     - HTTP: http_len += T; aconn->buf = buf; aconn->len = the new http_len
+ *       when T > 0, else 0 (a request that got no new bytes is not parsed
+ *       again: xyws_accept_streams reports len 0 as incomplete);
+ *       conn->buf = buf, conn->len = 0.
+ *     - dead: conn->buf = aconn->buf = buf, both lengths 0; http_len stays.
+ *     An idle connection therefore always ends with len 0: no stale length
+ *     survives a sweep.
+ *  6. EOF. The bytes are still delivered; the result row gets XYWS_IBR_EOF,
+ *     and the carry keeps it (a later row shows it again). n_eof counts the
+ *     connections whose entries of this sweep had it. Raising the roster's
+ *     leave stays with the caller.
+ *  7. Outputs. carry.bytes_total grows by the bytes placed. A result row is
+ *     written for every i < n: len (bytes placed: T or 0), lead, n_entries,
+ *     status (the carry's sticky bits, and XYWS_IBR_DROPPED / XYWS_IBR_OPENED
+ *     of this sweep). The summary is written once, every field exact:
+ *     n_entries = M, bytes = the sum of len over the rows, n_conns = rows
+ *     with n_entries > 0, n_opened, n_eof, n_broken (broken in this sweep),
+ *     n_bad_entries, status (XYWS_IBM_*).
+ *  8. Memory. No byte outside [buf + A, buf + A + T) of any range is written:
+ *     neighbouring ranges share 16-byte lines and have any alignment. Of the
+ *     pack only whole 16-byte lines that hold an entry's byte are loaded; off
+ *     has any alignment. Head and entries are read by the entry pass only,
+ *     which keeps what the later passes need in dev_scratch: in pinned memory
+ *     every entry crosses the host link once, and the 32-byte head once per
+ *     workgroup of that pass (at most 256 times). The iconn table, head, entries and pack
+ *     are only read. The ranges, carries and rows of two entries of dev_iconns
+ *     must not overlap.
+ *  9. Properties. Five launches on `stream`: clear the per-connection
+ *     accumulators; the entry pass (integer atomicAdd / atomicMax / atomicOr
+ *     on the accumulators, whose results do not depend on order); the
+ *     connection pass, one thread per connection, which also leaves tile
+ *     sums; the summary pass of one workgroup; the copy pass, whose grid comes
+ *     from m_cap alone, one wave per 1 KiB chunk of an entry. Nothing spins,
+ *     no workgroup waits for another. dev_scratch (8-byte aligned,
+ *     xyws_inbox_scratch_bytes(n, m_cap) bytes, the call's alone until the
+ *     stream has passed it) is the only hand-over. No context scratch; the
+ *     device error word is untouched, no device state is read on the host and
+ *     no reserve is needed: the call can be captured into a hipGraph at once
+ *     and runs concurrently on different streams. n == 0 returns XYWS_OK,
+ *     launches nothing and leaves the summary alone. XYWS_ERR_INVALID,
+ *     decided on the arguments alone: a null ctx; null dev_iconns, head,
+ *     summary or dev_scratch with n > 0; null entries with m_cap > 0; a null
+ *     pack with pack_cap > 0; with n > 0 a dev_scratch that is not 8-byte
+ *     aligned, or scratch_bytes below xyws_inbox_scratch_bytes(n, m_cap);
+ *     n or m_cap >= UINT32_MAX.
+ * 10. The invariant. Cut a connection's byte stream (request, then frames)
+ *     into entries and sweeps at any points and run xyws_inbox_streams,
+ *     xyws_accept_streams, xyws_decode_streams over the slot-stable tables,
+ *     sweep after sweep: the accept verdict equals xyws_accept_request on the
+ *     request, and the frames, the decoded bytes and the final xyws_carry
+ *     equal xyws_decode_stream over the bytes behind `consumed`.
+ *
+ * Head, entries and pack are device memory, or pinned host memory addressed
+ * by the device pointer that xyws_outbox_map returns. */
+typedef struct xyws_inbox_head {      /* 32 bytes */
+  uint64_t m;          /* entries in the list */
+  uint64_t pack_len;   /* bytes of the pack in use */
+  uint64_t reserved[2];
+} xyws_inbox_head;
+
+typedef struct xyws_inbox_entry {     /* 32 bytes: one completed recv */
+  uint32_t conn;       /* table index */
+  uint32_t flags;      /* XYWS_IBE_* */
+  uint64_t off;        /* in the pack, any alignment */
+  uint64_t len;        /* 0 allowed (an EOF alone) */
+  uint64_t at;         /* bytes of this connection in this sweep that precede this entry */
+} xyws_inbox_entry;
+#define XYWS_IBE_EOF 0x1u /* the peer closed behind these bytes */
+
+typedef struct xyws_inbox_carry {     /* 32 bytes; all zero: fresh, HTTP state */
+  uint64_t http_len;   /* bytes of the unfinished request in the range */
+  uint64_t bytes_total;
+  uint32_t state;      /* XYWS_IB_* */
+  uint32_t status;     /* the sticky XYWS_IBR_* bits */
+  uint64_t reserved;
+} xyws_inbox_carry;
+#define XYWS_IB_HTTP 0u
+#define XYWS_IB_OPEN 1u
+#define XYWS_IB_DEAD 2u
+
+typedef struct xyws_inbox_conn {      /* 64 bytes; entry i is connection i of the sweep's slot-stable tables */
+  void*                     buf;      /* device: the connection's receive range */
+  uint64_t                  cap;
+  xyws_inbox_carry*         carry;    /* device; read, then written */
+  xyws_conn*                conn;     /* device, nullable: the row whose buf and len are written */
+  xyws_accept_conn*         aconn;    /* device, nullable: the row whose buf and len are written */
+  const xyws_accept_result* aresult;  /* device, nullable: as the previous sweep left it */
+  uint32_t                  flags;    /* XYWS_IBC_* */
+  uint32_t                  reserved0;
+  uint64_t                  reserved;
+} xyws_inbox_conn;
+#define XYWS_IBC_NO_HANDSHAKE 0x1u /* the connection never was in HTTP state */
+
+typedef struct xyws_inbox_result {    /* 32 bytes */
+  uint64_t len;        /* bytes placed in this sweep */
+  uint64_t lead;       /* opening sweep with kept bytes: conn->buf = buf + lead */
+  uint32_t n_entries;  /* entries that named this connection */
+  uint32_t status;     /* XYWS_IBR_* */
+  uint64_t reserved;
+} xyws_inbox_result;
+#define XYWS_IBR_EOF          0x1u  /* sticky */
+#define XYWS_IBR_DROPPED      0x2u  /* this sweep's entries were dropped: the connection is dead */
+#define XYWS_IBR_REFUSED      0x4u  /* sticky: its handshake was rejected */
+#define XYWS_IBR_BAD_TILING   0x8u  /* sticky: S != T */
+#define XYWS_IBR_OVERFLOW     0x10u /* sticky: A + T > cap */
+#define XYWS_IBR_BAD_RANGE    0x20u /* sticky: an entry outside the pack */
+#define XYWS_IBR_BAD_CONSUMED 0x40u /* sticky: consumed > http_len */
+#define XYWS_IBR_OPENED       0x80u /* the connection opened in this sweep */
+
+typedef struct xyws_inbox_summary {   /* 64 bytes */
+  uint64_t n_entries;  /* M */
+  uint64_t bytes;      /* bytes placed */
+  uint32_t n_conns, n_opened, n_eof, n_broken, n_bad_entries;
+  uint32_t status;     /* XYWS_IBM_* */
+  uint64_t reserved[3];
+} xyws_inbox_summary;
+#define XYWS_IBM_BAD_ENTRIES 0x1u /* n_bad_entries > 0 */
+#define XYWS_IBM_BROKEN      0x2u /* n_broken > 0 */
+#define XYWS_IBM_CLIPPED     0x4u /* head.m > m_cap */
+
+uint64_t xyws_inbox_scratch_bytes(uint64_t n, uint64_t m_cap);   /* host */
+int xyws_inbox_streams(xyws_ctx* ctx, const xyws_inbox_conn* dev_iconns, uint64_t n,
+                       const xyws_inbox_head* head, const xyws_inbox_entry* entries, uint64_t m_cap,
+                       const void* pack, uint64_t pack_cap,
+                       xyws_inbox_result* dev_results /* n, nullable */, xyws_inbox_summary* summary,
+                       void* dev_scratch, uint64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

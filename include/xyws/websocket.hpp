@@ -504,6 +504,28 @@ inline void* outbox_map(void* pinned_host) {
   return dev;
 }
 
+// A sweep's received bytes scattered to the connections by its first call
+// (xyws_inbox_streams, five launches): dev_iconns[i] names connection i's
+// receive range, its inbox carry and the resident xyws_conn and
+// xyws_accept_conn rows whose buf and len the call writes. `head` says how
+// many of the `entries` (room for m_cap) the sweep brought, `pack` (pack_cap
+// bytes) holds their bytes; the three may be device memory or pinned host
+// memory addressed by its device pointer (outbox_map). dev_results (n rows,
+// nullable) and `summary` receive what was placed. dev_scratch:
+// inbox_scratch_bytes(n, m_cap) bytes of device memory, the call's own until
+// the stream has passed it.
+inline std::uint64_t inbox_scratch_bytes(std::uint64_t n, std::uint64_t m_cap) {
+  return xyws_inbox_scratch_bytes(n, m_cap);
+}
+inline void inbox_streams(context& ctx, const xyws_inbox_conn* dev_iconns, std::uint64_t n, const xyws_inbox_head* head,
+                          const xyws_inbox_entry* entries, std::uint64_t m_cap, const void* pack, std::uint64_t pack_cap,
+                          xyws_inbox_result* dev_results, xyws_inbox_summary* summary, void* dev_scratch,
+                          std::uint64_t scratch_bytes, void* stream = nullptr) {
+  check(xyws_inbox_streams(ctx.native(), dev_iconns, n, head, entries, m_cap, pack, pack_cap, dev_results, summary,
+                           dev_scratch, scratch_bytes, stream),
+        "xyws_inbox_streams");
+}
+
 // class websocket_request_handler (websocket_request_handler.h:66-264) over
 // xyws_accept_request: host memory only, no context, no device. parse() takes
 // the accumulated request and returns what the reference's does: the bytes

@@ -386,6 +386,52 @@ OB_CLOSE, OB_OVERFLOW, OB_TRUNCATED, OB_DEFERRED = 0x1, 0x2, 0x4, 0x8  # xyws_ou
 OBS_DEFERRED, OBS_TRUNCATED = 0x1, 0x2  # xyws_outbox_summary.status
 
 
+class InboxHead(C.Structure):
+    """xyws_inbox_head (include/xyws.h), 32 bytes: how many entries a sweep brought."""
+    _fields_ = [("m", C.c_uint64), ("pack_len", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+class InboxEntry(C.Structure):
+    """xyws_inbox_entry (include/xyws.h), 32 bytes: one completed recv."""
+    _fields_ = [("conn", C.c_uint32), ("flags", C.c_uint32), ("off", C.c_uint64), ("len", C.c_uint64),
+                ("at", C.c_uint64)]
+
+
+class InboxCarry(C.Structure):
+    """xyws_inbox_carry (include/xyws.h), 32 bytes; all zero: fresh, HTTP state."""
+    _fields_ = [("http_len", C.c_uint64), ("bytes_total", C.c_uint64), ("state", C.c_uint32), ("status", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+class InboxConn(C.Structure):
+    """xyws_inbox_conn (include/xyws.h), 64 bytes: entry i is connection i of the sweep's tables."""
+    _fields_ = [("buf", C.c_void_p), ("cap", C.c_uint64), ("carry", C.c_void_p), ("conn", C.c_void_p),
+                ("aconn", C.c_void_p), ("aresult", C.c_void_p), ("flags", C.c_uint32), ("reserved0", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+class InboxResult(C.Structure):
+    """xyws_inbox_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("len", C.c_uint64), ("lead", C.c_uint64), ("n_entries", C.c_uint32), ("status", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+class InboxSummary(C.Structure):
+    """xyws_inbox_summary (include/xyws.h), 64 bytes."""
+    _fields_ = [("n_entries", C.c_uint64), ("bytes", C.c_uint64), ("n_conns", C.c_uint32), ("n_opened", C.c_uint32),
+                ("n_eof", C.c_uint32), ("n_broken", C.c_uint32), ("n_bad_entries", C.c_uint32), ("status", C.c_uint32),
+                ("reserved", C.c_uint64 * 3)]
+
+
+assert (C.sizeof(InboxHead), C.sizeof(InboxEntry), C.sizeof(InboxCarry), C.sizeof(InboxConn), C.sizeof(InboxResult),
+        C.sizeof(InboxSummary)) == (32, 32, 32, 64, 32, 64)
+IBE_EOF = 0x1  # xyws_inbox_entry.flags
+IBC_NO_HANDSHAKE = 0x1  # xyws_inbox_conn.flags
+IB_HTTP, IB_OPEN, IB_DEAD = 0, 1, 2  # xyws_inbox_carry.state
+(IBR_EOF, IBR_DROPPED, IBR_REFUSED, IBR_BAD_TILING, IBR_OVERFLOW, IBR_BAD_RANGE, IBR_BAD_CONSUMED,
+ IBR_OPENED) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40, 0x80  # xyws_inbox_result.status
+IBM_BAD_ENTRIES, IBM_BROKEN, IBM_CLIPPED = 0x1, 0x2, 0x4  # xyws_inbox_summary.status
+
 
 class Table:
     """n rows of the ctypes structure `struct` (one of the row types above),
@@ -561,6 +607,16 @@ def load():
     # (measurements: one device-to-host copy per sender, issued from C by the calling thread)
     L.xyws_debug_outbox_host_fetch.restype = i32
     L.xyws_debug_outbox_host_fetch.argtypes = [vp, vp, u64, vp, u64, vp]
+    L.xyws_inbox_scratch_bytes.restype = u64
+    L.xyws_inbox_scratch_bytes.argtypes = [u64, u64]
+    L.xyws_inbox_streams.restype = i32
+    L.xyws_inbox_streams.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp]
+    # (no HIP call: connections per tile, bytes per step of the copy pass, its largest grid x and y, the entry pass's grid)
+    L.xyws_debug_inbox_geometry.restype = i32
+    L.xyws_debug_inbox_geometry.argtypes = [C.POINTER(u64)]
+    # (measurements: one host-to-device copy per entry, issued from C by the calling thread)
+    L.xyws_debug_inbox_host_scatter.restype = i32
+    L.xyws_debug_inbox_host_scatter.argtypes = [vp, vp, vp, u64, vp, vp]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]

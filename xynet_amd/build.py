@@ -23,7 +23,8 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-falign-loops=64", "-std=c++17", "-f
 TARGETS = {
     "libxyws.so": ["xyws.hip", "xyws_stream.hip", "xyws_frames.hip", "xyws_arena.hip", "xyws_shard.hip",
                    "xyws_streams.hip", "xyws_reply.hip", "xyws_reasm_streams.hip", "xyws_broadcast.hip", "xyws_hold.hip",
-                   "xyws_backlog.hip", "xyws_accept.hip", "xyws_roster.hip", "xyws_route.hip", "xyws_outbox.hip"],
+                   "xyws_backlog.hip", "xyws_accept.hip", "xyws_roster.hip", "xyws_route.hip", "xyws_outbox.hip",
+                   "xyws_inbox.hip"],
     "libxyws_tools.so": ["xyws_tools.hip"],
 }
 DEPS = ["xyws_device.h", "xyws_host.h", "xyws_stream.h", "xyws_ctx.h", "xyws_lattice.h", "xyws_frameops.h", "xyws_lines.h",

@@ -407,6 +407,83 @@ XYWS_HD void pack_outbox_summary(const outbox_summary_fields& s, uint64_t w[OBS_
   w[XYWS_WORD(xyws_outbox_summary, n_deferred)] = pack_outbox_state(s.state);
 }
 
+// ---------------------------------------------------------------- the inbox's rows
+// Head, entry, carry and result are four words each, the conn row and the
+// summary eight. Every word that holds two fields is stated here.
+struct inbox_tag { uint32_t conn, flags; };            // xyws_inbox_entry
+struct inbox_state { uint32_t state, status; };        // xyws_inbox_carry
+struct inbox_flags { uint32_t flags, reserved0; };     // xyws_inbox_conn
+struct inbox_counts { uint32_t n_entries, status; };   // xyws_inbox_result
+struct inbox_conns { uint32_t n_conns, n_opened; };    // xyws_inbox_summary
+struct inbox_ends { uint32_t n_eof, n_broken; };
+struct inbox_bad { uint32_t n_bad_entries, status; };
+XYWS_ONE_WORD(xyws_inbox_entry, conn, flags);
+XYWS_ONE_WORD(xyws_inbox_carry, state, status);
+XYWS_ONE_WORD(xyws_inbox_conn, flags, reserved0);
+XYWS_ONE_WORD(xyws_inbox_result, n_entries, status);
+XYWS_ONE_WORD(xyws_inbox_summary, n_conns, n_opened);
+XYWS_ONE_WORD(xyws_inbox_summary, n_eof, n_broken);
+XYWS_ONE_WORD(xyws_inbox_summary, n_bad_entries, status);
+constexpr uint32_t IBS_WORDS = sizeof(xyws_inbox_summary) / 8;
+static_assert(sizeof(xyws_inbox_head) == 4 * 8 && sizeof(xyws_inbox_entry) == 4 * 8 && sizeof(xyws_inbox_carry) == 4 * 8 &&
+                  sizeof(xyws_inbox_conn) == 8 * 8 && sizeof(xyws_inbox_result) == 4 * 8 &&
+                  XYWS_WORD(xyws_inbox_summary, reserved) + 3 == IBS_WORDS &&
+                  XYWS_WORD(xyws_inbox_result, reserved) == 3 * XYWS_WORD(xyws_inbox_result, lead),
+              "the inbox's rows: whole words, the summary ends with three reserved ones, a result row with one");
+XYWS_HD uint64_t pack_inbox_tag(inbox_tag t) {
+  return XYWS_PUT(xyws_inbox_entry, conn, t.conn) | XYWS_PUT(xyws_inbox_entry, flags, t.flags);
+}
+XYWS_HD inbox_tag unpack_inbox_tag(uint64_t w) {
+  return {XYWS_GET(xyws_inbox_entry, conn, w), XYWS_GET(xyws_inbox_entry, flags, w)};
+}
+XYWS_HD uint64_t pack_inbox_state(inbox_state s) {
+  return XYWS_PUT(xyws_inbox_carry, state, s.state) | XYWS_PUT(xyws_inbox_carry, status, s.status);
+}
+XYWS_HD inbox_state unpack_inbox_state(uint64_t w) {
+  return {XYWS_GET(xyws_inbox_carry, state, w), XYWS_GET(xyws_inbox_carry, status, w)};
+}
+XYWS_HD uint64_t pack_inbox_flags(inbox_flags f) {
+  return XYWS_PUT(xyws_inbox_conn, flags, f.flags) | XYWS_PUT(xyws_inbox_conn, reserved0, f.reserved0);
+}
+XYWS_HD inbox_flags unpack_inbox_flags(uint64_t w) {
+  return {XYWS_GET(xyws_inbox_conn, flags, w), XYWS_GET(xyws_inbox_conn, reserved0, w)};
+}
+XYWS_HD uint64_t pack_inbox_counts(inbox_counts c) {
+  return XYWS_PUT(xyws_inbox_result, n_entries, c.n_entries) | XYWS_PUT(xyws_inbox_result, status, c.status);
+}
+XYWS_HD inbox_counts unpack_inbox_counts(uint64_t w) {
+  return {XYWS_GET(xyws_inbox_result, n_entries, w), XYWS_GET(xyws_inbox_result, status, w)};
+}
+XYWS_HD uint64_t pack_inbox_conns(inbox_conns c) {
+  return XYWS_PUT(xyws_inbox_summary, n_conns, c.n_conns) | XYWS_PUT(xyws_inbox_summary, n_opened, c.n_opened);
+}
+XYWS_HD inbox_conns unpack_inbox_conns(uint64_t w) {
+  return {XYWS_GET(xyws_inbox_summary, n_conns, w), XYWS_GET(xyws_inbox_summary, n_opened, w)};
+}
+XYWS_HD uint64_t pack_inbox_ends(inbox_ends e) {
+  return XYWS_PUT(xyws_inbox_summary, n_eof, e.n_eof) | XYWS_PUT(xyws_inbox_summary, n_broken, e.n_broken);
+}
+XYWS_HD inbox_ends unpack_inbox_ends(uint64_t w) {
+  return {XYWS_GET(xyws_inbox_summary, n_eof, w), XYWS_GET(xyws_inbox_summary, n_broken, w)};
+}
+XYWS_HD uint64_t pack_inbox_bad(inbox_bad b) {
+  return XYWS_PUT(xyws_inbox_summary, n_bad_entries, b.n_bad_entries) | XYWS_PUT(xyws_inbox_summary, status, b.status);
+}
+XYWS_HD inbox_bad unpack_inbox_bad(uint64_t w) {
+  return {XYWS_GET(xyws_inbox_summary, n_bad_entries, w), XYWS_GET(xyws_inbox_summary, status, w)};
+}
+// A whole summary as the words the summary pass stores, one word per thread.
+struct inbox_summary_fields { uint64_t n_entries, bytes; inbox_conns conns; inbox_ends ends; inbox_bad bad; };
+XYWS_HD void pack_inbox_summary(const inbox_summary_fields& s, uint64_t w[IBS_WORDS]) {
+  XYWS_HD_UNROLL
+  for (uint32_t i = 0; i < IBS_WORDS; i++) w[i] = 0;  // (the reserved words)
+  w[XYWS_WORD(xyws_inbox_summary, n_entries)] = s.n_entries;
+  w[XYWS_WORD(xyws_inbox_summary, bytes)] = s.bytes;
+  w[XYWS_WORD(xyws_inbox_summary, n_conns)] = pack_inbox_conns(s.conns);
+  w[XYWS_WORD(xyws_inbox_summary, n_eof)] = pack_inbox_ends(s.ends);
+  w[XYWS_WORD(xyws_inbox_summary, n_bad_entries)] = pack_inbox_bad(s.bad);
+}
+
 }  // namespace xyws_rows
 
 // ================================================================ the device part
@@ -869,6 +946,59 @@ XYWS_DEV uint64_t load_backlog_send_len(const xyws_backlog_result* p) {
 // Word w of the entry at p / of the summary at p, one word per thread that calls it.
 XYWS_DEV void store_outbox_entry_word(xyws_outbox_entry* p, uint32_t w, uint64_t v) { ((g_u64*)p)[w] = v; }
 XYWS_DEV void store_outbox_summary_word(xyws_outbox_summary* p, uint32_t w, uint64_t v) { ((g_u64*)p)[w] = v; }
+
+// ---- the inbox's rows, and the words of other rows that xyws_inbox_streams reads or rewrites
+struct inbox_head_row { uint64_t m, pack_len; };
+XYWS_DEV inbox_head_row load_inbox_head(const xyws_inbox_head* p) {
+  return {XYWS_LD(false, xyws_inbox_head, p, m), XYWS_LD(false, xyws_inbox_head, p, pack_len)};
+}
+struct inbox_entry_row { inbox_tag tag; uint64_t off, len, at; };  // (each thread's own entry)
+XYWS_DEV inbox_entry_row load_inbox_entry(const xyws_inbox_entry* p) {
+  return {unpack_inbox_tag(XYWS_LD(false, xyws_inbox_entry, p, conn)), XYWS_LD(false, xyws_inbox_entry, p, off),
+          XYWS_LD(false, xyws_inbox_entry, p, len), XYWS_LD(false, xyws_inbox_entry, p, at)};
+}
+struct inbox_conn_row { uint64_t buf, cap, carry, conn, aconn, aresult; uint32_t flags; };
+XYWS_DEV inbox_conn_row load_inbox_conn(const xyws_inbox_conn* p) {
+  return {XYWS_LD(false, xyws_inbox_conn, p, buf),   XYWS_LD(false, xyws_inbox_conn, p, cap),
+          XYWS_LD(false, xyws_inbox_conn, p, carry), XYWS_LD(false, xyws_inbox_conn, p, conn),
+          XYWS_LD(false, xyws_inbox_conn, p, aconn), XYWS_LD(false, xyws_inbox_conn, p, aresult),
+          unpack_inbox_flags(XYWS_LD(false, xyws_inbox_conn, p, flags)).flags};
+}
+// The receive range alone (wave-uniform): what the copy pass reads of a row.
+XYWS_DEV uint64_t load_inbox_buf(const xyws_inbox_conn* p) { return XYWS_LD(true, xyws_inbox_conn, p, buf); }
+struct inbox_carry_row { uint64_t http_len, bytes_total; inbox_state state; };
+XYWS_DEV inbox_carry_row load_inbox_carry(const xyws_inbox_carry* p) {
+  return {XYWS_LD(false, xyws_inbox_carry, p, http_len), XYWS_LD(false, xyws_inbox_carry, p, bytes_total),
+          unpack_inbox_state(XYWS_LD(false, xyws_inbox_carry, p, state))};
+}
+// (the carry's reserved word stays the caller's)
+XYWS_DEV void store_inbox_carry(xyws_inbox_carry* p, const inbox_carry_row& c) {
+  XYWS_ST(xyws_inbox_carry, p, http_len, c.http_len);
+  XYWS_ST(xyws_inbox_carry, p, bytes_total, c.bytes_total);
+  XYWS_ST(xyws_inbox_carry, p, state, pack_inbox_state(c.state));
+}
+XYWS_DEV void store_inbox_result(xyws_inbox_result* p, uint64_t len, uint64_t lead, inbox_counts c) {
+  XYWS_ST(xyws_inbox_result, p, len, len);
+  XYWS_ST(xyws_inbox_result, p, lead, lead);
+  XYWS_ST(xyws_inbox_result, p, n_entries, pack_inbox_counts(c));
+  XYWS_ST(xyws_inbox_result, p, reserved, 0);
+}
+XYWS_DEV void store_inbox_summary_word(xyws_inbox_summary* p, uint32_t w, uint64_t v) { ((g_u64*)p)[w] = v; }
+// What the inbox reads of an accept row (each thread's own): the verdict and where the request ends.
+struct accept_end { uint32_t status, consumed; };
+XYWS_DEV accept_end load_accept_end(const xyws_accept_result* p) {
+  return {XYWS_GET(xyws_accept_result, status, XYWS_LD(false, xyws_accept_result, p, status)),
+          XYWS_GET(xyws_accept_result, consumed, XYWS_LD(false, xyws_accept_result, p, consumed))};
+}
+// The buf and len words of a decode row and of an accept row: no other word of the row is written.
+XYWS_DEV void store_conn_recv(xyws_conn* p, uint64_t buf, uint64_t len) {
+  XYWS_ST(xyws_conn, p, buf, buf);
+  XYWS_ST(xyws_conn, p, len, len);
+}
+XYWS_DEV void store_accept_recv(xyws_accept_conn* p, uint64_t buf, uint64_t len) {
+  XYWS_ST(xyws_accept_conn, p, buf, buf);
+  XYWS_ST(xyws_accept_conn, p, len, len);
+}
 
 }  // namespace xyws_rows
 #endif  // __HIPCC__

@@ -675,6 +675,48 @@ class GroupOutbox:
         return self.pack()[e.off:e.off + e.len]
 
 
+class GroupInbox:
+    """Results of one connection_group.inbox call (host copies on demand; every
+    accessor waits for the call). Row i is connection i of the group: the
+    tables behind it are the group's resident ones, which decode() and accept()
+    take in place of their item lists. The result rows, the xyws_conn rows and
+    the receive slab live in the group's tensors: result(), conn() and
+    received() are valid until the group's next inbox() call (a row read
+    before that stays as it was read); summary() belongs to this object."""
+
+    def __init__(self, group, tensors, m):
+        self.group, self._tensors, self.m = group, tensors, m
+        self.ids = list(range(group.n))
+        self._summary = self._rows = None
+
+    def _wait(self):
+        self._tensors["done"].synchronize()
+
+    def summary(self):
+        """xyws_inbox_summary of the call."""
+        if self._summary is None:
+            self._wait()
+            self._summary = _lib.InboxSummary.from_buffer_copy(self._tensors["summary"].cpu().numpy().tobytes())
+        return self._summary
+
+    def result(self, k):
+        """xyws_inbox_result of connection k."""
+        if self._rows is None:
+            self._wait()
+            self._rows = _lib.read_rows(_lib.InboxResult, self._tensors["results"], self.group.n)
+        return self._rows[k]
+
+    def conn(self, k):
+        """Host copy of connection k's resident xyws_conn row (synchronizes)."""
+        return _lib.read_rows(_lib.Conn, self.group._ib["conns"], 1, k)[0]
+
+    def received(self, k):
+        """The bytes connection k's xyws_conn row names after the call: what decode() reads (synchronizes)."""
+        g, row = self.group, self.conn(k)
+        off = row.buf - g._ib["slab"].data_ptr()
+        return g._ib["slab"][off:off + row.len].cpu().numpy().tobytes() if row.len else b""
+
+
 class connection_group:
     """The decoder states of n connections and one xyws_decode_streams call
     for whatever a sweep of the completion queue brought: decode() takes the
@@ -698,7 +740,14 @@ class connection_group:
     from the sweep's own rows, each said to the room as the reference's
     welcome and farewell lines. outbox() ends the sweep (xyws_outbox_streams):
     every connection's send bytes in one pack, with the list of who sends and
-    who is closed, in device or pinned host memory."""
+    who is closed, in device or pinned host memory. inbox()
+    (xyws_inbox_streams) is a receive path of its own so far: a dense pack of
+    the received bytes and one entry per completed recv scattered into a
+    receive slab the group owns, with resident n-row tables that accept() and
+    decode() then run over. What decode() returns for a GroupInbox gives counts
+    and frames; reply(), reassemble(), hold() and broadcast() take only the
+    result of a decode() over (conn_id, buffer) pairs, so in Python a sweep that
+    starts with inbox() ends at decode()."""
     RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
 
     def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
@@ -732,20 +781,32 @@ class connection_group:
         self.hcarry_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
         # backlog(): per room a log and a carry, made when the room is first seen and kept across sweeps
         self._blogs, self._bcarries = [], []
+        # inbox(): the receive slab, the inbox carries and the resident tables, made by the first inbox() call
+        self._ib = None
 
     def reset(self, ids=None):
-        """Fresh streams: every connection, or those in `ids`."""
+        """Fresh streams: every connection, or those in `ids`. A slot that
+        changes hands also loses the handshake verdict of the connection
+        before it: its inbox carry and its resident xyws_accept_result row are
+        both zeroed, or the next inbox() call would open or refuse the new
+        connection by the old one's row."""
         if ids is None:
             self.carry_t.zero_()
             self.rcarry_t.zero_()
             self.mcarry_t.zero_()
             self.hcarry_t.zero_()
+            if self._ib is not None:
+                self._ib["carries"].zero_()
+                self._ib["aresults"].zero_()
         else:
             for i in ids:
                 self.carry_t[64 * i:64 * i + 64].zero_()
                 self.rcarry_t[32 * i:32 * i + 32].zero_()
                 self.mcarry_t[64 * i:64 * i + 64].zero_()
                 self.hcarry_t[32 * i:32 * i + 32].zero_()
+                if self._ib is not None:
+                    self._ib["carries"][32 * i:32 * i + 32].zero_()
+                    self._ib["aresults"][32 * i:32 * i + 32].zero_()
 
     def carry(self, conn_id):
         """Host copy of a connection's carry (synchronizes)."""
@@ -755,8 +816,15 @@ class connection_group:
 
     def decode(self, items):
         """items: (conn_id, device uint8 tensor) pairs, each id at most once.
-        Every buffer is decoded in place; returns a GroupResult."""
+        Every buffer is decoded in place; returns a GroupResult. A GroupInbox
+        in place of the pairs decodes every connection of the group over the
+        resident xyws_conn table that inbox() keeps: item k is connection k.
+        That result gives nframes() and frames() only: reply(), reassemble(),
+        hold() and broadcast() refuse it (they need the table of a decode()
+        over pairs)."""
         import torch
+        if isinstance(items, GroupInbox):
+            return self._decode_resident(items)
         items = [(int(i), _dev_u8(t)) for i, t in items]
         ids = [i for i, _ in items]
         if len(set(ids)) != len(ids) or any(not 0 <= i < self.n for i in ids):
@@ -794,8 +862,16 @@ class connection_group:
         (ACC_REFERENCE) and answered; an incomplete one is reported as such:
         call again with more bytes. The call keeps no state: on ACCEPTED the
         bytes behind result(k).consumed are the connection's first decode()
-        input. Returns a GroupAccept."""
+        input. A GroupInbox in place of the items runs over the resident
+        xyws_accept_conn table that inbox() keeps (item k is connection k, the
+        responses go to the group's own response slab, out_items is None), and
+        the next inbox() call reads the rows this call leaves. The rows and
+        responses of that GroupAccept live in the group's tensors: they are
+        valid until the group's next accept() over a GroupInbox, or until
+        reset() clears a slot's row. Returns a GroupAccept."""
         import torch
+        if isinstance(items, GroupInbox):
+            return self._accept_resident(items, out_items, policy, max_request)
         pairs = [it if isinstance(it, tuple) else (k, it) for k, it in enumerate(items)]
         ids = [int(i) for i, _ in pairs]
         bufs = [_dev_u8(t) for _, t in pairs]
@@ -1393,6 +1469,124 @@ class connection_group:
             tensors["done"] = torch.cuda.Event()
             tensors["done"].record(stream)
         return GroupOutbox(self, ids, outs, tensors, cap, host)
+
+    def _inbox_state(self, recv_cap, resp_cap):
+        """The receive slab, the inbox carries and the resident tables (made once)."""
+        import torch
+        if self._ib is not None:
+            if (recv_cap, resp_cap) != (self._ib["recv_cap"], self._ib["resp_cap"]):
+                raise XywsError(-1, "recv_cap and resp_cap are fixed by the group's first inbox() call")
+            return self._ib
+        n, dev = self.n, self.device
+        with torch.cuda.device(dev):
+            ib = dict(recv_cap=recv_cap, resp_cap=resp_cap,
+                      slab=torch.zeros(max(n * recv_cap, 16), dtype=torch.uint8, device=dev),
+                      resp=torch.zeros(max(n * resp_cap, 16), dtype=torch.uint8, device=dev),
+                      carries=torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=dev),
+                      aresults=torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=dev),
+                      results=torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=dev))
+            conns, aconns = _lib.Table(_lib.Conn, n), _lib.Table(_lib.AcceptConn, n)
+            for i in range(n):
+                c, a = conns[i], aconns[i]
+                c.buf, c.len, c.carry = ib["slab"].data_ptr() + recv_cap * i, 0, self.carry_t.data_ptr() + 64 * i
+                c.frames, c.cap = (self.frames_t.data_ptr() + 32 * self.cap * i, self.cap) if self.cap else (0, 0)
+                a.buf, a.len, a.out, a.out_cap = c.buf, 0, ib["resp"].data_ptr() + resp_cap * i, resp_cap
+            ib["conns"], ib["aconns"] = conns.upload(dev), aconns.upload(dev)
+            iconns = _lib.Table(_lib.InboxConn, n)
+            for i in range(n):
+                r = iconns[i]
+                r.buf, r.cap, r.carry = ib["slab"].data_ptr() + recv_cap * i, recv_cap, ib["carries"].data_ptr() + 32 * i
+                r.conn, r.aconn = ib["conns"].data_ptr() + 64 * i, ib["aconns"].data_ptr() + 32 * i
+                r.aresult = ib["aresults"].data_ptr() + 32 * i
+            ib["iconns"] = iconns.upload(dev)
+        self._ib = ib
+        return ib
+
+    def inbox(self, pack, entries, recv_cap, m_cap=None, resp_cap=144):
+        """Scatter a sweep's received bytes to the connections
+        (xyws_inbox_streams, five launches, the sweep's first call). pack: the
+        received bytes, dense (bytes, or a uint8 tensor on the group's device);
+        entries: one (conn, off, len, at[, flags]) tuple per completed recv in
+        arrival order, `at` the connection's bytes in this sweep before it;
+        recv_cap: the size of every connection's receive range. The first call
+        makes the group's receive slab, inbox carries and the resident n-row
+        xyws_conn and xyws_accept_conn tables; decode() and accept() take the
+        returned GroupInbox in place of their item lists; the sweep's later
+        calls (reply() .. outbox()) do not take what that decode() returns.
+        reset(ids) before the call hands a slot to a new connection. m_cap: the
+        entry capacity of the call (default len(entries))."""
+        import numpy as np
+        import torch
+        recv_cap, resp_cap = int(recv_cap), int(resp_cap)
+        if recv_cap < 1 or resp_cap < 0:
+            raise XywsError(-1, "recv_cap must be positive and resp_cap not negative")
+        ents = [tuple(int(v) for v in e) for e in entries]
+        if any(len(e) not in (4, 5) or min(e) < 0 or e[0] > 0xFFFFFFFF for e in ents):
+            raise XywsError(-1, "an entry is (conn, off, len, at[, flags]), none of them negative")
+        m = len(ents)
+        m_cap = m if m_cap is None else int(m_cap)
+        if m_cap < m:
+            raise XywsError(-1, "more entries than m_cap")
+        if isinstance(pack, (bytes, bytearray, memoryview)):
+            raw = bytes(pack)
+            pack_t = torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).to(self.device) if raw else None
+        else:
+            pack_t = _dev_u8(pack) if pack.numel() else None
+            if pack_t is not None and pack_t.device != self.device:
+                raise XywsError(-1, "a pack on another device than the group's")
+        ib = self._inbox_state(recv_cap, resp_cap)
+        pack_len = pack_t.numel() if pack_t is not None else 0
+        L = self.ctx.L
+        need = L.xyws_inbox_scratch_bytes(self.n, m_cap)
+        head = _lib.Table(_lib.InboxHead, 1)
+        head[0].m, head[0].pack_len = m, pack_len
+        tab = _lib.Table(_lib.InboxEntry, m_cap)
+        for row, e in zip(tab.rows, ents):
+            row.conn, row.off, row.len, row.at, row.flags = e[0], e[1], e[2], e[3], e[4] if len(e) == 5 else 0
+        with torch.cuda.device(self.device):
+            tensors = dict(head=head.upload(self.device), entries=tab.upload(self.device), pack=pack_t,
+                           summary=torch.zeros(64, dtype=torch.uint8, device=self.device), results=ib["results"],
+                           scratch=torch.empty(max(need, 8), dtype=torch.uint8, device=self.device))
+            stream = torch.cuda.current_stream(self.device)
+            check(L.xyws_inbox_streams(
+                self.ctx.h, C.c_void_p(ib["iconns"].data_ptr()), self.n, C.c_void_p(tensors["head"].data_ptr()),
+                C.c_void_p(tensors["entries"].data_ptr()) if m_cap else None, m_cap,
+                C.c_void_p(pack_t.data_ptr()) if pack_len else None, pack_len, C.c_void_p(ib["results"].data_ptr()),
+                C.c_void_p(tensors["summary"].data_ptr()), C.c_void_p(tensors["scratch"].data_ptr()),
+                tensors["scratch"].numel(), C.c_void_p(stream.cuda_stream)), "xyws_inbox_streams")
+            tensors["done"] = torch.cuda.Event()
+            tensors["done"].record(stream)
+        return GroupInbox(self, tensors, m)
+
+    def inbox_carry(self, conn_id):
+        """Host copy of a connection's inbox carry (synchronizes)."""
+        if not 0 <= conn_id < self.n or self._ib is None:
+            raise XywsError(-1, "no such connection, or no inbox() call yet")
+        return _lib.read_rows(_lib.InboxCarry, self._ib["carries"], 1, conn_id)[0]
+
+    def _decode_resident(self, inbox):
+        import torch
+        if inbox.group is not self:
+            raise XywsError(-1, "decode() takes a GroupInbox of this group")
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            check(self.ctx.L.xyws_decode_streams(self.ctx.h, C.c_void_p(self._ib["conns"].data_ptr()), self.n,
+                                                 C.c_void_p(self.counts_t.data_ptr()), self.opts,
+                                                 C.c_void_p(stream.cuda_stream)), "xyws_decode_streams")
+        return GroupResult(self, list(range(self.n)))
+
+    def _accept_resident(self, inbox, out_items, policy, max_request):
+        import torch
+        if inbox.group is not self or out_items is not None:
+            raise XywsError(-1, "accept() takes a GroupInbox of this group and no send buffers with it")
+        ib = self._ib
+        outs = [ib["resp"][ib["resp_cap"] * i:ib["resp_cap"] * (i + 1)] for i in range(self.n)]
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            check(self.ctx.L.xyws_accept_streams(self.ctx.h, C.c_void_p(ib["aconns"].data_ptr()), self.n,
+                                                 int(max_request), int(policy), C.c_void_p(ib["aresults"].data_ptr()),
+                                                 C.c_void_p(stream.cuda_stream)), "xyws_accept_streams")
+        return GroupAccept(self, list(range(self.n)), outs, ib["aconns"], ib["aresults"])
 
     def msg_carry(self, conn_id):
         """Host copy of a connection's message carry (synchronizes)."""
