@@ -470,6 +470,19 @@ def read_rows(struct, t, n, first=0):
     return [struct.from_buffer_copy(raw, size * k) for k in range(n)]
 
 
+def alloc_rows(struct, n, device, zero=True, per=1):
+    """A uint8 tensor for max(n, 1) * per rows of the ctypes structure `struct`
+    on `device` (per: rows per connection), zeroed or left as allocated."""
+    import torch
+    make = torch.zeros if zero else torch.empty
+    return make(max(n, 1) * per * C.sizeof(struct), dtype=torch.uint8, device=device)
+
+
+def row_ptr(t, struct, k=0):
+    """The address of row k of the uint8 tensor t, which holds rows of `struct`."""
+    return t.data_ptr() + C.sizeof(struct) * k
+
+
 _lib = None
 _tools = None
 

@@ -211,11 +211,6 @@ def websocket_mask(data, mask, i=0):
     return out.value
 
 
-def _frames_from_device(frames_t, n):
-    import numpy as np
-    return _lib.read_rows(Frame, frames_t, n), np
-
-
 class _Rows:
     """The first n rows (ctypes structure `struct`) of a device uint8 tensor
     as host copies: the tensor is copied once, when a row is first asked for;
@@ -248,8 +243,7 @@ class DecodeResult:
     def frames(self):
         if self.frames_t is None:
             return []
-        n = min(self.nframes, self.cap)
-        return _frames_from_device(self.frames_t, n)[0]
+        return _lib.read_rows(Frame, self.frames_t, min(self.nframes, self.cap))
 
 
 class frame_decoder:
@@ -315,16 +309,60 @@ class frame_decoder:
         return DecodeResult(frames_t, n_t, cap)
 
 
+def _set_out(row, t):
+    """A row's out, out_cap pair: the tensor t."""
+    row.out, row.out_cap = t.data_ptr(), t.numel()
+
+
+class _Done:
+    """The event behind the last call that was marked: wait() returns when that call has run."""
+
+    def __init__(self):
+        self.event = None
+
+    def wait(self):
+        if self.event is not None:
+            self.event.synchronize()
+
+    def mark(self, stream):
+        import torch
+        self.event = torch.cuda.Event()
+        self.event.record(stream)
+
+
+class _Slot(_Done):
+    """One slot of a connection_group's ring: a pinned and a device tensor
+    for each table a sweep uploads (xyws_conn, xyws_reply_conn,
+    xyws_reasm_conn), and the event of the last call that read them. A pinned
+    table is rewritten only after its copy and its call have run: wait()."""
+
+    def __init__(self, n, device):
+        super().__init__()
+        structs = (_lib.Conn, _lib.ReplyConn, _lib.ReasmConn)
+        self.host = {s: _lib.alloc_rows(s, n, "cpu").pin_memory() for s in structs}
+        self.dev = {s: _lib.alloc_rows(s, n, device, zero=False) for s in structs}
+
+    def upload(self, struct, m, fill):
+        """The slot's table of m `struct` rows on the device, each row set by fill(row, k)."""
+        tab = _lib.Table(struct, m, self.host[struct])
+        for k in range(m):
+            fill(tab[k], k)
+        return tab.upload(self.dev[struct])
+
+
 class GroupResult:
     """Counts and frames of one connection_group.decode call, item k being the
     k-th (conn_id, buffer) pair of that call (host copies on demand). They
     live in the group's tensors: valid until the group's next decode."""
 
-    def __init__(self, group, ids, slot=None):
+    def __init__(self, group, ids, conns_t, slot=None, resident=False):
+        """conns_t: the device xyws_conn table the call ran over; slot: the
+        ring slot that holds it, which reply() and reassemble() put their own
+        tables into; resident: the table is the one inbox() keeps."""
         self.group, self.ids = group, ids
+        self.conns_t, self.slot, self.resident = conns_t, slot, resident
         self._counts = None
-        self._slot, self._replied = slot, False  # (the ring slot that holds this call's table: connection_group.reply)
-        self._reassembled = False                # (... and connection_group.reassemble)
+        self._replied = self._reassembled = False  # (a second reply() or reassemble() rewrites the slot's table)
 
     def nframes(self, k):
         if self._counts is None:
@@ -335,18 +373,16 @@ class GroupResult:
 
     def frames(self, k):
         g = self.group
-        n = min(self.nframes(k), g.cap)
-        row = g.frames_t[self.ids[k] * g.cap * 32:]
-        return _frames_from_device(row, n)[0]
+        return _lib.read_rows(Frame, g.frames_t, min(self.nframes(k), g.cap), g.cap * self.ids[k])
 
 
 class GroupReply:
     """Results and verdicts of one connection_group.reply call, item k as in
     the decode result it answered (host copies on demand; valid until the
-    group's next reply)."""
+    group's next reply). outs: the send tensors it wrote, which outbox() packs."""
 
-    def __init__(self, group, decoded):
-        self.group, self.decoded = group, decoded
+    def __init__(self, group, decoded, outs):
+        self.group, self.decoded, self.outs = group, decoded, outs
         self._rows = _Rows(_lib.ReplyResult, group.results_t, len(decoded.ids))
 
     def result(self, k):
@@ -439,11 +475,18 @@ class GroupRoute:
 class GroupMessages:
     """Results and message records of one connection_group.reassemble call,
     item k as in the decode result it took (host copies on demand; valid until
-    the group's next reassemble)."""
+    the group's next reassemble). outs: the message tensors it wrote (hold()
+    looks in front of them); out_caps: their sizes (broadcast() sizes the
+    wires by them)."""
 
-    def __init__(self, group, decoded, msg_cap):
-        self.group, self.decoded, self.msg_cap = group, decoded, msg_cap
+    def __init__(self, group, decoded, msg_cap, outs):
+        self.group, self.decoded, self.msg_cap, self.outs = group, decoded, msg_cap, outs
+        self.out_caps = [t.numel() for t in outs]
         self._rows = _Rows(_lib.ReasmResult, group.mresults_t, len(decoded.ids))
+
+    def tables(self):
+        """The xyws_reasm_conn table and the result rows that broadcast() and backlog() read (device tensors)."""
+        return self.decoded.slot.dev[_lib.ReasmConn], self.group.mresults_t
 
     def result(self, k):
         """xyws_reasm_result of item k."""
@@ -471,9 +514,9 @@ class GroupHold:
         self._rows = _Rows(_lib.HoldResult, tensors["results"], len(self.decoded.ids))
         self._vrows = _Rows(_lib.ReasmResult, tensors["view_results"], len(self.decoded.ids))
 
-    def _tables(self):
-        """The device addresses broadcast() reads instead of the reassembly's."""
-        return self._tensors["view"].data_ptr(), self._tensors["view_results"].data_ptr()
+    def tables(self):
+        """The view and its result rows, which broadcast() and backlog() read instead of the reassembly's."""
+        return self._tensors["view"], self._tensors["view_results"]
 
     def result(self, k):
         """xyws_hold_result of item k."""
@@ -494,12 +537,19 @@ class GroupBroadcast:
     """Results, room results and wires of one connection_group.broadcast call,
     item k as in the decode result of its sweep, room r as in the `rooms`
     argument (host copies on demand). It owns the call's tables, wires and
-    result rows."""
+    result rows. The sweep's later calls read its fields: messages (the
+    reassemble() or hold() result it delivered), outs and heads (per item),
+    replied (whether the sweep's reply rows are named), room_set (None over
+    lists) and the table tensors."""
 
-    def __init__(self, group, decoded, tensors, wires):
-        self.group, self.decoded, self._tensors, self._wires = group, decoded, tensors, wires
-        self._rows = _Rows(_lib.BcastResult, tensors["results"], len(decoded.ids))
-        self._rrows = _Rows(_lib.RoomResult, tensors["room_results"], len(wires))
+    def __init__(self, group, messages, outs, heads, replied, wires, tensors, room_set=None):
+        self.group, self.decoded, self.messages = group, messages.decoded, messages
+        self.outs, self.heads, self.replied, self.room_set = outs, heads, replied, room_set
+        self._tensors, self._wires = tensors, wires
+        self.members_t, self.rooms_t, self.bconns_t = tensors["members"], tensors["rooms"], tensors["bconns"]
+        self.results_t, self.room_results_t = tensors["results"], tensors["room_results"]
+        self._rows = _Rows(_lib.BcastResult, self.results_t, len(self.decoded.ids))
+        self._rrows = _Rows(_lib.RoomResult, self.room_results_t, len(wires))
 
     def result(self, k):
         """xyws_bcast_result of item k."""
@@ -519,11 +569,14 @@ class GroupBroadcast:
 class GroupBacklog:
     """Results of one connection_group.backlog call: item k as in the decode
     result of its sweep, room r as in the broadcast's `rooms` argument (host
-    copies on demand). The logs and carries belong to the group."""
+    copies on demand). The logs and carries belong to the group. bcast: the
+    sweep's GroupBroadcast; roster: its GroupRoster, or None."""
 
-    def __init__(self, group, decoded, tensors, nr):
-        self.group, self.decoded, self._tensors, self.nr = group, decoded, tensors, nr
-        self._rows = _Rows(_lib.BacklogResult, tensors["results"], len(decoded.ids))
+    def __init__(self, group, bcast, roster, tensors, nr):
+        self.group, self.decoded, self.bcast, self.roster = group, bcast.decoded, bcast, roster
+        self._tensors, self.nr = tensors, nr
+        self.results_t = tensors["results"]
+        self._rows = _Rows(_lib.BacklogResult, self.results_t, len(self.decoded.ids))
         self._rrows = _Rows(_lib.BacklogRoomResult, tensors["room_results"], nr)
 
     def result(self, k):
@@ -560,7 +613,7 @@ class RoomSet:
             # the `seen` rows: each sweep's lists as its broadcast read them, for that sweep's backlog fold
             self.seen_members_t = torch.zeros(max(self.nr * self.member_cap, 1), dtype=torch.int32, device=dev)
             rtab, stab = _lib.Table(_lib.Room, self.nr), _lib.Table(_lib.Room, self.nr)
-            self.seen_rooms_t = torch.zeros(32 * max(self.nr, 1), dtype=torch.uint8, device=dev)
+            self.seen_rooms_t = _lib.alloc_rows(_lib.Room, self.nr, dev)
             rrtab = _lib.Table(_lib.RosterRoom, self.nr)
             for r in range(self.nr):
                 rtab[r].members, rtab[r].n_members = self.members_t.data_ptr() + 4 * self.member_cap * r, 0
@@ -569,8 +622,8 @@ class RoomSet:
                     row.wire, row.wire_cap = self.wires[r].data_ptr(), self.wires[r].numel()
                 rrtab[r].member_cap = self.member_cap
                 rrtab[r].notes, rrtab[r].notes_cap = self.notes[r].data_ptr(), self.notes[r].numel()
-                rrtab[r].seen = self.seen_rooms_t.data_ptr() + 32 * r
-            self.seen_rooms_t.copy_(stab.upload(dev)[:32 * max(self.nr, 1)])
+                rrtab[r].seen = _lib.row_ptr(self.seen_rooms_t, _lib.Room, r)
+            self.seen_rooms_t.copy_(stab.upload(dev))
             self.rooms_t, self.rrooms_t = rtab.upload(dev), rrtab.upload(dev)
             btab = _lib.Table(_lib.BcastConn, n)
             for k in range(n):
@@ -607,7 +660,8 @@ class GroupRoster:
     def __init__(self, group, bcast, room_set, tensors):
         self.group, self.bcast, self.room_set, self._tensors = group, bcast, room_set, tensors
         self.decoded = bcast.decoded
-        self._rows = _Rows(_lib.RosterResult, tensors["results"], len(self.decoded.ids))
+        self.results_t, self.jconns_t = tensors["results"], tensors["jconns"]  # (outbox() and backlog() name them)
+        self._rows = _Rows(_lib.RosterResult, self.results_t, len(self.decoded.ids))
         self._rrows = _Rows(_lib.RosterRoomResult, tensors["room_results"], room_set.nr)
 
     def result(self, k):
@@ -635,28 +689,23 @@ class GroupOutbox:
     items that are no item of the sweep. conn_ids[i] is row i's connection id.
     It owns the call's table, outputs and scratch."""
 
-    def __init__(self, group, conn_ids, outs, tensors, pack_cap, host):
+    def __init__(self, group, conn_ids, outs, tensors, pack_cap, host, last, accept, done):
         self.group, self.conn_ids, self.outs, self._tensors = group, conn_ids, outs, tensors
         self.pack_cap, self.host = pack_cap, host
+        self.last, self.accept, self._done = last, accept, done  # (the sweep's results, whose rows the table names)
         self._summary = self._entries = self._pack = None
-
-    def _wait(self):
-        self._tensors["done"].synchronize()
 
     def summary(self):
         """xyws_outbox_summary of the call."""
         if self._summary is None:
-            self._wait()
-            raw = self._tensors["summary"].cpu().numpy().tobytes()
-            self._summary = _lib.OutboxSummary.from_buffer_copy(raw)
+            self._done.wait()
+            self._summary = _lib.read_rows(_lib.OutboxSummary, self._tensors["summary"], 1)[0]
         return self._summary
 
     def entries(self):
         """The send list: the n_entries xyws_outbox_entry rows, in table order."""
         if self._entries is None:
-            n, size = self.summary().n_entries, C.sizeof(_lib.OutboxEntry)
-            raw = self._tensors["entries"][:size * n].cpu().numpy().tobytes() if n else b""
-            self._entries = [_lib.OutboxEntry.from_buffer_copy(raw, size * k) for k in range(n)]
+            self._entries = _lib.read_rows(_lib.OutboxEntry, self._tensors["entries"], self.summary().n_entries)
         return self._entries
 
     def pack(self):
@@ -684,25 +733,22 @@ class GroupInbox:
     received() are valid until the group's next inbox() call (a row read
     before that stays as it was read); summary() belongs to this object."""
 
-    def __init__(self, group, tensors, m):
-        self.group, self._tensors, self.m = group, tensors, m
+    def __init__(self, group, tensors, m, done):
+        self.group, self._tensors, self.m, self._done = group, tensors, m, done
         self.ids = list(range(group.n))
         self._summary = self._rows = None
-
-    def _wait(self):
-        self._tensors["done"].synchronize()
 
     def summary(self):
         """xyws_inbox_summary of the call."""
         if self._summary is None:
-            self._wait()
-            self._summary = _lib.InboxSummary.from_buffer_copy(self._tensors["summary"].cpu().numpy().tobytes())
+            self._done.wait()
+            self._summary = _lib.read_rows(_lib.InboxSummary, self._tensors["summary"], 1)[0]
         return self._summary
 
     def result(self, k):
         """xyws_inbox_result of connection k."""
         if self._rows is None:
-            self._wait()
+            self._done.wait()
             self._rows = _lib.read_rows(_lib.InboxResult, self._tensors["results"], self.group.n)
         return self._rows[k]
 
@@ -747,42 +793,62 @@ class connection_group:
     decode() then run over. What decode() returns for a GroupInbox gives counts
     and frames; reply(), reassemble(), hold() and broadcast() take only the
     result of a decode() over (conn_id, buffer) pairs, so in Python a sweep that
-    starts with inbox() ends at decode()."""
+    starts with inbox() ends at decode().
+
+    The tables decode(), reply() and reassemble() upload go through one ring
+    of RING slots (_Slot): decode() takes the next slot, the sweep's later
+    calls use the slot of the decode() result they are given and move its
+    event behind themselves. Every xyws_*_streams call is made by _call()."""
     RING = 4  # tables in flight: a pinned table is rewritten only after its copy and its call have run
 
     def __init__(self, n, cap=0, device=None, ctx=None, parse_only=False):
         import torch
         self.ctx = ctx if ctx is not None else context(device)
-        self.device = torch.device("cuda", self.ctx.device)
-        self.n, self.cap = int(n), int(cap)
+        self.device = dev = torch.device("cuda", self.ctx.device)
+        self.n, self.cap = n, cap = int(n), int(cap)
         self.opts = _lib.OPT_PARSE_ONLY if parse_only else 0
-        self.carry_t = torch.zeros(max(self.n, 1) * 64, dtype=torch.uint8, device=self.device)
-        self.frames_t = torch.empty(max(self.n * self.cap, 1) * 32, dtype=torch.uint8, device=self.device)
-        self.counts_t = torch.zeros(max(self.n, 1), dtype=torch.int64, device=self.device)
-        self._host = [torch.zeros(max(self.n, 1) * 8, dtype=torch.int64).pin_memory() for _ in range(self.RING)]
-        self._dev = [torch.empty(max(self.n, 1) * 8, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
-        self._done = [None] * self.RING
+        self.carry_t = _lib.alloc_rows(Carry, n, dev)
+        self.frames_t = _lib.alloc_rows(Frame, n * cap, dev, zero=False)
+        self.counts_t = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        self._ring = [_Slot(n, dev) for _ in range(self.RING)]
         self._turn = 0
-        # reply(): the reply carries, a verdict row of cap per connection, a result row per item, and the
-        # xyws_reply_conn tables in the same ring
-        self.rcarry_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
-        self.verdicts_t = torch.empty(max(self.n * self.cap, 1) * 8, dtype=torch.uint8, device=self.device)
-        self.results_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
-        self._rhost = [torch.zeros(max(self.n, 1) * 4, dtype=torch.int64).pin_memory() for _ in range(self.RING)]
-        self._rdev = [torch.empty(max(self.n, 1) * 4, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
-        # reassemble(): the message carries, a record row of cap + 1 per connection, a result row per item, and
-        # the xyws_reasm_conn tables in the same ring
-        self.mcarry_t = torch.zeros(max(self.n, 1) * 64, dtype=torch.uint8, device=self.device)
-        self.msgs_t = torch.empty(max(self.n, 1) * (self.cap + 1) * 40, dtype=torch.uint8, device=self.device)
-        self.mresults_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
-        self._mhost = [torch.zeros(max(self.n, 1) * 8, dtype=torch.int64).pin_memory() for _ in range(self.RING)]
-        self._mdev = [torch.empty(max(self.n, 1) * 8, dtype=torch.int64, device=self.device) for _ in range(self.RING)]
+        # reply(): the reply carries, a verdict row of cap per connection, a result row per item
+        self.rcarry_t = _lib.alloc_rows(_lib.ReplyCarry, n, dev)
+        self.verdicts_t = _lib.alloc_rows(_lib.Verdict, n * cap, dev, zero=False)
+        self.results_t = _lib.alloc_rows(_lib.ReplyResult, n, dev)
+        # reassemble(): the message carries, a record row of cap + 1 per connection, a result row per item
+        self.mcarry_t = _lib.alloc_rows(_lib.MsgCarry, n, dev)
+        self.msgs_t = _lib.alloc_rows(_lib.Message, n, dev, zero=False, per=cap + 1)
+        self.mresults_t = _lib.alloc_rows(_lib.ReasmResult, n, dev)
         # hold(): the hold carries (its tables and rows belong to the GroupHold it returns)
-        self.hcarry_t = torch.zeros(max(self.n, 1) * 32, dtype=torch.uint8, device=self.device)
+        self.hcarry_t = _lib.alloc_rows(_lib.HoldCarry, n, dev)
         # backlog(): per room a log and a carry, made when the room is first seen and kept across sweeps
         self._blogs, self._bcarries = [], []
         # inbox(): the receive slab, the inbox carries and the resident tables, made by the first inbox() call
         self._ib = None
+
+    def _call(self, name, *args, slot=None, done=None):
+        """One call of the library on the group's device and its current
+        stream: getattr(L, name)(ctx, *args, stream), a tensor argument passed
+        as its address. The function is looked up when the call is made.
+        slot, done: the ring slot and the result's _Done whose events move
+        behind the call."""
+        import torch
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+            check(getattr(self.ctx.L, name)(self.ctx.h, *args, stream.cuda_stream), name)
+            for d in (slot, done):
+                if d is not None:
+                    d.mark(stream)
+
+    def _carries(self):
+        """The per-connection state a slot loses when it changes hands, as (tensor, row structure) pairs."""
+        pairs = [(self.carry_t, Carry), (self.rcarry_t, _lib.ReplyCarry), (self.mcarry_t, _lib.MsgCarry),
+                 (self.hcarry_t, _lib.HoldCarry)]
+        if self._ib is not None:
+            pairs += [(self._ib["carries"], _lib.InboxCarry), (self._ib["aresults"], _lib.AcceptResult)]
+        return pairs
 
     def reset(self, ids=None):
         """Fresh streams: every connection, or those in `ids`. A slot that
@@ -790,29 +856,29 @@ class connection_group:
         before it: its inbox carry and its resident xyws_accept_result row are
         both zeroed, or the next inbox() call would open or refuse the new
         connection by the old one's row."""
-        if ids is None:
-            self.carry_t.zero_()
-            self.rcarry_t.zero_()
-            self.mcarry_t.zero_()
-            self.hcarry_t.zero_()
-            if self._ib is not None:
-                self._ib["carries"].zero_()
-                self._ib["aresults"].zero_()
-        else:
-            for i in ids:
-                self.carry_t[64 * i:64 * i + 64].zero_()
-                self.rcarry_t[32 * i:32 * i + 32].zero_()
-                self.mcarry_t[64 * i:64 * i + 64].zero_()
-                self.hcarry_t[32 * i:32 * i + 32].zero_()
-                if self._ib is not None:
-                    self._ib["carries"][32 * i:32 * i + 32].zero_()
-                    self._ib["aresults"][32 * i:32 * i + 32].zero_()
+        ids = None if ids is None else list(ids)
+        for t, struct in self._carries():
+            if ids is None:
+                t.zero_()
+            else:
+                size = C.sizeof(struct)
+                for i in ids:
+                    t[size * i:size * (i + 1)].zero_()
+
+    def _carry_of(self, t, struct, conn_id):
+        """Host copy of connection conn_id's row of a carry tensor (synchronizes)."""
+        if not 0 <= conn_id < self.n:
+            raise XywsError(-1, "no such connection")
+        return _lib.read_rows(struct, t, 1, conn_id)[0]
 
     def carry(self, conn_id):
         """Host copy of a connection's carry (synchronizes)."""
-        if not 0 <= conn_id < self.n:
-            raise XywsError(-1, "no such connection")
-        return Carry.from_buffer_copy(self.carry_t[64 * conn_id:64 * conn_id + 64].cpu().numpy().tobytes())
+        return self._carry_of(self.carry_t, Carry, conn_id)
+
+    def _conn_row(self, row, buf, length, i):
+        """Connection i's xyws_conn row over `length` bytes at the device address buf."""
+        row.buf, row.len, row.carry = buf, length, _lib.row_ptr(self.carry_t, Carry, i)
+        row.frames, row.cap = (_lib.row_ptr(self.frames_t, Frame, self.cap * i), self.cap) if self.cap else (0, 0)
 
     def decode(self, items):
         """items: (conn_id, device uint8 tensor) pairs, each id at most once.
@@ -822,34 +888,28 @@ class connection_group:
         That result gives nframes() and frames() only: reply(), reassemble(),
         hold() and broadcast() refuse it (they need the table of a decode()
         over pairs)."""
-        import torch
         if isinstance(items, GroupInbox):
-            return self._decode_resident(items)
+            if items.group is not self:
+                raise XywsError(-1, "decode() takes a GroupInbox of this group")
+            conns_t = self._ib["conns"]
+            self._call("xyws_decode_streams", conns_t, self.n, self.counts_t, self.opts)
+            return GroupResult(self, list(range(self.n)), conns_t, resident=True)
         items = [(int(i), _dev_u8(t)) for i, t in items]
         ids = [i for i, _ in items]
         if len(set(ids)) != len(ids) or any(not 0 <= i < self.n for i in ids):
             raise XywsError(-1, "connection ids must be distinct and below n")
         if any(t.device != self.device for _, t in items):
             raise XywsError(-1, "a buffer on another device than the group's")
-        k = self._turn
-        self._turn = (k + 1) % self.RING
-        if self._done[k] is not None:
-            self._done[k].synchronize()
-        m = len(items)
-        tab = _lib.Table(_lib.Conn, m, self._host[k])
-        cbase, fbase = self.carry_t.data_ptr(), self.frames_t.data_ptr()
-        for row, (i, t) in zip(tab.rows, items):
-            row.buf, row.len, row.carry = t.data_ptr(), t.numel(), cbase + 64 * i
-            row.frames, row.cap = (fbase + 32 * self.cap * i, self.cap) if self.cap else (0, 0)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            tab.upload(self._dev[k])
-            check(self.ctx.L.xyws_decode_streams(self.ctx.h, C.c_void_p(self._dev[k].data_ptr()), m,
-                                                 C.c_void_p(self.counts_t.data_ptr()), self.opts,
-                                                 C.c_void_p(stream.cuda_stream)), "xyws_decode_streams")
-            self._done[k] = torch.cuda.Event()
-            self._done[k].record(stream)
-        return GroupResult(self, ids, k)
+        slot = self._ring[self._turn]
+        self._turn = (self._turn + 1) % self.RING
+        slot.wait()
+
+        def fill(row, k):
+            i, t = items[k]
+            self._conn_row(row, t.data_ptr(), t.numel(), i)
+        conns_t = slot.upload(_lib.Conn, len(items), fill)
+        self._call("xyws_decode_streams", conns_t, len(items), self.counts_t, self.opts, slot=slot)
+        return GroupResult(self, ids, conns_t, slot)
 
     def accept(self, items, out_items, policy=0, max_request=1024):
         """Answer the opening handshakes of the connections still in HTTP
@@ -869,26 +929,27 @@ class connection_group:
         responses of that GroupAccept live in the group's tensors: they are
         valid until the group's next accept() over a GroupInbox, or until
         reset() clears a slot's row. Returns a GroupAccept."""
-        import torch
         if isinstance(items, GroupInbox):
-            return self._accept_resident(items, out_items, policy, max_request)
-        pairs = [it if isinstance(it, tuple) else (k, it) for k, it in enumerate(items)]
-        ids = [int(i) for i, _ in pairs]
-        bufs = [_dev_u8(t) for _, t in pairs]
-        outs = [_dev_u8(t) for t in out_items]
-        if len(outs) != len(bufs) or any(t.device != self.device for t in bufs + outs):
-            raise XywsError(-1, "one request and one send buffer on the group's device per item")
-        m = len(bufs)
-        tab = _lib.Table(_lib.AcceptConn, m)
-        for row, b, o in zip(tab.rows, bufs, outs):
-            row.buf, row.len, row.out, row.out_cap = b.data_ptr(), b.numel(), o.data_ptr(), o.numel()
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
+            if items.group is not self or out_items is not None:
+                raise XywsError(-1, "accept() takes a GroupInbox of this group and no send buffers with it")
+            ib = self._ib
+            ids = list(range(self.n))
+            outs = [ib["resp"][ib["resp_cap"] * i:ib["resp_cap"] * (i + 1)] for i in ids]
+            table_t, results_t = ib["aconns"], ib["aresults"]
+        else:
+            pairs = [it if isinstance(it, tuple) else (k, it) for k, it in enumerate(items)]
+            ids = [int(i) for i, _ in pairs]
+            bufs = [_dev_u8(t) for _, t in pairs]
+            outs = [_dev_u8(t) for t in out_items]
+            if len(outs) != len(bufs) or any(t.device != self.device for t in bufs + outs):
+                raise XywsError(-1, "one request and one send buffer on the group's device per item")
+            tab = _lib.Table(_lib.AcceptConn, len(bufs))
+            for row, b, o in zip(tab.rows, bufs, outs):
+                row.buf, row.len = b.data_ptr(), b.numel()
+                _set_out(row, o)
             table_t = tab.upload(self.device)
-            results_t = torch.zeros(max(m, 1) * 32, dtype=torch.uint8, device=self.device)
-            check(self.ctx.L.xyws_accept_streams(self.ctx.h, C.c_void_p(table_t.data_ptr()), m, int(max_request),
-                                                 int(policy), C.c_void_p(results_t.data_ptr()),
-                                                 C.c_void_p(stream.cuda_stream)), "xyws_accept_streams")
+            results_t = _lib.alloc_rows(_lib.AcceptResult, len(bufs), self.device)
+        self._call("xyws_accept_streams", table_t, len(ids), int(max_request), int(policy), results_t)
         return GroupAccept(self, ids, outs, table_t, results_t)
 
     def routes(self, exact=None, prefix=None, slots=0):
@@ -908,7 +969,6 @@ class connection_group:
         with miss_404 gets `404 Not Found` over its 101 and counts as a
         rejected handshake from then on. Returns a GroupRoute, which
         roster(route=...) takes."""
-        import torch
         if not isinstance(accept, GroupAccept) or accept.group is not self or not isinstance(table, RouteTable) or \
                 table.group is not self:
             raise XywsError(-1, "route() takes this group's accept() result and one of its route tables")
@@ -927,23 +987,16 @@ class connection_group:
         rtab = _lib.Table(_lib.RosterConn, self.n)
         for i in range(self.n):
             rtab[i].room = _lib.ROOM_NONE
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            tensors = dict(rtconns=tab.upload(self.device), rconns=rtab.upload(self.device),
-                           results=torch.zeros(max(m, 1) * 32, dtype=torch.uint8, device=self.device))
-            check(self.ctx.L.xyws_route_streams(
-                self.ctx.h, C.c_void_p(accept._table_t.data_ptr()), C.c_void_p(accept.results_t.data_ptr()),
-                C.c_void_p(tensors["rtconns"].data_ptr()), m, C.c_void_p(table.blob_t.data_ptr()), table.nbytes,
-                C.c_void_p(tensors["rconns"].data_ptr()), self.n, int(default_room),
-                _lib.RT_MISS_404 if miss_404 else 0, C.c_void_p(tensors["results"].data_ptr()),
-                C.c_void_p(stream.cuda_stream)), "xyws_route_streams")
+        tensors = dict(rtconns=tab.upload(self.device), rconns=rtab.upload(self.device),
+                       results=_lib.alloc_rows(_lib.RouteResult, m, self.device))
+        self._call("xyws_route_streams", accept._table_t, accept.results_t, tensors["rtconns"], m, table.blob_t,
+                   table.nbytes, tensors["rconns"], self.n, int(default_room), _lib.RT_MISS_404 if miss_404 else 0,
+                   tensors["results"])
         return GroupRoute(self, accept, table, rconn_of, tensors)
 
     def reply_carry(self, conn_id):
         """Host copy of a connection's reply carry (synchronizes)."""
-        if not 0 <= conn_id < self.n:
-            raise XywsError(-1, "no such connection")
-        return _lib.ReplyCarry.from_buffer_copy(self.rcarry_t[32 * conn_id:32 * conn_id + 32].cpu().numpy().tobytes())
+        return self._carry_of(self.rcarry_t, _lib.ReplyCarry, conn_id)
 
     def reply(self, result, out_items, max_payload, policy=0, flags=0x11, enc_opts=0, action_mask=1):
         """Answer the frames of the decode() call that returned `result`
@@ -956,33 +1009,24 @@ class connection_group:
         group owns the reply carries; the verdict rows (cap per connection)
         and the result rows live in its tensors until the next reply().
         Call it before the group's next decode(): the counts are that call's."""
-        import torch
-        if result.group is not self or result._slot is None or not self.cap:
+        if result.group is not self or result.resident or not self.cap:
             raise XywsError(-1, "reply() takes the result of this group's decode(), and a group with cap > 0")
         outs = [_dev_u8(t) for t in out_items]
         if len(outs) != len(result.ids) or any(t.device != self.device for t in outs):
             raise XywsError(-1, "one send buffer on the group's device per decoded item")
-        k = result._slot
-        if result._replied and self._done[k] is not None:
-            self._done[k].synchronize()  # (the slot's reply table is rewritten)
+        slot = result.slot
+        if result._replied:
+            slot.wait()  # (the slot's reply table is rewritten)
         result._replied = True
-        m = len(outs)
-        tab = _lib.Table(_lib.ReplyConn, m, self._rhost[k])
-        rbase, vbase = self.rcarry_t.data_ptr(), self.verdicts_t.data_ptr()
-        for row, i, t in zip(tab.rows, result.ids, outs):
-            row.out, row.out_cap, row.rc, row.verdicts = t.data_ptr(), t.numel(), rbase + 32 * i, vbase + 8 * self.cap * i
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            tab.upload(self._rdev[k])
-            check(self.ctx.L.xyws_reply_streams(
-                self.ctx.h, C.c_void_p(self._dev[k].data_ptr()), C.c_void_p(self.counts_t.data_ptr()),
-                C.c_void_p(self._rdev[k].data_ptr()), m, int(max_payload), policy, flags, enc_opts, action_mask,
-                C.c_void_p(self.results_t.data_ptr()), C.c_void_p(stream.cuda_stream)), "xyws_reply_streams")
-            self._done[k] = torch.cuda.Event()
-            self._done[k].record(stream)
-        rep = GroupReply(self, result)
-        rep.outs = outs  # (outbox() packs them)
-        return rep
+
+        def fill(row, k):
+            _set_out(row, outs[k])
+            row.rc = _lib.row_ptr(self.rcarry_t, _lib.ReplyCarry, result.ids[k])
+            row.verdicts = _lib.row_ptr(self.verdicts_t, _lib.Verdict, self.cap * result.ids[k])
+        rconns_t = slot.upload(_lib.ReplyConn, len(outs), fill)
+        self._call("xyws_reply_streams", result.conns_t, self.counts_t, rconns_t, len(outs), int(max_payload), policy,
+                   flags, enc_opts, action_mask, self.results_t, slot=slot)
+        return GroupReply(self, result, outs)
 
     def reassemble(self, result, out_items, opts=_lib.REASM_UTF8, msg_cap=None):
         """Gather and validate the messages of the decode() call that returned
@@ -994,8 +1038,7 @@ class connection_group:
         connection, msg_cap of them used: default all) and the result rows live in
         its tensors until the next reassemble(). Works before or after reply() on
         the same result; call it before the group's next decode()."""
-        import torch
-        if result.group is not self or result._slot is None or not self.cap:
+        if result.group is not self or result.resident or not self.cap:
             raise XywsError(-1, "reassemble() takes the result of this group's decode(), and a group with cap > 0")
         outs = [_dev_u8(t) for t in out_items]
         if len(outs) != len(result.ids) or any(t.device != self.device for t in outs):
@@ -1003,35 +1046,23 @@ class connection_group:
         mcap = self.cap + 1 if msg_cap is None else int(msg_cap)
         if not 0 <= mcap <= self.cap + 1:
             raise XywsError(-1, "msg_cap above the group's record row (cap + 1)")
-        k = result._slot
-        if result._reassembled and self._done[k] is not None:
-            self._done[k].synchronize()  # (the slot's table is rewritten)
+        slot = result.slot
+        if result._reassembled:
+            slot.wait()  # (the slot's table is rewritten)
         result._reassembled = True
-        m = len(outs)
-        tab = _lib.Table(_lib.ReasmConn, m, self._mhost[k])
-        cbase, mbase = self.mcarry_t.data_ptr(), self.msgs_t.data_ptr()
-        for row, i, t in zip(tab.rows, result.ids, outs):
-            row.out, row.out_cap, row.mc = t.data_ptr(), t.numel(), cbase + 64 * i
-            row.msgs, row.msg_cap = mbase + 40 * (self.cap + 1) * i, mcap
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            tab.upload(self._mdev[k])
-            check(self.ctx.L.xyws_reassemble_streams(
-                self.ctx.h, C.c_void_p(self._dev[k].data_ptr()), C.c_void_p(self.counts_t.data_ptr()),
-                C.c_void_p(self._mdev[k].data_ptr()), m, opts, C.c_void_p(self.mresults_t.data_ptr()),
-                C.c_void_p(stream.cuda_stream)), "xyws_reassemble_streams")
-            self._done[k] = torch.cuda.Event()
-            self._done[k].record(stream)
-        got = GroupMessages(self, result, mcap)
-        got.out_caps = [t.numel() for t in outs]  # (broadcast() sizes the wires by them)
-        got.outs = outs                           # (hold() looks in front of them)
-        return got
+
+        def fill(row, k):
+            _set_out(row, outs[k])
+            row.mc = _lib.row_ptr(self.mcarry_t, _lib.MsgCarry, result.ids[k])
+            row.msgs, row.msg_cap = _lib.row_ptr(self.msgs_t, _lib.Message, (self.cap + 1) * result.ids[k]), mcap
+        mconns_t = slot.upload(_lib.ReasmConn, len(outs), fill)
+        self._call("xyws_reassemble_streams", result.conns_t, self.counts_t, mconns_t, len(outs), opts,
+                   self.mresults_t, slot=slot)
+        return GroupMessages(self, result, mcap, outs)
 
     def hold_carry(self, conn_id):
         """Host copy of a connection's hold carry (synchronizes)."""
-        if not 0 <= conn_id < self.n:
-            raise XywsError(-1, "no such connection")
-        return _lib.HoldCarry.from_buffer_copy(self.hcarry_t[32 * conn_id:32 * conn_id + 32].cpu().numpy().tobytes())
+        return self._carry_of(self.hcarry_t, _lib.HoldCarry, conn_id)
 
     def hold(self, messages, hold_cap):
         """Keep the messages that span sweeps (xyws_hold_streams, one launch),
@@ -1044,9 +1075,8 @@ class connection_group:
         suffices. The group owns the hold carries. Returns a GroupHold, which
         broadcast() takes in place of `messages`. Call it before the group's
         next decode(), reply() or reassemble()."""
-        import torch
         dec = messages.decoded
-        if messages.group is not self or dec._slot is None or not hasattr(messages, "outs"):
+        if messages.group is not self or dec.resident or not isinstance(messages, GroupMessages):
             raise XywsError(-1, "hold() takes the result of this group's reassemble()")
         hold_cap = int(hold_cap)
         if hold_cap < 0:
@@ -1055,27 +1085,19 @@ class connection_group:
             if t.storage_offset() * t.element_size() < hold_cap:
                 raise ValueError(f"item {k}: the out tensor needs hold_cap = {hold_cap} bytes of its storage in front "
                                  f"of it, has {t.storage_offset() * t.element_size()}")
-        m = len(dec.ids)
+        m, dev = len(dec.ids), self.device
         htab = _lib.Table(_lib.HoldConn, m)
-        with torch.cuda.device(self.device):
-            tensors = dict(vmsgs=torch.empty(max(m, 1) * (self.cap + 1) * 40, dtype=torch.uint8, device=self.device),
-                           view=torch.zeros(64 * max(m, 1), dtype=torch.uint8, device=self.device),
-                           view_results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
-                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
-                           outs=messages.outs)
-            hbase, vbase = self.hcarry_t.data_ptr(), tensors["vmsgs"].data_ptr()
-            for k, (row, i) in enumerate(zip(htab.rows, dec.ids)):
-                row.hold_cap, row.hc = hold_cap, hbase + 32 * i
-                row.vmsgs, row.vmsg_cap = vbase + 40 * (self.cap + 1) * k, messages.msg_cap
-            tensors["hold"] = htab.upload(self.device)
-            stream = torch.cuda.current_stream(self.device)
-            check(self.ctx.L.xyws_hold_streams(
-                self.ctx.h, C.c_void_p(self._mdev[dec._slot].data_ptr()), C.c_void_p(self.mresults_t.data_ptr()),
-                C.c_void_p(tensors["hold"].data_ptr()), m, C.c_void_p(tensors["view"].data_ptr()),
-                C.c_void_p(tensors["view_results"].data_ptr()), C.c_void_p(tensors["results"].data_ptr()),
-                C.c_void_p(stream.cuda_stream)), "xyws_hold_streams")
-            self._done[dec._slot] = torch.cuda.Event()
-            self._done[dec._slot].record(stream)
+        tensors = dict(vmsgs=_lib.alloc_rows(_lib.Message, m, dev, zero=False, per=self.cap + 1),
+                       view=_lib.alloc_rows(_lib.ReasmConn, m, dev),
+                       view_results=_lib.alloc_rows(_lib.ReasmResult, m, dev),
+                       results=_lib.alloc_rows(_lib.HoldResult, m, dev), outs=messages.outs)
+        for k, (row, i) in enumerate(zip(htab.rows, dec.ids)):
+            row.hold_cap, row.hc = hold_cap, _lib.row_ptr(self.hcarry_t, _lib.HoldCarry, i)
+            row.vmsgs = _lib.row_ptr(tensors["vmsgs"], _lib.Message, (self.cap + 1) * k)
+            row.vmsg_cap = messages.msg_cap
+        tensors["hold"] = htab.upload(dev)
+        self._call("xyws_hold_streams", *messages.tables(), tensors["hold"], m, tensors["view"],
+                   tensors["view_results"], tensors["results"], slot=dec.slot)
         return GroupHold(self, messages, tensors, hold_cap)
 
     def broadcast(self, messages, rooms, out_items, heads=None, reply=None, flags=0x11, enc_opts=0, wire_caps=None):
@@ -1098,13 +1120,9 @@ class connection_group:
         k: XywsError otherwise), and the wires are the room set's. Returns a
         GroupBroadcast. Call it before the group's next decode(), reply() or
         reassemble()."""
-        import numpy as np
-        import torch
         dec = messages.decoded
-        if messages.group is not self or dec._slot is None or not hasattr(messages, "out_caps"):
+        if messages.group is not self or dec.resident or not isinstance(messages, (GroupMessages, GroupHold)):
             raise XywsError(-1, "broadcast() takes the result of this group's reassemble() or hold()")
-        reasm_p, rres_p = messages._tables() if isinstance(messages, GroupHold) else \
-            (self._mdev[dec._slot].data_ptr(), self.mresults_t.data_ptr())
         if reply is not None and (reply.group is not self or reply.decoded is not dec):
             raise XywsError(-1, "reply must be the reply() result of the same sweep")
         outs = [_dev_u8(t) for t in out_items]
@@ -1114,9 +1132,40 @@ class connection_group:
         hds = [None] * m if heads is None else [None if h is None else _dev_u8(h) for h in heads]
         if len(hds) != m or any(h is not None and h.device != self.device for h in hds):
             raise XywsError(-1, "one head (or None) on the group's device per decoded item")
+        btab = _lib.Table(_lib.BcastConn, m)
+        for k, (row, t, h) in enumerate(zip(btab.rows, outs, hds)):
+            row.head, row.head_len = (h.data_ptr(), h.numel()) if h is not None and h.numel() else (0, 0)
+            _set_out(row, t)
+            row.reply = self._reply_row(k) if reply is not None else 0
         if isinstance(rooms, RoomSet):
-            return self._broadcast_resident(messages, rooms, outs, hds, reply, flags, enc_opts, reasm_p, rres_p)
-        item = {i: k for k, i in enumerate(dec.ids)}
+            # the lists, the counts and every connection's room are the device's: only the caller's fields are staged
+            if rooms.group is not self or list(dec.ids) != list(range(self.n)):
+                raise XywsError(-1, "a room set needs slot-stable sweeps: item k is connection k, every connection an item")
+            rooms.stage_bconns(btab)
+            room_set, wires = rooms, rooms.wires
+            tensors = dict(members=rooms.members_t, rooms=rooms.rooms_t, bconns=rooms.bconns_t)
+        else:
+            room_set = None
+            wires, tensors = self._room_tables(messages, rooms, hds, wire_caps, btab)
+        nr = len(wires)
+        tensors.update(room_results=_lib.alloc_rows(_lib.RoomResult, nr, self.device),
+                       results=_lib.alloc_rows(_lib.BcastResult, m, self.device))
+        self._call("xyws_broadcast_streams", *messages.tables(), tensors["bconns"], m, tensors["rooms"],
+                   tensors["room_results"], nr, flags, enc_opts, tensors["results"], slot=dec.slot)
+        return GroupBroadcast(self, messages, outs, hds, reply is not None, wires, tensors, room_set)
+
+    def _reply_row(self, k):
+        """The address of item k's xyws_reply_result row."""
+        return _lib.row_ptr(self.results_t, _lib.ReplyResult, k)
+
+    def _room_tables(self, messages, rooms, hds, wire_caps, btab):
+        """broadcast() over lists: every room's wire, and the member array, the
+        xyws_room table and the bconns table (btab with every item's room) on
+        the device."""
+        import numpy as np
+        import torch
+        ids_of = messages.decoded.ids
+        item = {i: k for k, i in enumerate(ids_of)}
         room_of, flat = {}, []
         for r, ids in enumerate(rooms):
             for i in ids:
@@ -1133,34 +1182,17 @@ class connection_group:
             need = sum(messages.out_caps[item[int(i)]] + messages.msg_cap * (10 + hlen[item[int(i)]]) for i in ids)
             wires.append(torch.empty(max(need if wire_caps is None else int(wire_caps[r]), 1), dtype=torch.uint8,
                                      device=self.device))
-        btab = _lib.Table(_lib.BcastConn, m)
-        rbase = self.results_t.data_ptr()
-        for k, (row, i, t, h) in enumerate(zip(btab.rows, dec.ids, outs, hds)):
-            row.head, row.head_len = (h.data_ptr(), h.numel()) if h is not None and h.numel() else (0, 0)
-            row.out, row.out_cap = t.data_ptr(), t.numel()
-            row.reply = rbase + 32 * k if reply is not None else 0
+        for row, i in zip(btab.rows, ids_of):
             row.room = room_of.get(i, _lib.ROOM_NONE)
-        with torch.cuda.device(self.device):
-            members_t = torch.from_numpy(np.asarray(flat + [0], np.uint32).view(np.uint8)).to(self.device)
-            rtab = _lib.Table(_lib.Room, nr)
-            pos = 0
-            for r, (row, ids) in enumerate(zip(rtab.rows, rooms)):
-                cap = wires[r].numel() if wire_caps is None else int(wire_caps[r])
-                row.members, row.n_members = members_t.data_ptr() + 4 * pos, len(ids)
-                row.wire, row.wire_cap = wires[r].data_ptr() if cap else 0, cap
-                pos += len(ids)
-            tensors = dict(members=members_t, rooms=rtab.upload(self.device), bconns=btab.upload(self.device),
-                           room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
-                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
-                           outs=outs, heads=hds, messages=messages, replied=reply is not None)
-            stream = torch.cuda.current_stream(self.device)
-            check(self.ctx.L.xyws_broadcast_streams(
-                self.ctx.h, C.c_void_p(reasm_p), C.c_void_p(rres_p), C.c_void_p(tensors["bconns"].data_ptr()), m,
-                C.c_void_p(tensors["rooms"].data_ptr()), C.c_void_p(tensors["room_results"].data_ptr()), nr, flags, enc_opts,
-                C.c_void_p(tensors["results"].data_ptr()), C.c_void_p(stream.cuda_stream)), "xyws_broadcast_streams")
-            self._done[dec._slot] = torch.cuda.Event()
-            self._done[dec._slot].record(stream)
-        return GroupBroadcast(self, dec, tensors, wires)
+        members_t = torch.from_numpy(np.asarray(flat + [0], np.uint32).view(np.uint8)).to(self.device)
+        rtab = _lib.Table(_lib.Room, nr)
+        pos = 0
+        for r, (row, ids) in enumerate(zip(rtab.rows, rooms)):
+            cap = wires[r].numel() if wire_caps is None else int(wire_caps[r])
+            row.members, row.n_members = members_t.data_ptr() + 4 * pos, len(ids)
+            row.wire, row.wire_cap = wires[r].data_ptr() if cap else 0, cap
+            pos += len(ids)
+        return wires, dict(members=members_t, rooms=rtab.upload(self.device), bconns=btab.upload(self.device))
 
     def rooms(self, n_rooms, member_cap, wire_cap=65536, notes_cap=65536):
         """A room set on the device: n_rooms rooms of at most member_cap
@@ -1168,38 +1200,6 @@ class connection_group:
         bytes, all empty. broadcast(..., rooms=room_set) reads it, roster()
         keeps it. Returns a RoomSet."""
         return RoomSet(self, n_rooms, member_cap, int(wire_cap), int(notes_cap))
-
-    def _broadcast_resident(self, messages, room_set, outs, hds, reply, flags, enc_opts, reasm_p, rres_p):
-        """broadcast() over a room set: the lists, the counts and every
-        connection's room are the device's; only the caller's fields of the
-        bconns rows are staged."""
-        import torch
-        dec = messages.decoded
-        m = len(dec.ids)
-        if room_set.group is not self or list(dec.ids) != list(range(self.n)):
-            raise XywsError(-1, "a room set needs slot-stable sweeps: item k is connection k, every connection an item")
-        btab = _lib.Table(_lib.BcastConn, m)
-        rbase = self.results_t.data_ptr()
-        for k, (row, t, h) in enumerate(zip(btab.rows, outs, hds)):
-            row.head, row.head_len = (h.data_ptr(), h.numel()) if h is not None and h.numel() else (0, 0)
-            row.out, row.out_cap = t.data_ptr(), t.numel()
-            row.reply = rbase + 32 * k if reply is not None else 0
-        with torch.cuda.device(self.device):
-            room_set.stage_bconns(btab)
-            nr = room_set.nr
-            tensors = dict(members=room_set.members_t, rooms=room_set.rooms_t, bconns=room_set.bconns_t,
-                           room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
-                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device),
-                           outs=outs, heads=hds, messages=messages, replied=reply is not None, room_set=room_set)
-            stream = torch.cuda.current_stream(self.device)
-            check(self.ctx.L.xyws_broadcast_streams(
-                self.ctx.h, C.c_void_p(reasm_p), C.c_void_p(rres_p), C.c_void_p(room_set.bconns_t.data_ptr()), m,
-                C.c_void_p(room_set.rooms_t.data_ptr()), C.c_void_p(tensors["room_results"].data_ptr()), nr, flags,
-                enc_opts, C.c_void_p(tensors["results"].data_ptr()), C.c_void_p(stream.cuda_stream)),
-                "xyws_broadcast_streams")
-            self._done[dec._slot] = torch.cuda.Event()
-            self._done[dec._slot].record(stream)
-        return GroupBroadcast(self, dec, tensors, room_set.wires)
 
     def roster(self, bcast, room_set, names=None, joins=(), leaves=(), accept=None, on_accept=None,
                leave_on_close=True, flags=0x11, text=None, route=None):
@@ -1221,10 +1221,9 @@ class connection_group:
         back: the next sweep's broadcast() finds the new lists on the device.
         Returns a GroupRoster, which backlog() takes in place of `bcast`."""
         import torch
-        if not isinstance(bcast, GroupBroadcast) or bcast.group is not self or \
-                bcast._tensors.get("room_set") is not room_set:
+        if not isinstance(bcast, GroupBroadcast) or bcast.group is not self or bcast.room_set is not room_set:
             raise XywsError(-1, "roster() takes the result of this group's broadcast() over the same room set")
-        dec, bt = bcast.decoded, bcast._tensors
+        dec = bcast.decoded
         m, nr = len(dec.ids), room_set.nr
         nms = [None] * m if names is None else [None if t is None else _dev_u8(t) for t in names]
         if len(nms) != m or any(t is not None and (t.device != self.device or t.numel() > _lib.ROSTER_NAME_MAX)
@@ -1257,40 +1256,40 @@ class connection_group:
         if text is not None and max(text.head_len, text.joined_len, text.left_len) > _lib.ROSTER_TEXT_MAX:
             raise XywsError(-1, "a text length above 32")
         rtab, jtab = _lib.Table(_lib.RosterConn, m), _lib.Table(_lib.BacklogConn, m)
-        with torch.cuda.device(self.device):
-            results_t = torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device)
-            bbase, pbase = bt["results"].data_ptr(), self.results_t.data_ptr()
-            abase = accept.results_t.data_ptr() if acc_row else 0
-            for k, (row, jrow, t, nm) in enumerate(zip(rtab.rows, jtab.rows, bt["outs"], nms)):
-                row.name, row.name_len = (nm.data_ptr(), nm.numel()) if nm is not None and nm.numel() else (0, 0)
-                row.out, row.out_cap = t.data_ptr(), t.numel()
-                room, fl = ask.get(k, (_lib.ROOM_NONE, 0))
-                if k in acc_row and fl & _lib.RS_JOIN_ON_ACCEPT:
-                    row.accept = abase + 32 * acc_row[k]  # (the 101 is all this sweep wrote for it)
-                else:
-                    row.bcast, row.reply = bbase + 32 * k, pbase + 32 * k if bt["replied"] else 0
-                fl |= (_lib.RS_LEAVE if k in gone else 0) | (_lib.RS_LEAVE_ON_CLOSE if leave_on_close else 0)
-                row.room, row.flags = room, fl
-                jrow.out, jrow.out_cap, jrow.bcast = t.data_ptr(), t.numel(), results_t.data_ptr() + 32 * k
-                jrow.reply = pbase + 32 * k if bt["replied"] and not row.accept else 0
-                jrow.room, jrow.flags = _lib.ROOM_NONE, 0
-            rconns_t = rtab.upload(self.device)
-            if routed:
-                rconns_t = route._complete(rconns_t, routed)
-            tensors = dict(rconns=rconns_t, jconns=jtab.upload(self.device), results=results_t,
-                           room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
-                           want=torch.zeros(max(m, 1), dtype=torch.int32, device=self.device), names=nms, accept=accept,
-                           text=text, route=route)
-            stream = torch.cuda.current_stream(self.device)
-            check(self.ctx.L.xyws_roster_streams(
-                self.ctx.h, C.c_void_p(room_set.bconns_t.data_ptr()), C.c_void_p(tensors["rconns"].data_ptr()), m,
-                C.c_void_p(room_set.rooms_t.data_ptr()), C.c_void_p(room_set.rrooms_t.data_ptr()),
-                C.c_void_p(tensors["room_results"].data_ptr()), nr, C.byref(text) if text is not None else None, flags,
-                C.c_void_p(tensors["jconns"].data_ptr()), C.c_void_p(tensors["want"].data_ptr()),
-                C.c_void_p(results_t.data_ptr()), C.c_void_p(stream.cuda_stream)), "xyws_roster_streams")
-            self._done[dec._slot] = torch.cuda.Event()
-            self._done[dec._slot].record(stream)
+        results_t = _lib.alloc_rows(_lib.RosterResult, m, self.device)
+        for k, (row, jrow, t, nm) in enumerate(zip(rtab.rows, jtab.rows, bcast.outs, nms)):
+            row.name, row.name_len = (nm.data_ptr(), nm.numel()) if nm is not None and nm.numel() else (0, 0)
+            _set_out(row, t)
+            room, fl = ask.get(k, (_lib.ROOM_NONE, 0))
+            if k in acc_row and fl & _lib.RS_JOIN_ON_ACCEPT:
+                # (the 101 is all this sweep wrote for it)
+                row.accept = _lib.row_ptr(accept.results_t, _lib.AcceptResult, acc_row[k])
+            else:
+                row.bcast = _lib.row_ptr(bcast.results_t, _lib.BcastResult, k)
+                row.reply = self._reply_row(k) if bcast.replied else 0
+            fl |= (_lib.RS_LEAVE if k in gone else 0) | (_lib.RS_LEAVE_ON_CLOSE if leave_on_close else 0)
+            row.room, row.flags = room, fl
+            self._backlog_row(jrow, t, k, _lib.row_ptr(results_t, _lib.RosterResult, k),
+                              bcast.replied and not row.accept)
+        rconns_t = rtab.upload(self.device)
+        if routed:
+            rconns_t = route._complete(rconns_t, routed)
+        tensors = dict(rconns=rconns_t, jconns=jtab.upload(self.device), results=results_t,
+                       room_results=_lib.alloc_rows(_lib.RosterRoomResult, nr, self.device),
+                       want=torch.zeros(max(m, 1), dtype=torch.int32, device=self.device), names=nms, accept=accept,
+                       text=text, route=route)
+        self._call("xyws_roster_streams", room_set.bconns_t, rconns_t, m, room_set.rooms_t, room_set.rrooms_t,
+                   tensors["room_results"], nr, C.byref(text) if text is not None else None, flags, tensors["jconns"],
+                   tensors["want"], results_t, slot=dec.slot)
         return GroupRoster(self, bcast, room_set, tensors)
+
+    def _backlog_row(self, row, t, k, bcast_row, replied, room=_lib.ROOM_NONE, flags=0):
+        """Item k's xyws_backlog_conn row: its send tensor t behind what the
+        row at bcast_row says was written, its reply row when the sweep has
+        one, and the room it joins (BL_JOIN in flags) or none."""
+        _set_out(row, t)
+        row.bcast, row.reply = bcast_row, self._reply_row(k) if replied else 0
+        row.room, row.flags = room, flags
 
     def state_tensors(self):
         """Every tensor of the group that carries state from one sweep to the
@@ -1336,10 +1335,7 @@ class connection_group:
             bcast = roster.bcast
         if not isinstance(bcast, GroupBroadcast) or bcast.group is not self:
             raise XywsError(-1, "backlog() takes the result of this group's broadcast() or roster()")
-        dec, bt = bcast.decoded, bcast._tensors
-        messages = bt["messages"]
-        reasm_p, rres_p = messages._tables() if isinstance(messages, GroupHold) else \
-            (self._mdev[dec._slot].data_ptr(), self.mresults_t.data_ptr())
+        dec = bcast.decoded
         m, nr = len(dec.ids), len(bcast._wires)
         keep = int(keep)
         cap = 2 * max(min(keep, _lib.BACKLOG_MAX), 1) * 4096 + 30 if log_cap is None else int(log_cap)
@@ -1352,41 +1348,31 @@ class connection_group:
             if int(i) not in item or int(i) in joined or not 0 <= int(r) < nr:
                 raise XywsError(-1, "a joiner must be an item of this sweep, join once, and name a room of the sweep")
             joined[int(i)] = int(r)
-        with torch.cuda.device(self.device):
-            if log_cap is not None and any(lcap != cap for _, lcap in self._blogs[:nr]):
-                raise XywsError(-1, "a room's log keeps the log_cap it was made with")
-            while len(self._blogs) < nr:
-                self._blogs.append((torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device), cap))
-                self._bcarries.append(torch.zeros(192, dtype=torch.uint8, device=self.device))
-            rtab = _lib.Table(_lib.BacklogRoom, nr)
-            for r in range(nr):
-                row, (log, lcap) = rtab[r], self._blogs[r]
-                row.log, row.log_cap, row.bc, row.keep = log.data_ptr(), lcap, self._bcarries[r].data_ptr(), keep
-            jtab = _lib.Table(_lib.BacklogConn, m)
-            bbase, rbase = bt["results"].data_ptr(), self.results_t.data_ptr()
-            for k, (row, i, t) in enumerate(zip(jtab.rows, dec.ids, bt["outs"])):
-                # (the reply row broadcast() named: only it says that a joiner, not yet a member, closed or overflowed)
-                row.out, row.out_cap, row.bcast = t.data_ptr(), t.numel(), bbase + 32 * k
-                row.reply = rbase + 32 * k if bt["replied"] else 0
-                row.room, row.flags = (joined[i], _lib.BL_JOIN) if i in joined else (_lib.ROOM_NONE, 0)
-            tensors = dict(brooms=rtab.upload(self.device),
-                           jconns=jtab.upload(self.device) if roster is None else roster._tensors["jconns"],
-                           room_results=torch.zeros(32 * max(nr, 1), dtype=torch.uint8, device=self.device),
-                           results=torch.zeros(32 * max(m, 1), dtype=torch.uint8, device=self.device), bcast=bcast,
-                           roster=roster)
-            stream = torch.cuda.current_stream(self.device)
-            # (after roster() the room table holds the next sweep's lists: the fold walks the ones this sweep's
-            # broadcast read, which roster() left in the room set's `seen` rows)
-            rooms_t = bt["rooms"] if roster is None else roster.room_set.seen_rooms_t
-            check(self.ctx.L.xyws_backlog_streams(
-                self.ctx.h, C.c_void_p(reasm_p), C.c_void_p(rres_p), C.c_void_p(bt["bconns"].data_ptr()), m,
-                C.c_void_p(rooms_t.data_ptr()), C.c_void_p(bt["room_results"].data_ptr()),
-                C.c_void_p(tensors["brooms"].data_ptr()), C.c_void_p(tensors["room_results"].data_ptr()), nr,
-                C.c_void_p(tensors["jconns"].data_ptr()), C.c_void_p(tensors["results"].data_ptr()),
-                C.c_void_p(stream.cuda_stream)), "xyws_backlog_streams")
-            self._done[dec._slot] = torch.cuda.Event()
-            self._done[dec._slot].record(stream)
-        return GroupBacklog(self, dec, tensors, nr)
+        if log_cap is not None and any(lcap != cap for _, lcap in self._blogs[:nr]):
+            raise XywsError(-1, "a room's log keeps the log_cap it was made with")
+        while len(self._blogs) < nr:
+            self._blogs.append((torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device), cap))
+            self._bcarries.append(_lib.alloc_rows(_lib.BacklogCarry, 1, self.device))
+        rtab = _lib.Table(_lib.BacklogRoom, nr)
+        for r in range(nr):
+            row, (log, lcap) = rtab[r], self._blogs[r]
+            row.log, row.log_cap, row.bc, row.keep = log.data_ptr(), lcap, self._bcarries[r].data_ptr(), keep
+        jtab = _lib.Table(_lib.BacklogConn, m)
+        for k, (row, i, t) in enumerate(zip(jtab.rows, dec.ids, bcast.outs)):
+            # (the reply row broadcast() named: only it says that a joiner, not yet a member, closed or overflowed)
+            room, fl = (joined[i], _lib.BL_JOIN) if i in joined else (_lib.ROOM_NONE, 0)
+            self._backlog_row(row, t, k, _lib.row_ptr(bcast.results_t, _lib.BcastResult, k), bcast.replied, room, fl)
+        tensors = dict(brooms=rtab.upload(self.device),
+                       jconns=jtab.upload(self.device) if roster is None else roster.jconns_t,
+                       room_results=_lib.alloc_rows(_lib.BacklogRoomResult, nr, self.device),
+                       results=_lib.alloc_rows(_lib.BacklogResult, m, self.device))
+        # (after roster() the room table holds the next sweep's lists: the fold walks the ones this sweep's
+        # broadcast read, which roster() left in the room set's `seen` rows)
+        rooms_t = bcast.rooms_t if roster is None else roster.room_set.seen_rooms_t
+        self._call("xyws_backlog_streams", *bcast.messages.tables(), bcast.bconns_t, m, rooms_t, bcast.room_results_t,
+                   tensors["brooms"], tensors["room_results"], nr, tensors["jconns"], tensors["results"],
+                   slot=dec.slot)
+        return GroupBacklog(self, bcast, roster, tensors, nr)
 
     def outbox(self, last, accept=None, pack_cap=None, host=False):
         """Pack what a sweep left to send (xyws_outbox_streams, three
@@ -1404,7 +1390,7 @@ class connection_group:
         roster = bcast = reply = None
         backlog = last if isinstance(last, GroupBacklog) else None
         if backlog is not None:
-            roster, bcast = backlog._tensors["roster"], backlog._tensors["bcast"]
+            roster, bcast = backlog.roster, backlog.bcast
         elif isinstance(last, GroupRoster):
             roster, bcast = last, last.bcast
         elif isinstance(last, GroupBroadcast):
@@ -1419,7 +1405,7 @@ class connection_group:
             raise ValueError("pack_cap must not be negative")
         ids = [] if last is None else list(last.decoded.ids)
         if bcast is not None:
-            outs, replied = list(bcast._tensors["outs"]), bcast._tensors["replied"]
+            outs, replied = list(bcast.outs), bcast.replied
         else:
             outs, replied = (list(reply.outs), True) if reply is not None else ([], False)
         m = len(ids)
@@ -1434,41 +1420,37 @@ class connection_group:
                 outs.append(accept.outs[j])
         n = len(ids)
         tab = _lib.Table(_lib.OutboxConn, n)
-        jbase = backlog._tensors["results"].data_ptr() if backlog is not None else 0
-        bbase = (roster or bcast)._tensors["results"].data_ptr() if bcast is not None else 0
-        pbase, abase = self.results_t.data_ptr(), accept.results_t.data_ptr() if accept is not None else 0
+        sent = roster if roster is not None else bcast  # (an xyws_roster_result reads as an xyws_bcast_result)
         for k, (row, t) in enumerate(zip(tab.rows, outs)):
             row.out, row.out_cap = (t.data_ptr(), t.numel()) if t.numel() else (0, 0)
             if k < m:
-                row.backlog, row.bcast = jbase and jbase + 32 * k, bbase and bbase + 32 * k
+                row.backlog = _lib.row_ptr(backlog.results_t, _lib.BacklogResult, k) if backlog is not None else 0
+                row.bcast = _lib.row_ptr(sent.results_t, _lib.BcastResult, k) if sent is not None else 0
                 # (as roster(): a connection still in HTTP state has no reply row of this sweep)
-                row.reply = pbase + 32 * k if replied and k not in acc_of else 0
-            row.accept = abase + 32 * acc_of[k] if k in acc_of else 0
+                row.reply = self._reply_row(k) if replied and k not in acc_of else 0
+            row.accept = _lib.row_ptr(accept.results_t, _lib.AcceptResult, acc_of[k]) if k in acc_of else 0
         cap = sum((t.numel() + 15) & ~15 for t in outs) if pack_cap is None else int(pack_cap)
         L = self.ctx.L
-        need = L.xyws_outbox_scratch_bytes(n)
-        with torch.cuda.device(self.device):
-            sizes = dict(pack=max(cap, 16), entries=32 * max(n, 1), summary=64)
-            if host:
-                keep = {k: torch.zeros(v, dtype=torch.uint8).pin_memory() for k, v in sizes.items()}
-                ptr = {}
+        where = "cpu" if host else self.device
+        keep = dict(pack=torch.zeros(max(cap, 16), dtype=torch.uint8, device=where),
+                    entries=_lib.alloc_rows(_lib.OutboxEntry, n, where),
+                    summary=_lib.alloc_rows(_lib.OutboxSummary, 1, where))
+        if host:
+            ptr = {}
+            with torch.cuda.device(self.device):
+                keep = {k: t.pin_memory() for k, t in keep.items()}
                 for k, t in keep.items():
                     d = C.c_void_p()
-                    check(L.xyws_outbox_map(C.c_void_p(t.data_ptr()), C.byref(d)), "xyws_outbox_map")
+                    check(L.xyws_outbox_map(t.data_ptr(), C.byref(d)), "xyws_outbox_map")
                     ptr[k] = d.value
-            else:
-                keep = {k: torch.zeros(v, dtype=torch.uint8, device=self.device) for k, v in sizes.items()}
-                ptr = {k: t.data_ptr() for k, t in keep.items()}
-            tensors = dict(keep, conns=tab.upload(self.device), last=last, accept=accept,
-                           scratch=torch.empty(max(need, 8), dtype=torch.uint8, device=self.device))
-            stream = torch.cuda.current_stream(self.device)
-            check(L.xyws_outbox_streams(
-                self.ctx.h, C.c_void_p(tensors["conns"].data_ptr()), n, C.c_void_p(ptr["pack"]) if cap else None, cap,
-                C.c_void_p(ptr["entries"]), C.c_void_p(ptr["summary"]), C.c_void_p(tensors["scratch"].data_ptr()),
-                tensors["scratch"].numel(), C.c_void_p(stream.cuda_stream)), "xyws_outbox_streams")
-            tensors["done"] = torch.cuda.Event()
-            tensors["done"].record(stream)
-        return GroupOutbox(self, ids, outs, tensors, cap, host)
+        else:
+            ptr = {k: t.data_ptr() for k, t in keep.items()}
+        tensors = dict(keep, conns=tab.upload(self.device),
+                       scratch=torch.empty(max(L.xyws_outbox_scratch_bytes(n), 8), dtype=torch.uint8, device=self.device))
+        done = _Done()
+        self._call("xyws_outbox_streams", tensors["conns"], n, ptr["pack"] if cap else None, cap, ptr["entries"],
+                   ptr["summary"], tensors["scratch"], tensors["scratch"].numel(), done=done)
+        return GroupOutbox(self, ids, outs, tensors, cap, host, last, accept, done)
 
     def _inbox_state(self, recv_cap, resp_cap):
         """The receive slab, the inbox carries and the resident tables (made once)."""
@@ -1482,22 +1464,22 @@ class connection_group:
             ib = dict(recv_cap=recv_cap, resp_cap=resp_cap,
                       slab=torch.zeros(max(n * recv_cap, 16), dtype=torch.uint8, device=dev),
                       resp=torch.zeros(max(n * resp_cap, 16), dtype=torch.uint8, device=dev),
-                      carries=torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=dev),
-                      aresults=torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=dev),
-                      results=torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=dev))
+                      carries=_lib.alloc_rows(_lib.InboxCarry, n, dev),
+                      aresults=_lib.alloc_rows(_lib.AcceptResult, n, dev),
+                      results=_lib.alloc_rows(_lib.InboxResult, n, dev))
             conns, aconns = _lib.Table(_lib.Conn, n), _lib.Table(_lib.AcceptConn, n)
             for i in range(n):
                 c, a = conns[i], aconns[i]
-                c.buf, c.len, c.carry = ib["slab"].data_ptr() + recv_cap * i, 0, self.carry_t.data_ptr() + 64 * i
-                c.frames, c.cap = (self.frames_t.data_ptr() + 32 * self.cap * i, self.cap) if self.cap else (0, 0)
+                self._conn_row(c, ib["slab"].data_ptr() + recv_cap * i, 0, i)
                 a.buf, a.len, a.out, a.out_cap = c.buf, 0, ib["resp"].data_ptr() + resp_cap * i, resp_cap
             ib["conns"], ib["aconns"] = conns.upload(dev), aconns.upload(dev)
             iconns = _lib.Table(_lib.InboxConn, n)
             for i in range(n):
                 r = iconns[i]
-                r.buf, r.cap, r.carry = ib["slab"].data_ptr() + recv_cap * i, recv_cap, ib["carries"].data_ptr() + 32 * i
-                r.conn, r.aconn = ib["conns"].data_ptr() + 64 * i, ib["aconns"].data_ptr() + 32 * i
-                r.aresult = ib["aresults"].data_ptr() + 32 * i
+                r.buf, r.cap = ib["slab"].data_ptr() + recv_cap * i, recv_cap
+                r.carry = _lib.row_ptr(ib["carries"], _lib.InboxCarry, i)
+                r.conn, r.aconn = _lib.row_ptr(ib["conns"], _lib.Conn, i), _lib.row_ptr(ib["aconns"], _lib.AcceptConn, i)
+                r.aresult = _lib.row_ptr(ib["aresults"], _lib.AcceptResult, i)
             ib["iconns"] = iconns.upload(dev)
         self._ib = ib
         return ib
@@ -1543,56 +1525,24 @@ class connection_group:
         tab = _lib.Table(_lib.InboxEntry, m_cap)
         for row, e in zip(tab.rows, ents):
             row.conn, row.off, row.len, row.at, row.flags = e[0], e[1], e[2], e[3], e[4] if len(e) == 5 else 0
-        with torch.cuda.device(self.device):
-            tensors = dict(head=head.upload(self.device), entries=tab.upload(self.device), pack=pack_t,
-                           summary=torch.zeros(64, dtype=torch.uint8, device=self.device), results=ib["results"],
-                           scratch=torch.empty(max(need, 8), dtype=torch.uint8, device=self.device))
-            stream = torch.cuda.current_stream(self.device)
-            check(L.xyws_inbox_streams(
-                self.ctx.h, C.c_void_p(ib["iconns"].data_ptr()), self.n, C.c_void_p(tensors["head"].data_ptr()),
-                C.c_void_p(tensors["entries"].data_ptr()) if m_cap else None, m_cap,
-                C.c_void_p(pack_t.data_ptr()) if pack_len else None, pack_len, C.c_void_p(ib["results"].data_ptr()),
-                C.c_void_p(tensors["summary"].data_ptr()), C.c_void_p(tensors["scratch"].data_ptr()),
-                tensors["scratch"].numel(), C.c_void_p(stream.cuda_stream)), "xyws_inbox_streams")
-            tensors["done"] = torch.cuda.Event()
-            tensors["done"].record(stream)
-        return GroupInbox(self, tensors, m)
+        tensors = dict(head=head.upload(self.device), entries=tab.upload(self.device), pack=pack_t,
+                       summary=_lib.alloc_rows(_lib.InboxSummary, 1, self.device), results=ib["results"],
+                       scratch=torch.empty(max(need, 8), dtype=torch.uint8, device=self.device))
+        done = _Done()
+        self._call("xyws_inbox_streams", ib["iconns"], self.n, tensors["head"], tensors["entries"] if m_cap else None,
+                   m_cap, pack_t if pack_len else None, pack_len, ib["results"], tensors["summary"], tensors["scratch"],
+                   tensors["scratch"].numel(), done=done)
+        return GroupInbox(self, tensors, m, done)
 
     def inbox_carry(self, conn_id):
         """Host copy of a connection's inbox carry (synchronizes)."""
         if not 0 <= conn_id < self.n or self._ib is None:
             raise XywsError(-1, "no such connection, or no inbox() call yet")
-        return _lib.read_rows(_lib.InboxCarry, self._ib["carries"], 1, conn_id)[0]
-
-    def _decode_resident(self, inbox):
-        import torch
-        if inbox.group is not self:
-            raise XywsError(-1, "decode() takes a GroupInbox of this group")
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            check(self.ctx.L.xyws_decode_streams(self.ctx.h, C.c_void_p(self._ib["conns"].data_ptr()), self.n,
-                                                 C.c_void_p(self.counts_t.data_ptr()), self.opts,
-                                                 C.c_void_p(stream.cuda_stream)), "xyws_decode_streams")
-        return GroupResult(self, list(range(self.n)))
-
-    def _accept_resident(self, inbox, out_items, policy, max_request):
-        import torch
-        if inbox.group is not self or out_items is not None:
-            raise XywsError(-1, "accept() takes a GroupInbox of this group and no send buffers with it")
-        ib = self._ib
-        outs = [ib["resp"][ib["resp_cap"] * i:ib["resp_cap"] * (i + 1)] for i in range(self.n)]
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            check(self.ctx.L.xyws_accept_streams(self.ctx.h, C.c_void_p(ib["aconns"].data_ptr()), self.n,
-                                                 int(max_request), int(policy), C.c_void_p(ib["aresults"].data_ptr()),
-                                                 C.c_void_p(stream.cuda_stream)), "xyws_accept_streams")
-        return GroupAccept(self, list(range(self.n)), outs, ib["aconns"], ib["aresults"])
+        return self._carry_of(self._ib["carries"], _lib.InboxCarry, conn_id)
 
     def msg_carry(self, conn_id):
         """Host copy of a connection's message carry (synchronizes)."""
-        if not 0 <= conn_id < self.n:
-            raise XywsError(-1, "no such connection")
-        return _lib.MsgCarry.from_buffer_copy(self.mcarry_t[64 * conn_id:64 * conn_id + 64].cpu().numpy().tobytes())
+        return self._carry_of(self.mcarry_t, _lib.MsgCarry, conn_id)
 
 
 def decode_indexed(buf, starts, frames=True, parse_only=False):
@@ -1602,7 +1552,7 @@ def decode_indexed(buf, starts, frames=True, parse_only=False):
     ctx = context(t.device.index)
     st = torch.as_tensor(starts, dtype=torch.int64).to(t.device)
     n = st.numel()
-    frames_t = torch.empty(max(n, 1) * 32, dtype=torch.uint8, device=t.device) if frames else None
+    frames_t = _lib.alloc_rows(Frame, n, t.device, zero=False) if frames else None
     check(ctx.L.xyws_decode_indexed(
         ctx.h, C.c_void_p(t.data_ptr()), t.numel(), C.c_void_p(st.data_ptr()), n,
         C.c_void_p(frames_t.data_ptr()) if frames_t is not None else None,
@@ -1767,10 +1717,10 @@ def classify_frames(src, frames_t, n, max_payload, policy=0, dev_n=None, verdict
     t = _dev_u8(src)
     ctx = context(t.device.index)
     if verdicts is None:
-        verd = torch.zeros(max(n, 1) * 8, dtype=torch.uint8, device=t.device)
+        verd = _lib.alloc_rows(_lib.Verdict, n, t.device)
     else:
         verd = _dev_u8(verdicts)
-        if verd.numel() < n * 8:
+        if verd.numel() < n * C.sizeof(_lib.Verdict):
             raise XywsError(-1, "verdicts tensor smaller than n records")
     first = torch.zeros(1, dtype=torch.int64, device=t.device)
     check(ctx.L.xyws_classify_frames(ctx.h, C.c_void_p(t.data_ptr()), t.numel(), _opt_ptr(frames_t), n,
@@ -1779,14 +1729,13 @@ def classify_frames(src, frames_t, n, max_payload, policy=0, dev_n=None, verdict
     return verd, first
 
 
-def reassemble(src, frames_t, n, opts=0, out_cap=None, msg_cap=None, dev_n=None, out=None, msgs=None):
-    """FIN=0 chains gathered into messages (xyws_reassemble): returns (out,
-    messages tensor (msg_cap*40 bytes), count tensor). out / msgs: the
-    caller's device uint8 tensors (out_cap defaults to out's size, msg_cap to
-    the records msgs holds) instead of fresh zeroed ones."""
+def _out_and_msgs(t, out, out_cap, msgs, msg_cap, records):
+    """The out tensor and the record tensor of a reassembly of the batch t,
+    each with its capacity: the caller's, checked against out_cap / msg_cap,
+    or a fresh zeroed one (as many bytes as t by default, and `records`
+    records). Returns (out, out_cap, msgs, msg_cap)."""
     import torch
-    t = _dev_u8(src)
-    ctx = context(t.device.index)
+    size = C.sizeof(_lib.Message)
     if out is not None:
         out = _dev_u8(out)
         cap = out.numel() if out_cap is None else out_cap
@@ -1797,12 +1746,24 @@ def reassemble(src, frames_t, n, opts=0, out_cap=None, msg_cap=None, dev_n=None,
         out = torch.zeros(max(cap, 1), dtype=torch.uint8, device=t.device)
     if msgs is not None:
         msgs = _dev_u8(msgs)
-        mcap = msgs.numel() // 40 if msg_cap is None else msg_cap
-        if mcap * 40 > msgs.numel():
+        mcap = msgs.numel() // size if msg_cap is None else msg_cap
+        if mcap * size > msgs.numel():
             raise XywsError(-1, "msg_cap exceeds the msgs tensor")
     else:
-        mcap = max(n, 1) if msg_cap is None else msg_cap
-        msgs = torch.zeros(max(mcap, 1) * 40, dtype=torch.uint8, device=t.device)
+        mcap = records if msg_cap is None else msg_cap
+        msgs = _lib.alloc_rows(_lib.Message, mcap, t.device)
+    return out, cap, msgs, mcap
+
+
+def reassemble(src, frames_t, n, opts=0, out_cap=None, msg_cap=None, dev_n=None, out=None, msgs=None):
+    """FIN=0 chains gathered into messages (xyws_reassemble): returns (out,
+    messages tensor (msg_cap records), count tensor). out / msgs: the
+    caller's device uint8 tensors (out_cap defaults to out's size, msg_cap to
+    the records msgs holds) instead of fresh zeroed ones."""
+    import torch
+    t = _dev_u8(src)
+    ctx = context(t.device.index)
+    out, cap, msgs, mcap = _out_and_msgs(t, out, out_cap, msgs, msg_cap, max(n, 1))
     cnt = torch.zeros(1, dtype=torch.int64, device=t.device)
     check(ctx.L.xyws_reassemble(ctx.h, C.c_void_p(t.data_ptr()), t.numel(), _opt_ptr(frames_t), n, _opt_ptr(dev_n),
                                 opts, C.c_void_p(out.data_ptr()), cap, C.c_void_p(msgs.data_ptr()), mcap,
@@ -1820,7 +1781,7 @@ class message_assembler:
         import torch
         self.ctx = ctx if ctx is not None else context(device)
         self.device = torch.device("cuda", self.ctx.device)
-        self.carry_t = torch.zeros(64, dtype=torch.uint8, device=self.device)
+        self.carry_t = _lib.alloc_rows(_lib.MsgCarry, 1, self.device)
         self.opts = opts
 
     def reset(self):
@@ -1828,30 +1789,15 @@ class message_assembler:
 
     def carry(self):
         """Host copy of the carry (synchronizes)."""
-        return _lib.MsgCarry.from_buffer_copy(self.carry_t.cpu().numpy().tobytes())
+        return _lib.read_rows(_lib.MsgCarry, self.carry_t, 1)[0]
 
     def feed(self, src, frames_t, n, dev_n=None, out=None, msgs=None, out_cap=None, msg_cap=None):
-        """One batch: returns (out, messages tensor (msg_cap*40 bytes), count
+        """One batch: returns (out, messages tensor (msg_cap records), count
         tensor) like reassemble(); record 0 continues the message the last
         batch left open (MSG_CONTINUED). msg_cap defaults to n + 1 records."""
         import torch
         t = _dev_u8(src)
-        if out is not None:
-            out = _dev_u8(out)
-            cap = out.numel() if out_cap is None else out_cap
-            if cap > out.numel():
-                raise XywsError(-1, "out_cap exceeds the out tensor")
-        else:
-            cap = t.numel() if out_cap is None else out_cap
-            out = torch.zeros(max(cap, 1), dtype=torch.uint8, device=t.device)
-        if msgs is not None:
-            msgs = _dev_u8(msgs)
-            mcap = msgs.numel() // 40 if msg_cap is None else msg_cap
-            if mcap * 40 > msgs.numel():
-                raise XywsError(-1, "msg_cap exceeds the msgs tensor")
-        else:
-            mcap = n + 1 if msg_cap is None else msg_cap
-            msgs = torch.zeros(max(mcap, 1) * 40, dtype=torch.uint8, device=t.device)
+        out, cap, msgs, mcap = _out_and_msgs(t, out, out_cap, msgs, msg_cap, n + 1)
         cnt = torch.zeros(1, dtype=torch.int64, device=t.device)
         cp = C.c_void_p(self.carry_t.data_ptr())
         check(self.ctx.L.xyws_reassemble_stream(
@@ -1944,7 +1890,7 @@ def shard_plan_frames(frames, length, n_shards):
     L = _lib.load()
     n = len(frames)
     arr = frames if isinstance(frames, C.Array) else \
-        (Frame * max(n, 1)).from_buffer_copy(b"".join(bytes(f) for f in frames).ljust(32 * max(n, 1), b"\0"))
+        (Frame * max(n, 1)).from_buffer_copy(b"".join(bytes(f) for f in frames).ljust(C.sizeof(Frame) * max(n, 1), b"\0"))
     out = (C.c_uint64 * (n_shards + 1))()
     check(L.xyws_shard_plan_frames(arr, n, int(length), int(n_shards), out), "xyws_shard_plan_frames")
     return list(out)
