@@ -516,7 +516,12 @@ typedef struct xyws_arena_result {
   xyws_carry carry;          /* the connection's carry after it */
 } xyws_arena_result;
 /* host == NULL: allocate `bytes` of pinned memory; else register the caller's
- * host range (unregistered at destroy). eventfd < 0: no notification. */
+ * host range (unregistered at destroy). Where the runtime cannot register
+ * memory the process already has, the arena keeps a pinned stand-in of
+ * `bytes`: submit() copies the range into it, and the completion callback
+ * copies the unmasked bytes back before the submission shows as complete, so
+ * the caller sees the same bytes in the same place. eventfd < 0: no
+ * notification. */
 int xyws_arena_create(xyws_ctx* ctx, void* host, uint64_t bytes, uint64_t max_frames, int eventfd,
                       xyws_arena** out);
 int xyws_arena_destroy(xyws_arena* a);

@@ -74,6 +74,9 @@ struct arena_slot {
 struct arena_cb {
   xyws_notifier* n;
   uint64_t seq;
+  uint8_t* back;       // a staged arena: the caller's range the unmasked bytes go back to ...
+  const uint8_t* from; // ... from the pinned stand-in, copy_len bytes (0 = nothing to copy)
+  uint64_t copy_len;
 };
 
 struct xyws_arena {
@@ -81,6 +84,7 @@ struct xyws_arena {
   hipStream_t stream;
   uint8_t* host;
   bool owned, registered;
+  uint8_t* staged;  // pinned stand-in for a caller's range the runtime could not register, else null
   uint64_t bytes, max_frames;
   uint8_t* dev;          // device mirror of the receive area
   xyws_carry* dev_carry;
@@ -95,6 +99,7 @@ namespace {
 
 void on_complete(void* p) {
   arena_cb* c = static_cast<arena_cb*>(p);
+  if (c->copy_len) memcpy(c->back, c->from, c->copy_len);
   notify(c->n, c->seq);
 }
 
@@ -117,6 +122,7 @@ void arena_free(xyws_arena* a) {
   if (a->dev_carry) (void)hipFree(a->dev_carry);
   if (a->host && a->owned) (void)hipHostFree(a->host);
   if (a->host && a->registered) (void)hipHostUnregister(a->host);
+  if (a->staged) (void)hipHostFree(a->staged);
   // (the stream is the context's: arena_stream)
   delete a;
 }
@@ -207,8 +213,17 @@ int xyws_arena_create(xyws_ctx* ctx, void* host, uint64_t bytes, uint64_t max_fr
   }
   if (!rc) {
     if (host) {
-      if (hipHostRegister(host, bytes, hipHostRegisterDefault) != hipSuccess) rc = XYWS_ERR_HIP;
-      else { a->host = static_cast<uint8_t*>(host); a->registered = true; }
+      a->host = static_cast<uint8_t*>(host);
+      if (hipHostRegister(host, bytes, hipHostRegisterDefault) == hipSuccess) {
+        a->registered = true;
+      } else {
+        // Some hosts (a guest that cannot lock memory it already has) refuse to
+        // register: the range then goes through pinned memory of the arena's own.
+        (void)hipGetLastError();  // (the refusal is not the next launch's error)
+        void* h = nullptr;
+        if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess) rc = XYWS_ERR_NOMEM;
+        else a->staged = static_cast<uint8_t*>(h);
+      }
     } else {
       void* h = nullptr;
       if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess) rc = XYWS_ERR_NOMEM;
@@ -259,15 +274,17 @@ int xyws_arena_submit(xyws_arena* a, uint64_t offset, uint64_t len, uint32_t opt
   if (!g.ok) return XYWS_ERR_HIP;
   hipStream_t st = a->stream;
   uint8_t* dv = a->dev + offset;
+  // the pinned side of both copies: the receive area itself, or its stand-in
+  uint8_t* const pin = (a->staged ? a->staged : a->host) + offset;
+  if (a->staged && len) memcpy(pin, a->host + offset, len);
   // nothing enqueued yet: a failure here leaves the arena as it was
-  if (len && hipMemcpyAsync(dv, a->host + offset, len, hipMemcpyHostToDevice, st) != hipSuccess) return XYWS_ERR_HIP;
+  if (len && hipMemcpyAsync(dv, pin, len, hipMemcpyHostToDevice, st) != hipSuccess) return XYWS_ERR_HIP;
   // from here on the device carry may move: a failure leaves the arena failed
   // (no result would report the bytes it passed; the caller destroys it)
   int rc = xyws_decode_stream(a->ctx, dv, len, a->dev_carry, a->dev_carry, s.dev_frames, a->max_frames,
                               s.dev_count, opts & ~XYWS_OPT_SERIAL_SCAN, st);
-  if (!rc && len && !(opts & XYWS_OPT_PARSE_ONLY) &&
-      hipMemcpyAsync(a->host + offset, dv, len, hipMemcpyDeviceToHost, st) != hipSuccess)
-    rc = XYWS_ERR_HIP;
+  const bool bytes_back = len && !(opts & XYWS_OPT_PARSE_ONLY);
+  if (!rc && bytes_back && hipMemcpyAsync(pin, dv, len, hipMemcpyDeviceToHost, st) != hipSuccess) rc = XYWS_ERR_HIP;
   if (!rc && (hipMemcpyAsync(s.host_meta, s.dev_count, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
               hipMemcpyAsync(s.host_meta + 8, a->dev_carry, sizeof(xyws_carry), hipMemcpyDeviceToHost, st) !=
                   hipSuccess ||
@@ -277,6 +294,10 @@ int xyws_arena_submit(xyws_arena* a, uint64_t offset, uint64_t len, uint32_t opt
   arena_cb& c = a->cb[s_no % XYWS_ARENA_SLOTS];
   c.n = &a->note;
   c.seq = s_no;
+  // a staged arena's bytes reach the caller's range in the callback, before the completion shows
+  c.back = a->host + offset;
+  c.from = pin;
+  c.copy_len = a->staged && bytes_back ? len : 0;
   if (!rc && hipLaunchHostFunc(st, on_complete, &c) != hipSuccess) rc = XYWS_ERR_HIP;
   if (!rc && hipEventRecord(s.done, st) != hipSuccess) rc = XYWS_ERR_HIP;
   if (rc) {
