@@ -1643,6 +1643,122 @@ int xyws_route_streams(xyws_ctx* ctx, const xyws_accept_conn* dev_aconns, xyws_a
                        uint32_t default_room, uint32_t policy /* XYWS_RT_MISS_404 */,
                        xyws_route_result* dev_results /* n, nullable */, void* stream);
 
+/* ---- rooms opened on the device ---------------------------------------------------
+ * Rooms that exist because somebody named them (`/rooms/<anything>`): a route
+ * table only knows the rooms the host registered. xyws_open_streams runs
+ * between xyws_route_streams (policy 0) and xyws_roster_streams, over the same
+ * dev_aconns, dev_rtconns, dev_rconns / n_rconns and the route call's result
+ * rows, which are required here and rewritten in place. It looks the key of
+ * every candidate row up in a room directory that lives on the device, opens a
+ * room for a key the directory does not hold yet, and writes the room into the
+ * route row and the roster row: the first joiner of a new room joins it in the
+ * sweep that accepts it, with no host read of device state.
+ *
+ * The directory. xyws_directory_init writes an empty one on the host as one
+ * opaque blob (magic, version; hash and slot layout are private to the library);
+ * the caller copies it to 16-byte-aligned device memory, passes that copy to
+ * every call and never writes it again: the calls insert into it. It hands out
+ * the rooms room_base .. room_base + room_cap - 1, which the caller has laid out
+ * as empty rooms in its room tables, and keeps the keys in an arena of keys_cap
+ * bytes. xyws_directory_init refuses with XYWS_ERR_INVALID: room_base + room_cap
+ * above UINT32_MAX (XYWS_ROOM_NONE is no room); a non-zero `slots` that is not a
+ * power of two or is < 2 * room_cap (0: the library chooses; the smallest legal
+ * value gives the longest probe chains); a blob of 4 GiB or more; a null
+ * host_blob with cap >= the size needed. *need receives the blob's size whenever
+ * the numbers are valid; XYWS_ERR_CAPACITY when cap < *need, and nothing is
+ * written. xyws_directory_lookup, xyws_directory_get and xyws_directory_stat
+ * read a blob copied back to the host, with the probe the device runs compiled
+ * for the host: the room of a key in normal form (XYWS_ROOM_NONE: not there),
+ * the first used slot at or behind slot `from` (key_off from the blob's start,
+ * *next the slot to go on from: one pass lists a directory; XYWS_ERR_INVALID
+ * when no used slot is left), and the counts. All three return
+ * XYWS_ERR_INVALID for a null argument or bytes that are no directory.
+ *   A damaged blob may answer wrongly, but nothing outside [blob, blob + len) is
+ *   ever read or written: every offset taken from the blob is bounds-checked, on
+ *   the host and on the device, and a probe ends after `slots` steps. A blob
+ *   whose magic, version or size is wrong (or that is not 16-byte aligned on the
+ *   device) opens nothing and is not written: every candidate gets
+ *   XYWS_RT_BAD_TABLE | XYWS_RT_DIR_FULL.
+ *
+ *  1. Candidates. Row k is a candidate when its route row has room == from_room;
+ *     its status has XYWS_RT_MISS, or XYWS_RT_MATCHED | XYWS_RT_BY_PREFIX; it has
+ *     none of XYWS_RT_NOT_FOUND, XYWS_RT_NOT_ACCEPTED, XYWS_RT_BAD_ROW; and
+ *     1 <= key_len <= XYWS_ROUTE_KEY_MAX. With from_room = the route call's
+ *     default_room the candidates are the misses; with a prefix route `/rooms`
+ *     whose room is from_room, everything below `/rooms` (an exact match of the
+ *     route itself is none). Every other row, and every table byte that belongs
+ *     to it, stays as it is.
+ *  2. The key of a candidate is buf[key_off, key_off + key_len) as its route row
+ *     names it (the route call's normal form). The row is trusted only as far as
+ *     key_off + key_len <= min(len, XYWS_ACCEPT_MAX_REQUEST): one for which that
+ *     does not hold gets XYWS_RT_BAD_ROW added to its status; nothing is read
+ *     from its request and nothing else is written for it. Of a trusted
+ *     request nothing is read but the 16-byte lines that hold the key.
+ *  3. A key the directory holds: the row gets that room and XYWS_RT_DIRECTORY.
+ *     A key it does not hold: the row gets a new room and XYWS_RT_OPENED, and so
+ *     does every row of this call that names the same key. No room left: the
+ *     row gets XYWS_RT_DIR_FULL and keeps from_room (a lobby, or XYWS_ROOM_NONE:
+ *     accepted, in no room); no 404 is written by this call.
+ *  4. Numbers. The new keys of a call are ordered by the lowest row index that
+ *     names them. The i-th gets room room_base + n_open + i, and its bytes go to
+ *     the arena at keys_used plus the summed lengths of the keys before it. It
+ *     is admitted iff that room is < room_base + room_cap and its arena end is
+ *     <= keys_cap; the sums count refused keys too, so the admitted keys are a
+ *     prefix of the order, whatever the scheduling. n_open and keys_used grow by
+ *     what was admitted. Once a key has been refused, or n_open == room_cap, or
+ *     keys_used == keys_cap, the directory is closed: later calls find what it
+ *     holds and open nothing. Which slot a key lands in is not specified;
+ *     everything a lookup returns is. So that every new key of a call finds
+ *     a slot whatever the scheduling, a call claims only when the directory
+ *     has at least n free slots (slots - n_open - dead >= n, n counting every
+ *     row): otherwise it finds what the directory holds and every other
+ *     candidate gets XYWS_RT_DIR_FULL, and the directory is not closed by it.
+ *     A table of slots >= room_cap + the largest n never gets there.
+ *  5. Stores. The row's status (the bits above added) and room go to its route
+ *     row: that one word, the rest of the row stays. With rconn < n_rconns,
+ *     dev_rconns[rconn].room = room by one 32-bit store, also when the room
+ *     stays from_room; XYWS_ROUTE_NO_ROW: only the route row; any other rconn
+ *     sets XYWS_RT_BAD_ROW and is never dereferenced. The accept tables and the
+ *     requests are only read.
+ *  6. Three launches in stream order (find or claim; number; commit and answer),
+ *     nothing spins, no host read of device state, no context scratch; the
+ *     device error word is untouched; no reserve is needed and the call can be
+ *     captured into a hipGraph at once. dev_work is caller scratch of
+ *     XYWS_OPEN_WORK_WORDS * n 32-bit words that carries state between the
+ *     launches: its contents before and after mean nothing. Two calls over one
+ *     directory must not run concurrently. n == 0 returns XYWS_OK and launches
+ *     nothing. XYWS_ERR_INVALID, decided on the arguments alone: a null ctx; a
+ *     null dev_directory or directory_len == 0; null dev_rconns with
+ *     n_rconns > 0; n >= UINT32_MAX; null dev_aconns, dev_rtconns, dev_results
+ *     or dev_work with n > 0. */
+#define XYWS_RT_DIRECTORY    0x80u     /* xyws_route_result.status after xyws_open_streams: the key was in the directory */
+#define XYWS_RT_OPENED       0x100u    /* a room was opened for the key by this call */
+#define XYWS_RT_DIR_FULL     0x200u    /* no room left: the row keeps from_room */
+#define XYWS_OPEN_WORK_WORDS 4u        /* 32-bit words of dev_work per row */
+
+typedef struct xyws_directory_info {   /* host; 32 bytes */
+  uint32_t slots;
+  uint32_t room_base;
+  uint32_t room_cap;
+  uint32_t n_open;       /* rooms handed out so far */
+  uint32_t keys_cap;
+  uint32_t keys_used;
+  uint32_t dead;         /* slots taken by keys that found no room */
+  uint32_t reserved;
+} xyws_directory_info;
+
+int xyws_directory_init(uint32_t slots /* 0: the library chooses */, uint32_t room_base, uint32_t room_cap,
+                        uint32_t keys_cap, void* host_blob, uint64_t cap, uint64_t* need /* always written when non-null */);
+int xyws_directory_lookup(const void* host_blob, uint64_t len, const void* key, uint32_t key_len, uint32_t* room);
+int xyws_directory_get(const void* host_blob, uint64_t len, uint32_t from, uint32_t* key_off, uint32_t* key_len,
+                       uint32_t* room, uint32_t* next /* nullable */);
+int xyws_directory_stat(const void* host_blob, uint64_t len, xyws_directory_info* info);
+int xyws_open_streams(xyws_ctx* ctx, const xyws_accept_conn* dev_aconns, const xyws_route_conn* dev_rtconns, uint64_t n,
+                      void* dev_directory, uint64_t directory_len,
+                      xyws_roster_conn* dev_rconns, uint64_t n_rconns, uint32_t from_room,
+                      xyws_route_result* dev_results /* n, required */,
+                      uint32_t* dev_work /* XYWS_OPEN_WORK_WORDS * n words of caller scratch */, void* stream);
+
 /* ---- a sweep's send bytes in one buffer ------------------------------------------
  * The last call of a sweep (the reference's chat_session::writer draining
  * m_write_msgs into m_socket.send, and websocket_send_close, once per

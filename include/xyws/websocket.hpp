@@ -478,6 +478,37 @@ inline void route_streams(context& ctx, const xyws_accept_conn* dev_aconns, xyws
         "xyws_route_streams");
 }
 
+// An empty room directory for open_streams, written on the host
+// (xyws_directory_init): one opaque blob, to be copied to 16-byte-aligned
+// device memory once; the calls insert into that copy. It hands out the rooms
+// room_base .. room_base + room_cap - 1 and keeps keys_cap key bytes. slots = 0
+// lets the library choose the table's size. Throws xyws::error for what the
+// init refuses.
+inline std::vector<std::byte> room_directory(std::uint32_t room_base, std::uint32_t room_cap, std::uint32_t keys_cap,
+                                             std::uint32_t slots = 0) {
+  std::uint64_t need = 0;
+  const int rc = xyws_directory_init(slots, room_base, room_cap, keys_cap, nullptr, 0, &need);
+  if (rc != XYWS_ERR_CAPACITY) check(rc ? rc : XYWS_ERR_INVALID, "xyws_directory_init");
+  std::vector<std::byte> blob(need);
+  check(xyws_directory_init(slots, room_base, room_cap, keys_cap, blob.data(), need, &need), "xyws_directory_init");
+  return blob;
+}
+
+// Rooms for the request paths no route serves, between route_streams (policy 0)
+// and roster_streams (xyws_open_streams, three launches): every row that the
+// route call left in from_room without an exact route gets the room its key has
+// in the device copy of a room_directory() blob, a new one for a key not seen
+// before, in its route row (dev_results, required) and its roster row.
+// dev_work: XYWS_OPEN_WORK_WORDS * n words of device scratch.
+inline void open_streams(context& ctx, const xyws_accept_conn* dev_aconns, const xyws_route_conn* dev_rtconns,
+                         std::uint64_t n, void* dev_directory, std::uint64_t directory_len, xyws_roster_conn* dev_rconns,
+                         std::uint64_t n_rconns, std::uint32_t from_room, xyws_route_result* dev_results,
+                         std::uint32_t* dev_work, void* stream = nullptr) {
+  check(xyws_open_streams(ctx.native(), dev_aconns, dev_rtconns, n, dev_directory, directory_len, dev_rconns, n_rconns,
+                          from_room, dev_results, dev_work, stream),
+        "xyws_open_streams");
+}
+
 // What a sweep left to send, packed into one buffer by its last call
 // (xyws_outbox_streams, three launches): dev_conns[i] names connection i's send
 // buffer and the rows the sweep's calls wrote for it. `pack` (16-byte aligned,

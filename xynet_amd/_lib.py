@@ -360,6 +360,17 @@ ROUTE_KEY_MAX, ROUTE_PREFIX, ROUTE_NO_ROW = 256, 0x1, 0xFFFFFFFF
 RT_MISS_404 = 0x1  # xyws_route_streams policy
 (RT_MATCHED, RT_BY_PREFIX, RT_MISS, RT_NOT_FOUND, RT_NOT_ACCEPTED, RT_BAD_ROW,
  RT_BAD_TABLE) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40  # xyws_route_result.status
+RT_DIRECTORY, RT_OPENED, RT_DIR_FULL = 0x80, 0x100, 0x200  # added by xyws_open_streams
+OPEN_WORK_WORDS = 4  # 32-bit words of xyws_open_streams' dev_work per row
+
+
+class DirectoryInfo(C.Structure):
+    """xyws_directory_info (include/xyws.h), 32 bytes, host memory: the counts of a room directory."""
+    _fields_ = [("slots", C.c_uint32), ("room_base", C.c_uint32), ("room_cap", C.c_uint32), ("n_open", C.c_uint32),
+                ("keys_cap", C.c_uint32), ("keys_used", C.c_uint32), ("dead", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(DirectoryInfo) == 32
 
 
 class OutboxConn(C.Structure):
@@ -608,6 +619,22 @@ def load():
     # (no HIP call: xyws_route_lookup over the targets of a host slab of n requests, on the calling thread)
     L.xyws_debug_route_host.restype = i32
     L.xyws_debug_route_host.argtypes = [vp, u64, vp, u64, vp, u64, u32, vp]
+    L.xyws_directory_init.restype = i32
+    L.xyws_directory_init.argtypes = [u32, u32, u32, u32, vp, u64, C.POINTER(u64)]
+    L.xyws_directory_lookup.restype = i32
+    L.xyws_directory_lookup.argtypes = [vp, u64, vp, u32, C.POINTER(u32)]
+    L.xyws_directory_get.restype = i32
+    L.xyws_directory_get.argtypes = [vp, u64, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.xyws_directory_stat.restype = i32
+    L.xyws_directory_stat.argtypes = [vp, u64, C.POINTER(DirectoryInfo)]
+    L.xyws_open_streams.restype = i32
+    L.xyws_open_streams.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, u32, vp, vp, vp]
+    # (no HIP call: lanes per row, key bytes per lane, rows per numbering round, grid cap)
+    L.xyws_debug_open_geometry.restype = i32
+    L.xyws_debug_open_geometry.argtypes = [C.POINTER(u64)]
+    # (no HIP call: the slot at which a key's chain begins in a directory of `slots` slots)
+    L.xyws_debug_directory_home.restype = u32
+    L.xyws_debug_directory_home.argtypes = [vp, u32, u32]
     L.xyws_outbox_scratch_bytes.restype = u64
     L.xyws_outbox_scratch_bytes.argtypes = [u64]
     L.xyws_outbox_map.restype = i32
@@ -728,6 +755,45 @@ def route_table_of(routes, slots=0):
     blob = C.create_string_buffer(need.value)
     check(lib.xyws_route_build(rows, len(routes), slots, blob, need.value, C.byref(need)), "xyws_route_build")
     return blob.raw
+
+
+def directory_blob(room_base, room_cap, slots=0, keys_cap=None):
+    """The empty room directory xyws_directory_init writes (host bytes);
+    keys_cap: the key arena's size, by default room for room_cap keys of
+    XYWS_ROUTE_KEY_MAX bytes."""
+    lib = load()
+    keys_cap = ROUTE_KEY_MAX * int(room_cap) if keys_cap is None else int(keys_cap)
+    need = C.c_uint64()
+    rc = lib.xyws_directory_init(slots, room_base, room_cap, keys_cap, None, 0, C.byref(need))
+    if rc != -4:
+        raise XywsError(rc if rc else -1, "xyws_directory_init")
+    blob = C.create_string_buffer(need.value)
+    check(lib.xyws_directory_init(slots, room_base, room_cap, keys_cap, blob, need.value, C.byref(need)),
+          "xyws_directory_init")
+    return blob.raw
+
+
+def directory_lookup(blob, key):
+    """The room a directory blob (host bytes) holds for a key, None when it holds none (xyws_directory_lookup)."""
+    room = C.c_uint32()
+    check(load().xyws_directory_lookup(blob, len(blob), key, len(key), C.byref(room)), "xyws_directory_lookup")
+    return None if room.value == ROOM_NONE else room.value
+
+
+def directory_names(blob):
+    """{key bytes: room} of every key a directory blob (host bytes) holds (xyws_directory_get)."""
+    lib, names = load(), {}
+    ko, kl, room, at = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(0)
+    while lib.xyws_directory_get(blob, len(blob), at, C.byref(ko), C.byref(kl), C.byref(room), C.byref(at)) == XYWS_OK:
+        names[blob[ko.value:ko.value + kl.value]] = room.value
+    return names
+
+
+def directory_info(blob):
+    """xyws_directory_info of a directory blob (host bytes)."""
+    info = DirectoryInfo()
+    check(load().xyws_directory_stat(blob, len(blob), C.byref(info)), "xyws_directory_stat")
+    return info
 
 
 def check(rc, what=""):

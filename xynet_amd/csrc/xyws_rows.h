@@ -923,6 +923,22 @@ XYWS_DEV void store_route_result(xyws_route_result* p, route_place pl, route_key
 // xyws_roster_conn.room alone, by one 32-bit store: no other byte of the row is written.
 XYWS_DEV void store_roster_room(xyws_roster_conn* p, uint32_t room) { ((g_u32*)p)[ROSTER_ROOM_HALF] = room; }
 
+// ---- what xyws_open_streams takes of a route row and of an accept table row (wave-uniform), and what it rewrites
+struct route_row { uint32_t status, room, key_off, key_len; };
+XYWS_DEV route_row load_route_row(const xyws_route_result* p) {
+  const route_place pl = unpack_route_place(XYWS_LD(true, xyws_route_result, p, status));
+  return {pl.status, pl.room, unpack_route_key(XYWS_LD(true, xyws_route_result, p, route)).key_off,
+          XYWS_GET(xyws_route_result, key_len, XYWS_LD(true, xyws_route_result, p, key_len))};
+}
+// status and room alone: the word they share; route, key_off, key_len and the reserved words stay.
+XYWS_DEV void store_route_place(xyws_route_result* p, route_place pl) {
+  XYWS_ST(xyws_route_result, p, status, pack_route_place(pl));
+}
+struct accept_recv { uint64_t buf, len; };
+XYWS_DEV accept_recv load_accept_recv(const xyws_accept_conn* p) {
+  return {XYWS_LD(true, xyws_accept_conn, p, buf), XYWS_LD(true, xyws_accept_conn, p, len)};
+}
+
 // ---- xyws_outbox_conn, and what xyws_outbox_streams takes of the sweep's result rows
 // (out_cap counts as 0 without out: then it is not loaded)
 struct outbox_conn_row { uint64_t out, out_cap, backlog, bcast, reply, accept; };

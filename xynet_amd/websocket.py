@@ -472,6 +472,37 @@ class GroupRoute:
         return self.rconns_t
 
 
+class RoomDirectory:
+    """A room directory on the device (connection_group.directory): the blob
+    xyws_directory_init writes, kept resident; open() inserts into it on the
+    device. It hands out the rooms room_base .. room_base + room_cap - 1, which
+    the caller has laid out as empty rooms of its room set."""
+
+    def __init__(self, group, room_base, room_cap, slots=0, keys_cap=0):
+        import numpy as np
+        import torch
+        self.group, self.room_base, self.room_cap = group, int(room_base), int(room_cap)
+        if not slots:  # every row of a call may name a room of its own: room_cap + n slots keep a full group's call exact
+            slots = 2
+            while slots < max(2 * self.room_cap, self.room_cap + group.n):
+                slots *= 2
+        host = _lib.directory_blob(self.room_base, self.room_cap, slots, keys_cap or None)
+        self.nbytes = len(host)
+        self.blob_t = torch.from_numpy(np.frombuffer(host, np.uint8).copy()).to(group.device)
+
+    def host(self):
+        """Host copy of the blob as it is now (synchronizes)."""
+        return self.blob_t.cpu().numpy().tobytes()
+
+    def names(self):
+        """{key bytes: room} of every room opened so far (copies the blob back)."""
+        return _lib.directory_names(self.host())
+
+    def info(self):
+        """xyws_directory_info: n_open, keys_used, dead and the sizes (copies the blob back)."""
+        return _lib.directory_info(self.host())
+
+
 class GroupMessages:
     """Results and message records of one connection_group.reassemble call,
     item k as in the decode result it took (host copies on demand; valid until
@@ -993,6 +1024,36 @@ class connection_group:
                    table.nbytes, tensors["rconns"], self.n, int(default_room), _lib.RT_MISS_404 if miss_404 else 0,
                    tensors["results"])
         return GroupRoute(self, accept, table, rconn_of, tensors)
+
+    def directory(self, room_base, room_cap, slots=0, keys_cap=0):
+        """A room directory on the device for rooms that joiners make by
+        naming them: it hands out the rooms room_base .. room_base + room_cap
+        - 1 of the group's room set, one per request key that open() has not
+        seen before. slots, keys_cap: the table's and the key arena's size (0:
+        chosen from room_cap and the group's size; a call opens rooms only
+        while the table has a free slot for each of its rows, so a table
+        given by hand wants slots >= room_cap + the most rows of a call).
+        Returns a RoomDirectory."""
+        return RoomDirectory(self, room_base, room_cap, slots, keys_cap)
+
+    def open(self, route_result, directory, from_room):
+        """Give every connection that route() left in from_room without an
+        exact route (a miss sent to that default room, or a match below a
+        prefix route whose room it is) the room of its key in `directory`,
+        opening one for a key not seen before (xyws_open_streams, three
+        launches), between route() (without miss_404) and roster(). The rooms
+        go into the GroupRoute's own rows; it is returned, and
+        roster(route=...) takes it as before."""
+        if not isinstance(route_result, GroupRoute) or route_result.group is not self or \
+                not isinstance(directory, RoomDirectory) or directory.group is not self:
+            raise XywsError(-1, "open() takes this group's route() result and one of its directories")
+        import torch
+        m, t = len(route_result.accept.ids), route_result._tensors
+        t["work"] = torch.empty(max(_lib.OPEN_WORK_WORDS * m, 1), dtype=torch.int32, device=self.device)
+        t["directory"] = directory.blob_t  # (kept alive until the call has run)
+        self._call("xyws_open_streams", route_result.accept._table_t, t["rtconns"], m, directory.blob_t, directory.nbytes,
+                   t["rconns"], self.n, int(from_room), t["results"], t["work"])
+        return route_result
 
     def reply_carry(self, conn_id):
         """Host copy of a connection's reply carry (synchronizes)."""
