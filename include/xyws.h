@@ -1042,6 +1042,150 @@ int xyws_hold_streams(xyws_ctx* ctx,
                       xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
                       xyws_hold_result* dev_results /* n, nullable */, void* stream);
 
+/* ---- many connections, one inflate call -------------------------------------
+ * permessage-deflate (RFC 7692) on the receive side: browsers offer it on every
+ * WebSocket they open, and a client that got it sets RSV1 on the first frame of
+ * a message whose payload is a raw DEFLATE stream (RFC 1951) without its last
+ * four bytes 00 00 ff ff. With XYWS_ACC_DEFLATE the handshake answers the offer
+ * with server_no_context_takeover and client_no_context_takeover, so every
+ * compressed message stands alone: it is inflated from an empty window, and no
+ * window is kept between sweeps. This call sits between xyws_hold_streams (or
+ * xyws_reassemble_streams) and xyws_broadcast_streams: decode, reassemble,
+ * hold, inflate, reply, broadcast, still with no host read of device state. It
+ * has the hold call's shape: dev_in and dev_in_results are the table and rows
+ * the broadcast would otherwise be given (the hold's view, or the reassembly's
+ * own), dev_view and dev_view_results (n entries each) are written here and
+ * passed on in their place. dev_conns is the xyws_conn table of the sweep's
+ * xyws_decode_streams call (buf, len, frames, cap and carry are read, after the
+ * decode), dev_hold_results (nullable) the hold call's result rows. Row i of
+ * every table is connection i. The server keeps sending RSV1 = 0 (RFC 7692 6:
+ * an endpoint may send uncompressed messages once the extension is agreed), so
+ * the wire, the notices and the backlog stay as they are. Limits: no context
+ * takeover in either direction; nothing the server sends is compressed;
+ * client_max_window_bits is not narrowed (the window is always 32 KiB).
+ *
+ * Per connection, with s = min(nmsgs, msg_cap) of the input row (0 for a null
+ * msgs) and the carry ic:
+ *
+ *  1. Pass-through. flags lacks XYWS_INFC_NEGOTIATED, or out is NULL, or ic is
+ *     NULL: dev_view[i] and dev_view_results[i] are the inputs copied verbatim,
+ *     the result is {0, 0, 0, XYWS_INF_PASSTHROUGH}; nothing else is touched.
+ *  2. Which records are compressed. A message is compressed when bit 0x40
+ *     (RSV1) of byte 0 of its first frame's header is set. xyws_frame does not
+ *     keep that bit: the byte is read from buf[frames[first_frame].frame_off];
+ *     with frame_off < 0 it is the byte the carry kept from the previous sweep
+ *     (XYWS_INFK_HDR0, hdr0). Record 0 with XYWS_MSG_CONTINUED, and the record
+ *     a hold delivered (dev_hold_results[i] has XYWS_HOLD_DELIVERED: record 0),
+ *     take the answer the carry kept when the message began
+ *     (XYWS_INFK_COMPRESSED). Nothing outside [buf, buf + len) is read, whatever
+ *     a record or a frame row says (first_frame >= cap, a null frames or buf, a
+ *     frame_off >= len, frame_off < 0 without a kept byte): such a record
+ *     counts as not compressed and the result has XYWS_INF_UNKNOWN.
+ *     The carry afterwards: the input row has XYWS_RSM_OPEN and record
+ *     nmsgs - 1 is stored: not CONTINUED, the carry keeps that record's answer;
+ *     CONTINUED, it keeps what it has. OPEN with that record not stored, or no
+ *     OPEN: the answer is cleared. When connection i's xyws_carry has
+ *     hdr_len > 0, its hdr[0] is kept for the next sweep (a NULL carry keeps
+ *     nothing).
+ *  3. The view. dev_view[i] = {out, out_cap, the input's mc, vmsgs,
+ *     min(msg_cap, vmsg_cap), 0...} (a null vmsgs counts as vmsg_cap 0). View
+ *     record j, j < min(s, vmsg_cap), is input record j with out_off and length
+ *     renamed into the new range, the bytes back to back in record order.
+ *     - A record that is not compressed, or is compressed but not inflatable,
+ *       is copied: its bytes in[out_off .. +length) as far as they lie inside
+ *       the input's out_cap, its status. Inflatable: COMPLETE, none of
+ *       CONTINUED, TRUNCATED or INTERRUPTED, and out_off + length inside the
+ *       input's out_cap. A compressed record that is not inflatable is never
+ *       handed on as text: it gains XYWS_MSG_TRUNCATED unless it is still open
+ *       (neither COMPLETE nor INTERRUPTED), so the broadcast skips it.
+ *     - An inflatable compressed record is inflated: its bytes followed by
+ *       00 00 ff ff (RFC 7692 7.2.2) as raw DEFLATE (stored, fixed and dynamic
+ *       blocks), the window empty at the first byte, until a block with BFINAL
+ *       ends or the input is used up at a block boundary. The view record has
+ *       the inflated length and the opcode; its status is the input's without
+ *       XYWS_MSG_UTF8_BAD and XYWS_MSG_UNCHECKED (the reassembly judged the
+ *       compressed bytes). With XYWS_INF_UTF8 in opts a text message's inflated
+ *       bytes are validated by xyws_reassemble's rules and UTF8_BAD is set
+ *       again when they fail.
+ *  4. Bad data: block type 3; a stored block whose LEN and NLEN disagree; more
+ *     than 286 literal/length or 30 distance codes declared; a code-length set
+ *     that is over-subscribed, or incomplete other than one single code of
+ *     length 1 (an incomplete code-length code always); a repeat code with
+ *     nothing to repeat or running past HLIT + HDIST; no end-of-block code; a
+ *     bit pattern that is no code; literal/length symbols 286-287 or distance
+ *     symbols 30-31; a distance that reaches in front of the message's first
+ *     byte; input that ends inside a block. The view record has length 0 and
+ *     gains XYWS_MSG_TRUNCATED, n_bad counts it, the result has
+ *     XYWS_INF_BAD_DATA (the caller closes with 1007 or 1002); later records
+ *     are processed as usual. No input makes the call read or write outside
+ *     the ranges the tables name, or loop without consuming input.
+ *  5. The cap. Bytes at positions >= out_cap are not written. A record that
+ *     does not fit gains XYWS_MSG_TRUNCATED and the result has
+ *     XYWS_INF_TOO_LONG (the caller closes with 1009). An inflated record is
+ *     decoded no further than the first byte that does not fit: with r bytes
+ *     of room left its length is min(inflated length, r + 1), so out_len, the
+ *     sum of the view records' lengths, exceeds out_cap exactly when a record
+ *     did not fit, and a small message that inflates without end costs no more
+ *     than out_cap allows. No byte outside [out, out + out_cap) is written
+ *     (a bad or too long record may leave bytes of its own behind out_len),
+ *     and no view record at index >= min(s, vmsg_cap): neighbouring
+ *     connections' ranges may share a 16-byte line and have any alignment.
+ *     dev_view_results[i] is the input row with out_len this call's,
+ *     XYWS_RSM_TRUNCATED added when out_len > out_cap, XYWS_RSM_MSG_CAP added
+ *     when s > vmsg_cap, and XYWS_RSM_UTF8_BAD set by the view's records.
+ *
+ * Like its siblings the call is one launch (one wave per connection), uses no
+ * context scratch, no scratch slot and no policy word, never touches the
+ * device error word, reads no device state on the host, needs no reserve, can
+ * be captured into a hipGraph at once and runs concurrently on different
+ * streams. n == 0 returns XYWS_OK and launches nothing. XYWS_ERR_INVALID,
+ * decided on the arguments alone: a null ctx; a null dev_conns, dev_in,
+ * dev_in_results, dev_iconns, dev_view or dev_view_results with n > 0; opts
+ * bits other than XYWS_INF_UTF8; n >= UINT32_MAX. The out ranges must not
+ * overlap each other or the input's; a carry or a view row must not appear
+ * twice in a call; vmsgs must not be the input's msgs. */
+#define XYWS_INF_UTF8         0x1u /* opts: validate inflated text messages */
+#define XYWS_INFC_NEGOTIATED  0x1u /* xyws_inflate_conn.flags: permessage-deflate was agreed for this connection */
+#define XYWS_INFK_HDR0        0x1u /* xyws_inflate_carry.flags: hdr0 is byte 0 of the header the last recv boundary cut */
+#define XYWS_INFK_COMPRESSED  0x2u /* xyws_inflate_carry.flags: the message open at the end of the last sweep is compressed */
+typedef struct xyws_inflate_carry {  /* 32 bytes; all zero = fresh */
+  uint32_t flags;      /* XYWS_INFK_* */
+  uint8_t  hdr0;
+  uint8_t  reserved0[3];
+  uint64_t reserved[3]; /* zero */
+} xyws_inflate_carry;
+
+typedef struct xyws_inflate_conn {   /* 64 bytes; entry i goes with dev_in[i] */
+  void*               out;      /* device: this connection's inflated and passed-through bytes; NULL: pass-through */
+  uint64_t            out_cap;
+  xyws_message*       vmsgs;    /* device, nullable (then vmsg_cap counts as 0): the view's record row */
+  uint64_t            vmsg_cap;
+  xyws_inflate_carry* ic;       /* device; read, then written. NULL: pass-through */
+  uint32_t            flags;    /* XYWS_INFC_* */
+  uint32_t            reserved0;
+  uint64_t            reserved[2]; /* zero */
+} xyws_inflate_conn;
+
+typedef struct xyws_inflate_result { /* 32 bytes */
+  uint64_t out_len;    /* the view records' lengths together (may exceed out_cap) */
+  uint32_t n_inflated; /* records inflated whole */
+  uint32_t n_bad;      /* records with bad data */
+  uint32_t status;     /* XYWS_INF_* */
+  uint32_t reserved0;
+  uint64_t reserved;
+} xyws_inflate_result;
+#define XYWS_INF_PASSTHROUGH 0x1u
+#define XYWS_INF_BAD_DATA    0x2u
+#define XYWS_INF_TOO_LONG    0x4u
+#define XYWS_INF_UNKNOWN     0x8u /* a record's first header byte could not be found: counted as not compressed */
+
+int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
+                         const xyws_reasm_conn* dev_in, const xyws_reasm_result* dev_in_results,
+                         const xyws_hold_result* dev_hold_results /* n, nullable */,
+                         const xyws_inflate_conn* dev_iconns, uint64_t n, uint32_t opts,
+                         xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
+                         xyws_inflate_result* dev_results /* n, nullable */, void* stream);
+
 /* ---- many rooms, one backlog call -------------------------------------------
  * The room's memory: chat_room::deliver keeps the last 10 messages in
  * m_recent_messages and chat_room::join sends them to every newcomer through
@@ -1263,7 +1407,29 @@ int xyws_backlog_streams(xyws_ctx* ctx,
  *  4. The 101 response is `HTTP/1.1 101 Switching Protocols`, `Upgrade:
  *     websocket`, `Connection: Upgrade`, `Sec-WebSocket-Accept: ` + base64(
  *     SHA-1(key + 258EAFA5-E914-47DA-95CA-C5AB0DC85B11)), blank line.
- *     Subprotocols and extensions are ignored and never negotiated.
+ *     Subprotocols are ignored and never negotiated, and so are extensions
+ *     without XYWS_ACC_DEFLATE. That policy bit (alone or with
+ *     XYWS_ACC_REFERENCE) agrees to permessage-deflate (RFC 7692) when the
+ *     request is accepted and a Sec-WebSocket-Extensions header (any of them;
+ *     under XYWS_ACC_REFERENCE one before the first folded line) carries an
+ *     offer of it that can be agreed to. The value is a comma-separated list;
+ *     an offer is a name and `;`-separated parameters, SP/HT trimmed, names
+ *     compared ASCII case-insensitively; offers of other extensions are passed
+ *     over; a comma or semicolon inside a quoted string separates nothing.
+ *     An offer can be agreed to when its parameters are among
+ *     server_no_context_takeover, client_no_context_takeover (both without a
+ *     value), server_max_window_bits (with a value in 8..15, bare or quoted)
+ *     and client_max_window_bits (without a value or with one in 8..15), none
+ *     twice. The first
+ *     such offer is taken: the 101 gains the line `Sec-WebSocket-Extensions:
+ *     permessage-deflate; server_no_context_takeover;
+ *     client_no_context_takeover` (102 bytes, 231 in all) before its blank
+ *     line and status gains XYWS_ACC_DEFLATED; what the client sends is then
+ *     inflated by xyws_inflate_streams. With no such offer the 101 is the
+ *     129 bytes above. No other response changes. The result row is the
+ *     only place that says whether the extension was agreed, so
+ *     XYWS_ACC_DEFLATE with a null dev_results (a null res for
+ *     xyws_accept_request) is XYWS_ERR_INVALID, whatever n.
  *  5. Nothing outside buf[0, E) is read but the whole 16-byte lines that hold
  *     one of those bytes; no byte outside [out, out + min(resp_len, out_cap))
  *     is written (neighbouring ranges share 16-byte lines); buffers may have
@@ -1282,7 +1448,9 @@ int xyws_backlog_streams(xyws_ctx* ctx,
 #define XYWS_ACC_ACCEPTED   0x1u /* xyws_accept_result.status */
 #define XYWS_ACC_REJECTED   0x2u
 #define XYWS_ACC_TRUNCATED  0x4u /* resp_len > out_cap */
+#define XYWS_ACC_DEFLATED   0x8u /* the 101 agrees to permessage-deflate (policy XYWS_ACC_DEFLATE) */
 #define XYWS_ACC_REFERENCE  0x100u /* policy bit */
+#define XYWS_ACC_DEFLATE    0x200u /* policy bit: agree to an offer of permessage-deflate (below) */
 #define XYWS_ACR_NONE        0
 #define XYWS_ACR_PARSE       1
 #define XYWS_ACR_TOO_LONG    2

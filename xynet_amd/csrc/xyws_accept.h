@@ -22,14 +22,18 @@ namespace xyws_accept {
 
 constexpr uint32_t RESP_101_LEN = 129, RESP_101_KEY = 97;  // the accept value's position in the 101
 constexpr uint32_t RESP_400_REF_LEN = 26, RESP_400_LEN = 66, RESP_426_LEN = 98;
-constexpr uint32_t RESP_MAX = 144;  // the 101 up to a multiple of 16
+constexpr uint32_t RESP_101_EXT_LEN = 102;  // the extension line XYWS_ACC_DEFLATE adds to the 101
+constexpr uint32_t RESP_MAX = 240;  // the longest 101 (129 + 102) up to a multiple of 16
 constexpr uint32_t MAX_HEADERS = 100;
 constexpr uint32_t NO_KEY = 0xFFFFFFFFu;
-constexpr uint32_t POLICY_BITS = XYWS_ACC_REFERENCE;
+constexpr uint32_t POLICY_BITS = XYWS_ACC_REFERENCE | XYWS_ACC_DEFLATE;
 
 // The refusals of both entry points that their common arguments decide.
-XYWS_HD bool args_ok(uint32_t max_request, uint32_t policy) {
-  return max_request != 0 && max_request <= XYWS_ACCEPT_MAX_REQUEST && !(policy & ~POLICY_BITS);
+// XYWS_ACC_DEFLATE needs the result row: XYWS_ACC_DEFLATED there is the only
+// way the caller learns which connections the inflate call must take.
+XYWS_HD bool args_ok(uint32_t max_request, uint32_t policy, bool has_result) {
+  return max_request != 0 && max_request <= XYWS_ACCEPT_MAX_REQUEST && !(policy & ~POLICY_BITS) &&
+         (has_result || !(policy & XYWS_ACC_DEFLATE));
 }
 
 // Request bytes: b[i] for i < E only.
@@ -187,6 +191,96 @@ XYWS_HD bool has_element(const R& b, uint32_t off, uint32_t len, lit L) {
   }
 }
 
+// ---------------------------------------------------------------- permessage-deflate (RFC 7692 7.1)
+XYWS_HD bool is_blank(uint32_t c) { return c == ' ' || c == '\t'; }
+template <class R>
+XYWS_HD void trim(const R& b, uint32_t& x, uint32_t& y) {
+  while (x < y && is_blank(b[x])) x++;
+  while (y > x && is_blank(b[y - 1])) y--;
+}
+
+// The first `sep` of b[x, y) outside a quoted string (a backslash inside one
+// quotes the next byte), or y.
+template <class R>
+XYWS_HD uint32_t next_sep(const R& b, uint32_t x, uint32_t y, uint32_t sep) {
+  bool quoted = false;
+  for (; x < y; x++) {
+    const uint32_t c = b[x];
+    if (quoted) {
+      if (c == '\\' && x + 1 < y) x++;
+      else if (c == '"') quoted = false;
+    } else if (c == '"') {
+      quoted = true;
+    } else if (c == sep) {
+      break;
+    }
+  }
+  return x;
+}
+
+// b[v0, v1), bare or quoted, is a window size 8..15 without a leading zero.
+template <class R>
+XYWS_HD bool is_window_bits(const R& b, uint32_t v0, uint32_t v1) {
+  if (v1 - v0 >= 2 && b[v0] == '"' && b[v1 - 1] == '"') {
+    v0++;
+    v1--;
+  }
+  const uint32_t d0 = v1 > v0 ? b[v0] : 0u, d1 = v1 - v0 == 2 ? b[v0 + 1] : 0u;
+  return (v1 - v0 == 1 && (d0 == '8' || d0 == '9')) || (v1 - v0 == 2 && d0 == '1' && d1 >= '0' && d1 <= '5');
+}
+
+// One element b[x, y) of an extension list is an offer of permessage-deflate
+// that can be agreed to (RFC 7692 7.1: an offer with a parameter that is
+// unknown, repeated or has an invalid value is declined): the name, then
+// `;`-separated parameters, each one of the four the RFC names, none twice;
+// the two _no_context_takeover ones without a value, server_max_window_bits
+// with a value in 8..15, client_max_window_bits with none or one in 8..15.
+// Names without regard to case.
+template <class R>
+XYWS_HD bool deflate_offer_ok(const R& b, uint32_t x, uint32_t y) {
+  uint32_t seen = 0;
+  for (uint32_t part = 0;; part++) {
+    const uint32_t e = next_sep(b, x, y, ';');
+    uint32_t p0 = x, p1 = e;
+    trim(b, p0, p1);
+    if (part == 0) {
+      if (!span_is(b, p0, p1 - p0, XYWS_LIT("permessage-deflate"), true)) return false;
+    } else {
+      const uint32_t q = next_sep(b, p0, p1, '=');
+      uint32_t n0 = p0, n1 = q;
+      trim(b, n0, n1);
+      const uint32_t side = n1 - n0 < 6 ? 2u : span_is(b, n0, 6, XYWS_LIT("server"), true) ? 0u
+                                            : span_is(b, n0, 6, XYWS_LIT("client"), true) ? 1u : 2u;
+      uint32_t kind = 4;  // 0, 1: server / client _no_context_takeover; 2, 3: _max_window_bits
+      if (side < 2 && span_is(b, n0 + 6, n1 - n0 - 6, XYWS_LIT("_no_context_takeover"), true)) kind = side;
+      else if (side < 2 && span_is(b, n0 + 6, n1 - n0 - 6, XYWS_LIT("_max_window_bits"), true)) kind = 2 + side;
+      if (kind == 4 || (seen & (1u << kind))) return false;
+      seen |= 1u << kind;
+      const bool valued = q < p1;
+      uint32_t v0 = valued ? q + 1 : p1, v1 = p1;
+      trim(b, v0, v1);
+      if (kind < 2 ? valued : valued ? !is_window_bits(b, v0, v1) : kind == 2) return false;
+    }
+    if (e >= y) return true;
+    x = e + 1;
+  }
+}
+
+// Some comma-separated element of b[off, off + len) is such an offer (offers
+// of other extensions, and offers that cannot be agreed to, are passed over;
+// a comma or semicolon inside a quoted string separates nothing).
+template <class R>
+XYWS_HD bool has_deflate_offer(const R& b, uint32_t off, uint32_t len) {
+  uint32_t s = off;
+  const uint32_t end = off + len;
+  for (;;) {
+    const uint32_t e = next_sep(b, s, end, ',');
+    if (deflate_offer_ok(b, s, e)) return true;
+    if (e >= end) return false;
+    s = e + 1;
+  }
+}
+
 // The canonical base64 of 16 bytes: 21 alphabet characters, one of AQgw, ==.
 template <class R>
 XYWS_HD bool key_is_canonical(const R& b, uint32_t off, uint32_t len) {
@@ -210,15 +304,21 @@ struct checks {
   uint32_t key_off = NO_KEY;
   uint32_t keys = 0, versions = 0;
   bool folded = false, host = false, upgrade = false, connection = false;
+  bool deflate = false;  // XYWS_ACC_DEFLATE: an offer of permessage-deflate that can be agreed to was seen
 };
 
 template <class R>
-XYWS_HD void check_header(const R& b, bool ref, checks& k, bool named, uint32_t n0, uint32_t nl, uint32_t v0,
+XYWS_HD void check_header(const R& b, uint32_t policy, checks& k, bool named, uint32_t n0, uint32_t nl, uint32_t v0,
                           uint32_t vl) {
+  const bool ref = (policy & XYWS_ACC_REFERENCE) != 0;
   if (ref) {
     // http_parser::headers() ends at the first nameless header
     if (!named) k.folded = true;
     if (k.folded) return;
+  }
+  if ((policy & XYWS_ACC_DEFLATE) && named && !k.deflate && span_is(b, n0, nl, XYWS_LIT("sec-websocket-extensions"), true))
+    k.deflate = has_deflate_offer(b, v0, vl);
+  if (ref) {
     if (span_is(b, n0, nl, XYWS_LIT("Connection"), false)) {
       if (!span_is(b, v0, vl, XYWS_LIT("Upgrade"), false)) k.fail |= 1u << XYWS_ACR_CONNECTION;
     } else if (span_is(b, n0, nl, XYWS_LIT("Upgrade"), false)) {
@@ -260,7 +360,7 @@ struct request {
 // phr_parse_request's walk over b[0, E) (picohttpparser.h:426-494 with
 // last_len == 0), each header handed to check_header as it ends.
 template <class R>
-XYWS_HD int walk(const R& b, uint32_t E, bool ref, request& rq, checks& k) {
+XYWS_HD int walk(const R& b, uint32_t E, uint32_t policy, request& rq, checks& k) {
   uint32_t p = 0;
   if (p == E) return EV_INCOMPLETE;
   if (b[p] == '\r') {  // one leading empty line
@@ -359,7 +459,7 @@ XYWS_HD int walk(const R& b, uint32_t E, bool ref, request& rq, checks& k) {
       return EV_ERROR;
     }
     while (vl && (b[v0 + vl - 1] == ' ' || b[v0 + vl - 1] == '\t')) vl--;
-    check_header(b, ref, k, named, n0, nl, v0, vl);
+    check_header(b, policy, k, named, n0, nl, v0, vl);
   }
   rq.consumed = p;
   rq.method_off = tok[0][0];
@@ -382,7 +482,7 @@ XYWS_HD verdict evaluate(const R& b, uint32_t E, bool full, uint32_t policy, uin
   verdict v = {0, 0, 0, 0, 0, 0, 0, NO_KEY};
   request rq = {0, 0, 0, 0, 0, 0};
   checks k;
-  const int ev = walk(b, E, ref, rq, k);
+  const int ev = walk(b, E, policy, rq, k);
   if (ev == EV_INCOMPLETE && !full) return v;
   uint32_t reason = XYWS_ACR_NONE;
   if (ev == EV_ERROR) {
@@ -437,7 +537,15 @@ XYWS_HD verdict evaluate(const R& b, uint32_t E, bool full, uint32_t policy, uin
                               "Sec-WebSocket-Accept: ",
                               RESP_101_KEY);
   accept_value(kw, resp + n);
-  v.resp_len = put_text(resp, n + 28, "\r\n\r\n", 4);
+  if (k.deflate) {  // RFC 7692 7.1.1: both sides without context takeover, whether the client offered that or not
+    v.status |= XYWS_ACC_DEFLATED;
+    v.resp_len = put_text(resp, n + 28,
+                          "\r\nSec-WebSocket-Extensions: permessage-deflate; server_no_context_takeover; "
+                          "client_no_context_takeover\r\n\r\n",
+                          RESP_101_EXT_LEN + 4);
+  } else {
+    v.resp_len = put_text(resp, n + 28, "\r\n\r\n", 4);
+  }
   return v;
 }
 
@@ -456,7 +564,7 @@ XYWS_HD void to_result(const verdict& v, uint64_t out_cap, xyws_accept_result* r
 // xyws_accept_request (include/xyws.h).
 inline int accept_request(const void* host_req, uint64_t len, uint32_t max_request, uint32_t policy, void* host_out,
                           uint64_t out_cap, xyws_accept_result* res) {
-  if (!args_ok(max_request, policy) || (len && !host_req) || (out_cap && !host_out)) return XYWS_ERR_INVALID;
+  if (!args_ok(max_request, policy, res != nullptr) || (len && !host_req) || (out_cap && !host_out)) return XYWS_ERR_INVALID;
   const uint32_t E = len < max_request ? (uint32_t)len : max_request;
   uint8_t resp[RESP_MAX];
   const verdict v = evaluate(host_bytes{(const uint8_t*)host_req}, E, len >= max_request, policy, resp);

@@ -16,7 +16,7 @@
 //      the same source xyws_accept_request compiles for the host, taken by
 //      all lanes together on scalar registers (staged_bytes below). SHA-1 and
 //      base64 are wave-uniform too. The verdict stays in registers, the whole
-//      response (at most 129 bytes) goes to LDS;
+//      response (at most 231 bytes) goes to LDS;
 //   3. send: the lanes write the response to the send range in 16-byte lines
 //      (xyws_lines.h), one line per lane; lane 0 writes the result row.
 // LDS is sized by the launch: the staged lines of max_request bytes at any
@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(ACCEPT_LANES) k_accept_streams(const xyws_acce
     const uint64_t olo = out & 15u;
     const uint64_t wlim = sat_add(olo, out_cap), P1 = olo + resp_len;
     const uint64_t wl = P1 < wlim ? P1 : wlim;
-    const uint64_t A = (uint64_t)ACCEPT_LINE * lane;  // (129 + 15 bytes: one step)
+    const uint64_t A = (uint64_t)ACCEPT_LINE * lane;  // (at most 231 + 15 bytes: one step)
     if (wl > olo && A < wl) {
       const uint64_t s = A > olo ? A : olo, e = A + 16 < P1 ? A + 16 : P1;
       bytes16 acc = {0, 0};
@@ -123,7 +123,7 @@ extern "C" {
 int xyws_accept_streams(xyws_ctx* ctx, const xyws_accept_conn* dev_conns, uint64_t n, uint32_t max_request,
                         uint32_t policy, xyws_accept_result* dev_results, void* stream) {
   if (!ctx || (n && !dev_conns)) return XYWS_ERR_INVALID;
-  if (!xyws_accept::args_ok(max_request, policy)) return XYWS_ERR_INVALID;
+  if (!xyws_accept::args_ok(max_request, policy, dev_results != nullptr)) return XYWS_ERR_INVALID;
   if (!n) return XYWS_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
   device_guard g(ctx->device);

@@ -484,6 +484,30 @@ XYWS_HD void pack_inbox_summary(const inbox_summary_fields& s, uint64_t w[IBS_WO
   w[XYWS_WORD(xyws_inbox_summary, n_bad_entries)] = pack_inbox_bad(s.bad);
 }
 
+// ---------------------------------------------------------------- the inflate's rows
+// The conn row is six words, flags in the sixth; the carry is one word of two
+// fields and three reserved ones; the result is a length and two words of two.
+struct inflate_kept { uint32_t flags, hdr0; };          // xyws_inflate_carry
+struct inflate_counts { uint32_t n_inflated, n_bad; };  // xyws_inflate_result
+XYWS_ONE_WORD(xyws_inflate_conn, flags, reserved0);
+XYWS_ONE_WORD(xyws_inflate_carry, flags, reserved0);
+XYWS_ONE_WORD(xyws_inflate_result, n_inflated, n_bad);
+XYWS_ONE_WORD(xyws_inflate_result, status, reserved0);
+static_assert(sizeof(xyws_inflate_conn) == 8 * 8 && sizeof(xyws_inflate_carry) == 4 * 8 && sizeof(xyws_inflate_result) == 4 * 8,
+              "the inflate's rows: whole words");
+XYWS_HD uint64_t pack_inflate_kept(inflate_kept k) {
+  return XYWS_PUT(xyws_inflate_carry, flags, k.flags) | XYWS_PUT(xyws_inflate_carry, hdr0, k.hdr0);
+}
+XYWS_HD inflate_kept unpack_inflate_kept(uint64_t w) {
+  return {XYWS_GET(xyws_inflate_carry, flags, w), XYWS_GET(xyws_inflate_carry, hdr0, w)};
+}
+XYWS_HD uint64_t pack_inflate_counts(inflate_counts c) {
+  return XYWS_PUT(xyws_inflate_result, n_inflated, c.n_inflated) | XYWS_PUT(xyws_inflate_result, n_bad, c.n_bad);
+}
+XYWS_HD inflate_counts unpack_inflate_counts(uint64_t w) {
+  return {XYWS_GET(xyws_inflate_result, n_inflated, w), XYWS_GET(xyws_inflate_result, n_bad, w)};
+}
+
 }  // namespace xyws_rows
 
 // ================================================================ the device part
@@ -1015,6 +1039,44 @@ XYWS_DEV void store_accept_recv(xyws_accept_conn* p, uint64_t buf, uint64_t len)
   XYWS_ST(xyws_accept_conn, p, buf, buf);
   XYWS_ST(xyws_accept_conn, p, len, len);
 }
+
+// ---- the inflate's rows (wave-uniform), and what xyws_inflate_streams reads of a decode row and a hold row
+struct inflate_conn_row { uint64_t out, out_cap, vmsgs, vmsg_cap, ic; uint32_t flags; };  // (vmsg_cap counts as 0 without vmsgs)
+XYWS_DEV inflate_conn_row load_inflate_conn(const xyws_inflate_conn* p) {
+  inflate_conn_row r;
+  r.out = XYWS_LD(true, xyws_inflate_conn, p, out);
+  r.out_cap = XYWS_LD(true, xyws_inflate_conn, p, out_cap);
+  r.vmsgs = XYWS_LD(true, xyws_inflate_conn, p, vmsgs);
+  r.vmsg_cap = r.vmsgs ? XYWS_LD(true, xyws_inflate_conn, p, vmsg_cap) : 0;
+  r.ic = XYWS_LD(true, xyws_inflate_conn, p, ic);
+  r.flags = XYWS_GET(xyws_inflate_conn, flags, XYWS_LD(true, xyws_inflate_conn, p, flags));
+  return r;
+}
+XYWS_DEV inflate_kept load_inflate_carry(const xyws_inflate_carry* p) {
+  return unpack_inflate_kept(XYWS_LD(true, xyws_inflate_carry, p, flags));
+}
+XYWS_DEV void store_inflate_carry(xyws_inflate_carry* p, inflate_kept k) {
+  XYWS_ST(xyws_inflate_carry, p, flags, pack_inflate_kept(k));
+  for (size_t w = XYWS_WORD(xyws_inflate_carry, reserved); w < sizeof(xyws_inflate_carry) / 8; w++) ((g_u64*)p)[w] = 0;
+}
+XYWS_DEV void store_inflate_result(xyws_inflate_result* p, uint64_t out_len, inflate_counts c, uint32_t status) {
+  XYWS_ST(xyws_inflate_result, p, out_len, out_len);
+  XYWS_ST(xyws_inflate_result, p, n_inflated, pack_inflate_counts(c));
+  XYWS_ST(xyws_inflate_result, p, status, status);
+  XYWS_ST(xyws_inflate_result, p, reserved, 0);
+}
+// The row {0, 0, 0, status}, one word per lane.
+XYWS_DEV void store_inflate_status(xyws_inflate_result* p, uint32_t status, uint32_t lane) {
+  if (lane < sizeof(xyws_inflate_result) / 8)
+    ((g_u64*)p)[lane] = lane == XYWS_WORD(xyws_inflate_result, status) ? (uint64_t)status : 0;
+}
+// A decode row with its carry's address, and the status of a hold row.
+XYWS_DEV uint64_t load_conn_carry(const xyws_conn* p) { return XYWS_LD(true, xyws_conn, p, carry); }
+XYWS_DEV uint32_t load_hold_status(const xyws_hold_result* p) {
+  return XYWS_GET(xyws_hold_result, status, XYWS_LD(true, xyws_hold_result, p, status));
+}
+// The frame_off word of a frame row (wave-uniform).
+XYWS_DEV int64_t load_frame_off(const xyws_frame* p) { return (int64_t)XYWS_LD(true, xyws_frame, p, frame_off); }
 
 }  // namespace xyws_rows
 #endif  // __HIPCC__

@@ -564,6 +564,56 @@ class GroupHold:
         return _lib.read_rows(_lib.Message, self._tensors["vmsgs"], n, (self.group.cap + 1) * k)
 
 
+class GroupInflate:
+    """The view and results of one connection_group.inflate call, item k as in
+    the decode result of its sweep (host copies on demand). broadcast() takes
+    it in place of the reassemble() or hold() result: the compressed messages
+    of the connections that negotiated permessage-deflate are inflated in the
+    view. An item whose connection did not negotiate passes through: its view
+    row is the input's, so its records, bytes and capacity are those of
+    `messages_in` (passed[k]). It owns the call's tables, out ranges, view rows
+    and result rows."""
+
+    def __init__(self, group, messages, tensors, out_cap, passed):
+        self.group, self.decoded, self.messages_in = group, messages.decoded, messages
+        self._tensors, self.out_cap, self.passed = tensors, out_cap, passed
+        self.msg_cap = messages.msg_cap
+        m = len(self.decoded.ids)
+        # what a record's out_off counts from: the item's inflate range, or what the input's records count from
+        self.outs = [self._input_bytes(k) if passed[k] else tensors["out"][out_cap * k:out_cap * (k + 1)] for k in range(m)]
+        self.out_caps = [messages.out_caps[k] if passed[k] else out_cap for k in range(m)]  # (broadcast() sizes the wires by them)
+        self._rows = _Rows(_lib.InflateResult, tensors["results"], m)
+        self._vrows = _Rows(_lib.ReasmResult, tensors["view_results"], m)
+
+    def tables(self):
+        """The view and its result rows, which broadcast() and backlog() read instead of the input's."""
+        return self._tensors["view"], self._tensors["view_results"]
+
+    def result(self, k):
+        """xyws_inflate_result of item k."""
+        return self._rows[k]
+
+    def view_result(self, k):
+        """Item k's row of the view (xyws_reasm_result)."""
+        return self._vrows[k]
+
+    def _input_bytes(self, k):
+        """The bytes item k's input records name: reassemble()'s out tensor, behind hold() with its hold in front."""
+        import torch
+        src = self.messages_in
+        if isinstance(src, GroupHold):
+            t = src.messages_in.outs[k]
+            return torch.as_strided(t, (src.hold_cap + t.numel(),), (1,), t.storage_offset() - src.hold_cap)
+        return src.outs[k]
+
+    def messages(self, k):
+        """The view's stored records of item k (out_off counts from outs[k]'s start)."""
+        if self.passed[k]:
+            return self.messages_in.messages(k)
+        n = min(self.view_result(k).nmsgs, self.msg_cap)
+        return _lib.read_rows(_lib.Message, self._tensors["vmsgs"], n, (self.group.cap + 1) * k)
+
+
 class GroupBroadcast:
     """Results, room results and wires of one connection_group.broadcast call,
     item k as in the decode result of its sweep, room r as in the `rooms`
@@ -853,6 +903,8 @@ class connection_group:
         self.mresults_t = _lib.alloc_rows(_lib.ReasmResult, n, dev)
         # hold(): the hold carries (its tables and rows belong to the GroupHold it returns)
         self.hcarry_t = _lib.alloc_rows(_lib.HoldCarry, n, dev)
+        # inflate(): the inflate carries (its tables, out ranges and rows belong to the GroupInflate it returns)
+        self.icarry_t = _lib.alloc_rows(_lib.InflateCarry, n, dev)
         # backlog(): per room a log and a carry, made when the room is first seen and kept across sweeps
         self._blogs, self._bcarries = [], []
         # inbox(): the receive slab, the inbox carries and the resident tables, made by the first inbox() call
@@ -876,7 +928,7 @@ class connection_group:
     def _carries(self):
         """The per-connection state a slot loses when it changes hands, as (tensor, row structure) pairs."""
         pairs = [(self.carry_t, Carry), (self.rcarry_t, _lib.ReplyCarry), (self.mcarry_t, _lib.MsgCarry),
-                 (self.hcarry_t, _lib.HoldCarry)]
+                 (self.hcarry_t, _lib.HoldCarry), (self.icarry_t, _lib.InflateCarry)]
         if self._ib is not None:
             pairs += [(self._ib["carries"], _lib.InboxCarry), (self._ib["aresults"], _lib.AcceptResult)]
         return pairs
@@ -948,7 +1000,9 @@ class connection_group:
         items[k] is the device uint8 tensor with every byte connection k has
         sent so far (or a (conn_id, tensor) pair; the ids are only kept for
         the caller), out_items[k] the device uint8 tensor that receives its
-        response (129 bytes always suffice). A whole request is checked by
+        response (129 bytes always suffice; 231 with ACC_DEFLATE in policy,
+        which agrees to an offer of permessage-deflate: result(k).status then
+        has ACC_DEFLATED and inflate() takes the connection as negotiated). A whole request is checked by
         RFC 6455 4.2.1 (policy 0) or as the reference's handler does
         (ACC_REFERENCE) and answered; an incomplete one is reported as such:
         call again with more bytes. The call keeps no state: on ACCEPTED the
@@ -1161,10 +1215,56 @@ class connection_group:
                    tensors["view_results"], tensors["results"], slot=dec.slot)
         return GroupHold(self, messages, tensors, hold_cap)
 
+    def inflate_carry(self, conn_id):
+        """Host copy of a connection's inflate carry (synchronizes)."""
+        return self._carry_of(self.icarry_t, _lib.InflateCarry, conn_id)
+
+    def inflate(self, messages_or_hold, negotiated, out_cap, utf8=True):
+        """Inflate the permessage-deflate messages of the sweep
+        (xyws_inflate_streams, one launch), between reassemble() or hold() and
+        broadcast(): `messages_or_hold` is the result of either, negotiated
+        the connection ids whose handshake agreed to the extension (accept()
+        with ACC_DEFLATE: result(k).status has ACC_DEFLATED), out_cap the bytes
+        each item gets for its inflated and passed-through messages: a message
+        that does not fit is truncated and the result has INF_TOO_LONG. With
+        utf8 the inflated text messages are validated. Items of other
+        connections pass through. The server keeps sending uncompressed
+        frames; no context is taken over between messages. The group owns the
+        inflate carries. Returns a GroupInflate, which broadcast() takes in
+        place of `messages_or_hold`. Call it before the group's next decode(),
+        reply() or reassemble()."""
+        src = messages_or_hold
+        if not isinstance(src, (GroupMessages, GroupHold)) or src.group is not self or src.decoded.resident:
+            raise XywsError(-1, "inflate() takes the result of this group's reassemble() or hold()")
+        dec, out_cap, agreed = src.decoded, int(out_cap), {int(i) for i in negotiated}
+        if out_cap < 0:
+            raise ValueError("out_cap must not be negative")
+        import torch
+        m, dev = len(dec.ids), self.device
+        itab = _lib.Table(_lib.InflateConn, m)
+        tensors = dict(vmsgs=_lib.alloc_rows(_lib.Message, m, dev, zero=False, per=self.cap + 1),
+                       view=_lib.alloc_rows(_lib.ReasmConn, m, dev),
+                       view_results=_lib.alloc_rows(_lib.ReasmResult, m, dev),
+                       results=_lib.alloc_rows(_lib.InflateResult, m, dev),
+                       out=torch.empty(max(m * out_cap, 1), dtype=torch.uint8, device=dev), src=src)
+        for k, (row, i) in enumerate(zip(itab.rows, dec.ids)):
+            row.out, row.out_cap = tensors["out"].data_ptr() + out_cap * k, out_cap
+            row.vmsgs = _lib.row_ptr(tensors["vmsgs"], _lib.Message, (self.cap + 1) * k)
+            row.vmsg_cap = src.msg_cap
+            row.ic = _lib.row_ptr(self.icarry_t, _lib.InflateCarry, i)
+            row.flags = _lib.INFC_NEGOTIATED if i in agreed else 0
+        tensors["iconns"] = itab.upload(dev)
+        hold_rows = src._tensors["results"] if isinstance(src, GroupHold) else 0
+        self._call("xyws_inflate_streams", dec.conns_t, *src.tables(), hold_rows, tensors["iconns"], m,
+                   _lib.INF_UTF8 if utf8 else 0, tensors["view"], tensors["view_results"], tensors["results"],
+                   slot=dec.slot)
+        return GroupInflate(self, src, tensors, out_cap, [i not in agreed for i in dec.ids])
+
     def broadcast(self, messages, rooms, out_items, heads=None, reply=None, flags=0x11, enc_opts=0, wire_caps=None):
         """Deliver the whole messages of the reassemble() call that returned
         `messages` (or of the hold() call that followed it: then also the
-        messages that call completed) to their rooms (xyws_broadcast_streams, two launches):
+        messages that call completed; or of the inflate() call after either:
+        then the compressed ones inflated) to their rooms (xyws_broadcast_streams, two launches):
         rooms[r] lists the connection ids of room r in delivery order; every
         one must be an item of this sweep (a member that received nothing is
         decoded with an empty buffer) and belongs to one room. Each room's
@@ -1182,8 +1282,8 @@ class connection_group:
         GroupBroadcast. Call it before the group's next decode(), reply() or
         reassemble()."""
         dec = messages.decoded
-        if messages.group is not self or dec.resident or not isinstance(messages, (GroupMessages, GroupHold)):
-            raise XywsError(-1, "broadcast() takes the result of this group's reassemble() or hold()")
+        if messages.group is not self or dec.resident or not isinstance(messages, (GroupMessages, GroupHold, GroupInflate)):
+            raise XywsError(-1, "broadcast() takes the result of this group's reassemble(), hold() or inflate()")
         if reply is not None and (reply.group is not self or reply.decoded is not dec):
             raise XywsError(-1, "reply must be the reply() result of the same sweep")
         outs = [_dev_u8(t) for t in out_items]
@@ -1557,7 +1657,10 @@ class connection_group:
         returned GroupInbox in place of their item lists; the sweep's later
         calls (reply() .. outbox()) do not take what that decode() returns.
         reset(ids) before the call hands a slot to a new connection. m_cap: the
-        entry capacity of the call (default len(entries))."""
+        entry capacity of the call (default len(entries)). resp_cap: every
+        connection's response range; the default holds the plain 101, a group
+        whose accept() runs with ACC_DEFLATE needs resp_cap=240 for the 101
+        that agrees to the extension (231 bytes)."""
         import numpy as np
         import torch
         recv_cap, resp_cap = int(recv_cap), int(resp_cap)
@@ -1710,8 +1813,8 @@ class websocket_request_handler:
         self._req, self._res, self._resp = b"", _lib.AcceptResult(), b""
 
     def _run(self, data):
-        res, out = _lib.AcceptResult(), (C.c_uint8 * 144)()
-        check(self.L.xyws_accept_request(data, len(data), self.max_request, self.policy, out, 144, C.byref(res)),
+        res, out = _lib.AcceptResult(), (C.c_uint8 * _lib.ACCEPT_RESP_MAX)()
+        check(self.L.xyws_accept_request(data, len(data), self.max_request, self.policy, out, len(out), C.byref(res)),
               "xyws_accept_request")
         return res, bytes(out[:res.resp_len])
 
