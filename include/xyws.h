@@ -1058,11 +1058,11 @@ int xyws_hold_streams(xyws_ctx* ctx,
  * passed on in their place. dev_conns is the xyws_conn table of the sweep's
  * xyws_decode_streams call (buf, len, frames, cap and carry are read, after the
  * decode), dev_hold_results (nullable) the hold call's result rows. Row i of
- * every table is connection i. The server keeps sending RSV1 = 0 (RFC 7692 6:
- * an endpoint may send uncompressed messages once the extension is agreed), so
- * the wire, the notices and the backlog stay as they are. Limits: no context
- * takeover in either direction; nothing the server sends is compressed;
- * client_max_window_bits is not narrowed (the window is always 32 KiB).
+ * every table is connection i. This call leaves what the server sends alone
+ * (xyws_deflate_streams, below, compresses the broadcast; RFC 7692 6 lets an
+ * endpoint send uncompressed messages once the extension is agreed). Limits:
+ * no context takeover in either direction; client_max_window_bits is not
+ * narrowed (the window is always 32 KiB).
  *
  * Per connection, with s = min(nmsgs, msg_cap) of the input row (0 for a null
  * msgs) and the carry ic:
@@ -1185,6 +1185,140 @@ int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
                          const xyws_inflate_conn* dev_iconns, uint64_t n, uint32_t opts,
                          xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
                          xyws_inflate_result* dev_results /* n, nullable */, void* stream);
+
+/* ---- many connections, one deflate call -------------------------------------
+ * permessage-deflate on the send side. The handshake agreed to
+ * server_no_context_takeover, so every outbound message is a raw DEFLATE stream
+ * of its own and nothing is kept between sweeps. The broadcast frames a message
+ * once per room and copies it to every member, so a message compressed once is
+ * compressed for all of them. This call runs after the hold, the inflate and
+ * the reply and in front of xyws_broadcast_deflated_streams: decode,
+ * reassemble, hold, inflate, reply, deflate, broadcast, still with no host read
+ * of device state. It has the hold's and the inflate's shape: dev_reasm and
+ * dev_reasm_results are the table and rows this sweep's broadcast is given,
+ * dev_bconns the broadcast's own table (head, head_len, reply and room are
+ * read, as the broadcast reads them); dev_view, dev_view_results and
+ * dev_view_bconns (n entries each) are written here: over them the broadcast's
+ * wire build frames the compressed messages. Row i of every table is
+ * connection i.
+ *
+ *  1. Deliverable records. Connection i's deliverable records are exactly those
+ *     xyws_broadcast_streams would frame (its 2.: one rule, stated there and
+ *     computed by the same code).
+ *  2. A connection whose room is XYWS_ROOM_NONE has none.
+ *  3. Compression. For each deliverable record, in record order, the
+ *     L = head_len_i + length bytes head_i | message are compressed to a raw
+ *     DEFLATE stream (RFC 1951) of non-final blocks that ends in an empty stored
+ *     block without that block's 00 00 ff ff (RFC 7692 7.2.1), and the
+ *     compressed bytes are appended to out. Whoever inflates them appends
+ *     00 00 ff ff first, as xyws_inflate_streams does.
+ *  4. The view's records. One per deliverable record, in order: out_off points
+ *     into out, length is the compressed length, the status is
+ *     XYWS_MSG_COMPLETE, opcode, first_frame and nframes are the input
+ *     record's. Other records are left out of the view.
+ *  5. dev_view[i] = {out, out_cap, the input's mc, vmsgs, vmsg_cap, 0...} (a
+ *     null out counts as out_cap 0, a null vmsgs as vmsg_cap 0).
+ *  6. dev_view_results[i] = {out_len, nmsgs = the deliverable records,
+ *     completed = the view records stored, status}: XYWS_RSM_TRUNCATED when
+ *     out_len > out_cap, XYWS_RSM_MSG_CAP when a record was not stored.
+ *  7. dev_view_bconns[i] is dev_bconns[i] with head = NULL and head_len = 0:
+ *     the head is inside the compressed bytes now.
+ *  8. Block choice. Per record the shorter of fixed-Huffman blocks (matches
+ *     found in the record itself, at distances of at most the kernel's stage)
+ *     and stored blocks; both sizes are known before a byte is written. A tie
+ *     goes to the stored form.
+ *  9. A record's compressed length never exceeds L + 5 * ceil(L / 65535) + 1:
+ *     the all-stored form, blocks of 65535 bytes; L = 0 gives the single byte
+ *     00.
+ * 10. Sizing. out_cap >= sum over the deliverable records of that bound always
+ *     suffices; with s stored records of out_len_i message bytes in all, none
+ *     longer than 65535 bytes with its head, that is at most
+ *     out_len_i + s * (head_len_i + 6).
+ * 11. The caps. A record that does not fit in what is left of out_cap is not
+ *     written at all: its view record has XYWS_MSG_TRUNCATED beside COMPLETE
+ *     (the wire build skips it), the result has XYWS_DFL_TOO_LONG, out_len
+ *     keeps counting. A deliverable record at index >= vmsg_cap of the view is
+ *     neither compressed nor counted in out_len: the result has
+ *     XYWS_DFL_MSG_CAP. No byte at or behind out + out_cap is written, no view
+ *     record at index >= vmsg_cap, and no byte outside the connection's own
+ *     range: neighbouring ranges may share 16-byte lines and have any
+ *     alignment (whole lines inside a record, byte stores on its first and
+ *     last line).
+ * 12. Like its siblings the call is one launch (one wave per connection), uses
+ *     no context scratch, no scratch slot and no policy word, never touches the
+ *     device error word, reads no device state on the host, needs no reserve,
+ *     can be captured into a hipGraph at once and runs concurrently on
+ *     different streams. n == 0 returns XYWS_OK and launches nothing.
+ *     XYWS_ERR_INVALID, decided on the arguments alone, before the context is
+ *     used: a null ctx; a null dev_reasm, dev_reasm_results, dev_bconns,
+ *     dev_dconns, dev_view, dev_view_results or dev_view_bconns with n > 0;
+ *     n >= UINT32_MAX; opts != 0. The out ranges must not overlap each other,
+ *     the inputs or the heads; a view row must not appear twice in a call;
+ *     vmsgs must not be the input's msgs.
+ *
+ * Not built: dynamic-Huffman blocks (fixed blocks win only through matches;
+ * prose with no repeats falls back to stored); context takeover;
+ * server_max_window_bits; skipping rooms that have no negotiated member;
+ * compressing the roster's notices and the backlog, which stay RSV1 = 0 frames
+ * behind the compressed wire (RFC 7692 allows that per message). */
+#define XYWS_DFC_NEGOTIATED 0x1u /* xyws_deflate_conn.flags: this connection is sent the compressed wire (read by the fan-out only) */
+typedef struct xyws_deflate_conn {   /* 64 bytes; entry i goes with dev_reasm[i] */
+  void*         out;      /* device: this connection's compressed bytes; NULL = out_cap 0 */
+  uint64_t      out_cap;
+  xyws_message* vmsgs;    /* device, nullable (then vmsg_cap counts as 0): the view's record row */
+  uint64_t      vmsg_cap;
+  uint32_t      flags;    /* XYWS_DFC_* */
+  uint32_t      reserved0;
+  uint64_t      reserved[3]; /* zero */
+} xyws_deflate_conn;
+
+typedef struct xyws_deflate_result { /* 32 bytes */
+  uint64_t out_len;    /* the compressed lengths together (may exceed out_cap) */
+  uint64_t in_len;     /* the L of the records compressed, together */
+  uint32_t n_deflated; /* records sent as fixed-Huffman blocks */
+  uint32_t n_stored;   /* records sent as stored blocks */
+  uint32_t status;     /* XYWS_DFL_* */
+  uint32_t reserved0;
+} xyws_deflate_result;
+#define XYWS_DFL_TOO_LONG 0x1u /* a record did not fit in out_cap */
+#define XYWS_DFL_MSG_CAP  0x2u /* a deliverable record beyond vmsg_cap */
+
+int xyws_deflate_streams(xyws_ctx* ctx,
+                         const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                         const xyws_bcast_conn* dev_bconns,
+                         const xyws_deflate_conn* dev_dconns, uint64_t n, uint32_t opts /* must be 0 */,
+                         xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
+                         xyws_bcast_conn* dev_view_bconns,
+                         xyws_deflate_result* dev_results /* n, nullable */, void* stream);
+
+/* xyws_broadcast_streams with two wires per room: the plain one, and the one
+ * of the compressed messages for the members that negotiated
+ * permessage-deflate. The first eleven arguments are those of
+ * xyws_broadcast_streams and mean the same; dev_view, dev_view_results and
+ * dev_view_bconns are what this sweep's xyws_deflate_streams wrote, dev_dconns
+ * its table; dev_zrooms and dev_zroom_results are a second room table of
+ * n_rooms rows whose member lists are dev_rooms' and whose wire and wire_cap
+ * are the compressed wire's. Three launches: the wire build over the plain
+ * tables into the plain wires, as today; the same wire build over the view
+ * into the z wires, with RSV1 (0x40) set in byte 0 of every header; the
+ * fan-out, in which a connection with XYWS_DFC_NEGOTIATED gets its room's z
+ * wire and z wire_len and everyone else the plain wire, byte for byte as
+ * xyws_broadcast_streams gives it. dev_results and dev_room_results keep their
+ * meaning, so the roster, the backlog (which keeps folding the plain wire) and
+ * the outbox take them unchanged. XYWS_ERR_INVALID: what
+ * xyws_broadcast_streams refuses; flags with XYWS_FLAG_RSV1; a null dev_view,
+ * dev_view_results, dev_view_bconns or dev_dconns with n > 0; a null
+ * dev_zrooms or dev_zroom_results with n_rooms > 0. */
+#define XYWS_FLAG_RSV1 0x40 /* refused in `flags`: the call sets the bit on the compressed wire itself */
+int xyws_broadcast_deflated_streams(xyws_ctx* ctx,
+                                    const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                                    const xyws_bcast_conn* dev_bconns, uint64_t n,
+                                    const xyws_room* dev_rooms, xyws_room_result* dev_room_results, uint64_t n_rooms,
+                                    uint8_t flags, uint32_t enc_opts,
+                                    xyws_bcast_result* dev_results /* n, nullable */,
+                                    const xyws_reasm_conn* dev_view, const xyws_reasm_result* dev_view_results,
+                                    const xyws_bcast_conn* dev_view_bconns, const xyws_deflate_conn* dev_dconns,
+                                    const xyws_room* dev_zrooms, xyws_room_result* dev_zroom_results, void* stream);
 
 /* ---- many rooms, one backlog call -------------------------------------------
  * The room's memory: chat_room::deliver keeps the last 10 messages in

@@ -246,6 +246,24 @@ INFK_HDR0, INFK_COMPRESSED = 0x1, 0x2  # xyws_inflate_carry.flags
 INF_PASSTHROUGH, INF_BAD_DATA, INF_TOO_LONG, INF_UNKNOWN = 0x1, 0x2, 0x4, 0x8  # xyws_inflate_result.status
 
 
+class DeflateConn(C.Structure):
+    """xyws_deflate_conn (include/xyws.h), 64 bytes: entry i goes with entry i of the xyws_reasm_conn table."""
+    _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("vmsgs", C.c_void_p), ("vmsg_cap", C.c_uint64),
+                ("flags", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 3)]
+
+
+class DeflateResult(C.Structure):
+    """xyws_deflate_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("out_len", C.c_uint64), ("in_len", C.c_uint64), ("n_deflated", C.c_uint32), ("n_stored", C.c_uint32),
+                ("status", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+assert C.sizeof(DeflateConn) == 64 and C.sizeof(DeflateResult) == 32
+DFC_NEGOTIATED = 0x1  # xyws_deflate_conn.flags
+DFL_TOO_LONG, DFL_MSG_CAP = 0x1, 0x2  # xyws_deflate_result.status
+FLAG_RSV1 = 0x40  # refused by xyws_broadcast_deflated_streams, which sets it on the compressed wire itself
+
+
 BACKLOG_MAX = 16
 
 
@@ -612,6 +630,14 @@ def load():
     # (no HIP call: lanes per connection, ring bytes, LDS bytes per wave, grid cap)
     L.xyws_debug_inflate_geometry.restype = i32
     L.xyws_debug_inflate_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_deflate_streams.restype = i32
+    L.xyws_deflate_streams.argtypes = [vp, vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp]
+    # (no HIP call: stage bytes W, hash slots, grid cap, wave size)
+    L.xyws_debug_deflate_geometry.restype = i32
+    L.xyws_debug_deflate_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_broadcast_deflated_streams.restype = i32
+    L.xyws_broadcast_deflated_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, u64, C.c_uint8, u32, vp, vp, vp, vp, vp, vp,
+                                                  vp, vp]
     L.xyws_backlog_streams.restype = i32
     L.xyws_backlog_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp]
     # (no HIP call: members per tile of the fold, bytes per delivery step, grid cap, wave size)

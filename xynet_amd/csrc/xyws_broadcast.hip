@@ -185,10 +185,16 @@ __global__ void __launch_bounds__(BC_WIRE_THREADS)
   }
 }
 
+// Z (xyws_broadcast_deflated_streams): a connection whose dconns row has
+// XYWS_DFC_NEGOTIATED takes its room's row of zrooms and zroom_results instead.
+template <bool Z>
 __global__ void __launch_bounds__(BC_THREADS) k_room_fanout(const xyws_bcast_conn* __restrict__ bconns, uint64_t n,
                                                             const xyws_room* __restrict__ rooms,
                                                             const xyws_room_result* __restrict__ room_results,
-                                                            uint64_t n_rooms, xyws_bcast_result* __restrict__ results) {
+                                                            uint64_t n_rooms, xyws_bcast_result* __restrict__ results,
+                                                            const xyws_deflate_conn* __restrict__ dconns,
+                                                            const xyws_room* __restrict__ zrooms,
+                                                            const xyws_room_result* __restrict__ zroom_results) {
   const uint32_t tid = threadIdx.x;
   for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
     const rows::bcast_conn_row bq = rows::load_bcast_conn<true>(bconns + ci);
@@ -207,9 +213,11 @@ __global__ void __launch_bounds__(BC_THREADS) k_room_fanout(const xyws_bcast_con
     } else if (pst & (XYWS_RPL_CLOSED | XYWS_RPL_OVERFLOW)) {
       st = XYWS_BC_NOT_RECEIVER;
     } else {
-      const rows::room_row rq = rows::load_room(rooms + room);
+      const bool z = Z && (rows::load_deflate_flags(dconns + ci) & XYWS_DFC_NEGOTIATED);
+      const rows::room_row rq = rows::load_room((z ? zrooms : rooms) + room);
       wire = rq.wire;
-      const uint64_t wire_cap = rq.wire_cap, wire_len = rows::load_room_result(room_results + room).wire_len;
+      const uint64_t wire_cap = rq.wire_cap,
+                     wire_len = rows::load_room_result((z ? zroom_results : room_results) + room).wire_len;
       w = wire_len < wire_cap ? wire_len : wire_cap;
     }
     const uint64_t send_len = sat_add(base, w);
@@ -240,6 +248,26 @@ __global__ void __launch_bounds__(BC_THREADS) k_room_fanout(const xyws_bcast_con
   }
 }
 
+// What both broadcast calls refuse, on the arguments alone.
+bool broadcast_args_ok(xyws_ctx* ctx, const void* dev_reasm, const void* dev_reasm_results, const void* dev_bconns,
+                       uint64_t n, const void* dev_rooms, const void* dev_room_results, uint64_t n_rooms, uint8_t flags,
+                       uint32_t enc_opts) {
+  if (!ctx || (n && (!dev_reasm || !dev_reasm_results || !dev_bconns))) return false;
+  if (n_rooms && (!dev_rooms || !dev_room_results)) return false;
+  if (n >= UINT32_MAX) return false;             // (a member index is 32 bits, UINT32_MAX is no index)
+  if (flags & XYWS_FLAG_HAS_MASK) return false;  // server role only
+  return !(enc_opts & ~XYWS_ENC_FRAME_OPCODE);
+}
+
+int launch_room_wire(const xyws_reasm_conn* reasm, const xyws_reasm_result* rres, const xyws_bcast_conn* bconns, uint64_t n,
+                     const xyws_room* rooms, xyws_room_result* room_results, uint64_t n_rooms, uint32_t flags,
+                     uint32_t enc_opts, void* stream) {
+  const uint32_t grid = grid_for(n_rooms, 1, BC_GRID_CAP);
+  hipLaunchKernelGGL(k_room_wire, dim3(grid), dim3(BC_WIRE_THREADS), 0, (hipStream_t)stream, reasm, rres, bconns, n, rooms,
+                     room_results, n_rooms, flags, enc_opts);
+  return hip_err(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -248,25 +276,52 @@ int xyws_broadcast_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm, cons
                            const xyws_bcast_conn* dev_bconns, uint64_t n, const xyws_room* dev_rooms,
                            xyws_room_result* dev_room_results, uint64_t n_rooms, uint8_t flags, uint32_t enc_opts,
                            xyws_bcast_result* dev_results, void* stream) {
-  if (!ctx || (n && (!dev_reasm || !dev_reasm_results || !dev_bconns))) return XYWS_ERR_INVALID;
-  if (n_rooms && (!dev_rooms || !dev_room_results)) return XYWS_ERR_INVALID;
-  if (n >= UINT32_MAX) return XYWS_ERR_INVALID;            // (a member index is 32 bits, UINT32_MAX is no index)
-  if (flags & XYWS_FLAG_HAS_MASK) return XYWS_ERR_INVALID;  // server role only
-  if (enc_opts & ~XYWS_ENC_FRAME_OPCODE) return XYWS_ERR_INVALID;
+  if (!broadcast_args_ok(ctx, dev_reasm, dev_reasm_results, dev_bconns, n, dev_rooms, dev_room_results, n_rooms, flags,
+                         enc_opts))
+    return XYWS_ERR_INVALID;
   if (!n) return XYWS_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
   device_guard g(ctx->device);
   if (!g.ok) return XYWS_ERR_HIP;
   if (n_rooms) {
-    const uint32_t grid = grid_for(n_rooms, 1, BC_GRID_CAP);
-    hipLaunchKernelGGL(k_room_wire, dim3(grid), dim3(BC_WIRE_THREADS), 0, (hipStream_t)stream, dev_reasm,
-                       dev_reasm_results, dev_bconns, n, dev_rooms, dev_room_results, n_rooms, (uint32_t)flags, enc_opts);
-    const int rc = hip_err(hipGetLastError());
+    const int rc = launch_room_wire(dev_reasm, dev_reasm_results, dev_bconns, n, dev_rooms, dev_room_results, n_rooms, flags,
+                                    enc_opts, stream);
     if (rc != XYWS_OK) return rc;
   }
   const dim3 grid = fanout_grid(n, n_rooms != 0, BC_GRID_CAP, BC_BLOCKS_AIM, BC_SLICES_MAX);
-  hipLaunchKernelGGL(k_room_fanout, grid, dim3(BC_THREADS), 0, (hipStream_t)stream, dev_bconns, n, dev_rooms,
-                     dev_room_results, n_rooms, dev_results);
+  hipLaunchKernelGGL(k_room_fanout<false>, grid, dim3(BC_THREADS), 0, (hipStream_t)stream, dev_bconns, n, dev_rooms,
+                     dev_room_results, n_rooms, dev_results, nullptr, nullptr, nullptr);
+  return hip_err(hipGetLastError());
+}
+
+int xyws_broadcast_deflated_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm,
+                                    const xyws_reasm_result* dev_reasm_results, const xyws_bcast_conn* dev_bconns, uint64_t n,
+                                    const xyws_room* dev_rooms, xyws_room_result* dev_room_results, uint64_t n_rooms,
+                                    uint8_t flags, uint32_t enc_opts, xyws_bcast_result* dev_results,
+                                    const xyws_reasm_conn* dev_view, const xyws_reasm_result* dev_view_results,
+                                    const xyws_bcast_conn* dev_view_bconns, const xyws_deflate_conn* dev_dconns,
+                                    const xyws_room* dev_zrooms, xyws_room_result* dev_zroom_results, void* stream) {
+  if (!broadcast_args_ok(ctx, dev_reasm, dev_reasm_results, dev_bconns, n, dev_rooms, dev_room_results, n_rooms, flags,
+                         enc_opts))
+    return XYWS_ERR_INVALID;
+  if (flags & XYWS_FLAG_RSV1) return XYWS_ERR_INVALID;  // (set here, on the compressed wire only)
+  if (n && (!dev_view || !dev_view_results || !dev_view_bconns || !dev_dconns)) return XYWS_ERR_INVALID;
+  if (n_rooms && (!dev_zrooms || !dev_zroom_results)) return XYWS_ERR_INVALID;
+  if (!n) return XYWS_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  device_guard g(ctx->device);
+  if (!g.ok) return XYWS_ERR_HIP;
+  if (n_rooms) {
+    int rc = launch_room_wire(dev_reasm, dev_reasm_results, dev_bconns, n, dev_rooms, dev_room_results, n_rooms, flags,
+                              enc_opts, stream);
+    if (rc != XYWS_OK) return rc;
+    rc = launch_room_wire(dev_view, dev_view_results, dev_view_bconns, n, dev_zrooms, dev_zroom_results, n_rooms,
+                          (uint32_t)flags | BC_FLAG_RSV1, enc_opts, stream);
+    if (rc != XYWS_OK) return rc;
+  }
+  const dim3 grid = fanout_grid(n, n_rooms != 0, BC_GRID_CAP, BC_BLOCKS_AIM, BC_SLICES_MAX);
+  hipLaunchKernelGGL(k_room_fanout<true>, grid, dim3(BC_THREADS), 0, (hipStream_t)stream, dev_bconns, n, dev_rooms,
+                     dev_room_results, n_rooms, dev_results, dev_dconns, dev_zrooms, dev_zroom_results);
   return hip_err(hipGetLastError());
 }
 

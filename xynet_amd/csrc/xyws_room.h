@@ -25,6 +25,9 @@
 #define BC_GRID_CAP 8192u   // rooms / connections per launch in x; further ones are grid-strided
 #define BC_BLOCKS_AIM 4096u // workgroups wanted in flight (256 CUs x 16)
 #define BC_SLICES_MAX 256u  // at most this many workgroups share one connection
+// Above the public 8-bit flags, so no caller can pass it: the wire build of the compressed wire
+// (xyws_broadcast_deflated_streams) sets RSV1 in byte 0 of every header.
+#define BC_FLAG_RSV1 0x100u
 
 namespace xyws_internal {
 
@@ -87,6 +90,7 @@ XYWS_DEV bool frame_of(const xyws_message* rec, const member& m, uint32_t flags,
   f.len = len;
   const uint32_t fl = (enc_opts & XYWS_ENC_FRAME_OPCODE) ? (flags & ~(uint32_t)XYWS_FLAG_OP_MASK) | op : flags;
   f.h = build_header(fl, m.head_len + len, false, 0, f.hw);
+  if (flags & BC_FLAG_RSV1) f.hw[0] |= 0x40u;
   return true;
 }
 

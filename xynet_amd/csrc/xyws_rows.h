@@ -508,6 +508,21 @@ XYWS_HD inflate_counts unpack_inflate_counts(uint64_t w) {
   return {XYWS_GET(xyws_inflate_result, n_inflated, w), XYWS_GET(xyws_inflate_result, n_bad, w)};
 }
 
+// ---------------------------------------------------------------- the deflate's rows
+// The conn row is five words, flags in the fifth; the result is two lengths
+// and two words of two.
+struct deflate_counts { uint32_t n_deflated, n_stored; };  // xyws_deflate_result
+XYWS_ONE_WORD(xyws_deflate_conn, flags, reserved0);
+XYWS_ONE_WORD(xyws_deflate_result, n_deflated, n_stored);
+XYWS_ONE_WORD(xyws_deflate_result, status, reserved0);
+static_assert(sizeof(xyws_deflate_conn) == 8 * 8 && sizeof(xyws_deflate_result) == 4 * 8, "the deflate's rows: whole words");
+XYWS_HD uint64_t pack_deflate_counts(deflate_counts c) {
+  return XYWS_PUT(xyws_deflate_result, n_deflated, c.n_deflated) | XYWS_PUT(xyws_deflate_result, n_stored, c.n_stored);
+}
+XYWS_HD deflate_counts unpack_deflate_counts(uint64_t w) {
+  return {XYWS_GET(xyws_deflate_result, n_deflated, w), XYWS_GET(xyws_deflate_result, n_stored, w)};
+}
+
 }  // namespace xyws_rows
 
 // ================================================================ the device part
@@ -1077,6 +1092,32 @@ XYWS_DEV uint32_t load_hold_status(const xyws_hold_result* p) {
 }
 // The frame_off word of a frame row (wave-uniform).
 XYWS_DEV int64_t load_frame_off(const xyws_frame* p) { return (int64_t)XYWS_LD(true, xyws_frame, p, frame_off); }
+
+// ---- the deflate's rows (wave-uniform), and the broadcast row its view hands on
+struct deflate_conn_row { uint64_t out, out_cap, vmsgs, vmsg_cap; };  // (out_cap counts as 0 without out, vmsg_cap without vmsgs)
+XYWS_DEV deflate_conn_row load_deflate_conn(const xyws_deflate_conn* p) {
+  deflate_conn_row r;
+  r.out = XYWS_LD(true, xyws_deflate_conn, p, out);
+  r.out_cap = r.out ? XYWS_LD(true, xyws_deflate_conn, p, out_cap) : 0;
+  r.vmsgs = XYWS_LD(true, xyws_deflate_conn, p, vmsgs);
+  r.vmsg_cap = r.vmsgs ? XYWS_LD(true, xyws_deflate_conn, p, vmsg_cap) : 0;
+  return r;
+}
+XYWS_DEV uint32_t load_deflate_flags(const xyws_deflate_conn* p) {
+  return XYWS_GET(xyws_deflate_conn, flags, XYWS_LD(true, xyws_deflate_conn, p, flags));
+}
+XYWS_DEV void store_deflate_result(xyws_deflate_result* p, uint64_t out_len, uint64_t in_len, deflate_counts c, uint32_t status) {
+  XYWS_ST(xyws_deflate_result, p, out_len, out_len);
+  XYWS_ST(xyws_deflate_result, p, in_len, in_len);
+  XYWS_ST(xyws_deflate_result, p, n_deflated, pack_deflate_counts(c));
+  XYWS_ST(xyws_deflate_result, p, status, status);
+}
+// The broadcast row at src without its head, one word per lane.
+XYWS_DEV void copy_bcast_conn_headless(xyws_bcast_conn* dst, const xyws_bcast_conn* src, uint32_t lane) {
+  if (lane < sizeof(xyws_bcast_conn) / 8)
+    ((g_u64*)dst)[lane] = lane == XYWS_WORD(xyws_bcast_conn, head) || lane == XYWS_WORD(xyws_bcast_conn, head_len)
+                              ? 0 : ((const g_u64*)src)[lane];
+}
 
 }  // namespace xyws_rows
 #endif  // __HIPCC__

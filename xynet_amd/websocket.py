@@ -614,6 +614,47 @@ class GroupInflate:
         return _lib.read_rows(_lib.Message, self._tensors["vmsgs"], n, (self.group.cap + 1) * k)
 
 
+class GroupDeflate:
+    """The compressed messages of one sweep (connection_group.deflate), item k
+    as in the decode result of its sweep (host copies on demand).
+    xyws_deflate_streams reads the broadcast's own table (heads, reply rows,
+    rooms), so deflate() lays out the tables and ranges and
+    broadcast(..., deflated=this) issues the call in front of its launches;
+    the accessors are valid after that broadcast(). It owns the call's tables,
+    out ranges, view rows, result rows and, after the broadcast, the
+    compressed wires (zwire)."""
+
+    def __init__(self, group, messages, negotiated, tensors, out_cap):
+        self.group, self.decoded, self.messages_in = group, messages.decoded, messages
+        self.negotiated, self._tensors, self.out_cap, self.msg_cap = negotiated, tensors, out_cap, messages.msg_cap
+        m = len(self.decoded.ids)
+        self.outs = [tensors["out"][out_cap * k:out_cap * (k + 1)] for k in range(m)]
+        self._rows = _Rows(_lib.DeflateResult, tensors["results"], m)
+        self._vrows = _Rows(_lib.ReasmResult, tensors["view_results"], m)
+        self._zwires, self._zrows = [], None
+
+    def result(self, k):
+        """xyws_deflate_result of item k."""
+        return self._rows[k]
+
+    def view_result(self, k):
+        """Item k's row of the view (xyws_reasm_result)."""
+        return self._vrows[k]
+
+    def messages(self, k):
+        """The view's stored records of item k (out_off counts from outs[k]'s start)."""
+        n = min(self.view_result(k).nmsgs, self.msg_cap)
+        return _lib.read_rows(_lib.Message, self._tensors["vmsgs"], n, (self.group.cap + 1) * k)
+
+    def zroom_result(self, r):
+        """xyws_room_result of room r's compressed wire."""
+        return self._zrows[r]
+
+    def zwire(self, r):
+        """Room r's compressed wire of this sweep (a device tensor: the first min(wire_len, wire_cap) bytes)."""
+        return self._zwires[r][:min(self.zroom_result(r).wire_len, self._zwires[r].numel())]
+
+
 class GroupBroadcast:
     """Results, room results and wires of one connection_group.broadcast call,
     item k as in the decode result of its sweep, room r as in the `rooms`
@@ -1260,7 +1301,64 @@ class connection_group:
                    slot=dec.slot)
         return GroupInflate(self, src, tensors, out_cap, [i not in agreed for i in dec.ids])
 
-    def broadcast(self, messages, rooms, out_items, heads=None, reply=None, flags=0x11, enc_opts=0, wire_caps=None):
+    def deflate(self, messages_or_hold_or_inflate, negotiated, out_cap):
+        """Compress the sweep's outbound messages once per message
+        (xyws_deflate_streams, one launch) for the members that negotiated
+        permessage-deflate: `messages_or_hold_or_inflate` is what broadcast()
+        is given, negotiated the connection ids that are sent the compressed
+        wire, out_cap the bytes each item gets for its compressed messages
+        (a message of L bytes with its head needs at most
+        L + 5 * ceil(L / 65535) + 1). Returns a GroupDeflate for
+        broadcast(..., deflated=...), which issues the launch: the call reads
+        the heads, reply rows and rooms that broadcast() lays out."""
+        src = messages_or_hold_or_inflate
+        if not isinstance(src, (GroupMessages, GroupHold, GroupInflate)) or src.group is not self or src.decoded.resident:
+            raise XywsError(-1, "deflate() takes the result of this group's reassemble(), hold() or inflate()")
+        dec, out_cap, agreed = src.decoded, int(out_cap), {int(i) for i in negotiated}
+        if out_cap < 0:
+            raise ValueError("out_cap must not be negative")
+        import torch
+        m, dev = len(dec.ids), self.device
+        dtab = _lib.Table(_lib.DeflateConn, m)
+        tensors = dict(vmsgs=_lib.alloc_rows(_lib.Message, m, dev, zero=False, per=self.cap + 1),
+                       view=_lib.alloc_rows(_lib.ReasmConn, m, dev), view_results=_lib.alloc_rows(_lib.ReasmResult, m, dev),
+                       view_bconns=_lib.alloc_rows(_lib.BcastConn, m, dev), results=_lib.alloc_rows(_lib.DeflateResult, m, dev),
+                       out=torch.empty(max(m * out_cap, 1), dtype=torch.uint8, device=dev), src=src)
+        for k, (row, i) in enumerate(zip(dtab.rows, dec.ids)):
+            row.out, row.out_cap = tensors["out"].data_ptr() + out_cap * k, out_cap
+            row.vmsgs = _lib.row_ptr(tensors["vmsgs"], _lib.Message, (self.cap + 1) * k)
+            row.vmsg_cap = src.msg_cap
+            row.flags = _lib.DFC_NEGOTIATED if i in agreed else 0
+        tensors["dconns"] = dtab.upload(dev)
+        return GroupDeflate(self, src, agreed, tensors, out_cap)
+
+    def _broadcast_deflated(self, messages, deflated, tensors, wires, m, nr, flags, enc_opts, slot):
+        """broadcast(..., deflated=...): xyws_deflate_streams, then
+        xyws_broadcast_deflated_streams over a second room table whose rows
+        are the first one's with the compressed wires (copied on the device:
+        a room set's counts are the device's)."""
+        import torch
+        if not isinstance(deflated, GroupDeflate) or deflated.group is not self or deflated.messages_in is not messages:
+            raise XywsError(-1, "deflated must be this group's deflate() result over the same messages")
+        d, dev = deflated._tensors, self.device
+        # a compressed record is at most 6 bytes longer than the plain one (5 more per further 65535 bytes)
+        zwires = [torch.empty(w.numel() + 6 * messages.msg_cap * m + 5 * (w.numel() // 65535), dtype=torch.uint8, device=dev)
+                  for w in wires]
+        zrooms = tensors["rooms"].clone()
+        if nr:
+            cols = zrooms.view(torch.int64).view(nr, -1)
+            cols[:, _lib.Room.wire.offset // 8] = torch.tensor([w.data_ptr() for w in zwires], dtype=torch.int64).to(dev)
+            cols[:, _lib.Room.wire_cap.offset // 8] = torch.tensor([w.numel() for w in zwires], dtype=torch.int64).to(dev)
+        d.update(zrooms=zrooms, zroom_results=_lib.alloc_rows(_lib.RoomResult, nr, dev), bcast=tensors)
+        deflated._zwires, deflated._zrows = zwires, _Rows(_lib.RoomResult, d["zroom_results"], nr)
+        self._call("xyws_deflate_streams", *messages.tables(), tensors["bconns"], d["dconns"], m, 0, d["view"],
+                   d["view_results"], d["view_bconns"], d["results"], slot=slot)
+        self._call("xyws_broadcast_deflated_streams", *messages.tables(), tensors["bconns"], m, tensors["rooms"],
+                   tensors["room_results"], nr, flags, enc_opts, tensors["results"], d["view"], d["view_results"],
+                   d["view_bconns"], d["dconns"], d["zrooms"], d["zroom_results"], slot=slot)
+
+    def broadcast(self, messages, rooms, out_items, heads=None, reply=None, flags=0x11, enc_opts=0, wire_caps=None,
+                  deflated=None):
         """Deliver the whole messages of the reassemble() call that returned
         `messages` (or of the hold() call that followed it: then also the
         messages that call completed; or of the inflate() call after either:
@@ -1278,7 +1376,13 @@ class connection_group:
         that always suffices). rooms may be the RoomSet of rooms() instead:
         the lists are then the ones roster() keeps on the device, every
         connection of the group is an item of the sweep (item k is connection
-        k: XywsError otherwise), and the wires are the room set's. Returns a
+        k: XywsError otherwise), and the wires are the room set's. deflated:
+        the GroupDeflate of deflate() over the same `messages`: the messages
+        are compressed once each and framed into a second wire per room with
+        RSV1 set (xyws_deflate_streams, then xyws_broadcast_deflated_streams,
+        three launches), which the connections deflate() was told negotiated
+        get in place of the plain wire; everyone else gets what they get
+        without it. Returns a
         GroupBroadcast. Call it before the group's next decode(), reply() or
         reassemble()."""
         dec = messages.decoded
@@ -1311,8 +1415,11 @@ class connection_group:
         nr = len(wires)
         tensors.update(room_results=_lib.alloc_rows(_lib.RoomResult, nr, self.device),
                        results=_lib.alloc_rows(_lib.BcastResult, m, self.device))
-        self._call("xyws_broadcast_streams", *messages.tables(), tensors["bconns"], m, tensors["rooms"],
-                   tensors["room_results"], nr, flags, enc_opts, tensors["results"], slot=dec.slot)
+        if deflated is not None:
+            self._broadcast_deflated(messages, deflated, tensors, wires, m, nr, flags, enc_opts, dec.slot)
+        else:
+            self._call("xyws_broadcast_streams", *messages.tables(), tensors["bconns"], m, tensors["rooms"],
+                       tensors["room_results"], nr, flags, enc_opts, tensors["results"], slot=dec.slot)
         return GroupBroadcast(self, messages, outs, hds, reply is not None, wires, tensors, room_set)
 
     def _reply_row(self, k):
