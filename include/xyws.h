@@ -1226,7 +1226,14 @@ int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
  *  8. Block choice. Per record the shorter of fixed-Huffman blocks (matches
  *     found in the record itself, at distances of at most the kernel's stage)
  *     and stored blocks; both sizes are known before a byte is written. A tie
- *     goes to the stored form.
+ *     goes to the stored form. With XYWS_DFO_DYNAMIC in opts the choice has a
+ *     step in front of it: per piece of a record (the kernel's stage, 8 KiB)
+ *     the block is the shorter of the fixed and the dynamic-Huffman form over
+ *     the same tokens, a tie going to fixed; per record the form is the
+ *     shorter of the sum of those blocks and the stored form, a tie going to
+ *     stored. All sizes are known before a byte of the record is written, a
+ *     record is never longer than it is with opts == 0, and 9. to 11. hold
+ *     unchanged. With opts == 0 the call is byte for byte what it was.
  *  9. A record's compressed length never exceeds L + 5 * ceil(L / 65535) + 1:
  *     the all-stored form, blocks of 65535 bytes; L = 0 gives the single byte
  *     00.
@@ -1252,15 +1259,15 @@ int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
  *     XYWS_ERR_INVALID, decided on the arguments alone, before the context is
  *     used: a null ctx; a null dev_reasm, dev_reasm_results, dev_bconns,
  *     dev_dconns, dev_view, dev_view_results or dev_view_bconns with n > 0;
- *     n >= UINT32_MAX; opts != 0. The out ranges must not overlap each other,
+ *     n >= UINT32_MAX; a bit of opts other than XYWS_DFO_DYNAMIC. The out ranges must not overlap each other,
  *     the inputs or the heads; a view row must not appear twice in a call;
  *     vmsgs must not be the input's msgs.
  *
- * Not built: dynamic-Huffman blocks (fixed blocks win only through matches;
- * prose with no repeats falls back to stored); context takeover;
- * server_max_window_bits; skipping rooms that have no negotiated member;
+ * Not built: splitting a piece into several blocks, lazy matching; context
+ * takeover; server_max_window_bits; skipping rooms that have no negotiated member;
  * compressing the roster's notices and the backlog, which stay RSV1 = 0 frames
  * behind the compressed wire (RFC 7692 allows that per message). */
+#define XYWS_DFO_DYNAMIC 0x2u /* opts: a piece may go out as a dynamic-Huffman block where that is shorter */
 #define XYWS_DFC_NEGOTIATED 0x1u /* xyws_deflate_conn.flags: this connection is sent the compressed wire (read by the fan-out only) */
 typedef struct xyws_deflate_conn {   /* 64 bytes; entry i goes with dev_reasm[i] */
   void*         out;      /* device: this connection's compressed bytes; NULL = out_cap 0 */
@@ -1275,10 +1282,10 @@ typedef struct xyws_deflate_conn {   /* 64 bytes; entry i goes with dev_reasm[i]
 typedef struct xyws_deflate_result { /* 32 bytes */
   uint64_t out_len;    /* the compressed lengths together (may exceed out_cap) */
   uint64_t in_len;     /* the L of the records compressed, together */
-  uint32_t n_deflated; /* records sent as fixed-Huffman blocks */
+  uint32_t n_deflated; /* records sent as Huffman blocks, fixed or dynamic */
   uint32_t n_stored;   /* records sent as stored blocks */
   uint32_t status;     /* XYWS_DFL_* */
-  uint32_t reserved0;
+  uint32_t reserved0;  /* with XYWS_DFO_DYNAMIC: the records among n_deflated with at least one dynamic block; else 0 */
 } xyws_deflate_result;
 #define XYWS_DFL_TOO_LONG 0x1u /* a record did not fit in out_cap */
 #define XYWS_DFL_MSG_CAP  0x2u /* a deliverable record beyond vmsg_cap */
@@ -1286,7 +1293,7 @@ typedef struct xyws_deflate_result { /* 32 bytes */
 int xyws_deflate_streams(xyws_ctx* ctx,
                          const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
                          const xyws_bcast_conn* dev_bconns,
-                         const xyws_deflate_conn* dev_dconns, uint64_t n, uint32_t opts /* must be 0 */,
+                         const xyws_deflate_conn* dev_dconns, uint64_t n, uint32_t opts /* 0 or XYWS_DFO_DYNAMIC */,
                          xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
                          xyws_bcast_conn* dev_view_bconns,
                          xyws_deflate_result* dev_results /* n, nullable */, void* stream);

@@ -20,7 +20,13 @@ inflated on the host and compared. The variants are alternated in one process
 after a warm-up, each timed by device events around a loop that ends in a
 synchronise; every cell is repeated and reports median and range.
 
-usage: deflate_rate.py [--out FILE] [--repeats R]
+With --dynamic the cells are measured once more for XYWS_DFO_DYNAMIC and one
+row per cell ("option": "dynamic") is appended to the file: the deflate call
+with the bit next to the deflate call with opts = 0 on the same build,
+alternated; the ratio with the bit next to the same zlib columns; the share of
+messages that went out with a dynamic block.
+
+usage: deflate_rate.py [--out FILE] [--repeats R] [--dynamic]
 """
 import argparse
 import ctypes as C
@@ -41,6 +47,7 @@ from xynet_amd import _lib, websocket as ws  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deflate_rate.jsonl"))
 ap.add_argument("--repeats", type=int, default=5)
+ap.add_argument("--dynamic", action="store_true")
 args = ap.parse_args()
 assert args.repeats >= 5, "the spread needs at least 5 repeats"
 assert torch.cuda.is_available(), "deflate_rate.py measures on the GPU: no device, no number"
@@ -131,16 +138,19 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
     mres_t, mtab_t, btab_t, dtab_t, rtab_t, ztab_t = (dev(t) for t in (mres, mtab, btab, dtab, rtab, ztab))
     view, vres, vbc, dres, bres, rres, zres = (zeros(s * n) for s in (64, 32, 64, 32, 32, 32, 32))
 
-    def deflate_call():
-        _lib.check(L.xyws_deflate_streams(ctx.h, vp(mtab_t), vp(mres_t), vp(btab_t), vp(dtab_t), n, 0, vp(view), vp(vres),
+    def deflate_call(opts=0):
+        _lib.check(L.xyws_deflate_streams(ctx.h, vp(mtab_t), vp(mres_t), vp(btab_t), vp(dtab_t), n, opts, vp(view), vp(vres),
                                           vp(vbc), vp(dres), sp))
+
+    def deflate_call_dynamic():
+        deflate_call(_lib.DFO_DYNAMIC)
 
     def broadcast_plain():
         _lib.check(L.xyws_broadcast_streams(ctx.h, vp(mtab_t), vp(mres_t), vp(btab_t), n, vp(rtab_t), vp(rres), nr, 0x11, 0,
                                             vp(bres), sp))
 
     def broadcast_deflated():
-        deflate_call()
+        deflate_call(_lib.DFO_DYNAMIC if args.dynamic else 0)
         _lib.check(L.xyws_broadcast_deflated_streams(ctx.h, vp(mtab_t), vp(mres_t), vp(btab_t), n, vp(rtab_t), vp(rres), nr,
                                                      0x11, 0, vp(bres), vp(view), vp(vres), vp(vbc), vp(dtab_t), vp(ztab_t),
                                                      vp(zres), sp))
@@ -157,6 +167,8 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
     z_len = zres.cpu().numpy().view(np.uint64).reshape(n, 4)[:nr, 0]
     assert (bres.cpu().numpy().view(np.uint64).reshape(n, 4)[:, 1] == np.repeat(z_len, ROOM)).all()
     modes = {"deflate_call": deflate_call, "broadcast_plain": broadcast_plain, "broadcast_deflated": broadcast_deflated}
+    if args.dynamic:
+        modes = {"deflate_call": deflate_call, "deflate_call_dynamic": deflate_call_dynamic}
     for fn in modes.values():
         fn()
         fn()
@@ -178,11 +190,15 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
     row["ratio_zlib6"] = round(row["zlib6_bytes"] / total, 3)
     row["ratio_zlib_fixed"] = round(row["zlib_fixed_bytes"] / total, 3)
     row["deflate_MBps_in"] = round(total / row["deflate_call"]["median_us"], 1)
+    if args.dynamic:  # (compressed_bytes, ratio and the send bytes are the bit's; Huffman records of either kind: n_deflated)
+        row["n_deflated"] = row.pop("n_fixed")
+        row.update(option="dynamic", n_dynamic=int(kinds[:, 7].sum()), dynamic_share=round(int(kinds[:, 7].sum()) / n, 3),
+                   deflate_dynamic_MBps_in=round(total / row["deflate_call_dynamic"]["median_us"], 1))
     rows.append(row)
     print(json.dumps(row), flush=True)
 
 assert ctx.last_device_error() == 0
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
+with open(args.out, "a" if args.dynamic else "w") as f:
     for row in rows:
         f.write(json.dumps(row) + "\n")

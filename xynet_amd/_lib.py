@@ -256,10 +256,12 @@ class DeflateResult(C.Structure):
     """xyws_deflate_result (include/xyws.h), 32 bytes."""
     _fields_ = [("out_len", C.c_uint64), ("in_len", C.c_uint64), ("n_deflated", C.c_uint32), ("n_stored", C.c_uint32),
                 ("status", C.c_uint32), ("reserved0", C.c_uint32)]
+    n_dynamic = property(lambda self: self.reserved0, doc="With DFO_DYNAMIC: the records with at least one dynamic block.")
 
 
 assert C.sizeof(DeflateConn) == 64 and C.sizeof(DeflateResult) == 32
 DFC_NEGOTIATED = 0x1  # xyws_deflate_conn.flags
+DFO_DYNAMIC = 0x2  # xyws_deflate_streams' opts
 DFL_TOO_LONG, DFL_MSG_CAP = 0x1, 0x2  # xyws_deflate_result.status
 FLAG_RSV1 = 0x40  # refused by xyws_broadcast_deflated_streams, which sets it on the compressed wire itself
 
@@ -635,6 +637,9 @@ def load():
     # (no HIP call: stage bytes W, hash slots, grid cap, wave size)
     L.xyws_debug_deflate_geometry.restype = i32
     L.xyws_debug_deflate_geometry.argtypes = [C.POINTER(u64)]
+    # (internal: build_code, the dynamic blocks' code builder, by one wave: freq u32[nsym] -> lens u8[nsym])
+    L.xyws_debug_deflate_code_lengths.restype = i32
+    L.xyws_debug_deflate_code_lengths.argtypes = [vp, vp, u32, u32, vp, vp]
     L.xyws_broadcast_deflated_streams.restype = i32
     L.xyws_broadcast_deflated_streams.argtypes = [vp, vp, vp, vp, u64, vp, vp, u64, C.c_uint8, u32, vp, vp, vp, vp, vp, vp,
                                                   vp, vp]

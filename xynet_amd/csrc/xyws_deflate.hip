@@ -37,6 +37,19 @@
 // the staged bytes written out behind 5-byte block headers.
 // LDS: 8 KiB piece + 8 KiB table + 9 KiB output stage: six waves per CU on
 // gfx950's 160 KiB; the grid cap is that.
+//
+// With XYWS_DFO_DYNAMIC (k_deflate_streams<true>; <false> is the kernel above,
+// unchanged) a piece may go out as a dynamic-Huffman block over the same
+// tokens. The counting pass adds every token to two LDS histograms (286
+// literal/length counters, 30 distance counters); between the passes, when the
+// hash table is dead, the wave builds the three codes in the table's 8 KiB
+// (build_code: a bitonic sort of the used symbols by (frequency, symbol), the
+// two-queue merge, depths top-down, zlib's repair on the counts per length,
+// lengths handed out by rank, canonical codes), run-length codes the lengths
+// (one position per lane, runs found with ballots) and lays the block's header
+// bits down there. The packed table code << 8 | length overwrites the
+// histograms: 316 words, the only LDS the option adds. The emitting pass looks
+// a token's bits up there: up to 48 bits, ORed into up to three words.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
@@ -58,6 +71,20 @@
 #define DFL_MIN_MATCH 4u
 #define DFL_MAX_MATCH 258u
 #define DFL_STORED_MAX 65535u
+#define DFL_LITLEN 286u                        // the literal/length alphabet; its table is code[0, 286)
+#define DFL_DIST 30u                           // the distance alphabet; its table is code[286, 316)
+#define DFL_CLEN 19u                           // the code-length alphabet
+// The builder's workspace, in words of the hash table (dead between two passes):
+#define WS_KEY 0u                              // 512 sort keys: frequency << 9 | symbol, ~0 for an unused symbol
+#define WS_IW 512u                             // 288: the weights of the internal nodes, in the order they are made
+#define WS_IP 800u                             // 288: an internal node's parent, then its depth
+#define WS_LP 1088u                            // 288: the parent of the leaf of rank r
+#define WS_BLC 1376u                           // 16: symbols per length
+#define WS_CLF 1392u                           // 20: the code-length alphabet's frequencies, then its packed table
+#define WS_SEQ 1412u                           // 316: the run-length coded lengths, symbol | extra << 8, ~0: none here
+#define WS_HDR 1728u                           // 76: the block's header bits (17 + 57 + 316 * 7 at most), from bit 0
+#define WS_HDR_WORDS 76u
+#define WS_RUN WS_IW                           // 316: the first position of the run a position lies in (the trees are done)
 
 using namespace xyws_internal;
 namespace rows = xyws_rows;
@@ -65,6 +92,9 @@ namespace rows = xyws_rows;
 namespace {
 
 static_assert(DFL_SLOTS == 1u << DFL_HASH_BITS && DFL_STAGE <= DFL_STORED_MAX && DFL_STAGE % 16u == 0, "the geometry");
+static_assert(WS_HDR + WS_HDR_WORDS <= DFL_SLOTS && WS_RUN + DFL_LITLEN + DFL_DIST <= WS_BLC &&
+                  32u * (WS_HDR_WORDS - 2u) >= 17u + 57u + 7u * (DFL_LITLEN + DFL_DIST) && DFL_STAGE < 1u << 14,
+              "the workspace fits the table; a frequency fits its key");
 
 // What one wave keeps in LDS.
 struct deflate_lds {
@@ -72,6 +102,15 @@ struct deflate_lds {
   __attribute__((aligned(16))) uint32_t tab[DFL_SLOTS];              // position + 1 of the newest 4 bytes with this hash; 0: none
   __attribute__((aligned(16))) uint32_t out[DFL_OUT / 4u];           // the piece's bits
 };
+
+// With XYWS_DFO_DYNAMIC: and the two histograms, then the two codes, code << 8 | length.
+struct deflate_lds_dynamic : deflate_lds {
+  uint32_t code[DFL_LITLEN + DFL_DIST];
+};
+template <bool DYN>
+struct lds_of { typedef deflate_lds type; };
+template <>
+struct lds_of<true> { typedef deflate_lds_dynamic type; };
 
 XYWS_DEV uint64_t below(uint32_t p) { return (1ull << p) - 1ull; }  // (p < 64)
 XYWS_DEV uint32_t lane_value(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
@@ -101,8 +140,10 @@ XYWS_DEV uint32_t litlen_code(uint32_t s, uint32_t& len) {
   else c = 0xC0u + (s - 280u), len = 8;
   return rev(c, len);
 }
-// A match of mlen bytes (4..258) at distance dist (1..DFL_STAGE): its bits, at most 8 + 5 + 5 + 13.
-XYWS_DEV uint32_t match_bits(uint32_t mlen, uint32_t dist, uint32_t& nbits) {
+// A match of mlen bytes (4..258) at distance dist (1..DFL_STAGE): its length
+// symbol s and distance symbol ds, each with e / de extra bits of value x / dx.
+struct match_syms { uint32_t s, e, x, ds, de, dx; };
+XYWS_DEV match_syms syms_of(uint32_t mlen, uint32_t dist) {
   uint32_t s, e = 0, x = 0;
   const uint32_t l = mlen - 3u;
   if (mlen <= 10u) s = 254u + mlen;
@@ -112,10 +153,6 @@ XYWS_DEV uint32_t match_bits(uint32_t mlen, uint32_t dist, uint32_t& nbits) {
     s = 261u + 4u * e + ((l >> e) - 4u);
     x = l & ((1u << e) - 1u);
   }
-  uint32_t n;
-  uint32_t v = litlen_code(s, n);
-  v |= x << n;
-  n += e;
   const uint32_t dd = dist - 1u;
   uint32_t ds = dd, de = 0, dx = 0;
   if (dd >= 4u) {
@@ -123,6 +160,16 @@ XYWS_DEV uint32_t match_bits(uint32_t mlen, uint32_t dist, uint32_t& nbits) {
     ds = 2u * de + 2u + ((dd >> de) & 1u);
     dx = dd & ((1u << de) - 1u);
   }
+  return {s, e, x, ds, de, dx};
+}
+// Its bits in the fixed code, at most 8 + 5 + 5 + 13.
+XYWS_DEV uint32_t match_bits(uint32_t mlen, uint32_t dist, uint32_t& nbits) {
+  const match_syms m = syms_of(mlen, dist);
+  const uint32_t e = m.e, x = m.x, ds = m.ds, de = m.de, dx = m.dx;
+  uint32_t n;
+  uint32_t v = litlen_code(m.s, n);
+  v |= x << n;
+  n += e;
   v |= rev(ds, 5) << n;
   n += 5u;
   v |= dx << n;
@@ -169,21 +216,255 @@ XYWS_DEV void flush_stage(const uint32_t* src, uint32_t nb, g_u8* dbase, uint64_
   }
 }
 
+XYWS_DEV uint32_t wave_sum(uint32_t v, uint32_t lane) { return lane_value(scan32(v, lane), DFL_LANES - 1u); }
+XYWS_DEV uint32_t top_bit(uint64_t m) { return 64u - (uint32_t)__clzll((long long)m); }  // 1 + the highest set bit; 0: none
+
+// A length-limited Huffman code over the frequencies fc[0, nsym) (nsym <= 286,
+// each below 2^22, limit <= 15, 2^limit >= the used symbols), built by the wave
+// in the workspace ws (DFL_SLOTS words). fc[s] becomes code << 8 | length, the
+// code canonical (RFC 1951 3.2.2) and bit-reversed; an unused symbol keeps 0, a
+// single used one gets length 1. Returns the sum of frequency x length.
+XYWS_DEV uint32_t build_code(uint32_t* ws, uint32_t* fc, uint32_t nsym, uint32_t limit, uint32_t lane) {
+  __syncthreads();
+  // 1. the used symbols sorted by (frequency, symbol): a bitonic sort of N keys
+  const uint32_t N = nsym <= 64u ? 64u : nsym <= 128u ? 128u : nsym <= 256u ? 256u : 512u;
+  uint32_t m = 0;
+  for (uint32_t i = lane; i < N; i += DFL_LANES) {
+    const uint32_t f = i < nsym ? fc[i] : 0u;
+    ws[WS_KEY + i] = f ? (f << 9) | i : ~0u;
+    m += (uint32_t)__popcll(__ballot(f != 0u));
+  }
+  if (lane < 16u) ws[WS_BLC + lane] = 0;
+  __syncthreads();
+  for (uint32_t k = 2; k <= N; k <<= 1)
+    for (uint32_t j = k >> 1; j; j >>= 1) {
+      uint32_t a[4], b[4];  // (a stage's pairs are disjoint: all loads first, so that they overlap)
+#pragma unroll
+      for (uint32_t u = 0; u < 4u; u++) {
+        const uint32_t q = lane + DFL_LANES * u, i = ((q & ~(j - 1u)) << 1) | (q & (j - 1u));
+        if (q < N / 2u) a[u] = ws[WS_KEY + i], b[u] = ws[WS_KEY + (i | j)];
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < 4u; u++) {
+        const uint32_t q = lane + DFL_LANES * u, i = ((q & ~(j - 1u)) << 1) | (q & (j - 1u));
+        if (q < N / 2u && (a[u] > b[u]) == !(i & k)) ws[WS_KEY + i] = b[u], ws[WS_KEY + (i | j)] = a[u];
+      }
+      __syncthreads();
+    }
+  if (m < 2u) {
+    const uint32_t key = ws[WS_KEY];
+    if (m && lane == 0) fc[key & 511u] = 1u;  // length 1, code 0
+    __syncthreads();
+    return m ? key >> 9 : 0u;
+  }
+  // 2. the two-queue merge over the sorted leaves: the one serial chain, m - 1
+  // steps on one lane. 3. depths top-down: a parent is made after its children.
+  if (lane == 0) {
+    uint32_t li = 0, ii = 0, lw = ws[WS_KEY] >> 9, iv = ~0u;  // the two queues' heads and their weights; ~0: empty
+    for (uint32_t k = 0; k + 1u < m; k++) {
+      uint32_t w = 0;
+      for (uint32_t t = 0; t < 2u; t++) {
+        if (lw <= iv) ws[WS_LP + li++] = k, w += lw, lw = li < m ? ws[WS_KEY + li] >> 9 : ~0u;
+        else ws[WS_IP + ii++] = k, w += iv, iv = ii < k ? ws[WS_IW + ii] : ~0u;
+      }
+      ws[WS_IW + k] = w;
+      if (ii == k) iv = w;  // (the node just made is the internal queue's head)
+    }
+    ws[WS_IP + m - 2u] = 0;
+    for (uint32_t k = m - 2u; k-- > 0u;) ws[WS_IP + k] = ws[WS_IP + ws[WS_IP + k]] + 1u;
+  }
+  __syncthreads();
+  // 4. symbols per length, the too long ones at the limit; then zlib's repair
+  // on the counts, once per unit of 2^-limit that the Kraft sum is above 1
+  for (uint32_t r = lane; r < m; r += DFL_LANES) {
+    const uint32_t d = ws[WS_IP + ws[WS_LP + r]] + 1u;
+    atomicAdd(&ws[WS_BLC + (d < limit ? d : limit)], 1u);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    uint32_t sum = 0;
+    for (uint32_t l = 1; l <= limit; l++) sum += ws[WS_BLC + l] << (limit - l);
+    for (uint32_t over = sum > 1u << limit ? sum - (1u << limit) : 0u; over; over--) {
+      uint32_t b = limit - 1u;
+      while (b && !ws[WS_BLC + b]) b--;
+      if (!b) break;  // (2^limit < m: no code; not reached by the caller's alphabets)
+      ws[WS_BLC + b] -= 1u, ws[WS_BLC + b + 1u] += 2u, ws[WS_BLC + limit] -= 1u;
+    }
+  }
+  __syncthreads();
+  // 5. lengths by rank: the rarest symbol gets the longest code
+  uint32_t cost = 0;
+  for (uint32_t r = lane; r < m; r += DFL_LANES) {
+    const uint32_t key = ws[WS_KEY + r];
+    uint32_t l = limit;
+    for (uint32_t c = ws[WS_BLC + l]; r >= c && l > 1u;) c += ws[WS_BLC + --l];
+    fc[key & 511u] = l;
+    cost += (key >> 9) * l;
+  }
+  __syncthreads();
+  // 6. canonical codes: next_code on scalar registers, a symbol's place among
+  // the symbols of its length by ballot, 64 symbols a step
+  uint32_t nc[16];
+  nc[0] = 0;
+#pragma unroll
+  for (uint32_t l = 1; l < 16u; l++) nc[l] = (nc[l - 1u] + (l > 1u ? uniform32(ws[WS_BLC + l - 1u]) : 0u)) << 1;
+  for (uint32_t s0 = 0; s0 < nsym; s0 += DFL_LANES) {
+    const uint32_t s = s0 + lane, l = s < nsym ? fc[s] : 0u;
+    uint32_t code = 0;
+#pragma unroll
+    for (uint32_t q = 1; q < 16u; q++) {
+      const uint64_t b = __ballot(l == q);
+      if (l == q) code = nc[q] + (uint32_t)__popcll(b & below(lane));
+      nc[q] += (uint32_t)__popcll(b);
+    }
+    if (l) fc[s] = (rev(code, l) << 8) | l;
+  }
+  __syncthreads();
+  return wave_sum(cost, lane);
+}
+
+// The order in which the code-length code's lengths are sent (RFC 1951 3.2.7).
+XYWS_DEV uint32_t clen_order(uint32_t i) {
+  return (uint32_t)((i < 8u ? 0x0609070800121110ull : i < 16u ? 0x020D030C040B050Aull : 0x0F010Eull) >> (8u * (i & 7u))) & 0xFFu;
+}
+
+// After the counting pass of a piece (huff_block<true> without emit, whose
+// result is fbits): the two codes from the histograms, into S.code, and where
+// the dynamic block can be shorter than the fbits of the fixed one, its header
+// bits in the workspace. Returns the header's bits with the dynamic block's
+// bits in dbits, or 0 when the fixed block is no longer (a tie goes to it).
+XYWS_DEV uint32_t plan_piece(deflate_lds_dynamic& S, uint32_t fbits, uint32_t& dbits, uint32_t lane) {
+  uint32_t* const ws = S.tab;
+  __syncthreads();
+  // HLIT and HDIST end at the last used symbol; the extra bits depend on the symbol alone
+  const uint32_t fl = lane < 29u ? S.code[257u + lane] : 0u, fd = lane < DFL_DIST ? S.code[DFL_LITLEN + lane] : 0u;
+  const uint32_t hlit = 257u + top_bit(__ballot(fl != 0u)), used_d = top_bit(__ballot(fd != 0u)), hdist = used_d ? used_d : 1u;
+  const uint32_t extra = wave_sum(fl * (lane >= 8u && lane < 28u ? (lane - 4u) >> 2 : 0u) + fd * (lane >= 4u ? (lane >> 1) - 1u : 0u), lane);
+  uint32_t payload = extra + build_code(ws, S.code, DFL_LITLEN, 15u, lane);
+  payload += build_code(ws, S.code + DFL_LITLEN, DFL_DIST, 15u, lane);
+  dbits = 0;
+  if (17u + 3u * 4u + payload >= fbits) return 0;
+
+  // the lengths, HLIT of the one code and HDIST of the other, are one sequence
+  const uint32_t T = hlit + hdist;
+  auto len_at = [&](uint32_t t) { return S.code[t < hlit ? t : DFL_LITLEN + t - hlit] & 0xFFu; };
+  uint32_t edge = 0;  // the run that reaches this step began there
+  for (uint32_t t0 = 0; t0 < T; t0 += DFL_LANES) {
+    const uint32_t t = t0 + lane;
+    const uint64_t b = __ballot(t < T && (t == 0 || len_at(t) != len_at(t - 1u)));
+    const uint64_t mine = b & ((2ull << lane) - 1ull);
+    if (t < T) ws[WS_RUN + t] = mine ? t0 + top_bit(mine) - 1u : edge;
+    if (b) edge = t0 + top_bit(b) - 1u;
+  }
+  ws[WS_HDR + lane] = 0, ws[WS_HDR + DFL_LANES + lane] = 0;  // (the header's 76 words; nothing is live up to 128)
+  if (lane < 20u) ws[WS_CLF + lane] = 0;
+  __syncthreads();
+  // a position's symbol, if one begins there: zeros in runs of up to 138 (18:
+  // 11 and more, 17: 3 to 10), another length once and then in runs of 3 to 6 (16)
+  edge = T;  // the next run behind this step begins there
+  for (uint32_t t0 = (T - 1u) & ~(DFL_LANES - 1u);; t0 -= DFL_LANES) {
+    const uint32_t t = t0 + lane, st = t < T ? ws[WS_RUN + t] : 0u;
+    const uint64_t b = __ballot(t < T && st == t);
+    const uint64_t behind = b & ~((2ull << lane) - 1ull);
+    const uint32_t en = behind ? t0 + (uint32_t)__ffsll((long long)behind) - 1u : edge;
+    if (t < T) {
+      const uint32_t v = len_at(t), o = t - st, R = en - st;
+      uint32_t sym = ~0u;
+      if (v == 0) {
+        const uint32_t o2 = o % 138u, c = R - (o - o2) < 138u ? R - (o - o2) : 138u;
+        if (c >= 11u) sym = o2 ? ~0u : 18u | ((c - 11u) << 8);
+        else if (c >= 3u) sym = o2 ? ~0u : 17u | ((c - 3u) << 8);
+        else sym = 0;
+      } else if (o == 0) {
+        sym = v;
+      } else {
+        const uint32_t o2 = (o - 1u) % 6u, c = R - (o - o2) < 6u ? R - (o - o2) : 6u;
+        if (c >= 3u) sym = o2 ? ~0u : 16u | ((c - 3u) << 8);
+        else sym = v;
+      }
+      ws[WS_SEQ + t] = sym;
+      if (sym != ~0u) atomicAdd(&ws[WS_CLF + (sym & 0xFFu)], 1u);
+    }
+    if (b) edge = t0 + (uint32_t)__ffsll((long long)b) - 1u;
+    if (!t0) break;
+  }
+  __syncthreads();
+  // the code-length code: the same builder, 19 symbols, 7 bits; HCLEN ends at the last used one in the sending order
+  const uint32_t xbits = 2u * uniform32(ws[WS_CLF + 16u]) + 3u * uniform32(ws[WS_CLF + 17u]) + 7u * uniform32(ws[WS_CLF + 18u]);
+  const uint32_t clbits = build_code(ws, ws + WS_CLF, DFL_CLEN, 7u, lane);
+  const uint32_t mylen = lane < DFL_CLEN ? ws[WS_CLF + clen_order(lane)] & 0xFFu : 0u;
+  const uint32_t last = top_bit(__ballot(mylen != 0u)), hclen = last > 4u ? last : 4u;
+  const uint32_t hbits = 17u + 3u * hclen + clbits + xbits;
+  dbits = hbits + payload;
+  if (dbits >= fbits) return 0;
+
+  // the header: BFINAL 0, BTYPE 10, HLIT, HDIST, HCLEN; the code-length code's lengths; the sequence
+  if (lane == 0) ws[WS_HDR] = 4u | ((hlit - 257u) << 3) | ((hdist - 1u) << 8) | ((hclen - 4u) << 13);
+  __syncthreads();
+  if (lane < hclen && mylen) {
+    const uint32_t at = 17u + 3u * lane;
+    const uint64_t v = (uint64_t)mylen << (at & 31u);
+    atomicOr(&ws[WS_HDR + (at >> 5)], (uint32_t)v);
+    if (v >> 32) atomicOr(&ws[WS_HDR + (at >> 5) + 1u], (uint32_t)(v >> 32));
+  }
+  uint32_t bits = 17u + 3u * hclen;
+  for (uint32_t t0 = 0; t0 < T; t0 += DFL_LANES) {
+    const uint32_t t = t0 + lane, sym = t < T ? ws[WS_SEQ + t] : ~0u;
+    uint32_t tb = 0, tl = 0;
+    if (sym != ~0u) {
+      const uint32_t c = ws[WS_CLF + (sym & 0xFFu)];
+      tb = (c >> 8) | ((sym >> 8) << (c & 0xFFu));
+      tl = (c & 0xFFu) + ((sym & 0xFFu) < 16u ? 0u : (sym & 0xFFu) == 16u ? 2u : (sym & 0xFFu) == 17u ? 3u : 7u);
+    }
+    const uint32_t incl = scan32(tl, lane);
+    if (tl) {
+      const uint32_t at = bits + incl - tl;
+      const uint64_t v = (uint64_t)tb << (at & 31u);
+      atomicOr(&ws[WS_HDR + (at >> 5)], (uint32_t)v);
+      if (v >> 32) atomicOr(&ws[WS_HDR + (at >> 5) + 1u], (uint32_t)(v >> 32));
+    }
+    bits += lane_value(incl, DFL_LANES - 1u);
+  }
+  __syncthreads();
+  return hbits;
+}
+
 // One fixed-Huffman block of the n (1..DFL_STAGE) staged bytes: header, tokens,
 // end of block. With emit the bits go to S.out, which is zeroed first and
 // begins with the `bit0` (0..7) bits of `carry` that the piece before left
 // over. Returns the bit position behind the block (bit0 + its bits).
 // Wave-uniform but for the lanes' own tokens.
-XYWS_DEV uint32_t fixed_block(deflate_lds& S, uint32_t n, bool emit, uint32_t carry, uint32_t bit0, uint32_t lane) {
+//
+// DYN (XYWS_DFO_DYNAMIC). Without emit the tokens are also counted into the
+// histograms S.code, end of block once. With emit and hbits != 0 the block is
+// the dynamic one that plan_piece prepared: its hbits header bits are copied
+// from the workspace (before the table is zeroed for the search) and a token's
+// bits are looked up in S.code; hbits == 0 emits the fixed block.
+template <bool DYN>
+XYWS_DEV uint32_t huff_block(typename lds_of<DYN>::type& S, uint32_t n, bool emit, uint32_t hbits, uint32_t carry,
+                             uint32_t bit0, uint32_t lane) {
+  const bool dyn = DYN && emit && hbits;
+  const uint32_t lines = (n + n / 8u + 63u) / 16u + 1u;  // (9 n + 25 bits at most, a word of slack; <= DFL_OUT / 16)
   __syncthreads();
+  if constexpr (DYN) {
+    if (dyn) {  // (a dynamic block is chosen where it is shorter than the fixed one: the same lines hold it)
+      for (uint32_t k = lane; k < lines; k += DFL_LANES) reinterpret_cast<u32x4*>(S.out)[k] = u32x4{k == 0 ? carry : 0u, 0, 0, 0};
+      __syncthreads();
+      const uint32_t* const hdr = S.tab + WS_HDR;  // (a zero word behind the bits)
+      for (uint32_t w = lane; w <= (hbits + 31u) / 32u; w += DFL_LANES)
+        S.out[w] |= (uint32_t)((((uint64_t)hdr[w] << 32) | (w ? hdr[w - 1u] : 0u)) >> (32u - bit0));
+      __syncthreads();
+    } else if (!emit) {
+      for (uint32_t k = lane; k < DFL_LITLEN + DFL_DIST; k += DFL_LANES) S.code[k] = k == 256u;
+    }
+  }
   for (uint32_t k = lane; k < DFL_SLOTS / 4u; k += DFL_LANES) reinterpret_cast<u32x4*>(S.tab)[k] = u32x4{0, 0, 0, 0};
-  if (emit) {
-    const uint32_t lines = (n + n / 8u + 63u) / 16u + 1u;  // (9 n + 25 bits at most, a word of slack; <= DFL_OUT / 16)
+  if (emit && !dyn) {
     for (uint32_t k = lane; k < lines; k += DFL_LANES)
       reinterpret_cast<u32x4*>(S.out)[k] = u32x4{k == 0 ? carry | (2u << bit0) : 0u, 0, 0, 0};  // BFINAL 0, BTYPE 01
   }
   __syncthreads();
-  uint32_t bits = bit0 + 3u;
+  uint32_t bits = bit0 + (dyn ? hbits : 3u);
   for (uint32_t p0 = 0; p0 < n;) {
     // search: this lane's position
     const uint32_t p = p0 + lane;
@@ -228,30 +509,78 @@ XYWS_DEV uint32_t fixed_block(deflate_lds& S, uint32_t n, bool emit, uint32_t ca
     }
     // emission
     uint32_t tb = 0, tl = 0;
-    if (kind == 1) tb = litlen_code(word & 0xFFu, tl);
-    else if (kind == 2) tb = match_bits(mlen, dist, tl);
+    uint64_t tb64 = 0;  // (DYN: the token's bits, up to 15 + 5 + 15 + 13)
+    if constexpr (DYN) {
+      if (dyn) {
+        if (kind == 1) {
+          const uint32_t c = S.code[word & 0xFFu];
+          tb64 = c >> 8, tl = c & 0xFFu;
+        } else if (kind == 2) {
+          const match_syms m = syms_of(mlen, dist);
+          const uint32_t cl = S.code[m.s], cd = S.code[DFL_LITLEN + m.ds], ll = (cl & 0xFFu) + m.e, dl = cd & 0xFFu;
+          tb64 = (uint64_t)((cl >> 8) | (m.x << (cl & 0xFFu))) | ((uint64_t)(cd >> 8) << ll) | ((uint64_t)m.dx << (ll + dl));
+          tl = ll + dl + m.de;
+        }
+      } else {
+        if (kind == 1) tb = litlen_code(word & 0xFFu, tl);
+        else if (kind == 2) tb = match_bits(mlen, dist, tl);
+        tb64 = tb;
+        if (!emit) {  // the histograms
+          if (kind == 1) atomicAdd(&S.code[word & 0xFFu], 1u);
+          else if (kind == 2) {
+            const match_syms m = syms_of(mlen, dist);
+            atomicAdd(&S.code[m.s], 1u);
+            atomicAdd(&S.code[DFL_LITLEN + m.ds], 1u);
+          }
+        }
+      }
+    } else {
+      if (kind == 1) tb = litlen_code(word & 0xFFu, tl);
+      else if (kind == 2) tb = match_bits(mlen, dist, tl);
+    }
     const uint32_t incl = scan32(tl, lane);
     __syncthreads();  // (the step's lookups are done)
     if (hashed) atomicMax(&S.tab[slot], p + 1u);
     if (emit && tl) {
       const uint32_t at = bits + incl - tl;
-      const uint64_t v = (uint64_t)tb << (at & 31u);
-      atomicOr(&S.out[at >> 5], (uint32_t)v);
-      if (v >> 32) atomicOr(&S.out[(at >> 5) + 1u], (uint32_t)(v >> 32));
+      if constexpr (DYN) {
+        const uint32_t sh = at & 31u;
+        const uint64_t v = tb64 << sh;
+        const uint32_t top = sh ? (uint32_t)(tb64 >> (64u - sh)) : 0u;
+        atomicOr(&S.out[at >> 5], (uint32_t)v);
+        if (v >> 32) atomicOr(&S.out[(at >> 5) + 1u], (uint32_t)(v >> 32));
+        if (top) atomicOr(&S.out[(at >> 5) + 2u], top);
+      } else {
+        const uint64_t v = (uint64_t)tb << (at & 31u);
+        atomicOr(&S.out[at >> 5], (uint32_t)v);
+        if (v >> 32) atomicOr(&S.out[(at >> 5) + 1u], (uint32_t)(v >> 32));
+      }
     }
     __syncthreads();
     bits += lane_value(incl, DFL_LANES - 1u);
     p0 += r;
   }
+  if constexpr (DYN) {
+    if (dyn) {  // end of block: the code of 256, at most 15 bits
+      const uint32_t c = S.code[256];
+      if (lane == 0) {
+        const uint64_t v = (uint64_t)(c >> 8) << (bits & 31u);
+        atomicOr(&S.out[bits >> 5], (uint32_t)v);
+        if (v >> 32) atomicOr(&S.out[(bits >> 5) + 1u], (uint32_t)(v >> 32));
+      }
+      return bits + (c & 0xFFu);
+    }
+  }
   return bits + 7u;  // end of block: seven zero bits
 }
 
+template <bool DYN>  // XYWS_DFO_DYNAMIC
 __global__ void __launch_bounds__(DFL_LANES)
     k_deflate_streams(const xyws_reasm_conn* __restrict__ reasm, const xyws_reasm_result* __restrict__ rres,
                       const xyws_bcast_conn* __restrict__ bconns, const xyws_deflate_conn* __restrict__ dconns, uint64_t n,
                       xyws_reasm_conn* __restrict__ view, xyws_reasm_result* __restrict__ vres,
                       xyws_bcast_conn* __restrict__ vbconns, xyws_deflate_result* __restrict__ results) {
-  __shared__ deflate_lds S;
+  __shared__ typename lds_of<DYN>::type S;
   const uint32_t lane = threadIdx.x;
   for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
     const rows::deflate_conn_row dq = rows::load_deflate_conn(dconns + ci);
@@ -265,7 +594,7 @@ __global__ void __launch_bounds__(DFL_LANES)
     const uint64_t olo = dq.out & 15u;
 
     uint64_t opos = 0, in_len = 0, found = 0, kept = 0;  // out_len so far; deliverable records; view records stored
-    uint32_t st = 0, n_deflated = 0, n_stored = 0;
+    uint32_t st = 0, n_deflated = 0, n_stored = 0, n_dynamic = 0;
     for (uint32_t j = 0; j < stored; j++) {
       const xyws_message* const rp = rows::row_at<const xyws_message>(msgs, j);
       frame_info f;
@@ -279,12 +608,23 @@ __global__ void __launch_bounds__(DFL_LANES)
       const uint64_t blocks = (L + DFL_STORED_MAX - 1u) / DFL_STORED_MAX, stored_len = L + 5u * blocks + 1u;
       const bool single = L <= DFL_STAGE;
 
-      // the fixed form's bits: a record of one piece is emitted into LDS on the way
+      // the Huffman form's bits: a record of one piece is emitted into LDS on the
+      // way; under DYN every piece is planned (the shorter of its two blocks), a
+      // record of one piece keeps its plan for the emission
       uint64_t fbits = 0;
+      uint32_t hbits = 0, dynamic = 0;  // the last piece's dynamic header, 0: fixed; pieces that chose the dynamic block
       for (uint64_t q0 = 0; q0 < L; q0 += DFL_STAGE) {
         const uint32_t pn = L - q0 < DFL_STAGE ? (uint32_t)(L - q0) : DFL_STAGE;
         stage_piece(S.in, head, hl, msg, q0, pn, lane);
-        fbits += fixed_block(S, pn, single, 0, 0, lane);
+        if constexpr (DYN) {
+          const uint32_t fb = huff_block<true>(S, pn, false, 0, 0, 0, lane);
+          uint32_t db;
+          hbits = plan_piece(S, fb, db, lane);
+          fbits += hbits ? db : fb;
+          dynamic += hbits != 0u;
+        } else {
+          fbits += huff_block<false>(S, pn, single, 0, 0, 0, lane);
+        }
       }
       const uint64_t fixed_len = (fbits + 3u + 7u) >> 3;  // behind it the empty stored block: 3 bits, then to the byte
       const bool fixed = L && fixed_len < stored_len;
@@ -294,15 +634,23 @@ __global__ void __launch_bounds__(DFL_LANES)
 
       if (!fits) {
         st |= XYWS_DFL_TOO_LONG;
-      } else if (fixed && single) {
+      } else if (!DYN && fixed && single) {
         flush_stage(S.out, (uint32_t)clen, obase, D, lane);
       } else if (fixed) {
         uint64_t at = D;
         uint32_t carry = 0, bit0 = 0;
         for (uint64_t q0 = 0; q0 < L; q0 += DFL_STAGE) {
           const uint32_t pn = L - q0 < DFL_STAGE ? (uint32_t)(L - q0) : DFL_STAGE;
-          stage_piece(S.in, head, hl, msg, q0, pn, lane);
-          const uint32_t end = fixed_block(S, pn, true, carry, bit0, lane);
+          if constexpr (DYN) {
+            if (!single) {  // the piece's plan again: the codes of the one before it are gone
+              stage_piece(S.in, head, hl, msg, q0, pn, lane);
+              uint32_t db;
+              hbits = plan_piece(S, huff_block<true>(S, pn, false, 0, 0, 0, lane), db, lane);
+            }
+          } else {
+            stage_piece(S.in, head, hl, msg, q0, pn, lane);
+          }
+          const uint32_t end = huff_block<DYN>(S, pn, true, hbits, carry, bit0, lane);
           const bool last = q0 + pn == L;
           const uint32_t nb = last ? (end + 3u + 7u) >> 3 : end >> 3;
           flush_stage(S.out, nb, obase, at, lane);
@@ -328,7 +676,7 @@ __global__ void __launch_bounds__(DFL_LANES)
       }
       if (fits) {
         in_len += L;
-        if (fixed) n_deflated++;
+        if (fixed) n_deflated++, n_dynamic += dynamic != 0u;
         else n_stored++;
       }
       if (lane == 0)
@@ -346,9 +694,22 @@ __global__ void __launch_bounds__(DFL_LANES)
       rows::store_reasm_conn(view + ci, {dq.out, dq.out_cap, mc, dq.vmsgs, dq.vmsg_cap});
       const uint32_t rst = (opos > dq.out_cap ? XYWS_RSM_TRUNCATED : 0u) | (found > kept ? XYWS_RSM_MSG_CAP : 0u);
       rows::store_reasm_result(vres + ci, {opos, found, {(uint32_t)kept, rst}, 0});
-      if (results) rows::store_deflate_result(results + ci, opos, in_len, {n_deflated, n_stored}, st);
+      if (results) {
+        if constexpr (DYN) rows::store_deflate_result_dynamic(results + ci, opos, in_len, {n_deflated, n_stored}, st, n_dynamic);
+        else rows::store_deflate_result(results + ci, opos, in_len, {n_deflated, n_stored}, st);
+      }
     }
   }
+}
+
+// xyws_debug_deflate_code_lengths: one wave, build_code over the caller's frequencies.
+__global__ void __launch_bounds__(DFL_LANES)
+    k_code_lengths(const uint32_t* __restrict__ freq, uint32_t nsym, uint32_t limit, uint8_t* __restrict__ lens) {
+  __shared__ uint32_t ws[DFL_SLOTS], fc[DFL_LITLEN];
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t s = lane; s < nsym; s += DFL_LANES) fc[s] = freq[s];
+  build_code(ws, fc, nsym, limit, lane);
+  for (uint32_t s = lane; s < nsym; s += DFL_LANES) lens[s] = (uint8_t)fc[s];
 }
 
 }  // namespace
@@ -362,14 +723,34 @@ int xyws_deflate_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm, const 
   if (!ctx || (n && (!dev_reasm || !dev_reasm_results || !dev_bconns || !dev_dconns || !dev_view || !dev_view_results ||
                      !dev_view_bconns)))
     return XYWS_ERR_INVALID;
-  if (opts || n >= UINT32_MAX) return XYWS_ERR_INVALID;
+  if ((opts & ~XYWS_DFO_DYNAMIC) || n >= UINT32_MAX) return XYWS_ERR_INVALID;
   if (!n) return XYWS_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
   device_guard g(ctx->device);
   if (!g.ok) return XYWS_ERR_HIP;
   const uint32_t grid = grid_for(n, 1, DFL_GRID_CAP);
-  hipLaunchKernelGGL(k_deflate_streams, dim3(grid), dim3(DFL_LANES), 0, (hipStream_t)stream, dev_reasm, dev_reasm_results,
-                     dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results);
+  if (opts & XYWS_DFO_DYNAMIC)
+    hipLaunchKernelGGL(k_deflate_streams<true>, dim3(grid), dim3(DFL_LANES), 0, (hipStream_t)stream, dev_reasm, dev_reasm_results,
+                       dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results);
+  else
+    hipLaunchKernelGGL(k_deflate_streams<false>, dim3(grid), dim3(DFL_LANES), 0, (hipStream_t)stream, dev_reasm, dev_reasm_results,
+                       dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results);
+  return hip_err(hipGetLastError());
+}
+
+// Internal (tests and measurements): build_code, the device function the
+// dynamic blocks' codes come from, by one wave over the frequencies
+// dev_freq[0, nsym) (each below 2^22, no more than 2^limit of them non-zero);
+// dev_lens[s] is symbol s's code length. The host cannot see the frequencies:
+// outside those two conditions the call still returns XYWS_OK and writes
+// nothing out of bounds, but the lengths are undefined and may be no code.
+int xyws_debug_deflate_code_lengths(xyws_ctx* ctx, const uint32_t* dev_freq, uint32_t nsym, uint32_t limit, uint8_t* dev_lens,
+                                    void* stream) {
+  if (!ctx || !dev_freq || !dev_lens || !nsym || nsym > DFL_LITLEN || !limit || limit > 15u) return XYWS_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  device_guard g(ctx->device);
+  if (!g.ok) return XYWS_ERR_HIP;
+  hipLaunchKernelGGL(k_code_lengths, dim3(1), dim3(DFL_LANES), 0, (hipStream_t)stream, dev_freq, nsym, limit, dev_lens);
   return hip_err(hipGetLastError());
 }
 
@@ -381,7 +762,7 @@ int xyws_debug_deflate_geometry(uint64_t out[4]) {
   out[1] = DFL_SLOTS;
   out[2] = DFL_GRID_CAP;
   out[3] = DFL_LANES;
-  static_assert(sizeof(deflate_lds) * (DFL_GRID_CAP / 256u) <= 160u * 1024u, "six waves' LDS per CU");
+  static_assert(sizeof(deflate_lds_dynamic) * (DFL_GRID_CAP / 256u) <= 160u * 1024u, "six waves' LDS per CU");
   return XYWS_OK;
 }
 

@@ -1112,6 +1112,14 @@ XYWS_DEV void store_deflate_result(xyws_deflate_result* p, uint64_t out_len, uin
   XYWS_ST(xyws_deflate_result, p, n_deflated, pack_deflate_counts(c));
   XYWS_ST(xyws_deflate_result, p, status, status);
 }
+// Under XYWS_DFO_DYNAMIC: the same row, reserved0 the records with at least one dynamic block.
+XYWS_DEV void store_deflate_result_dynamic(xyws_deflate_result* p, uint64_t out_len, uint64_t in_len, deflate_counts c,
+                                           uint32_t status, uint32_t n_dynamic) {
+  XYWS_ST(xyws_deflate_result, p, out_len, out_len);
+  XYWS_ST(xyws_deflate_result, p, in_len, in_len);
+  XYWS_ST(xyws_deflate_result, p, n_deflated, pack_deflate_counts(c));
+  XYWS_ST(xyws_deflate_result, p, status, XYWS_PUT(xyws_deflate_result, status, status) | XYWS_PUT(xyws_deflate_result, reserved0, n_dynamic));
+}
 // The broadcast row at src without its head, one word per lane.
 XYWS_DEV void copy_bcast_conn_headless(xyws_bcast_conn* dst, const xyws_bcast_conn* src, uint32_t lane) {
   if (lane < sizeof(xyws_bcast_conn) / 8)

@@ -624,8 +624,8 @@ class GroupDeflate:
     out ranges, view rows, result rows and, after the broadcast, the
     compressed wires (zwire)."""
 
-    def __init__(self, group, messages, negotiated, tensors, out_cap):
-        self.group, self.decoded, self.messages_in = group, messages.decoded, messages
+    def __init__(self, group, messages, negotiated, tensors, out_cap, dynamic=False):
+        self.group, self.decoded, self.messages_in, self.dynamic = group, messages.decoded, messages, bool(dynamic)
         self.negotiated, self._tensors, self.out_cap, self.msg_cap = negotiated, tensors, out_cap, messages.msg_cap
         m = len(self.decoded.ids)
         self.outs = [tensors["out"][out_cap * k:out_cap * (k + 1)] for k in range(m)]
@@ -1301,14 +1301,16 @@ class connection_group:
                    slot=dec.slot)
         return GroupInflate(self, src, tensors, out_cap, [i not in agreed for i in dec.ids])
 
-    def deflate(self, messages_or_hold_or_inflate, negotiated, out_cap):
+    def deflate(self, messages_or_hold_or_inflate, negotiated, out_cap, dynamic=False):
         """Compress the sweep's outbound messages once per message
         (xyws_deflate_streams, one launch) for the members that negotiated
         permessage-deflate: `messages_or_hold_or_inflate` is what broadcast()
         is given, negotiated the connection ids that are sent the compressed
         wire, out_cap the bytes each item gets for its compressed messages
         (a message of L bytes with its head needs at most
-        L + 5 * ceil(L / 65535) + 1). Returns a GroupDeflate for
+        L + 5 * ceil(L / 65535) + 1). dynamic: a piece of a message may go out
+        as a dynamic-Huffman block where that is shorter (XYWS_DFO_DYNAMIC;
+        result(k).n_dynamic counts the messages with one). Returns a GroupDeflate for
         broadcast(..., deflated=...), which issues the launch: the call reads
         the heads, reply rows and rooms that broadcast() lays out."""
         src = messages_or_hold_or_inflate
@@ -1330,7 +1332,7 @@ class connection_group:
             row.vmsg_cap = src.msg_cap
             row.flags = _lib.DFC_NEGOTIATED if i in agreed else 0
         tensors["dconns"] = dtab.upload(dev)
-        return GroupDeflate(self, src, agreed, tensors, out_cap)
+        return GroupDeflate(self, src, agreed, tensors, out_cap, dynamic)
 
     def _broadcast_deflated(self, messages, deflated, tensors, wires, m, nr, flags, enc_opts, slot):
         """broadcast(..., deflated=...): xyws_deflate_streams, then
@@ -1351,7 +1353,8 @@ class connection_group:
             cols[:, _lib.Room.wire_cap.offset // 8] = torch.tensor([w.numel() for w in zwires], dtype=torch.int64).to(dev)
         d.update(zrooms=zrooms, zroom_results=_lib.alloc_rows(_lib.RoomResult, nr, dev), bcast=tensors)
         deflated._zwires, deflated._zrows = zwires, _Rows(_lib.RoomResult, d["zroom_results"], nr)
-        self._call("xyws_deflate_streams", *messages.tables(), tensors["bconns"], d["dconns"], m, 0, d["view"],
+        self._call("xyws_deflate_streams", *messages.tables(), tensors["bconns"], d["dconns"], m,
+                   _lib.DFO_DYNAMIC if deflated.dynamic else 0, d["view"],
                    d["view_results"], d["view_bconns"], d["results"], slot=slot)
         self._call("xyws_broadcast_deflated_streams", *messages.tables(), tensors["bconns"], m, tensors["rooms"],
                    tensors["room_results"], nr, flags, enc_opts, tensors["results"], d["view"], d["view_results"],
