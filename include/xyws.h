@@ -1061,8 +1061,9 @@ int xyws_hold_streams(xyws_ctx* ctx,
  * every table is connection i. This call leaves what the server sends alone
  * (xyws_deflate_streams, below, compresses the broadcast; RFC 7692 6 lets an
  * endpoint send uncompressed messages once the extension is agreed). Limits:
- * no context takeover in either direction; client_max_window_bits is not
- * narrowed (the window is always 32 KiB).
+ * no context takeover in this call (xyws_inflate_windows_streams, below, keeps
+ * the client's); client_max_window_bits is not narrowed (the window is always
+ * 32 KiB).
  *
  * Per connection, with s = min(nmsgs, msg_cap) of the input row (0 for a null
  * msgs) and the carry ic:
@@ -1146,13 +1147,16 @@ int xyws_hold_streams(xyws_ctx* ctx,
  * twice in a call; vmsgs must not be the input's msgs. */
 #define XYWS_INF_UTF8         0x1u /* opts: validate inflated text messages */
 #define XYWS_INFC_NEGOTIATED  0x1u /* xyws_inflate_conn.flags: permessage-deflate was agreed for this connection */
+#define XYWS_INFC_TAKEOVER    0x2u /* xyws_inflate_conn.flags: the client keeps its context (xyws_inflate_windows_streams only) */
 #define XYWS_INFK_HDR0        0x1u /* xyws_inflate_carry.flags: hdr0 is byte 0 of the header the last recv boundary cut */
 #define XYWS_INFK_COMPRESSED  0x2u /* xyws_inflate_carry.flags: the message open at the end of the last sweep is compressed */
 typedef struct xyws_inflate_carry {  /* 32 bytes; all zero = fresh */
   uint32_t flags;      /* XYWS_INFK_* */
   uint8_t  hdr0;
   uint8_t  reserved0[3];
-  uint64_t reserved[3]; /* zero */
+  uint32_t win_len;    /* xyws_inflate_windows_streams: the valid bytes of history in the connection's window, 0..32768 */
+  uint32_t win_pos;    /* where in the window the history ends: its last byte is window[(win_pos - 1) % 32768] */
+  uint64_t reserved[2]; /* zero */
 } xyws_inflate_carry;
 
 typedef struct xyws_inflate_conn {   /* 64 bytes; entry i goes with dev_in[i] */
@@ -1163,7 +1167,8 @@ typedef struct xyws_inflate_conn {   /* 64 bytes; entry i goes with dev_in[i] */
   xyws_inflate_carry* ic;       /* device; read, then written. NULL: pass-through */
   uint32_t            flags;    /* XYWS_INFC_* */
   uint32_t            reserved0;
-  uint64_t            reserved[2]; /* zero */
+  void*               window;   /* device, 16-byte aligned: 32768 bytes the connection owns for its lifetime (XYWS_INFC_TAKEOVER) */
+  uint64_t            reserved; /* zero */
 } xyws_inflate_conn;
 
 typedef struct xyws_inflate_result { /* 32 bytes */
@@ -1171,7 +1176,7 @@ typedef struct xyws_inflate_result { /* 32 bytes */
   uint32_t n_inflated; /* records inflated whole */
   uint32_t n_bad;      /* records with bad data */
   uint32_t status;     /* XYWS_INF_* */
-  uint32_t reserved0;
+  uint32_t n_history;  /* xyws_inflate_windows_streams: records inflated whole in which a match reached in front of the record's first byte */
   uint64_t reserved;
 } xyws_inflate_result;
 #define XYWS_INF_PASSTHROUGH 0x1u
@@ -1185,6 +1190,57 @@ int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
                          const xyws_inflate_conn* dev_iconns, uint64_t n, uint32_t opts,
                          xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
                          xyws_inflate_result* dev_results /* n, nullable */, void* stream);
+
+/* ---- the same call with client context takeover: a window per connection ----
+ * With XYWS_ACC_DEFLATE_TAKEOVER beside XYWS_ACC_DEFLATE the handshake leaves
+ * client_no_context_takeover out of its answer unless the client offered it,
+ * and the accept row has XYWS_ACC_TAKEOVER: the client keeps its LZ77 window
+ * from message to message, as every WebSocket stack does by default, and a
+ * message may point back into what the same client sent before.
+ * xyws_inflate_windows_streams is xyws_inflate_streams (same arguments, same
+ * rules 1 to 5, same refusals) and is the only call that reads
+ * xyws_inflate_conn.window and XYWS_INFC_TAKEOVER; xyws_inflate_streams
+ * ignores both, leaves `window` alone and writes win_len and win_pos as zero.
+ * A row takes over when it has XYWS_INFC_TAKEOVER and XYWS_INFC_NEGOTIATED, a
+ * non-null ic and a non-null, 16-byte-aligned window; any other row is treated
+ * exactly as by xyws_inflate_streams, its window never touched.
+ *
+ * For a row that takes over:
+ *  - The history is the inflated bytes of all its earlier compressed messages:
+ *    the records that were inflated whole, in record order, across calls, cut
+ *    to the last 32768 bytes. The carry's win_len counts them; they lie in
+ *    `window` as a ring that ends in front of win_pos. A fresh carry (all zero)
+ *    has no history.
+ *  - A record that is not compressed passes through as in rule 3 and leaves the
+ *    history alone, and so does a compressed record that is not inflatable.
+ *  - An inflatable compressed record is inflated with the history as its
+ *    window: a distance may reach up to win_len bytes in front of the record's
+ *    first byte (exactly 32768 when the history has that much); further back is
+ *    bad data (rule 4). A block with BFINAL ends the message as in rule 3 and
+ *    does not clear the history (RFC 7692 7.2.3.4). UTF-8 is judged on the
+ *    message alone: the bytes in front of its first byte count as zero.
+ *  - After a record is inflated whole the history is the history followed by
+ *    the record's bytes; n_history counts the records in which a match reached
+ *    in front of the record's first byte. Several records of one connection in
+ *    one call chain on the device, and `window`, win_len and win_pos are
+ *    written before the call ends: only the bytes this call added (all 32768
+ *    once it added that many); a call that inflated nothing writes no byte of
+ *    the window.
+ *  - Bad data, or a record cut by the cap (XYWS_INF_TOO_LONG), ends the
+ *    connection's context: win_len is 0 afterwards, the connection's later
+ *    records in that call are inflated from an empty window as a row without
+ *    XYWS_INFC_TAKEOVER would be, and the caller closes the connection.
+ *  - Nothing outside [window, window + 32768) is read or written through
+ *    `window`.
+ * Like xyws_inflate_streams the call is one launch, can be captured at once,
+ * reads no device state on the host and needs no reserve. The send side keeps
+ * server_no_context_takeover; client_max_window_bits is not narrowed. */
+int xyws_inflate_windows_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
+                                 const xyws_reasm_conn* dev_in, const xyws_reasm_result* dev_in_results,
+                                 const xyws_hold_result* dev_hold_results /* n, nullable */,
+                                 const xyws_inflate_conn* dev_iconns, uint64_t n, uint32_t opts,
+                                 xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
+                                 xyws_inflate_result* dev_results /* n, nullable */, void* stream);
 
 /* ---- many connections, one deflate call -------------------------------------
  * permessage-deflate on the send side. The handshake agreed to
@@ -1264,7 +1320,7 @@ int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
  *     vmsgs must not be the input's msgs.
  *
  * Not built: splitting a piece into several blocks, lazy matching; context
- * takeover; server_max_window_bits; skipping rooms that have no negotiated member;
+ * takeover on the send side; server_max_window_bits; skipping rooms that have no negotiated member;
  * compressing the roster's notices and the backlog, which stay RSV1 = 0 frames
  * behind the compressed wire (RFC 7692 allows that per message). */
 #define XYWS_DFO_DYNAMIC 0x2u /* opts: a piece may go out as a dynamic-Huffman block where that is shorter */
@@ -1567,7 +1623,15 @@ int xyws_backlog_streams(xyws_ctx* ctx,
  *     client_no_context_takeover` (102 bytes, 231 in all) before its blank
  *     line and status gains XYWS_ACC_DEFLATED; what the client sends is then
  *     inflated by xyws_inflate_streams. With no such offer the 101 is the
- *     129 bytes above. No other response changes. The result row is the
+ *     129 bytes above. With XYWS_ACC_DEFLATE_TAKEOVER beside
+ *     XYWS_ACC_DEFLATE (alone it means nothing) the answer carries
+ *     client_no_context_takeover only when the offer that was taken has that
+ *     parameter; otherwise the line is `Sec-WebSocket-Extensions:
+ *     permessage-deflate; server_no_context_takeover` (74 bytes, 203 in all)
+ *     and status gains XYWS_ACC_TAKEOVER: the client may keep its context, and
+ *     what it sends is inflated by xyws_inflate_windows_streams with a window
+ *     for the connection. An offered client_max_window_bits is not answered:
+ *     the window stays 32 KiB. No other response changes. The result row is the
  *     only place that says whether the extension was agreed, so
  *     XYWS_ACC_DEFLATE with a null dev_results (a null res for
  *     xyws_accept_request) is XYWS_ERR_INVALID, whatever n.
@@ -1590,8 +1654,10 @@ int xyws_backlog_streams(xyws_ctx* ctx,
 #define XYWS_ACC_REJECTED   0x2u
 #define XYWS_ACC_TRUNCATED  0x4u /* resp_len > out_cap */
 #define XYWS_ACC_DEFLATED   0x8u /* the 101 agrees to permessage-deflate (policy XYWS_ACC_DEFLATE) */
+#define XYWS_ACC_TAKEOVER   0x10u /* the 101 leaves client_no_context_takeover out (policy XYWS_ACC_DEFLATE_TAKEOVER) */
 #define XYWS_ACC_REFERENCE  0x100u /* policy bit */
 #define XYWS_ACC_DEFLATE    0x200u /* policy bit: agree to an offer of permessage-deflate (below) */
+#define XYWS_ACC_DEFLATE_TAKEOVER 0x400u /* policy bit, with XYWS_ACC_DEFLATE: let the client keep its context between messages */
 #define XYWS_ACR_NONE        0
 #define XYWS_ACR_PARSE       1
 #define XYWS_ACR_TOO_LONG    2

@@ -222,26 +222,46 @@ assert C.sizeof(HoldCarry) == 32 and C.sizeof(HoldConn) == 32 and C.sizeof(HoldR
 HOLD_DELIVERED, HOLD_ACTIVE, HOLD_LOST, HOLD_DROPPED, HOLD_TOO_LONG, HOLD_PASSTHROUGH = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 
 
+class _Named:
+    """A field that include/xyws.h has since named inside bytes a row's _fields_ still list as reserved: read and
+    written by name like any other, with the offset and size a ctypes field has. (_fields_ stay as they were stated
+    first, so a table filled through the reserved names is the same bytes.)"""
+
+    def __init__(self, ctype, offset):
+        self.ctype, self.offset, self.size = ctype, offset, C.sizeof(ctype)
+
+    def __get__(self, row, owner=None):
+        return self if row is None else (self.ctype.from_buffer(row, self.offset).value or 0)
+
+    def __set__(self, row, value):
+        self.ctype.from_buffer(row, self.offset).value = value
+
+
 class InflateCarry(C.Structure):
-    """xyws_inflate_carry (include/xyws.h), 32 bytes: one connection's state between xyws_inflate_streams calls."""
+    """xyws_inflate_carry (include/xyws.h), 32 bytes: one connection's state between xyws_inflate_streams calls.
+    win_len, win_pos: the history xyws_inflate_windows_streams keeps in the connection's window (reserved[0])."""
     _fields_ = [("flags", C.c_uint32), ("hdr0", C.c_uint8), ("reserved0", C.c_uint8 * 3), ("reserved", C.c_uint64 * 3)]
+    win_len, win_pos = _Named(C.c_uint32, 8), _Named(C.c_uint32, 12)
 
 
 class InflateConn(C.Structure):
     """xyws_inflate_conn (include/xyws.h), 64 bytes: entry i goes with entry i of the xyws_reasm_conn table."""
     _fields_ = [("out", C.c_void_p), ("out_cap", C.c_uint64), ("vmsgs", C.c_void_p), ("vmsg_cap", C.c_uint64),
                 ("ic", C.c_void_p), ("flags", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+    window = _Named(C.c_void_p, 48)  # (reserved[0]) 32768 device bytes, 16-byte aligned: INFC_TAKEOVER
 
 
 class InflateResult(C.Structure):
     """xyws_inflate_result (include/xyws.h), 32 bytes."""
     _fields_ = [("out_len", C.c_uint64), ("n_inflated", C.c_uint32), ("n_bad", C.c_uint32), ("status", C.c_uint32),
                 ("reserved0", C.c_uint32), ("reserved", C.c_uint64)]
+    n_history = _Named(C.c_uint32, 20)  # (reserved0) records in which a match reached into the connection's history
 
 
 assert C.sizeof(InflateCarry) == 32 and C.sizeof(InflateConn) == 64 and C.sizeof(InflateResult) == 32
 INF_UTF8 = 0x1  # xyws_inflate_streams opts
-INFC_NEGOTIATED = 0x1  # xyws_inflate_conn.flags
+INFC_NEGOTIATED, INFC_TAKEOVER = 0x1, 0x2  # xyws_inflate_conn.flags (TAKEOVER: xyws_inflate_windows_streams only)
+INF_WINDOW = 32768  # bytes of a connection's window
 INFK_HDR0, INFK_COMPRESSED = 0x1, 0x2  # xyws_inflate_carry.flags
 INF_PASSTHROUGH, INF_BAD_DATA, INF_TOO_LONG, INF_UNKNOWN = 0x1, 0x2, 0x4, 0x8  # xyws_inflate_result.status
 
@@ -375,8 +395,8 @@ class AcceptResult(C.Structure):
 
 assert C.sizeof(AcceptConn) == 32 and C.sizeof(AcceptResult) == 32
 ACCEPT_MAX_REQUEST = 8192
-ACC_ACCEPTED, ACC_REJECTED, ACC_TRUNCATED, ACC_DEFLATED = 0x1, 0x2, 0x4, 0x8  # xyws_accept_result.status
-ACC_REFERENCE, ACC_DEFLATE = 0x100, 0x200  # xyws_accept_streams policy
+ACC_ACCEPTED, ACC_REJECTED, ACC_TRUNCATED, ACC_DEFLATED, ACC_TAKEOVER = 0x1, 0x2, 0x4, 0x8, 0x10  # xyws_accept_result.status
+ACC_REFERENCE, ACC_DEFLATE, ACC_DEFLATE_TAKEOVER = 0x100, 0x200, 0x400  # xyws_accept_streams policy
 ACCEPT_RESP_MAX = 231  # the longest response: the 101 that agrees to permessage-deflate
 (ACR_NONE, ACR_PARSE, ACR_TOO_LONG, ACR_METHOD, ACR_VERSION, ACR_FOLDED, ACR_HOST, ACR_UPGRADE, ACR_CONNECTION,
  ACR_KEY, ACR_WS_VERSION) = range(11)  # xyws_accept_result.reason
@@ -629,6 +649,8 @@ def load():
     L.xyws_debug_hold_geometry.argtypes = [C.POINTER(u64)]
     L.xyws_inflate_streams.restype = i32
     L.xyws_inflate_streams.argtypes = [vp, vp, vp, vp, vp, vp, u64, u32, vp, vp, vp, vp]
+    L.xyws_inflate_windows_streams.restype = i32
+    L.xyws_inflate_windows_streams.argtypes = L.xyws_inflate_streams.argtypes
     # (no HIP call: lanes per connection, ring bytes, LDS bytes per wave, grid cap)
     L.xyws_debug_inflate_geometry.restype = i32
     L.xyws_debug_inflate_geometry.argtypes = [C.POINTER(u64)]

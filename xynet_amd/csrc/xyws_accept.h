@@ -26,7 +26,9 @@ constexpr uint32_t RESP_101_EXT_LEN = 102;  // the extension line XYWS_ACC_DEFLA
 constexpr uint32_t RESP_MAX = 240;  // the longest 101 (129 + 102) up to a multiple of 16
 constexpr uint32_t MAX_HEADERS = 100;
 constexpr uint32_t NO_KEY = 0xFFFFFFFFu;
-constexpr uint32_t POLICY_BITS = XYWS_ACC_REFERENCE | XYWS_ACC_DEFLATE;
+constexpr uint32_t RESP_101_NCT_LEN = 28;   // "; client_no_context_takeover", which XYWS_ACC_DEFLATE_TAKEOVER may leave out of it
+constexpr uint32_t POLICY_BITS = XYWS_ACC_REFERENCE | XYWS_ACC_DEFLATE | XYWS_ACC_DEFLATE_TAKEOVER;
+constexpr uint32_t OFFER_OK = 0x10u, OFFER_CLIENT_NCT = 1u << 1;  // deflate_offer_ok: agreeable; parameter kind 1 seen
 
 // The refusals of both entry points that their common arguments decide.
 // XYWS_ACC_DEFLATE needs the result row: XYWS_ACC_DEFLATED there is the only
@@ -235,16 +237,17 @@ XYWS_HD bool is_window_bits(const R& b, uint32_t v0, uint32_t v1) {
 // `;`-separated parameters, each one of the four the RFC names, none twice;
 // the two _no_context_takeover ones without a value, server_max_window_bits
 // with a value in 8..15, client_max_window_bits with none or one in 8..15.
-// Names without regard to case.
+// Names without regard to case. Returns 0, or OFFER_OK with bit `kind` for
+// each parameter the offer has.
 template <class R>
-XYWS_HD bool deflate_offer_ok(const R& b, uint32_t x, uint32_t y) {
+XYWS_HD uint32_t deflate_offer_ok(const R& b, uint32_t x, uint32_t y) {
   uint32_t seen = 0;
   for (uint32_t part = 0;; part++) {
     const uint32_t e = next_sep(b, x, y, ';');
     uint32_t p0 = x, p1 = e;
     trim(b, p0, p1);
     if (part == 0) {
-      if (!span_is(b, p0, p1 - p0, XYWS_LIT("permessage-deflate"), true)) return false;
+      if (!span_is(b, p0, p1 - p0, XYWS_LIT("permessage-deflate"), true)) return 0;
     } else {
       const uint32_t q = next_sep(b, p0, p1, '=');
       uint32_t n0 = p0, n1 = q;
@@ -254,29 +257,31 @@ XYWS_HD bool deflate_offer_ok(const R& b, uint32_t x, uint32_t y) {
       uint32_t kind = 4;  // 0, 1: server / client _no_context_takeover; 2, 3: _max_window_bits
       if (side < 2 && span_is(b, n0 + 6, n1 - n0 - 6, XYWS_LIT("_no_context_takeover"), true)) kind = side;
       else if (side < 2 && span_is(b, n0 + 6, n1 - n0 - 6, XYWS_LIT("_max_window_bits"), true)) kind = 2 + side;
-      if (kind == 4 || (seen & (1u << kind))) return false;
+      if (kind == 4 || (seen & (1u << kind))) return 0;
       seen |= 1u << kind;
       const bool valued = q < p1;
       uint32_t v0 = valued ? q + 1 : p1, v1 = p1;
       trim(b, v0, v1);
-      if (kind < 2 ? valued : valued ? !is_window_bits(b, v0, v1) : kind == 2) return false;
+      if (kind < 2 ? valued : valued ? !is_window_bits(b, v0, v1) : kind == 2) return 0;
     }
-    if (e >= y) return true;
+    if (e >= y) return OFFER_OK | seen;
     x = e + 1;
   }
 }
 
-// Some comma-separated element of b[off, off + len) is such an offer (offers
-// of other extensions, and offers that cannot be agreed to, are passed over;
-// a comma or semicolon inside a quoted string separates nothing).
+// The first comma-separated element of b[off, off + len) that is such an offer,
+// as deflate_offer_ok returns it, or 0 (offers of other extensions, and offers
+// that cannot be agreed to, are passed over; a comma or semicolon inside a
+// quoted string separates nothing).
 template <class R>
-XYWS_HD bool has_deflate_offer(const R& b, uint32_t off, uint32_t len) {
+XYWS_HD uint32_t has_deflate_offer(const R& b, uint32_t off, uint32_t len) {
   uint32_t s = off;
   const uint32_t end = off + len;
   for (;;) {
     const uint32_t e = next_sep(b, s, end, ',');
-    if (deflate_offer_ok(b, s, e)) return true;
-    if (e >= end) return false;
+    const uint32_t offer = deflate_offer_ok(b, s, e);
+    if (offer) return offer;
+    if (e >= end) return 0;
     s = e + 1;
   }
 }
@@ -304,7 +309,7 @@ struct checks {
   uint32_t key_off = NO_KEY;
   uint32_t keys = 0, versions = 0;
   bool folded = false, host = false, upgrade = false, connection = false;
-  bool deflate = false;  // XYWS_ACC_DEFLATE: an offer of permessage-deflate that can be agreed to was seen
+  uint32_t deflate = 0;  // XYWS_ACC_DEFLATE: the first offer of permessage-deflate that can be agreed to (OFFER_*), or 0
 };
 
 template <class R>
@@ -537,7 +542,12 @@ XYWS_HD verdict evaluate(const R& b, uint32_t E, bool full, uint32_t policy, uin
                               "Sec-WebSocket-Accept: ",
                               RESP_101_KEY);
   accept_value(kw, resp + n);
-  if (k.deflate) {  // RFC 7692 7.1.1: both sides without context takeover, whether the client offered that or not
+  if (k.deflate && (policy & XYWS_ACC_DEFLATE_TAKEOVER) && !(k.deflate & OFFER_CLIENT_NCT)) {
+    // the client keeps its context: it did not ask to drop it, and the answer does not tell it to
+    v.status |= XYWS_ACC_DEFLATED | XYWS_ACC_TAKEOVER;
+    v.resp_len = put_text(resp, n + 28, "\r\nSec-WebSocket-Extensions: permessage-deflate; server_no_context_takeover\r\n\r\n",
+                          RESP_101_EXT_LEN - RESP_101_NCT_LEN + 4);
+  } else if (k.deflate) {  // RFC 7692 7.1.1: both sides without context takeover, whether the client offered that or not
     v.status |= XYWS_ACC_DEFLATED;
     v.resp_len = put_text(resp, n + 28,
                           "\r\nSec-WebSocket-Extensions: permessage-deflate; server_no_context_takeover; "

@@ -33,6 +33,16 @@
 //            start + k % distance when it repeats. Matches never leave LDS;
 //   UTF-8    each lane judges the line it writes out, with the three ring
 //            bytes in front of it (the rules of k_reasm_streams).
+//   window   xyws_inflate_windows_streams launches the second instantiation,
+//            k_inflate_streams<true>: a connection whose client keeps its
+//            context has its last 32 KiB of inflated bytes in a window in
+//            global memory, the ring's own image. The history is loaded into
+//            the ring before the connection's first compressed record, records
+//            go on where the history ends (so the ring keeps the history's
+//            phase, not the destination's, and write_out funnels each line out
+//            of six ring words), and what the call added is stored back at its
+//            end. <false> is the code it was: every difference is behind
+//            `if constexpr`;
 // LDS: 32 KiB ring + 2 KiB stage + 2.3 KiB of code lengths and symbols: four
 // waves per CU on gfx950's 160 KiB (one per SIMD); the grid cap is that.
 #include <hip/hip_runtime.h>
@@ -164,6 +174,7 @@ struct inflate_lds {
   uint16_t flsym[INF_NLIT], fdsym[INF_NDIST];  // the fixed block's
   uint16_t csym[32];
 };
+static_assert(4 * sizeof(inflate_lds) <= 160 * 1024, "four one-wave workgroups per CU, with or without a window");
 
 // Positions q count from the 16-byte-aligned address at or below the message's
 // first byte: the message is [lo, hi), the tail [hi, hi + 4), zeros follow.
@@ -203,22 +214,39 @@ XYWS_DEV uint64_t staged64(const uint8_t* s_in, uint32_t o) {
 // record's first destination byte (dbase): the record is [W0, ..), at most
 // [W0, wlim) is written. Writes out [wf, the last finished line), or with
 // `final` everything up to we; returns the new wf. utf8: judge the bytes
-// written; *bad is each lane's own.
+// written; *bad is each lane's own. With a window (T) the ring keeps the
+// history's own phase: position W lies at ring byte W + rd, any alignment, and
+// a line is funnelled out of the six ring words that hold it and the four bytes
+// in front of it (each word wraps on its own).
+template <bool T>
 XYWS_DEV uint64_t write_out(const uint8_t* s_win, g_u8* dbase, uint64_t W0, uint64_t wlim, uint64_t wf, uint64_t we,
-                            bool final, bool utf8, uint32_t lane, bool* bad) {
+                            bool final, bool utf8, uint32_t lane, bool* bad, uint32_t rd) {
   const uint64_t upto = final ? we : we & ~15ull;
   if (upto <= wf) return wf;
   const uint64_t wl = upto < wlim ? upto : wlim;
   for (uint64_t A0 = wf & ~15ull; A0 < wl; A0 += INF_STEP) {
     const uint64_t A = A0 + INF_LINE * lane;
     if (A >= wl) break;
-    const u32x4 x = *reinterpret_cast<const u32x4*>(s_win + ((uint32_t)A & RING));
+    u32x4 x;
+    uint32_t pw;  // the 4 ring bytes before the line
+    if constexpr (T) {
+      const uint32_t i = (uint32_t)A + rd - 4u, sh = i & 3u;
+      const uint32_t* const w = reinterpret_cast<const uint32_t*>(s_win);
+      uint32_t d[6];
+#pragma unroll
+      for (uint32_t k = 0; k < 6; k++) d[k] = w[((i >> 2) + k) & (INF_WINDOW / 4u - 1u)];
+      pw = __builtin_amdgcn_alignbyte(d[1], d[0], sh);
+      x = u32x4{__builtin_amdgcn_alignbyte(d[2], d[1], sh), __builtin_amdgcn_alignbyte(d[3], d[2], sh),
+                __builtin_amdgcn_alignbyte(d[4], d[3], sh), __builtin_amdgcn_alignbyte(d[5], d[4], sh)};
+    } else {
+      x = *reinterpret_cast<const u32x4*>(s_win + ((uint32_t)A & RING));
+    }
     bytes16 v = {(uint64_t)x.x | ((uint64_t)x.y << 32), (uint64_t)x.z | ((uint64_t)x.w << 32)};
     const uint64_t s = A > wf ? A : wf, e = A + 16 < upto ? A + 16 : upto;
     put_line(dbase, A, s, e, W0, wlim, v);
     if (!utf8) continue;
-    // the line and the 4 ring bytes before it, those in front of the record zero
-    uint32_t pw = *reinterpret_cast<const uint32_t*>(s_win + ((uint32_t)(A - 4) & RING));
+    // the line and the 4 ring bytes before it, those in front of the record zero (also where they are history)
+    if constexpr (!T) pw = *reinterpret_cast<const uint32_t*>(s_win + ((uint32_t)(A - 4) & RING));
     if (A < W0 + 4) {
       const uint32_t z = (uint32_t)(W0 + 4 - A);  // 1..19 bytes of the 20
       pw = z >= 4 ? 0u : pw & (0xFFFFFFFFu << (8u * z));
@@ -253,10 +281,13 @@ XYWS_DEV uint64_t write_out(const uint8_t* s_win, g_u8* dbase, uint64_t W0, uint
 
 // Inflates the len bytes at src (and the tail) to dbase + [W0, ..), at most
 // `room` bytes of them written. *length: the inflated length, room + 1 when it
-// does not fit, 0 when the data are bad. Wave-uniform throughout.
+// does not fit, 0 when the data are bad. Wave-uniform throughout. With a
+// window (T) the record's first byte lies at ring byte r0, behind `hist` bytes
+// of history that a distance may reach; *reached: one did.
+template <bool T>
 XYWS_DEV uint32_t inflate_message(inflate_lds& S, uint64_t src, uint64_t len, g_u8* dbase, uint64_t W0, uint64_t room,
                                   bool utf8, bool& have_fixed, code_table& fl, code_table& fd, uint32_t lane,
-                                  uint64_t* length) {
+                                  uint64_t* length, uint32_t r0, uint32_t hist, bool* reached) {
   const g_u8* const base = (const g_u8*)(src & ~15ull);
   const uint64_t lo = src & 15u, hi = lo + len;
   const uint64_t total = 8u * (len + 4u);  // bits of input (len < 2^60: it lies in device memory)
@@ -267,6 +298,10 @@ XYWS_DEV uint32_t inflate_message(inflate_lds& S, uint64_t src, uint64_t len, g_
   uint64_t op = 0, wf = W0;  // bytes inflated; written out up to
   uint32_t lit = 0, nlit = 0;  // a run of literals: literal k in lane k
   bool bad = false, lng = false, ubad = false;
+  const uint32_t rd = T ? r0 - (uint32_t)W0 : 0u;
+  auto ring_at = [&](uint32_t k) -> uint32_t {  // the ring byte of the record's byte op + k
+    return T ? (r0 + (uint32_t)op + k) & RING : (uint32_t)(W0 + op + k) & RING;
+  };
 
   stage_input(S.in, base, lo, hi, sq, lane);
   auto refill = [&]() {  // 56..63 bits
@@ -287,7 +322,7 @@ XYWS_DEV uint32_t inflate_message(inflate_lds& S, uint64_t src, uint64_t len, g_
   auto used = [&]() -> uint64_t { return 8u * (iq - lo) - nb; };
   auto put_lits = [&]() {
     if (nlit) {
-      if (lane < nlit) S.win[(uint32_t)(W0 + op + lane) & RING] = (uint8_t)lit;
+      if (lane < nlit) S.win[ring_at(lane)] = (uint8_t)lit;
       op += nlit;
       nlit = 0;
     }
@@ -296,7 +331,7 @@ XYWS_DEV uint32_t inflate_message(inflate_lds& S, uint64_t src, uint64_t len, g_
     if (op > room) lng = true;
     else if (W0 + op - wf >= INF_FLUSH) {
       __syncthreads();
-      wf = write_out(S.win, dbase, W0, wlim, wf, W0 + op, false, utf8, lane, &ubad);
+      wf = write_out<T>(S.win, dbase, W0, wlim, wf, W0 + op, false, utf8, lane, &ubad, rd);
     }
   };
 
@@ -327,7 +362,7 @@ XYWS_DEV uint32_t inflate_message(inflate_lds& S, uint64_t src, uint64_t len, g_
         const uint64_t have = sq + INF_STAGE - p;
         const uint32_t nn = left < have ? left : (uint32_t)have;
         __syncthreads();
-        for (uint32_t k = lane; k < nn; k += INF_LANES) S.win[(uint32_t)(W0 + op + k) & RING] = S.in[(uint32_t)(p - sq) + k];
+        for (uint32_t k = lane; k < nn; k += INF_LANES) S.win[ring_at(k)] = S.in[(uint32_t)(p - sq) + k];
         op += nn;
         p += nn;
         left -= nn;
@@ -479,12 +514,16 @@ XYWS_DEV uint32_t inflate_message(inflate_lds& S, uint64_t src, uint64_t len, g_
           dist = 1u + ((2u + (d & 1u)) << e) + take(e);
         }
         put_lits();
-        if (used() > total || dist > op) {  // input ended inside the block; a distance in front of the first byte
+        // input ended inside the block; a distance in front of the first byte (of the history's, with a window)
+        if (used() > total || (T ? dist > op + hist : dist > op)) {
           bad = true;
           break;
         }
+        if constexpr (T) {
+          if (dist > op) *reached = true;
+        }
         __syncthreads();
-        const uint32_t to = (uint32_t)(W0 + op), from = to - dist;
+        const uint32_t to = T ? r0 + (uint32_t)op : (uint32_t)(W0 + op), from = to - dist;
         for (uint32_t k = lane; k < mlen; k += INF_LANES)
           S.win[(to + k) & RING] = S.win[(from + (dist >= mlen ? k : k % dist)) & RING];
         __syncthreads();
@@ -503,7 +542,7 @@ XYWS_DEV uint32_t inflate_message(inflate_lds& S, uint64_t src, uint64_t len, g_
     return R_BAD;
   }
   __syncthreads();
-  wf = write_out(S.win, dbase, W0, wlim, wf, W0 + op, true, utf8 && !lng, lane, &ubad);
+  wf = write_out<T>(S.win, dbase, W0, wlim, wf, W0 + op, true, utf8 && !lng, lane, &ubad, rd);
   if (lng) {
     *length = room + 1;
     return R_LONG;
@@ -511,13 +550,58 @@ XYWS_DEV uint32_t inflate_message(inflate_lds& S, uint64_t src, uint64_t len, g_
   *length = op;
   bool u = __ballot(ubad) != 0;
   if (utf8 && op) {  // a sequence that runs past the message's last byte
-    const uint32_t e = (uint32_t)(W0 + op);
+    const uint32_t e = T ? r0 + (uint32_t)op : (uint32_t)(W0 + op);
     const uint32_t b0 = S.win[(e - 1) & RING], b1 = op > 1 ? S.win[(e - 2) & RING] : 0u, b2 = op > 2 ? S.win[(e - 3) & RING] : 0u;
     u = u || uniform32(lead_len(b0) > 1 || lead_len(b1) > 2 || lead_len(b2) > 3);
   }
   return u ? R_UTF8 : 0u;
 }
 
+// The window of a connection that keeps its client's context is the ring's own
+// image: window[i] is ring byte i, and the carry says where the history ends
+// (win_pos) and how long it is (win_len). Linear positions below count ring
+// bytes from one turn before win_pos, so the history is [e - win_len, e) with
+// e = win_pos + INF_WINDOW and nothing is negative.
+
+// The history's bytes from the window into the ring: whole 16-byte lines, the
+// bytes of the first and last line that are not history masked off. A history
+// within two lines of the full ring may begin and end in the same ring line:
+// then every line is taken whole (all of the window is the connection's).
+XYWS_DEV void restore_window(uint8_t* s_win, const g_u8* window, uint32_t win_len, uint32_t win_pos, uint32_t lane) {
+  const uint32_t e = win_pos + INF_WINDOW, b = e - win_len;
+  const bool masks = win_len <= INF_WINDOW - 2u * INF_LINE;
+  __syncthreads();
+  for (uint32_t A0 = b & ~15u; A0 < e; A0 += INF_STEP) {
+    const uint32_t A = A0 + INF_LINE * lane;
+    if (A >= e) break;
+    const uint32_t o = A & RING;  // (a multiple of 16, <= INF_WINDOW - 16)
+    bytes16 v = line_of(window + o);
+    if (masks) {
+      const uint32_t s = A < b ? b - A : 0u, n = (A + 16u > e ? e - A : 16u) - s;
+      v = shl_bytes(low_bytes(shr_bytes(v, s), n), s);
+    }
+    *reinterpret_cast<u32x4*>(s_win + o) = u32x4{(uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32)};
+  }
+  __syncthreads();
+}
+
+// The last `fresh` bytes of the history (what this call added, 1..INF_WINDOW)
+// from the ring to the window: whole lines, byte stores on the first and last.
+XYWS_DEV void save_window(const uint8_t* s_win, g_u8* window, uint32_t fresh, uint32_t win_pos, uint32_t lane) {
+  const uint32_t e = win_pos + INF_WINDOW, b = e - fresh;
+  __syncthreads();
+  for (uint32_t A0 = b & ~15u; A0 < e; A0 += INF_STEP) {
+    const uint32_t A = A0 + INF_LINE * lane;
+    if (A >= e) break;
+    const uint32_t o = A & RING;
+    const u32x4 x = *reinterpret_cast<const u32x4*>(s_win + o);
+    const bytes16 v = {(uint64_t)x.x | ((uint64_t)x.y << 32), (uint64_t)x.z | ((uint64_t)x.w << 32)};
+    const uint32_t s = A < b ? b - A : 0u, n = A + 16u > e ? e - A : 16u;
+    put_line(window, o, o + s, o + n, 0, INF_WINDOW, v);
+  }
+}
+
+template <bool T>
 __global__ void __launch_bounds__(INF_LANES)
     k_inflate_streams(const xyws_conn* __restrict__ conns, const xyws_reasm_conn* __restrict__ in,
                       const xyws_reasm_result* __restrict__ ires, const xyws_hold_result* __restrict__ hres,
@@ -551,6 +635,20 @@ __global__ void __launch_bounds__(INF_LANES)
     const uint64_t ccarry = rows::load_conn_carry(conns + ci);
     const rows::inflate_kept kept = rows::load_inflate_carry(ic);
     const bool delivered = hres && (rows::load_hold_status(hres + ci) & XYWS_HOLD_DELIVERED);
+    // the client's context: the history (in the window until a record needs it), what this call added to it
+    bool takeover = false, in_ring = false;
+    rows::inflate_history hist = {0, 0};
+    uint64_t window = 0;
+    uint32_t fresh = 0, n_history = 0;
+    if constexpr (T) {
+      window = rows::load_inflate_window(iconns + ci);
+      takeover = (iq.flags & XYWS_INFC_TAKEOVER) && window && !(window & 15u);
+      if (takeover) {
+        hist = rows::load_inflate_history(ic);
+        if (hist.win_len > INF_WINDOW) hist.win_len = 0;  // (no carry this call wrote)
+        hist.win_pos &= RING;
+      }
+    }
     const uint64_t nmsgs = ar.nmsgs, s = nmsgs < rq.msg_cap ? nmsgs : rq.msg_cap;
     const uint64_t vs = s < iq.vmsg_cap ? s : iq.vmsg_cap;
     const uint64_t out = iq.out, out_cap = iq.out_cap;
@@ -591,8 +689,28 @@ __global__ void __launch_bounds__(INF_LANES)
       uint64_t L = rec.length;
       if (comp && whole) {
         const bool text = m.opcode == XYWS_FLAG_OP_TEXT;
-        const uint32_t r = inflate_message(S, rq.out + rec.out_off, rec.length, (g_u8*)(D & ~15ull), D & 15u, room,
-                                           (opts & XYWS_INF_UTF8) && text, have_fixed, fl, fd, lane, &L);
+        bool reached = false;
+        if constexpr (T) {
+          if (takeover && !in_ring) {
+            if (hist.win_len) restore_window(S.win, (const g_u8*)window, hist.win_len, hist.win_pos, lane);
+            in_ring = true;
+          }
+        }
+        const uint32_t r = inflate_message<T>(S, rq.out + rec.out_off, rec.length, (g_u8*)(D & ~15ull), D & 15u, room,
+                                              (opts & XYWS_INF_UTF8) && text, have_fixed, fl, fd, lane, &L,
+                                              takeover ? hist.win_pos : (uint32_t)(D & 15u), takeover ? hist.win_len : 0u, &reached);
+        if constexpr (T) {
+          if (takeover && (r & (R_BAD | R_LONG))) {  // the context ends: the rest of the call goes without
+            takeover = false;
+            hist = {0, 0};
+            fresh = 0;
+          } else if (takeover) {  // (L <= room < 2^60)
+            hist.win_len = (uint32_t)(hist.win_len + L < INF_WINDOW ? hist.win_len + L : INF_WINDOW);
+            hist.win_pos = (hist.win_pos + (uint32_t)L) & RING;
+            fresh = (uint32_t)(fresh + L < INF_WINDOW ? fresh + L : INF_WINDOW);
+            if (reached) n_history++;
+          }
+        }
         ms &= ~(XYWS_MSG_UTF8_BAD | XYWS_MSG_UNCHECKED);
         if (r & R_BAD) {
           ms |= XYWS_MSG_TRUNCATED;
@@ -639,25 +757,28 @@ __global__ void __launch_bounds__(INF_LANES)
       }
     }
 
+    if constexpr (T) {
+      if (takeover && fresh) save_window(S.win, (g_u8*)window, fresh, hist.win_pos, lane);
+    }
     if (lane == 0) {
-      rows::store_inflate_carry(ic, {kf, hdr0});
+      rows::store_inflate_carry(ic, {kf, hdr0}, hist);
       rows::store_reasm_conn(vq, {out, out_cap, rq.mc, iq.vmsgs, rq.msg_cap < iq.vmsg_cap ? rq.msg_cap : iq.vmsg_cap});
       const uint32_t rst = (ar.counts.status & ~XYWS_RSM_UTF8_BAD) | (opos > out_cap ? XYWS_RSM_TRUNCATED : 0u) |
                            (s > iq.vmsg_cap ? XYWS_RSM_MSG_CAP : 0u) | (anybad ? XYWS_RSM_UTF8_BAD : 0u);
       rows::store_reasm_result(vr, {opos, nmsgs, {ar.counts.completed, rst}, ar.reserved});
-      if (res) rows::store_inflate_result(res, opos, {n_inflated, n_bad}, st);
+      if (res) rows::store_inflate_result(res, opos, {n_inflated, n_bad}, {st, n_history});
     }
   }
 }
 
 }  // namespace
 
-extern "C" {
-
-int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const xyws_reasm_conn* dev_in,
-                         const xyws_reasm_result* dev_in_results, const xyws_hold_result* dev_hold_results,
-                         const xyws_inflate_conn* dev_iconns, uint64_t n, uint32_t opts, xyws_reasm_conn* dev_view,
-                         xyws_reasm_result* dev_view_results, xyws_inflate_result* dev_results, void* stream) {
+// Both entry points: the refusals, then one launch of the instantiation asked for.
+template <bool T>
+static int inflate_call(xyws_ctx* ctx, const xyws_conn* dev_conns, const xyws_reasm_conn* dev_in,
+                        const xyws_reasm_result* dev_in_results, const xyws_hold_result* dev_hold_results,
+                        const xyws_inflate_conn* dev_iconns, uint64_t n, uint32_t opts, xyws_reasm_conn* dev_view,
+                        xyws_reasm_result* dev_view_results, xyws_inflate_result* dev_results, void* stream) {
   if (!ctx || (n && (!dev_conns || !dev_in || !dev_in_results || !dev_iconns || !dev_view || !dev_view_results)))
     return XYWS_ERR_INVALID;
   if ((opts & ~XYWS_INF_UTF8) || n >= UINT32_MAX) return XYWS_ERR_INVALID;
@@ -666,9 +787,27 @@ int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const xyws_r
   device_guard g(ctx->device);
   if (!g.ok) return XYWS_ERR_HIP;
   const uint32_t grid = grid_for(n, 1, INF_GRID_CAP);
-  hipLaunchKernelGGL(k_inflate_streams, dim3(grid), dim3(INF_LANES), 0, (hipStream_t)stream, dev_conns, dev_in,
+  hipLaunchKernelGGL(k_inflate_streams<T>, dim3(grid), dim3(INF_LANES), 0, (hipStream_t)stream, dev_conns, dev_in,
                      dev_in_results, dev_hold_results, dev_iconns, n, opts, dev_view, dev_view_results, dev_results);
   return hip_err(hipGetLastError());
+}
+
+extern "C" {
+
+int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const xyws_reasm_conn* dev_in,
+                         const xyws_reasm_result* dev_in_results, const xyws_hold_result* dev_hold_results,
+                         const xyws_inflate_conn* dev_iconns, uint64_t n, uint32_t opts, xyws_reasm_conn* dev_view,
+                         xyws_reasm_result* dev_view_results, xyws_inflate_result* dev_results, void* stream) {
+  return inflate_call<false>(ctx, dev_conns, dev_in, dev_in_results, dev_hold_results, dev_iconns, n, opts, dev_view,
+                             dev_view_results, dev_results, stream);
+}
+
+int xyws_inflate_windows_streams(xyws_ctx* ctx, const xyws_conn* dev_conns, const xyws_reasm_conn* dev_in,
+                                 const xyws_reasm_result* dev_in_results, const xyws_hold_result* dev_hold_results,
+                                 const xyws_inflate_conn* dev_iconns, uint64_t n, uint32_t opts, xyws_reasm_conn* dev_view,
+                                 xyws_reasm_result* dev_view_results, xyws_inflate_result* dev_results, void* stream) {
+  return inflate_call<true>(ctx, dev_conns, dev_in, dev_in_results, dev_hold_results, dev_iconns, n, opts, dev_view,
+                            dev_view_results, dev_results, stream);
 }
 
 // Internal (tests and measurements, no HIP call): the geometry of

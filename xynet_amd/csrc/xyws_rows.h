@@ -485,14 +485,20 @@ XYWS_HD void pack_inbox_summary(const inbox_summary_fields& s, uint64_t w[IBS_WO
 }
 
 // ---------------------------------------------------------------- the inflate's rows
-// The conn row is six words, flags in the sixth; the carry is one word of two
-// fields and three reserved ones; the result is a length and two words of two.
+// The conn row is six words, flags in the sixth, and the window's address; the
+// carry is one word of two fields, the history's word and two reserved ones;
+// the result is a length and two words of two.
 struct inflate_kept { uint32_t flags, hdr0; };          // xyws_inflate_carry
+struct inflate_history { uint32_t win_len, win_pos; };  // xyws_inflate_carry (all zero: none)
 struct inflate_counts { uint32_t n_inflated, n_bad; };  // xyws_inflate_result
+struct inflate_outcome { uint32_t status, n_history; };  // xyws_inflate_result
 XYWS_ONE_WORD(xyws_inflate_conn, flags, reserved0);
 XYWS_ONE_WORD(xyws_inflate_carry, flags, reserved0);
+XYWS_ONE_WORD(xyws_inflate_carry, win_len, win_pos);
 XYWS_ONE_WORD(xyws_inflate_result, n_inflated, n_bad);
-XYWS_ONE_WORD(xyws_inflate_result, status, reserved0);
+XYWS_ONE_WORD(xyws_inflate_result, status, n_history);
+static_assert(XYWS_WORD(xyws_inflate_carry, win_len) + 1 == XYWS_WORD(xyws_inflate_carry, reserved),
+              "xyws_inflate_carry: the history's word, then the reserved ones");
 static_assert(sizeof(xyws_inflate_conn) == 8 * 8 && sizeof(xyws_inflate_carry) == 4 * 8 && sizeof(xyws_inflate_result) == 4 * 8,
               "the inflate's rows: whole words");
 XYWS_HD uint64_t pack_inflate_kept(inflate_kept k) {
@@ -500,6 +506,15 @@ XYWS_HD uint64_t pack_inflate_kept(inflate_kept k) {
 }
 XYWS_HD inflate_kept unpack_inflate_kept(uint64_t w) {
   return {XYWS_GET(xyws_inflate_carry, flags, w), XYWS_GET(xyws_inflate_carry, hdr0, w)};
+}
+XYWS_HD uint64_t pack_inflate_history(inflate_history h) {
+  return XYWS_PUT(xyws_inflate_carry, win_len, h.win_len) | XYWS_PUT(xyws_inflate_carry, win_pos, h.win_pos);
+}
+XYWS_HD inflate_history unpack_inflate_history(uint64_t w) {
+  return {XYWS_GET(xyws_inflate_carry, win_len, w), XYWS_GET(xyws_inflate_carry, win_pos, w)};
+}
+XYWS_HD uint64_t pack_inflate_outcome(inflate_outcome o) {
+  return XYWS_PUT(xyws_inflate_result, status, o.status) | XYWS_PUT(xyws_inflate_result, n_history, o.n_history);
 }
 XYWS_HD uint64_t pack_inflate_counts(inflate_counts c) {
   return XYWS_PUT(xyws_inflate_result, n_inflated, c.n_inflated) | XYWS_PUT(xyws_inflate_result, n_bad, c.n_bad);
@@ -1070,14 +1085,19 @@ XYWS_DEV inflate_conn_row load_inflate_conn(const xyws_inflate_conn* p) {
 XYWS_DEV inflate_kept load_inflate_carry(const xyws_inflate_carry* p) {
   return unpack_inflate_kept(XYWS_LD(true, xyws_inflate_carry, p, flags));
 }
-XYWS_DEV void store_inflate_carry(xyws_inflate_carry* p, inflate_kept k) {
+XYWS_DEV uint64_t load_inflate_window(const xyws_inflate_conn* p) { return XYWS_LD(true, xyws_inflate_conn, p, window); }
+XYWS_DEV inflate_history load_inflate_history(const xyws_inflate_carry* p) {
+  return unpack_inflate_history(XYWS_LD(true, xyws_inflate_carry, p, win_len));
+}
+XYWS_DEV void store_inflate_carry(xyws_inflate_carry* p, inflate_kept k, inflate_history h) {
   XYWS_ST(xyws_inflate_carry, p, flags, pack_inflate_kept(k));
+  XYWS_ST(xyws_inflate_carry, p, win_len, pack_inflate_history(h));
   for (size_t w = XYWS_WORD(xyws_inflate_carry, reserved); w < sizeof(xyws_inflate_carry) / 8; w++) ((g_u64*)p)[w] = 0;
 }
-XYWS_DEV void store_inflate_result(xyws_inflate_result* p, uint64_t out_len, inflate_counts c, uint32_t status) {
+XYWS_DEV void store_inflate_result(xyws_inflate_result* p, uint64_t out_len, inflate_counts c, inflate_outcome o) {
   XYWS_ST(xyws_inflate_result, p, out_len, out_len);
   XYWS_ST(xyws_inflate_result, p, n_inflated, pack_inflate_counts(c));
-  XYWS_ST(xyws_inflate_result, p, status, status);
+  XYWS_ST(xyws_inflate_result, p, status, pack_inflate_outcome(o));
   XYWS_ST(xyws_inflate_result, p, reserved, 0);
 }
 // The row {0, 0, 0, status}, one word per lane.

@@ -946,6 +946,7 @@ class connection_group:
         self.hcarry_t = _lib.alloc_rows(_lib.HoldCarry, n, dev)
         # inflate(): the inflate carries (its tables, out ranges and rows belong to the GroupInflate it returns)
         self.icarry_t = _lib.alloc_rows(_lib.InflateCarry, n, dev)
+        self._iwindows = {}  # inflate(takeover=...): connection id -> its 32 KiB window, made when first named, kept
         # backlog(): per room a log and a carry, made when the room is first seen and kept across sweeps
         self._blogs, self._bcarries = [], []
         # inbox(): the receive slab, the inbox carries and the resident tables, made by the first inbox() call
@@ -1260,7 +1261,7 @@ class connection_group:
         """Host copy of a connection's inflate carry (synchronizes)."""
         return self._carry_of(self.icarry_t, _lib.InflateCarry, conn_id)
 
-    def inflate(self, messages_or_hold, negotiated, out_cap, utf8=True):
+    def inflate(self, messages_or_hold, negotiated, out_cap, utf8=True, takeover=()):
         """Inflate the permessage-deflate messages of the sweep
         (xyws_inflate_streams, one launch), between reassemble() or hold() and
         broadcast(): `messages_or_hold` is the result of either, negotiated
@@ -1270,16 +1271,25 @@ class connection_group:
         that does not fit is truncated and the result has INF_TOO_LONG. With
         utf8 the inflated text messages are validated. Items of other
         connections pass through. The server keeps sending uncompressed
-        frames; no context is taken over between messages. The group owns the
-        inflate carries. Returns a GroupInflate, which broadcast() takes in
+        frames. `takeover`: the negotiated connection ids whose client keeps
+        its context between messages (accept() with ACC_DEFLATE |
+        ACC_DEFLATE_TAKEOVER: result(k).status has ACC_TAKEOVER); with any, the
+        call is xyws_inflate_windows_streams and each of them gets a 32 KiB
+        window that the group allocates once and keeps: a message may point
+        back into what the connection sent before, result(k).n_history counts
+        those that did, and after INF_BAD_DATA or INF_TOO_LONG the connection
+        is to be closed. No other connection's messages share context. The
+        group owns the inflate carries. Returns a GroupInflate, which broadcast() takes in
         place of `messages_or_hold`. Call it before the group's next decode(),
         reply() or reassemble()."""
         src = messages_or_hold
         if not isinstance(src, (GroupMessages, GroupHold)) or src.group is not self or src.decoded.resident:
             raise XywsError(-1, "inflate() takes the result of this group's reassemble() or hold()")
-        dec, out_cap, agreed = src.decoded, int(out_cap), {int(i) for i in negotiated}
+        dec, out_cap, agreed, keeps = src.decoded, int(out_cap), {int(i) for i in negotiated}, {int(i) for i in takeover}
         if out_cap < 0:
             raise ValueError("out_cap must not be negative")
+        if not keeps <= agreed:
+            raise ValueError("takeover names connections that are not in negotiated")
         import torch
         m, dev = len(dec.ids), self.device
         itab = _lib.Table(_lib.InflateConn, m)
@@ -1294,9 +1304,15 @@ class connection_group:
             row.vmsg_cap = src.msg_cap
             row.ic = _lib.row_ptr(self.icarry_t, _lib.InflateCarry, i)
             row.flags = _lib.INFC_NEGOTIATED if i in agreed else 0
+            if i in keeps:
+                if i not in self._iwindows:
+                    self._iwindows[i] = torch.empty(_lib.INF_WINDOW, dtype=torch.uint8, device=dev)
+                row.flags |= _lib.INFC_TAKEOVER
+                row.window = self._iwindows[i].data_ptr()
         tensors["iconns"] = itab.upload(dev)
         hold_rows = src._tensors["results"] if isinstance(src, GroupHold) else 0
-        self._call("xyws_inflate_streams", dec.conns_t, *src.tables(), hold_rows, tensors["iconns"], m,
+        self._call("xyws_inflate_windows_streams" if keeps else "xyws_inflate_streams", dec.conns_t, *src.tables(), hold_rows,
+                   tensors["iconns"], m,
                    _lib.INF_UTF8 if utf8 else 0, tensors["view"], tensors["view_results"], tensors["results"],
                    slot=dec.slot)
         return GroupInflate(self, src, tensors, out_cap, [i not in agreed for i in dec.ids])
