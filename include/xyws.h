@@ -1233,8 +1233,9 @@ int xyws_inflate_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
  *  - Nothing outside [window, window + 32768) is read or written through
  *    `window`.
  * Like xyws_inflate_streams the call is one launch, can be captured at once,
- * reads no device state on the host and needs no reserve. The send side keeps
- * server_no_context_takeover; client_max_window_bits is not narrowed. */
+ * reads no device state on the host and needs no reserve. The send side's
+ * context is xyws_deflate_windows_streams'; client_max_window_bits is not
+ * narrowed. */
 int xyws_inflate_windows_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
                                  const xyws_reasm_conn* dev_in, const xyws_reasm_result* dev_in_results,
                                  const xyws_hold_result* dev_hold_results /* n, nullable */,
@@ -1319,8 +1320,8 @@ int xyws_inflate_windows_streams(xyws_ctx* ctx, const xyws_conn* dev_conns,
  *     the inputs or the heads; a view row must not appear twice in a call;
  *     vmsgs must not be the input's msgs.
  *
- * Not built: splitting a piece into several blocks, lazy matching; context
- * takeover on the send side; server_max_window_bits; skipping rooms that have no negotiated member;
+ * Not built: splitting a piece into several blocks, lazy matching;
+ * server_max_window_bits; skipping rooms that have no negotiated member;
  * compressing the roster's notices and the backlog, which stay RSV1 = 0 frames
  * behind the compressed wire (RFC 7692 allows that per message). */
 #define XYWS_DFO_DYNAMIC 0x2u /* opts: a piece may go out as a dynamic-Huffman block where that is shorter */
@@ -1353,6 +1354,131 @@ int xyws_deflate_streams(xyws_ctx* ctx,
                          xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
                          xyws_bcast_conn* dev_view_bconns,
                          xyws_deflate_result* dev_results /* n, nullable */, void* stream);
+
+/* ---- xyws_deflate_streams with the server's context kept: one history per room
+ * A room has one compressed wire and every negotiated member inflates all of
+ * it, the speaker included (xyws_broadcast_streams 4.), so all of them hold the
+ * same window and one history per room serves them. This call is
+ * xyws_deflate_streams whose records may point back into what the room's z
+ * wire carried before them, in this sweep and in earlier ones. It is for
+ * members whose 101 left server_no_context_takeover out (xyws_accept_streams
+ * with XYWS_ACC_DEFLATE_SERVER_TAKEOVER: the row has XYWS_ACC_SERVER_TAKEOVER).
+ * dev_rooms is the broadcast's room table (members and n_members are read),
+ * dev_drooms[r] and dev_droom_results[r] go with dev_rooms[r].
+ *
+ *  1. Same contract. 1., 2., 4. to 7. and 9. to 12. of xyws_deflate_streams
+ *     hold unchanged: the deliverable records, the view, the caps, nothing
+ *     written outside a connection's own range.
+ *  2. Rooms that do not take over. A connection without a room, with a room
+ *     index >= n_rooms, or whose room has a null carry or a null text is
+ *     compressed exactly as xyws_deflate_streams (opts 0) compresses it, byte
+ *     for byte; so is one that dev_rooms[room].members does not list (every
+ *     connection of a takeover room is listed there once, and its bconns row
+ *     names that room: the fan-out assumes the same).
+ *  3. Room text. The text of a room is its members' deliverable records in the
+ *     wire order of xyws_broadcast_streams 3. (members[] order, each member's
+ *     records in record order; the same code computes it), each record
+ *     head_i | message, written from text + hist_len on.
+ *  4. Window. A record at text offset P is compressed with the bytes in front
+ *     of it as its window: what it emits inflates correctly in an inflater
+ *     that holds exactly the last 32768 bytes in front of P, and no distance
+ *     reaches in front of text. The kernel looks back at most its window
+ *     geometry (xyws_debug_deflate_windows_geometry: 8 KiB); the later pieces
+ *     of a long record see the piece before them. Blocks stay non-final and
+ *     fixed-Huffman, the record ends in the empty stored block without its
+ *     00 00 ff ff. Per piece the block is the shorter of the search with and
+ *     without the window (a tie goes to without), per record the stored form
+ *     is the fallback as in 8. of xyws_deflate_streams: a record is never
+ *     longer than xyws_deflate_streams makes it.
+ *  5. Reset. The room starts the call with an empty history when
+ *     dev_last_roster is given and dev_last_roster[r].joined != 0 (the previous
+ *     sweep's xyws_roster_streams rows), or when the carry is all zero. In the
+ *     first case hist_len is taken as 0 and the status gets XYWS_DFR_RESET;
+ *     the sweep's own records still chain on each other. This is what makes
+ *     one history right for every member: a joiner's inflater is empty when it
+ *     gets its first z wire, and nobody is ever pointed behind the newest join.
+ *  6. After the call the history is what it was (0 after a reset) plus the
+ *     sweep's text, cut to the last 32768 bytes and moved to text[0, hist_len);
+ *     hist_len and n_sweeps are updated on the device. A call in which the
+ *     room had no record and was not reset writes neither text nor the carry.
+ *  7. Caps. Text that does not fit in text_cap is not written: the first record
+ *     that does not fit and every record behind it are compressed without
+ *     history, as xyws_deflate_streams would; the room's history is empty after
+ *     the call and the status gets XYWS_DFR_TEXT_CAP. text_cap >= 32768 + the
+ *     sweep's text always suffices. A record of the text that the connection's
+ *     own caps leave out of the z wire (XYWS_DFL_TOO_LONG, XYWS_DFL_MSG_CAP)
+ *     has already entered the window of the records behind it; the call cannot
+ *     repair that: it sets XYWS_DFR_DESYNC on the room and empties the history
+ *     for the next sweep. The caller sizes out_cap and vmsg_cap by 10. of
+ *     xyws_deflate_streams so that this never happens, and closes the room's
+ *     negotiated members if it does (as after XYWS_INF_BAD_DATA on the receive
+ *     side): their inflaters no longer hold what the server assumed.
+ *     What the call cannot see is the caller's to watch in the same way: a
+ *     negotiated member's inflater also falls out of step when the member is
+ *     not sent a sweep's whole z wire, that is when the z room's wire_cap was
+ *     exceeded (XYWS_ROOM_TRUNCATED on its xyws_broadcast_deflated_streams
+ *     room row), when the member's own send range cut the wire
+ *     (XYWS_BC_TRUNCATED), or when the member stays in the room but is not a
+ *     receiver for a sweep (XYWS_BC_NOT_RECEIVER). The next sweep points into bytes that member never
+ *     inflated: close it (every negotiated member after a truncated z wire);
+ *     where it only missed whole sweeps, zeroing the room's carry before the
+ *     next call serves too, as the reset in 5. serves a joiner.
+ *  8. Who is XYWS_DFC_NEGOTIATED in a takeover room: only connections whose
+ *     accept row has XYWS_ACC_SERVER_TAKEOVER. A negotiated client that
+ *     insisted on server_no_context_takeover is sent the plain wire there
+ *     (RFC 7692 allows that per message). Notices and the backlog stay
+ *     RSV1 = 0 frames and touch nobody's context.
+ *  9. At most three launches on `stream`: the text build (one workgroup per
+ *     room), the compression (one wave per connection), the slide (one
+ *     workgroup per room). Between them dev_view_results[i] and the reserved
+ *     words of dev_droom_results[r] are the call's scratch. No host read of
+ *     device state, no reserve; capturable into a hipGraph at once.
+ *     XYWS_ERR_INVALID, on the arguments alone: what xyws_deflate_streams
+ *     refuses; any bit of opts (XYWS_DFO_DYNAMIC included); a null dev_rooms,
+ *     dev_drooms or dev_droom_results with n_rooms > 0; n_rooms >= UINT32_MAX.
+ *
+ * Not built: dynamic blocks over a history; a second z wire for the members
+ * of a takeover room that refuse server takeover; server_max_window_bits. */
+typedef struct xyws_deflate_room_carry { /* 32 bytes; all zero = no history */
+  uint64_t hist_len;   /* bytes of history in front of the text: text[0, hist_len), <= 32768 */
+  uint64_t n_sweeps;   /* calls that added to it since it was last empty */
+  uint32_t flags;      /* zero */
+  uint32_t reserved0;
+  uint64_t reserved;
+} xyws_deflate_room_carry;
+
+typedef struct xyws_deflate_room {        /* 32 bytes; entry r goes with dev_rooms[r] */
+  void*    text;       /* device, 16-byte aligned, nullable: the history, then this sweep's plaintext */
+  uint64_t text_cap;
+  xyws_deflate_room_carry* carry; /* device; nullable = the room takes nothing over */
+  uint64_t reserved;
+} xyws_deflate_room;
+
+typedef struct xyws_deflate_room_result { /* 32 bytes */
+  uint64_t text_len;   /* head | message bytes of the room's deliverable records this sweep (exact, whatever the cap) */
+  uint32_t n_records;  /* of them */
+  uint32_t n_history;  /* records in which a match reached in front of the record's first byte */
+  uint32_t status;     /* XYWS_DFR_* */
+  uint32_t reserved0;
+  uint64_t reserved;
+} xyws_deflate_room_result;
+#define XYWS_DFR_RESET    0x1u /* the room began the call with an empty history because a member joined */
+#define XYWS_DFR_TEXT_CAP 0x2u /* the sweep's text did not fit in text_cap */
+#define XYWS_DFR_DESYNC   0x4u /* a record of the text was left out of the z wire: close the negotiated members */
+#define XYWS_DFL_WINDOW 32768u /* bytes of history a room keeps */
+
+struct xyws_roster_room_result;
+int xyws_deflate_windows_streams(xyws_ctx* ctx,
+                                 const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                                 const xyws_bcast_conn* dev_bconns,
+                                 const xyws_deflate_conn* dev_dconns, uint64_t n,
+                                 const xyws_room* dev_rooms, const xyws_deflate_room* dev_drooms,
+                                 const struct xyws_roster_room_result* dev_last_roster /* n_rooms, nullable */,
+                                 uint64_t n_rooms, uint32_t opts /* 0 */,
+                                 xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
+                                 xyws_bcast_conn* dev_view_bconns,
+                                 xyws_deflate_result* dev_results /* n, nullable */,
+                                 xyws_deflate_room_result* dev_droom_results /* n_rooms */, void* stream);
 
 /* xyws_broadcast_streams with two wires per room: the plain one, and the one
  * of the compressed messages for the members that negotiated
@@ -1630,7 +1756,16 @@ int xyws_backlog_streams(xyws_ctx* ctx,
  *     permessage-deflate; server_no_context_takeover` (74 bytes, 203 in all)
  *     and status gains XYWS_ACC_TAKEOVER: the client may keep its context, and
  *     what it sends is inflated by xyws_inflate_windows_streams with a window
- *     for the connection. An offered client_max_window_bits is not answered:
+ *     for the connection. With XYWS_ACC_DEFLATE_SERVER_TAKEOVER beside
+ *     XYWS_ACC_DEFLATE (alone it means nothing) the answer carries
+ *     server_no_context_takeover only when the offer that was taken has that
+ *     parameter; otherwise it is left out and status gains
+ *     XYWS_ACC_SERVER_TAKEOVER: the server may keep its context, and the
+ *     room's wire may be compressed by xyws_deflate_windows_streams. The two
+ *     bits combine freely, so the line has four forms: with only
+ *     client_no_context_takeover it is again 74 bytes (203 in all), with
+ *     neither parameter it is `Sec-WebSocket-Extensions: permessage-deflate`
+ *     (46 bytes, 175 in all). An offered client_max_window_bits is not answered:
  *     the window stays 32 KiB. No other response changes. The result row is the
  *     only place that says whether the extension was agreed, so
  *     XYWS_ACC_DEFLATE with a null dev_results (a null res for
@@ -1655,9 +1790,11 @@ int xyws_backlog_streams(xyws_ctx* ctx,
 #define XYWS_ACC_TRUNCATED  0x4u /* resp_len > out_cap */
 #define XYWS_ACC_DEFLATED   0x8u /* the 101 agrees to permessage-deflate (policy XYWS_ACC_DEFLATE) */
 #define XYWS_ACC_TAKEOVER   0x10u /* the 101 leaves client_no_context_takeover out (policy XYWS_ACC_DEFLATE_TAKEOVER) */
+#define XYWS_ACC_SERVER_TAKEOVER 0x20u /* the 101 leaves server_no_context_takeover out (policy XYWS_ACC_DEFLATE_SERVER_TAKEOVER) */
 #define XYWS_ACC_REFERENCE  0x100u /* policy bit */
 #define XYWS_ACC_DEFLATE    0x200u /* policy bit: agree to an offer of permessage-deflate (below) */
 #define XYWS_ACC_DEFLATE_TAKEOVER 0x400u /* policy bit, with XYWS_ACC_DEFLATE: let the client keep its context between messages */
+#define XYWS_ACC_DEFLATE_SERVER_TAKEOVER 0x800u /* policy bit, with XYWS_ACC_DEFLATE: let the server keep its context (xyws_deflate_windows_streams) */
 #define XYWS_ACR_NONE        0
 #define XYWS_ACR_PARSE       1
 #define XYWS_ACR_TOO_LONG    2

@@ -384,6 +384,44 @@ inline void hold_streams(context& ctx, const xyws_reasm_conn* dev_reasm, const x
         "xyws_hold_streams");
 }
 
+// The sweep's outbound messages compressed once per message for the members
+// that negotiated permessage-deflate, in front of
+// xyws_broadcast_deflated_streams (xyws_deflate_streams): dev_dconns[i] names
+// connection i's out range and view record row; dev_view, dev_view_results and
+// dev_view_bconns (n entries each) are written for the compressed wire's build.
+inline void deflate_streams(context& ctx, const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                            const xyws_bcast_conn* dev_bconns, const xyws_deflate_conn* dev_dconns, std::uint64_t n,
+                            xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
+                            xyws_bcast_conn* dev_view_bconns, std::uint32_t opts = 0,
+                            xyws_deflate_result* dev_results = nullptr, void* stream = nullptr) {
+  check(xyws_deflate_streams(ctx.native(), dev_reasm, dev_reasm_results, dev_bconns, dev_dconns, n, opts, dev_view,
+                             dev_view_results, dev_view_bconns, dev_results, stream),
+        "xyws_deflate_streams");
+}
+
+// The same with the server's context kept (xyws_deflate_windows_streams, at
+// most three launches): dev_rooms is the broadcast's room table, dev_drooms[r]
+// names room r's text area and carry (null: the room takes nothing over), and
+// a room's records are compressed against what its wire carried before them,
+// in this sweep and in earlier ones. dev_last_roster (nullable, n_rooms rows):
+// the previous sweep's roster rows; a room that admitted a joiner starts from
+// an empty history. dev_droom_results (n_rooms entries) is required with
+// n_rooms > 0: XYWS_DFR_DESYNC there means the room's negotiated members are
+// to be closed.
+inline void deflate_windows_streams(context& ctx, const xyws_reasm_conn* dev_reasm,
+                                    const xyws_reasm_result* dev_reasm_results, const xyws_bcast_conn* dev_bconns,
+                                    const xyws_deflate_conn* dev_dconns, std::uint64_t n, const xyws_room* dev_rooms,
+                                    const xyws_deflate_room* dev_drooms, const xyws_roster_room_result* dev_last_roster,
+                                    std::uint64_t n_rooms, xyws_reasm_conn* dev_view,
+                                    xyws_reasm_result* dev_view_results, xyws_bcast_conn* dev_view_bconns,
+                                    xyws_deflate_room_result* dev_droom_results,
+                                    xyws_deflate_result* dev_results = nullptr, void* stream = nullptr) {
+  check(xyws_deflate_windows_streams(ctx.native(), dev_reasm, dev_reasm_results, dev_bconns, dev_dconns, n, dev_rooms,
+                                     dev_drooms, dev_last_roster, n_rooms, 0, dev_view, dev_view_results,
+                                     dev_view_bconns, dev_results, dev_droom_results, stream),
+        "xyws_deflate_windows_streams");
+}
+
 // The room's recent messages, after broadcast_streams of the same sweep, in at
 // most two launches (xyws_backlog_streams; the reference's m_recent_messages
 // and deliver_recent_messages): the first seven table arguments are the ones

@@ -26,7 +26,25 @@ with the bit next to the deflate call with opts = 0 on the same build,
 alternated; the ratio with the bit next to the same zlib columns; the share of
 messages that went out with a dynamic block.
 
-usage: deflate_rate.py [--out FILE] [--repeats R] [--dynamic]
+With --takeover the cells are measured once more for
+xyws_deflate_windows_streams and one row per cell ("option": "takeover") is
+appended: every room takes over and is reset in front of every call (the
+previous roster's `joined`), so a message's history is what the room's members
+in front of it said in the same sweep, up to 15 messages; the call (text build,
+compression, slide) next to xyws_deflate_streams on the same build and next to
+the same call over rooms with a null carry (the third instantiation's plain
+path), alternated; the ratio next to the same zlib columns; the records that
+reached into the history. The difference between the two windows calls is text
+build, priming, the second search per piece and the slide together. With
+--noprime-lib FILE, a libxyws.so built from the same sources with
+-DDFL_WIN_PRIME=0, the same call of that library is timed in the same
+alternation ("deflate_call_takeover_noprime": both searches run, nothing is
+entered into the table in front of the second), and "priming_net_share" is the
+part of the takeover call's median that this leaves out: the priming steps
+and what the search then does with the window's positions (longer chains of
+candidates, matches extended into the window).
+
+usage: deflate_rate.py [--out FILE] [--repeats R] [--dynamic | --takeover [--noprime-lib FILE]]
 """
 import argparse
 import ctypes as C
@@ -48,6 +66,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deflate_rate.jsonl"))
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--dynamic", action="store_true")
+ap.add_argument("--takeover", action="store_true")
+ap.add_argument("--noprime-lib")
 args = ap.parse_args()
 assert args.repeats >= 5, "the spread needs at least 5 repeats"
 assert torch.cuda.is_available(), "deflate_rate.py measures on the GPU: no device, no number"
@@ -55,6 +75,10 @@ assert torch.cuda.is_available(), "deflate_rate.py measures on the GPU: no devic
 ctx = ws.Context(0)
 L = ctx.L
 sp = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+NOPRIME = C.CDLL(os.path.abspath(args.noprime_lib)) if args.takeover and args.noprime_lib else None
+if NOPRIME:  # (the same sources: the context's layout is the same, so this library takes ctx.h)
+    NOPRIME.xyws_deflate_windows_streams.argtypes = L.xyws_deflate_windows_streams.argtypes
+    NOPRIME.xyws_deflate_windows_streams.restype = L.xyws_deflate_windows_streams.restype
 ROOM = 16
 WORDS = ("the quick brown fox jumps over a lazy dog while we talk about rooms messages sweeps and frames "
          "hello thanks ok sure see you later what time is it there today").split()
@@ -145,6 +169,27 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
     def deflate_call_dynamic():
         deflate_call(_lib.DFO_DYNAMIC)
 
+    # --takeover: a text area of 32 KiB + the room's sweep and a carry per room; roster rows that say "joined"
+    tcap = 32768 + wcap
+    texts, tcarries, drres = zeros(nr * tcap), zeros(32 * nr), zeros(32 * nr)
+    drtab, nulltab, joined = np.zeros((nr, 4), np.uint64), np.zeros((nr, 4), np.uint64), np.zeros((nr, 8), np.uint32)
+    drtab[:, 0], drtab[:, 1], drtab[:, 2] = texts.data_ptr() + tcap * ridx, tcap, tcarries.data_ptr() + 32 * ridx
+    joined[:, 4] = 1
+    drtab_t, nulltab_t, joined_t = dev(drtab), dev(nulltab), dev(joined)
+
+    def windows_call(drooms, lib=L):
+        _lib.check(lib.xyws_deflate_windows_streams(ctx.h, vp(mtab_t), vp(mres_t), vp(btab_t), vp(dtab_t), n, vp(rtab_t), vp(drooms),
+                                                  vp(joined_t), nr, 0, vp(view), vp(vres), vp(vbc), vp(dres), vp(drres), sp))
+
+    def deflate_call_takeover():
+        windows_call(drtab_t)
+
+    def deflate_call_windows_plain():
+        windows_call(nulltab_t)
+
+    def deflate_call_takeover_noprime():
+        windows_call(drtab_t, NOPRIME)
+
     def broadcast_plain():
         _lib.check(L.xyws_broadcast_streams(ctx.h, vp(mtab_t), vp(mres_t), vp(btab_t), n, vp(rtab_t), vp(rres), nr, 0x11, 0,
                                             vp(bres), sp))
@@ -166,7 +211,25 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
     plain_len = rres.cpu().numpy().view(np.uint64).reshape(n, 4)[:nr, 0]
     z_len = zres.cpu().numpy().view(np.uint64).reshape(n, 4)[:nr, 0]
     assert (bres.cpu().numpy().view(np.uint64).reshape(n, 4)[:, 1] == np.repeat(z_len, ROOM)).all()
+    if args.takeover:  # every message inflates against what its room said in front of it; the bytes are the takeover's
+        deflate_call_takeover()
+        torch.cuda.synchronize()
+        res = dres.cpu().numpy().view(np.uint64).reshape(n, 4)
+        got, kinds = zout.cpu().numpy().reshape(n, ocap), dres.cpu().numpy().view(np.uint32).reshape(n, 8)
+        for r in range(nr):
+            hist = b""
+            for i in range(ROOM * r, ROOM * (r + 1)):
+                d = zlib.decompressobj(-15, zdict=hist[-32768:]) if hist else zlib.decompressobj(-15)
+                assert d.decompress(got[i, :int(res[i, 0])].tobytes() + b"\x00\x00\xff\xff") == msgs[i], i
+                hist += msgs[i]
+        room_rows = drres.cpu().numpy().view(np.uint32).reshape(nr, 8)
+        assert not (room_rows[:, 4] & ~np.uint32(1)).any()  # (reset, neither cap nor desync)
     modes = {"deflate_call": deflate_call, "broadcast_plain": broadcast_plain, "broadcast_deflated": broadcast_deflated}
+    if args.takeover:
+        modes = {"deflate_call": deflate_call, "deflate_call_takeover": deflate_call_takeover,
+                 "deflate_call_windows_plain": deflate_call_windows_plain}
+        if NOPRIME:
+            modes["deflate_call_takeover_noprime"] = deflate_call_takeover_noprime
     if args.dynamic:
         modes = {"deflate_call": deflate_call, "deflate_call_dynamic": deflate_call_dynamic}
     for fn in modes.values():
@@ -194,11 +257,26 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
         row["n_deflated"] = row.pop("n_fixed")
         row.update(option="dynamic", n_dynamic=int(kinds[:, 7].sum()), dynamic_share=round(int(kinds[:, 7].sum()) / n, 3),
                    deflate_dynamic_MBps_in=round(total / row["deflate_call_dynamic"]["median_us"], 1))
+    if args.takeover:  # (compressed_bytes and ratio are the takeover's; the send bytes are left out: no wire was built)
+        one = zlib.compressobj(6, zlib.DEFLATED, -15)
+        chained = 0
+        for i, m in enumerate(msgs):  # zlib level 6 with its context kept through a room's sweep
+            if i % ROOM == 0:
+                one = zlib.compressobj(6, zlib.DEFLATED, -15)
+            chained += len(one.compress(m) + one.flush(zlib.Z_SYNC_FLUSH)) - 4
+        row["n_deflated"] = row.pop("n_fixed")
+        for k in ("send_bytes_per_member_plain", "send_bytes_per_member_deflated"):
+            row.pop(k)
+        row.update(option="takeover", n_history=int(room_rows[:, 3].sum()), ratio_zlib6_chained=round(chained / total, 3),
+                   takeover_MBps_in=round(total / row["deflate_call_takeover"]["median_us"], 1))
+        if NOPRIME:
+            took = row["deflate_call_takeover"]["median_us"]
+            row["priming_net_share"] = round((took - row["deflate_call_takeover_noprime"]["median_us"]) / took, 3)
     rows.append(row)
     print(json.dumps(row), flush=True)
 
 assert ctx.last_device_error() == 0
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "a" if args.dynamic else "w") as f:
+with open(args.out, "a" if args.dynamic or args.takeover else "w") as f:
     for row in rows:
         f.write(json.dumps(row) + "\n")

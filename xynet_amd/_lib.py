@@ -286,6 +286,28 @@ DFL_TOO_LONG, DFL_MSG_CAP = 0x1, 0x2  # xyws_deflate_result.status
 FLAG_RSV1 = 0x40  # refused by xyws_broadcast_deflated_streams, which sets it on the compressed wire itself
 
 
+class DeflateRoomCarry(C.Structure):
+    """xyws_deflate_room_carry (include/xyws.h), 32 bytes: one room's history between xyws_deflate_windows_streams calls."""
+    _fields_ = [("hist_len", C.c_uint64), ("n_sweeps", C.c_uint64), ("flags", C.c_uint32), ("reserved0", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+class DeflateRoom(C.Structure):
+    """xyws_deflate_room (include/xyws.h), 32 bytes: entry r goes with entry r of the xyws_room table."""
+    _fields_ = [("text", C.c_void_p), ("text_cap", C.c_uint64), ("carry", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+class DeflateRoomResult(C.Structure):
+    """xyws_deflate_room_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("text_len", C.c_uint64), ("n_records", C.c_uint32), ("n_history", C.c_uint32), ("status", C.c_uint32),
+                ("reserved0", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(DeflateRoomCarry) == 32 and C.sizeof(DeflateRoom) == 32 and C.sizeof(DeflateRoomResult) == 32
+DFR_RESET, DFR_TEXT_CAP, DFR_DESYNC = 0x1, 0x2, 0x4  # xyws_deflate_room_result.status
+DFL_WINDOW = 32768  # bytes of history a room keeps
+
+
 BACKLOG_MAX = 16
 
 
@@ -396,7 +418,9 @@ class AcceptResult(C.Structure):
 assert C.sizeof(AcceptConn) == 32 and C.sizeof(AcceptResult) == 32
 ACCEPT_MAX_REQUEST = 8192
 ACC_ACCEPTED, ACC_REJECTED, ACC_TRUNCATED, ACC_DEFLATED, ACC_TAKEOVER = 0x1, 0x2, 0x4, 0x8, 0x10  # xyws_accept_result.status
+ACC_SERVER_TAKEOVER = 0x20  # xyws_accept_result.status: the 101 leaves server_no_context_takeover out
 ACC_REFERENCE, ACC_DEFLATE, ACC_DEFLATE_TAKEOVER = 0x100, 0x200, 0x400  # xyws_accept_streams policy
+ACC_DEFLATE_SERVER_TAKEOVER = 0x800  # policy, with ACC_DEFLATE: the server may keep its context (deflate(takeover=...))
 ACCEPT_RESP_MAX = 231  # the longest response: the 101 that agrees to permessage-deflate
 (ACR_NONE, ACR_PARSE, ACR_TOO_LONG, ACR_METHOD, ACR_VERSION, ACR_FOLDED, ACR_HOST, ACR_UPGRADE, ACR_CONNECTION,
  ACR_KEY, ACR_WS_VERSION) = range(11)  # xyws_accept_result.reason
@@ -659,6 +683,11 @@ def load():
     # (no HIP call: stage bytes W, hash slots, grid cap, wave size)
     L.xyws_debug_deflate_geometry.restype = i32
     L.xyws_debug_deflate_geometry.argtypes = [C.POINTER(u64)]
+    L.xyws_deflate_windows_streams.restype = i32
+    L.xyws_deflate_windows_streams.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp]
+    # (no HIP call: stage bytes W, window bytes in front of a piece, hash slots, grid cap, wave size, history bytes)
+    L.xyws_debug_deflate_windows_geometry.restype = i32
+    L.xyws_debug_deflate_windows_geometry.argtypes = [C.POINTER(u64)]
     # (internal: build_code, the dynamic blocks' code builder, by one wave: freq u32[nsym] -> lens u8[nsym])
     L.xyws_debug_deflate_code_lengths.restype = i32
     L.xyws_debug_deflate_code_lengths.argtypes = [vp, vp, u32, u32, vp, vp]

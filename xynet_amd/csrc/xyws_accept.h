@@ -26,9 +26,13 @@ constexpr uint32_t RESP_101_EXT_LEN = 102;  // the extension line XYWS_ACC_DEFLA
 constexpr uint32_t RESP_MAX = 240;  // the longest 101 (129 + 102) up to a multiple of 16
 constexpr uint32_t MAX_HEADERS = 100;
 constexpr uint32_t NO_KEY = 0xFFFFFFFFu;
-constexpr uint32_t RESP_101_NCT_LEN = 28;   // "; client_no_context_takeover", which XYWS_ACC_DEFLATE_TAKEOVER may leave out of it
-constexpr uint32_t POLICY_BITS = XYWS_ACC_REFERENCE | XYWS_ACC_DEFLATE | XYWS_ACC_DEFLATE_TAKEOVER;
-constexpr uint32_t OFFER_OK = 0x10u, OFFER_CLIENT_NCT = 1u << 1;  // deflate_offer_ok: agreeable; parameter kind 1 seen
+// "; client_no_context_takeover" and "; server_no_context_takeover", which XYWS_ACC_DEFLATE_TAKEOVER and
+// XYWS_ACC_DEFLATE_SERVER_TAKEOVER may each leave out of it
+constexpr uint32_t RESP_101_NCT_LEN = 28;
+constexpr uint32_t POLICY_BITS =
+    XYWS_ACC_REFERENCE | XYWS_ACC_DEFLATE | XYWS_ACC_DEFLATE_TAKEOVER | XYWS_ACC_DEFLATE_SERVER_TAKEOVER;
+// deflate_offer_ok: agreeable; parameter kinds 0 and 1 seen
+constexpr uint32_t OFFER_OK = 0x10u, OFFER_SERVER_NCT = 1u << 0, OFFER_CLIENT_NCT = 1u << 1;
 
 // The refusals of both entry points that their common arguments decide.
 // XYWS_ACC_DEFLATE needs the result row: XYWS_ACC_DEFLATED there is the only
@@ -542,17 +546,16 @@ XYWS_HD verdict evaluate(const R& b, uint32_t E, bool full, uint32_t policy, uin
                               "Sec-WebSocket-Accept: ",
                               RESP_101_KEY);
   accept_value(kw, resp + n);
-  if (k.deflate && (policy & XYWS_ACC_DEFLATE_TAKEOVER) && !(k.deflate & OFFER_CLIENT_NCT)) {
-    // the client keeps its context: it did not ask to drop it, and the answer does not tell it to
-    v.status |= XYWS_ACC_DEFLATED | XYWS_ACC_TAKEOVER;
-    v.resp_len = put_text(resp, n + 28, "\r\nSec-WebSocket-Extensions: permessage-deflate; server_no_context_takeover\r\n\r\n",
-                          RESP_101_EXT_LEN - RESP_101_NCT_LEN + 4);
-  } else if (k.deflate) {  // RFC 7692 7.1.1: both sides without context takeover, whether the client offered that or not
-    v.status |= XYWS_ACC_DEFLATED;
-    v.resp_len = put_text(resp, n + 28,
-                          "\r\nSec-WebSocket-Extensions: permessage-deflate; server_no_context_takeover; "
-                          "client_no_context_takeover\r\n\r\n",
-                          RESP_101_EXT_LEN + 4);
+  if (k.deflate) {
+    // RFC 7692 7.1.1: a side drops its context unless the policy lets it keep it and the offer taken did not ask
+    // to drop it; the answer then leaves that side's parameter out
+    const bool client_keeps = (policy & XYWS_ACC_DEFLATE_TAKEOVER) && !(k.deflate & OFFER_CLIENT_NCT);
+    const bool server_keeps = (policy & XYWS_ACC_DEFLATE_SERVER_TAKEOVER) && !(k.deflate & OFFER_SERVER_NCT);
+    v.status |= XYWS_ACC_DEFLATED | (client_keeps ? XYWS_ACC_TAKEOVER : 0u) | (server_keeps ? XYWS_ACC_SERVER_TAKEOVER : 0u);
+    uint32_t e = put_text(resp, n + 28, "\r\nSec-WebSocket-Extensions: permessage-deflate", RESP_101_EXT_LEN - 2 * RESP_101_NCT_LEN);
+    if (!server_keeps) e = put_text(resp, e, "; server_no_context_takeover", RESP_101_NCT_LEN);
+    if (!client_keeps) e = put_text(resp, e, "; client_no_context_takeover", RESP_101_NCT_LEN);
+    v.resp_len = put_text(resp, e, "\r\n\r\n", 4);
   } else {
     v.resp_len = put_text(resp, n + 28, "\r\n\r\n", 4);
   }

@@ -50,6 +50,16 @@
 // bits down there. The packed table code << 8 | length overwrites the
 // histograms: 316 words, the only LDS the option adds. The emitting pass looks
 // a token's bits up there: up to 48 bits, ORed into up to three words.
+//
+// xyws_deflate_windows_streams keeps the server's context: one
+// history per room, since every negotiated member inflates the room's whole
+// wire. k_room_text lays the sweep's records behind the room's history in wire
+// order; k_deflate_streams<false, true> stages DFL_HIST bytes of that text in
+// front of every piece, enters the window's positions into the table before
+// the first search step and keeps, per piece, the shorter of the blocks
+// searched without and with the window; k_room_slide moves the last 32 KiB to
+// the front for the next sweep. LDS: 16 KiB window and piece + 8 KiB table +
+// 9 KiB output stage: four waves per CU.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
@@ -68,6 +78,16 @@
 #define DFL_HASH_BITS 11u
 #define DFL_OUT (DFL_STAGE + DFL_STAGE / 8u + 64u)  // the output stage: 9 bits a byte, the block's ends, a flush's read-ahead
 #define DFL_GRID_CAP 1536u                     // 256 CUs x 6 one-wave workgroups (LDS); further connections are grid-strided
+// xyws_deflate_windows_streams (k_deflate_streams<false, true>): the window in front of the piece
+#define DFL_HIST 8192u                         // bytes of window staged in front of a piece (<= 32768, the inflater's)
+#define DFL_WIN_GRID_CAP 1024u                 // 256 CUs x 4 one-wave workgroups (LDS)
+#define DFL_WIN_PIECES 64u                     // a record's pieces that may use the window (one choice bit each)
+#ifndef DFL_WIN_PRIME                          // 0: a measurement build (scripts/deflate_rate.py --noprime-lib) that leaves the
+#define DFL_WIN_PRIME 1                        // priming out: the second search then finds what the first found, and runs
+#endif                                         // into the window; what it emits still inflates
+#define DFL_TEXT_THREADS BC_WIRE_THREADS       // the text build: the wire build's workgroup, a member per thread
+#define DFL_SLIDE_THREADS 256u                 // the slide: 4 KiB a step
+#define DFL_WIN_TAG 0x5857494E444F5721ull      // ^ the room: marks the text offset the text build left a connection
 #define DFL_MIN_MATCH 4u
 #define DFL_MAX_MATCH 258u
 #define DFL_STORED_MAX 65535u
@@ -107,10 +127,20 @@ struct deflate_lds {
 struct deflate_lds_dynamic : deflate_lds {
   uint32_t code[DFL_LITLEN + DFL_DIST];
 };
-template <bool DYN>
+// With a window: the piece begins at byte DFL_HIST of `in`, the window ends there.
+struct deflate_lds_window {
+  __attribute__((aligned(16))) uint32_t in[(DFL_HIST + DFL_STAGE + 32u) / 4u];
+  __attribute__((aligned(16))) uint32_t tab[DFL_SLOTS];
+  __attribute__((aligned(16))) uint32_t out[DFL_OUT / 4u];
+};
+static_assert(DFL_HIST % 16u == 0 && DFL_HIST <= XYWS_DFL_WINDOW && DFL_HIST + DFL_STAGE <= XYWS_DFL_WINDOW,
+              "a distance is at most DFL_HIST + DFL_STAGE: inside the inflater's window, and syms_of covers it");
+template <bool DYN, bool WIN = false>
 struct lds_of { typedef deflate_lds type; };
 template <>
-struct lds_of<true> { typedef deflate_lds_dynamic type; };
+struct lds_of<true, false> { typedef deflate_lds_dynamic type; };
+template <>
+struct lds_of<false, true> { typedef deflate_lds_window type; };
 
 XYWS_DEV uint64_t below(uint32_t p) { return (1ull << p) - 1ull; }  // (p < 64)
 XYWS_DEV uint32_t lane_value(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
@@ -195,6 +225,24 @@ XYWS_DEV void stage_piece(uint32_t* s_in, uint64_t head, uint64_t hl, uint64_t m
     }
     *reinterpret_cast<u32x4*>(s_in + (o >> 2)) =
         u32x4{(uint32_t)acc.lo, (uint32_t)(acc.lo >> 32), (uint32_t)acc.hi, (uint32_t)(acc.hi >> 32)};
+  }
+  __syncthreads();
+}
+
+// A room's text bytes [T - H, T + n) to s_in[DFL_HIST - H, DFL_HIST + n): the
+// H (<= DFL_HIST, <= T) bytes of window in front of the piece, then the piece.
+// Whole LDS lines; the bytes of a line outside the range are zero, no text byte
+// outside the range is asked for. Wave-uniform arguments.
+XYWS_DEV void stage_text(uint32_t* s_in, uint64_t text, uint64_t T, uint32_t H, uint32_t n, uint32_t lane) {
+  __syncthreads();
+  const uint32_t lo = DFL_HIST - H, end = DFL_HIST + n;
+  const uint64_t src0 = text + T - DFL_HIST;  // the address LDS byte 0 would have (bytes below lo are never formed)
+  for (uint32_t A = (lo & ~15u) + 16u * lane; A < end; A += 16u * DFL_LANES) {
+    const uint32_t s = A > lo ? A : lo, e = A + 16u < end ? A + 16u : end;
+    bytes16 v = load_bytes(src0 + s, e - s);
+    if (s != A || e != A + 16u) v = shl_bytes(low_bytes(v, e - s), s - A);
+    *reinterpret_cast<u32x4*>(s_in + (A >> 2)) =
+        u32x4{(uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32)};
   }
   __syncthreads();
 }
@@ -440,10 +488,20 @@ XYWS_DEV uint32_t plan_piece(deflate_lds_dynamic& S, uint32_t fbits, uint32_t& d
 // the dynamic one that plan_piece prepared: its hbits header bits are copied
 // from the workspace (before the table is zeroed for the search) and a token's
 // bits are looked up in S.code; hbits == 0 emits the fixed block.
-template <bool DYN>
-XYWS_DEV uint32_t huff_block(typename lds_of<DYN>::type& S, uint32_t n, bool emit, uint32_t hbits, uint32_t carry,
-                             uint32_t bit0, uint32_t lane) {
+//
+// WIN (xyws_deflate_windows_streams). The piece lies at byte DFL_HIST of S.in
+// and the H bytes in front of it are its window. With prime the window's
+// positions enter the table before the first search step, 64 a step, inserts
+// only, so a match may begin there: distances reach H + n. Without prime the
+// search is the one above over the piece alone, token for token. *hist is set
+// when a match's source ends at or before S.in byte `front`, the record's first.
+template <bool DYN, bool WIN = false>
+XYWS_DEV uint32_t huff_block(typename lds_of<DYN, WIN>::type& S, uint32_t n, bool emit, uint32_t hbits, uint32_t carry,
+                             uint32_t bit0, uint32_t lane, uint32_t H = 0, bool prime = false, uint32_t front = 0,
+                             uint32_t* hist = nullptr) {
   const bool dyn = DYN && emit && hbits;
+  const uint32_t base = WIN ? DFL_HIST : 0u, end = base + n;  // the piece: S.in[base, end)
+  const uint32_t lo = WIN && prime ? base - H : base;          // the first byte a match may begin at
   const uint32_t lines = (n + n / 8u + 63u) / 16u + 1u;  // (9 n + 25 bits at most, a word of slack; <= DFL_OUT / 16)
   __syncthreads();
   if constexpr (DYN) {
@@ -464,20 +522,27 @@ XYWS_DEV uint32_t huff_block(typename lds_of<DYN>::type& S, uint32_t n, bool emi
       reinterpret_cast<u32x4*>(S.out)[k] = u32x4{k == 0 ? carry | (2u << bit0) : 0u, 0, 0, 0};  // BFINAL 0, BTYPE 01
   }
   __syncthreads();
+  if constexpr (WIN) {
+    if (prime && DFL_WIN_PRIME) {  // (a position's 4 bytes lie in front of `end`, as the search's do)
+      for (uint32_t q = lo + lane; q < base && q + DFL_MIN_MATCH <= end; q += DFL_LANES)
+        atomicMax(&S.tab[(rd32(S.in, q) * 2654435761u) >> (32u - DFL_HASH_BITS)], q + 1u);
+      __syncthreads();
+    }
+  }
   uint32_t bits = bit0 + (dyn ? hbits : 3u);
   for (uint32_t p0 = 0; p0 < n;) {
     // search: this lane's position
-    const uint32_t p = p0 + lane;
+    const uint32_t p = base + p0 + lane;
     uint32_t mlen = 0, dist = 0, word = 0, slot = 0;
-    const bool hashed = p + DFL_MIN_MATCH <= n;
-    if (p < n) word = rd32(S.in, p);
+    const bool hashed = p + DFL_MIN_MATCH <= end;
+    if (p < end) word = rd32(S.in, p);
     if (hashed) {
       slot = (word * 2654435761u) >> (32u - DFL_HASH_BITS);
       uint32_t c = S.tab[slot];                              // (a position of an earlier step: c - 1 < p0)
-      if (p && rd32(S.in, p - 1u) == word) c = p;            // a run: the byte before, distance 1
+      if (p > lo && rd32(S.in, p - 1u) == word) c = p;       // a run: the byte before, distance 1
       if (c) {
         c -= 1u;
-        const uint32_t maxl = n - p < DFL_MAX_MATCH ? n - p : DFL_MAX_MATCH;
+        const uint32_t maxl = end - p < DFL_MAX_MATCH ? end - p : DFL_MAX_MATCH;
         uint32_t l = 0;
         while (l < maxl) {
           const uint32_t x = rd32(S.in, p + l) ^ rd32(S.in, c + l);
@@ -506,6 +571,9 @@ XYWS_DEV uint32_t huff_block(typename lds_of<DYN>::type& S, uint32_t n, bool emi
       if (lane >= r && lane < l) kind = 1;
       if (lane == l) kind = 2;
       r = l + lane_value(mlen, l);
+    }
+    if constexpr (WIN) {
+      if (hist && __ballot(kind == 2u && p - dist + mlen <= front)) *hist = 1u;
     }
     // emission
     uint32_t tb = 0, tl = 0;
@@ -574,15 +642,42 @@ XYWS_DEV uint32_t huff_block(typename lds_of<DYN>::type& S, uint32_t n, bool emi
   return bits + 7u;  // end of block: seven zero bits
 }
 
-template <bool DYN>  // XYWS_DFO_DYNAMIC
+// WIN (xyws_deflate_windows_streams, after k_room_text): a connection whose
+// room takes over finds the text offset of its first record in its view result
+// row, marked with the room's tag. Its records up to the room's cut are staged
+// from the room's text with up to DFL_HIST bytes of window in front; each piece
+// is searched without the window and with it and takes the shorter block (the
+// choices of a record's first DFL_WIN_PIECES pieces are kept in a mask for the
+// emitting pass; later pieces go without). Every other record takes the path
+// of k_deflate_streams<false>, the piece at byte DFL_HIST of the stage.
+template <bool DYN, bool WIN = false>  // XYWS_DFO_DYNAMIC; xyws_deflate_windows_streams
 __global__ void __launch_bounds__(DFL_LANES)
     k_deflate_streams(const xyws_reasm_conn* __restrict__ reasm, const xyws_reasm_result* __restrict__ rres,
                       const xyws_bcast_conn* __restrict__ bconns, const xyws_deflate_conn* __restrict__ dconns, uint64_t n,
                       xyws_reasm_conn* __restrict__ view, xyws_reasm_result* __restrict__ vres,
-                      xyws_bcast_conn* __restrict__ vbconns, xyws_deflate_result* __restrict__ results) {
-  __shared__ typename lds_of<DYN>::type S;
+                      xyws_bcast_conn* __restrict__ vbconns, xyws_deflate_result* __restrict__ results,
+                      const xyws_deflate_room* __restrict__ drooms = nullptr, xyws_deflate_room_result* droom_results = nullptr,
+                      uint64_t n_rooms = 0) {
+  static_assert(!(DYN && WIN), "dynamic blocks over a history are not built");
+  __shared__ typename lds_of<DYN, WIN>::type S;
+  uint32_t* const s_piece = S.in + (WIN ? DFL_HIST / 4u : 0u);
   const uint32_t lane = threadIdx.x;
   for (uint64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
+    // WIN: the room's text, this connection's place in it, the room's cut and result row
+    uint64_t text = 0, tpos = 0, cut = 0;
+    xyws_deflate_room_result* rrow = nullptr;
+    bool desync = false;
+    if constexpr (WIN) {
+      const uint64_t room = uniform32(rows::load_bcast_room(bconns + ci));
+      if (room < n_rooms) {
+        const rows::deflate_room_row dr = rows::load_deflate_room(drooms + room);
+        const rows::reasm_result_row mark = rows::load_reasm_result<true>(vres + ci);
+        if (dr.text && dr.carry && mark.nmsgs == (DFL_WIN_TAG ^ room)) {
+          text = dr.text, tpos = mark.out_len, rrow = droom_results + room;
+          cut = rows::load_deflate_room_result(rrow).cut;
+        }
+      }
+    }
     const rows::deflate_conn_row dq = rows::load_deflate_conn(dconns + ci);
     const uint64_t mc = rows::load_reasm_conn<true>(reasm + ci).mc;
     member m;
@@ -599,8 +694,18 @@ __global__ void __launch_bounds__(DFL_LANES)
       const xyws_message* const rp = rows::row_at<const xyws_message>(msgs, j);
       frame_info f;
       if (!frame_of(rp, m, 0, 0, f)) continue;
+      bool inwin = false;  // WIN: the record lies in the room's text, at offset P
+      uint64_t P = 0;
+      if constexpr (WIN) {
+        if (text) {
+          const uint64_t Lt = hl + uniform64(f.len);
+          P = tpos, tpos += Lt;
+          inwin = P + Lt <= cut;
+        }
+      }
       if (found++ >= dq.vmsg_cap) {
         st |= XYWS_DFL_MSG_CAP;
+        desync |= inwin;
         continue;
       }
       const rows::message_row rec = rows::load_message<true>(rp);
@@ -613,9 +718,30 @@ __global__ void __launch_bounds__(DFL_LANES)
       // record of one piece keeps its plan for the emission
       uint64_t fbits = 0;
       uint32_t hbits = 0, dynamic = 0;  // the last piece's dynamic header, 0: fixed; pieces that chose the dynamic block
+      uint64_t wmask = 0;               // WIN: bit k: piece k goes out as the block searched with the window
+      uint32_t hist = 0;                // WIN: such a block has a match whose source lies in front of the record
+      bool staged = single;             // the stage holds the record's one block when the counting is done
       for (uint64_t q0 = 0; q0 < L; q0 += DFL_STAGE) {
         const uint32_t pn = L - q0 < DFL_STAGE ? (uint32_t)(L - q0) : DFL_STAGE;
-        stage_piece(S.in, head, hl, msg, q0, pn, lane);
+        if constexpr (WIN) {
+          if (inwin) {
+            const uint64_t T = P + q0, k = q0 / DFL_STAGE;
+            const uint32_t H = T < DFL_HIST ? (uint32_t)T : DFL_HIST;
+            stage_text(S.in, text, T, H, pn, lane);
+            if (H && k < DFL_WIN_PIECES) {
+              const uint32_t front = q0 < DFL_HIST ? DFL_HIST - (uint32_t)q0 : 0u;
+              uint32_t h = 0;
+              const uint32_t pb = huff_block<false, true>(S, pn, false, 0, 0, 0, lane);
+              const uint32_t wb = huff_block<false, true>(S, pn, single, 0, 0, 0, lane, H, true, front, &h);
+              if (wb < pb) wmask |= 1ull << k, hist |= h, fbits += wb;
+              else staged = false, fbits += pb;
+            } else {
+              fbits += huff_block<false, true>(S, pn, single, 0, 0, 0, lane);
+            }
+            continue;
+          }
+        }
+        stage_piece(s_piece, head, hl, msg, q0, pn, lane);
         if constexpr (DYN) {
           const uint32_t fb = huff_block<true>(S, pn, false, 0, 0, 0, lane);
           uint32_t db;
@@ -623,7 +749,7 @@ __global__ void __launch_bounds__(DFL_LANES)
           fbits += hbits ? db : fb;
           dynamic += hbits != 0u;
         } else {
-          fbits += huff_block<false>(S, pn, single, 0, 0, 0, lane);
+          fbits += huff_block<false, WIN>(S, pn, single, 0, 0, 0, lane);
         }
       }
       const uint64_t fixed_len = (fbits + 3u + 7u) >> 3;  // behind it the empty stored block: 3 bits, then to the byte
@@ -634,23 +760,32 @@ __global__ void __launch_bounds__(DFL_LANES)
 
       if (!fits) {
         st |= XYWS_DFL_TOO_LONG;
-      } else if (!DYN && fixed && single) {
+      } else if (!DYN && fixed && staged) {
         flush_stage(S.out, (uint32_t)clen, obase, D, lane);
       } else if (fixed) {
         uint64_t at = D;
         uint32_t carry = 0, bit0 = 0;
         for (uint64_t q0 = 0; q0 < L; q0 += DFL_STAGE) {
           const uint32_t pn = L - q0 < DFL_STAGE ? (uint32_t)(L - q0) : DFL_STAGE;
+          bool win = false;  // WIN: this piece's block is the one searched with its window of wh bytes
+          uint32_t wh = 0;
           if constexpr (DYN) {
             if (!single) {  // the piece's plan again: the codes of the one before it are gone
               stage_piece(S.in, head, hl, msg, q0, pn, lane);
               uint32_t db;
               hbits = plan_piece(S, huff_block<true>(S, pn, false, 0, 0, 0, lane), db, lane);
             }
+          } else if (WIN && inwin) {
+            if constexpr (WIN) {
+              const uint64_t T = P + q0, k = q0 / DFL_STAGE;
+              const uint32_t H = T < DFL_HIST ? (uint32_t)T : DFL_HIST;
+              if (!single) stage_text(S.in, text, T, H, pn, lane);  // (a record of one piece is staged still)
+              win = k < DFL_WIN_PIECES && ((wmask >> k) & 1u), wh = H;
+            }
           } else {
-            stage_piece(S.in, head, hl, msg, q0, pn, lane);
+            stage_piece(s_piece, head, hl, msg, q0, pn, lane);
           }
-          const uint32_t end = huff_block<DYN>(S, pn, true, hbits, carry, bit0, lane);
+          const uint32_t end = huff_block<DYN, WIN>(S, pn, true, hbits, carry, bit0, lane, wh, win);
           const bool last = q0 + pn == L;
           const uint32_t nb = last ? (end + 3u + 7u) >> 3 : end >> 3;
           flush_stage(S.out, nb, obase, at, lane);
@@ -667,8 +802,11 @@ __global__ void __launch_bounds__(DFL_LANES)
           at += 5u;
           for (uint32_t q = 0; q < bl; q += DFL_STAGE) {
             const uint32_t pn = bl - q < DFL_STAGE ? bl - q : DFL_STAGE;
-            if (!single) stage_piece(S.in, head, hl, msg, b0 + q, pn, lane);
-            flush_stage(S.in, pn, obase, at, lane);
+            if (!single) {
+              if (WIN && inwin) stage_text(S.in, text, P + b0 + q, 0, pn, lane);
+              else stage_piece(s_piece, head, hl, msg, b0 + q, pn, lane);
+            }
+            flush_stage(s_piece, pn, obase, at, lane);
             at += pn;
           }
         }
@@ -678,6 +816,10 @@ __global__ void __launch_bounds__(DFL_LANES)
         in_len += L;
         if (fixed) n_deflated++, n_dynamic += dynamic != 0u;
         else n_stored++;
+      }
+      if constexpr (WIN) {
+        desync |= inwin && !fits;
+        if (inwin && fits && fixed && hist && lane == 0) rows::count_deflate_room_history(rrow);
       }
       if (lane == 0)
         rows::store_message(rows::row_at<xyws_message>(dq.vmsgs, kept),
@@ -690,6 +832,9 @@ __global__ void __launch_bounds__(DFL_LANES)
     }
 
     rows::copy_bcast_conn_headless(vbconns + ci, bconns + ci, lane);
+    if constexpr (WIN) {
+      if (desync && lane == 0) rows::raise_deflate_room_status(rrow, XYWS_DFR_DESYNC);
+    }
     if (lane == 0) {
       rows::store_reasm_conn(view + ci, {dq.out, dq.out_cap, mc, dq.vmsgs, dq.vmsg_cap});
       const uint32_t rst = (opos > dq.out_cap ? XYWS_RSM_TRUNCATED : 0u) | (found > kept ? XYWS_RSM_MSG_CAP : 0u);
@@ -698,6 +843,201 @@ __global__ void __launch_bounds__(DFL_LANES)
         if constexpr (DYN) rows::store_deflate_result_dynamic(results + ci, opos, in_len, {n_deflated, n_stored}, st, n_dynamic);
         else rows::store_deflate_result(results + ci, opos, in_len, {n_deflated, n_stored}, st);
       }
+    }
+  }
+}
+
+// xyws_deflate_windows_streams, first launch: a room's text. One workgroup per
+// room, the members in tiles of one per thread, as k_room_wire walks them
+// (load_member and frame_of decide what is deliverable; a record contributes
+// head | message, no frame header):
+//   1. the thread sizes its member's records; a workgroup scan places the
+//      member in the text, behind the history the room begins the call with;
+//   2. the member whose range crosses text_cap walks its records once more for
+//      the first one that does not fit: the smallest such offset is the room's
+//      cut (an LDS atomic min), nothing at or behind it is written;
+//   3. each member's view result row gets the text offset of its first record
+//      and the room's tag, which the compression reads;
+//   4. the tile's bytes go to the text in 16-byte lines (xyws_lines.h), as the
+//      wire build composes them.
+// The room's result row carries the history's length and the cut on to the
+// other two launches. A room without text or carry gets a zero row.
+__global__ void __launch_bounds__(DFL_TEXT_THREADS)
+    k_room_text(const xyws_reasm_conn* __restrict__ reasm, const xyws_reasm_result* __restrict__ rres,
+                const xyws_bcast_conn* __restrict__ bconns, uint64_t n, const xyws_room* __restrict__ rooms,
+                const xyws_deflate_room* __restrict__ drooms, const xyws_roster_room_result* __restrict__ last_roster,
+                uint64_t n_rooms, xyws_reasm_result* __restrict__ vres, xyws_deflate_room_result* __restrict__ droom_results) {
+  constexpr uint32_t TILE = DFL_TEXT_THREADS;
+  __shared__ uint64_t s_off[TILE + 1];
+  __shared__ uint64_t s_msgs[TILE], s_gate[TILE], s_out[TILE], s_ocap[TILE], s_head[TILE], s_hlen[TILE];
+  __shared__ uint32_t s_stored[TILE];
+  __shared__ uint64_t s_w[TILE / BC_WAVE];
+  __shared__ unsigned long long s_cut;
+  const uint32_t tid = threadIdx.x;
+  for (uint64_t ri = blockIdx.x; ri < n_rooms; ri += gridDim.x) {
+    const rows::room_row rq = rows::load_room(rooms + ri);
+    const rows::deflate_room_row dr = rows::load_deflate_room(drooms + ri);
+    if (!dr.text || !dr.carry) {
+      if (tid == 0) rows::store_deflate_room_result(droom_results + ri, {0, {0, 0}, {0, 0}, 0});
+      continue;
+    }
+    g_u8* const tbase = (g_u8*)(dr.text & ~15ull);
+    const uint64_t tlo = dr.text & 15u;
+    uint64_t h0 = rows::load_deflate_room_carry((const xyws_deflate_room_carry*)dr.carry).hist_len;
+    if (h0 > XYWS_DFL_WINDOW) h0 = XYWS_DFL_WINDOW;
+    if (h0 > dr.text_cap) h0 = dr.text_cap;
+    uint32_t st = 0;
+    if (last_roster && rows::load_roster_joined(last_roster + ri)) h0 = 0, st = XYWS_DFR_RESET;
+    if (tid == 0) s_cut = XYWS_NPOS;
+    __syncthreads();
+
+    uint64_t wpos = h0;  // the text so far, from `text` (uniform)
+    uint32_t c_recs = 0;
+    for (uint64_t base = 0; base < rq.n_members; base += TILE) {
+      // 1. this thread's member: one of this room's, by its own row too
+      member m = {0, 0, 0, 0, 0, 0, 0};
+      uint64_t size = 0, ci = n;
+      if (base + tid < rq.n_members) {
+        ci = ((const XYWS_GLOBAL uint32_t*)rq.members)[base + tid];
+        if (ci < n && rows::load_bcast_room(bconns + ci) == ri) {
+          bool receiver, over_cap;
+          load_member(reasm, rres, bconns, ci, m, receiver, over_cap);
+#pragma unroll 1
+          for (uint32_t r = 0; r < m.stored; r++) {
+            frame_info f;
+            if (frame_of(rows::row_at<const xyws_message>(m.msgs, r), m, 0, 0, f)) size += m.head_len + f.len, c_recs++;
+          }
+        } else {
+          ci = n;
+        }
+      }
+      uint64_t total;
+      const uint64_t incl = block_scan(size, tid, s_w, total);
+      const uint64_t o0 = wpos, o1 = wpos + total, mine = o0 + (incl - size);
+      // 2. the cut
+      if (ci < n && mine + size > dr.text_cap) {
+        uint64_t at = mine;
+#pragma unroll 1
+        for (uint32_t r = 0; r < m.stored; r++) {
+          frame_info f;
+          if (!frame_of(rows::row_at<const xyws_message>(m.msgs, r), m, 0, 0, f)) continue;
+          if (at + m.head_len + f.len > dr.text_cap) break;
+          at += m.head_len + f.len;
+        }
+        atomicMin(&s_cut, (unsigned long long)at);
+      }
+      // 3. the member's place, for the compression
+      if (ci < n) rows::store_reasm_result(vres + ci, {mine, DFL_WIN_TAG ^ ri, {0, 0}, 0});
+      s_off[tid] = mine;
+      s_msgs[tid] = m.msgs;
+      s_gate[tid] = m.gate;
+      s_out[tid] = m.out;
+      s_ocap[tid] = m.out_cap;
+      s_head[tid] = m.head;
+      s_hlen[tid] = m.head_len;
+      s_stored[tid] = size ? m.stored : 0u;
+      if (tid == 0) s_off[TILE] = o1;
+      __syncthreads();
+
+      // 4. the tile's bytes [o0, min(o1, cut))
+      const uint64_t cut = s_cut, oe = o1 < cut ? o1 : cut;
+      const uint64_t P0 = tlo + o0, P1 = tlo + oe;
+      if (oe > o0) {
+        for (uint64_t A = ((P0 >> 4) + tid) << 4; A < P1; A += (uint64_t)BC_LINE * TILE) {
+          const uint64_t s = A > P0 ? A : P0, e = A + 16 < P1 ? A + 16 : P1;
+          uint64_t q = s - tlo;
+          uint32_t i = item_at(s_off, TILE, q);
+          bytes16 acc = {0, 0};
+          uint32_t a = (uint32_t)(s - A);
+          const uint32_t ae = (uint32_t)(e - A);
+          while (a < ae && i < TILE) {
+            member k;
+            k.msgs = s_msgs[i];
+            k.gate = s_gate[i];
+            k.out = s_out[i];
+            k.out_cap = s_ocap[i];
+            k.head = s_head[i];
+            k.head_len = s_hlen[i];
+            k.stored = s_stored[i];
+            uint64_t fo = s_off[i];  // the start of the record under test
+#pragma unroll 1
+            for (uint32_t r = 0; r < k.stored && a < ae; r++) {
+              frame_info f;
+              if (!frame_of(rows::row_at<const xyws_message>(k.msgs, r), k, 0, 0, f)) continue;
+              const uint64_t rsz = k.head_len + f.len;
+              if (fo + rsz > q) {
+                uint64_t rr = q - fo;
+                if (rr < k.head_len) {  // head bytes rr.. at line offset a
+                  const uint64_t left = k.head_len - rr;
+                  const uint32_t nb = left < ae - a ? (uint32_t)left : ae - a;
+                  add_bytes(acc, a, q, load_bytes(k.head + rr, nb), nb);
+                  rr += nb;
+                }
+                if (a < ae && rr < rsz) {  // message bytes
+                  const uint64_t left = rsz - rr;
+                  const uint32_t nb = left < ae - a ? (uint32_t)left : ae - a;
+                  add_bytes(acc, a, q, load_bytes(k.out + f.off + (rr - k.head_len), nb), nb);
+                }
+              }
+              fo += rsz;
+            }
+            i++;
+          }
+          put_line(tbase, A, s, e, P0, P1, acc);
+        }
+      }
+      wpos = o1;
+      __syncthreads();  // (LDS is rewritten by the next tile)
+    }
+
+    uint64_t recs;
+    block_scan((uint64_t)c_recs, tid, s_w, recs);
+    if (tid == 0) {
+      const uint64_t cut = s_cut;
+      if (cut != XYWS_NPOS) st |= XYWS_DFR_TEXT_CAP;
+      rows::store_deflate_room_result(droom_results + ri, {wpos - h0, {(uint32_t)recs, 0}, {st, (uint32_t)h0}, cut});
+    }
+    __syncthreads();  // (s_cut and s_w are reused by the next room)
+  }
+}
+
+// xyws_deflate_windows_streams, last launch: the room's history for the next
+// sweep. One workgroup per room: the last XYWS_DFL_WINDOW bytes of history and
+// text move to the front of the text, ascending, a chunk's loads before its
+// stores (source and destination overlap below twice the window); the carry
+// gets the new length. After XYWS_DFR_TEXT_CAP or XYWS_DFR_DESYNC the history
+// is empty; a room with no record that was not reset keeps text and carry.
+__global__ void __launch_bounds__(DFL_SLIDE_THREADS)
+    k_room_slide(const xyws_deflate_room* __restrict__ drooms, uint64_t n_rooms, xyws_deflate_room_result* __restrict__ droom_results) {
+  const uint32_t tid = threadIdx.x;
+  for (uint64_t ri = blockIdx.x; ri < n_rooms; ri += gridDim.x) {
+    const rows::deflate_room_row dr = rows::load_deflate_room(drooms + ri);
+    if (!dr.text || !dr.carry) continue;
+    rows::deflate_room_result_row rr = rows::load_deflate_room_result(droom_results + ri);
+    xyws_deflate_room_carry* const carry = (xyws_deflate_room_carry*)dr.carry;
+    const uint64_t h0 = rr.state.hist0, total = h0 + rr.text_len;
+    const bool empty = (rr.state.status & (XYWS_DFR_TEXT_CAP | XYWS_DFR_DESYNC)) != 0;
+    const uint64_t keep = empty ? 0 : total < XYWS_DFL_WINDOW ? total : XYWS_DFL_WINDOW;
+    const uint64_t sweeps = h0 ? rows::load_deflate_room_carry(carry).n_sweeps : 0;
+    __syncthreads();  // (every thread has the row before it is rewritten)
+    if (keep && total > keep) {
+      g_u8* const tbase = (g_u8*)(dr.text & ~15ull);
+      const uint64_t P0 = dr.text & 15u, P1 = P0 + keep, src = dr.text + (total - keep);
+      for (uint64_t A0 = 0; A0 < P1; A0 += 16u * DFL_SLIDE_THREADS) {
+        const uint64_t A = A0 + 16u * tid;
+        const uint64_t s = A > P0 ? A : P0, e = A + 16 < P1 ? A + 16 : P1;
+        bytes16 v = {0, 0};
+        if (A < P1) v = shl_bytes(low_bytes(load_bytes(src + (s - P0), (uint32_t)(e - s)), (uint32_t)(e - s)), (uint32_t)(s - A));
+        __syncthreads();
+        if (A < P1) put_line(tbase, A, s, e, P0, P1, v);
+        __syncthreads();
+      }
+    }
+    if (tid == 0) {
+      if (rr.counts.n_records || (rr.state.status & XYWS_DFR_RESET))
+        rows::store_deflate_room_carry(carry, keep, keep ? sweeps + (rr.counts.n_records ? 1u : 0u) : 0);
+      rr.state.hist0 = 0, rr.cut = 0;
+      rows::store_deflate_room_result(droom_results + ri, rr);
     }
   }
 }
@@ -731,11 +1071,62 @@ int xyws_deflate_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm, const 
   const uint32_t grid = grid_for(n, 1, DFL_GRID_CAP);
   if (opts & XYWS_DFO_DYNAMIC)
     hipLaunchKernelGGL(k_deflate_streams<true>, dim3(grid), dim3(DFL_LANES), 0, (hipStream_t)stream, dev_reasm, dev_reasm_results,
-                       dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results);
+                       dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results, nullptr, nullptr, 0);
   else
     hipLaunchKernelGGL(k_deflate_streams<false>, dim3(grid), dim3(DFL_LANES), 0, (hipStream_t)stream, dev_reasm, dev_reasm_results,
-                       dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results);
+                       dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results, nullptr, nullptr, 0);
   return hip_err(hipGetLastError());
+}
+
+int xyws_deflate_windows_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm, const xyws_reasm_result* dev_reasm_results,
+                                 const xyws_bcast_conn* dev_bconns, const xyws_deflate_conn* dev_dconns, uint64_t n,
+                                 const xyws_room* dev_rooms, const xyws_deflate_room* dev_drooms,
+                                 const xyws_roster_room_result* dev_last_roster, uint64_t n_rooms, uint32_t opts,
+                                 xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results, xyws_bcast_conn* dev_view_bconns,
+                                 xyws_deflate_result* dev_results, xyws_deflate_room_result* dev_droom_results, void* stream) {
+  if (!ctx || (n && (!dev_reasm || !dev_reasm_results || !dev_bconns || !dev_dconns || !dev_view || !dev_view_results ||
+                     !dev_view_bconns)))
+    return XYWS_ERR_INVALID;
+  if (n_rooms && (!dev_rooms || !dev_drooms || !dev_droom_results)) return XYWS_ERR_INVALID;
+  if (opts || n >= UINT32_MAX || n_rooms >= UINT32_MAX) return XYWS_ERR_INVALID;
+  if (!n) return XYWS_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  device_guard g(ctx->device);
+  if (!g.ok) return XYWS_ERR_HIP;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!n_rooms) {  // nobody takes over: the sibling's launch
+    hipLaunchKernelGGL(k_deflate_streams<false>, dim3(grid_for(n, 1, DFL_GRID_CAP)), dim3(DFL_LANES), 0, s, dev_reasm,
+                       dev_reasm_results, dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results,
+                       nullptr, nullptr, 0);
+    return hip_err(hipGetLastError());
+  }
+  const uint32_t rgrid = grid_for(n_rooms, 1, BC_GRID_CAP);
+  hipLaunchKernelGGL(k_room_text, dim3(rgrid), dim3(DFL_TEXT_THREADS), 0, s, dev_reasm, dev_reasm_results, dev_bconns, n,
+                     dev_rooms, dev_drooms, dev_last_roster, n_rooms, dev_view_results, dev_droom_results);
+  int rc = hip_err(hipGetLastError());
+  if (rc != XYWS_OK) return rc;
+  hipLaunchKernelGGL((k_deflate_streams<false, true>), dim3(grid_for(n, 1, DFL_WIN_GRID_CAP)), dim3(DFL_LANES), 0, s, dev_reasm,
+                     dev_reasm_results, dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results,
+                     dev_drooms, dev_droom_results, n_rooms);
+  rc = hip_err(hipGetLastError());
+  if (rc != XYWS_OK) return rc;
+  hipLaunchKernelGGL(k_room_slide, dim3(rgrid), dim3(DFL_SLIDE_THREADS), 0, s, dev_drooms, n_rooms, dev_droom_results);
+  return hip_err(hipGetLastError());
+}
+
+// Internal (tests and measurements, no HIP call): the geometry of
+// k_deflate_streams<false, true>. out: {stage bytes W, window bytes in front of
+// a piece, hash slots, grid cap, wave size, the room's history in bytes}.
+int xyws_debug_deflate_windows_geometry(uint64_t out[6]) {
+  if (!out) return XYWS_ERR_INVALID;
+  out[0] = DFL_STAGE;
+  out[1] = DFL_HIST;
+  out[2] = DFL_SLOTS;
+  out[3] = DFL_WIN_GRID_CAP;
+  out[4] = DFL_LANES;
+  out[5] = XYWS_DFL_WINDOW;
+  static_assert(sizeof(deflate_lds_window) * (DFL_WIN_GRID_CAP / 256u) <= 160u * 1024u, "four waves' LDS per CU");
+  return XYWS_OK;
 }
 
 // Internal (tests and measurements): build_code, the device function the

@@ -538,6 +538,31 @@ XYWS_HD deflate_counts unpack_deflate_counts(uint64_t w) {
   return {XYWS_GET(xyws_deflate_result, n_deflated, w), XYWS_GET(xyws_deflate_result, n_stored, w)};
 }
 
+// xyws_deflate_windows_streams: a room's row, carry and result, four words each.
+// Between the call's launches the result's reserved0 is the history the room
+// began with and its reserved word the text offset behind the last record that
+// fits the cap; the slide zeroes both.
+struct deflate_room_counts { uint32_t n_records, n_history; };  // xyws_deflate_room_result
+struct deflate_room_state { uint32_t status, hist0; };          // (hist0: reserved0)
+XYWS_ONE_WORD(xyws_deflate_room_carry, flags, reserved0);
+XYWS_ONE_WORD(xyws_deflate_room_result, n_records, n_history);
+XYWS_ONE_WORD(xyws_deflate_room_result, status, reserved0);
+static_assert(sizeof(xyws_deflate_room) == 4 * 8 && sizeof(xyws_deflate_room_carry) == 4 * 8 &&
+                  sizeof(xyws_deflate_room_result) == 4 * 8,
+              "the takeover's rows: four words");
+XYWS_HD uint64_t pack_deflate_room_counts(deflate_room_counts c) {
+  return XYWS_PUT(xyws_deflate_room_result, n_records, c.n_records) | XYWS_PUT(xyws_deflate_room_result, n_history, c.n_history);
+}
+XYWS_HD deflate_room_counts unpack_deflate_room_counts(uint64_t w) {
+  return {XYWS_GET(xyws_deflate_room_result, n_records, w), XYWS_GET(xyws_deflate_room_result, n_history, w)};
+}
+XYWS_HD uint64_t pack_deflate_room_state(deflate_room_state s) {
+  return XYWS_PUT(xyws_deflate_room_result, status, s.status) | XYWS_PUT(xyws_deflate_room_result, reserved0, s.hist0);
+}
+XYWS_HD deflate_room_state unpack_deflate_room_state(uint64_t w) {
+  return {XYWS_GET(xyws_deflate_room_result, status, w), XYWS_GET(xyws_deflate_room_result, reserved0, w)};
+}
+
 }  // namespace xyws_rows
 
 // ================================================================ the device part
@@ -1140,6 +1165,52 @@ XYWS_DEV void store_deflate_result_dynamic(xyws_deflate_result* p, uint64_t out_
   XYWS_ST(xyws_deflate_result, p, n_deflated, pack_deflate_counts(c));
   XYWS_ST(xyws_deflate_result, p, status, XYWS_PUT(xyws_deflate_result, status, status) | XYWS_PUT(xyws_deflate_result, reserved0, n_dynamic));
 }
+// ---- xyws_deflate_windows_streams: the room's row, carry and result (wave-uniform)
+struct deflate_room_row { uint64_t text, text_cap, carry; };  // (text_cap counts as 0 without text)
+XYWS_DEV deflate_room_row load_deflate_room(const xyws_deflate_room* p) {
+  deflate_room_row r;
+  r.text = XYWS_LD(true, xyws_deflate_room, p, text);
+  r.text_cap = r.text ? XYWS_LD(true, xyws_deflate_room, p, text_cap) : 0;
+  r.carry = XYWS_LD(true, xyws_deflate_room, p, carry);
+  return r;
+}
+struct deflate_room_carry_row { uint64_t hist_len, n_sweeps; };
+XYWS_DEV deflate_room_carry_row load_deflate_room_carry(const xyws_deflate_room_carry* p) {
+  return {XYWS_LD(true, xyws_deflate_room_carry, p, hist_len), XYWS_LD(true, xyws_deflate_room_carry, p, n_sweeps)};
+}
+XYWS_DEV void store_deflate_room_carry(xyws_deflate_room_carry* p, uint64_t hist_len, uint64_t n_sweeps) {
+  XYWS_ST(xyws_deflate_room_carry, p, hist_len, hist_len);
+  XYWS_ST(xyws_deflate_room_carry, p, n_sweeps, n_sweeps);
+  XYWS_ST(xyws_deflate_room_carry, p, flags, 0);
+  XYWS_ST(xyws_deflate_room_carry, p, reserved, 0);
+}
+struct deflate_room_result_row { uint64_t text_len; deflate_room_counts counts; deflate_room_state state; uint64_t cut; };
+XYWS_DEV deflate_room_result_row load_deflate_room_result(const xyws_deflate_room_result* p) {
+  return {XYWS_LD(true, xyws_deflate_room_result, p, text_len),
+          unpack_deflate_room_counts(XYWS_LD(true, xyws_deflate_room_result, p, n_records)),
+          unpack_deflate_room_state(XYWS_LD(true, xyws_deflate_room_result, p, status)),
+          XYWS_LD(true, xyws_deflate_room_result, p, reserved)};
+}
+XYWS_DEV void store_deflate_room_result(xyws_deflate_room_result* p, const deflate_room_result_row& r) {
+  XYWS_ST(xyws_deflate_room_result, p, text_len, r.text_len);
+  XYWS_ST(xyws_deflate_room_result, p, n_records, pack_deflate_room_counts(r.counts));
+  XYWS_ST(xyws_deflate_room_result, p, status, pack_deflate_room_state(r.state));
+  XYWS_ST(xyws_deflate_room_result, p, reserved, r.cut);
+}
+// What the compression's waves add to a room's row: one more record with a match into the history; status bits.
+XYWS_DEV void count_deflate_room_history(xyws_deflate_room_result* p) {
+  atomicAdd((unsigned long long*)p + XYWS_WORD(xyws_deflate_room_result, n_history),
+            (unsigned long long)XYWS_PUT(xyws_deflate_room_result, n_history, 1u));
+}
+XYWS_DEV void raise_deflate_room_status(xyws_deflate_room_result* p, uint32_t bits) {
+  atomicOr((unsigned long long*)p + XYWS_WORD(xyws_deflate_room_result, status),
+           (unsigned long long)XYWS_PUT(xyws_deflate_room_result, status, bits));
+}
+// The joiners a roster row admitted.
+XYWS_DEV uint32_t load_roster_joined(const xyws_roster_room_result* p) {
+  return unpack_roster_counts(XYWS_LD(true, xyws_roster_room_result, p, joined)).joined;
+}
+
 // The broadcast row at src without its head, one word per lane.
 XYWS_DEV void copy_bcast_conn_headless(xyws_bcast_conn* dst, const xyws_bcast_conn* src, uint32_t lane) {
   if (lane < sizeof(xyws_bcast_conn) / 8)

@@ -624,8 +624,10 @@ class GroupDeflate:
     out ranges, view rows, result rows and, after the broadcast, the
     compressed wires (zwire)."""
 
-    def __init__(self, group, messages, negotiated, tensors, out_cap, dynamic=False):
+    def __init__(self, group, messages, negotiated, tensors, out_cap, dynamic=False, takeover=(), last_roster=None,
+                 text_caps=None):
         self.group, self.decoded, self.messages_in, self.dynamic = group, messages.decoded, messages, bool(dynamic)
+        self.takeover, self.last_roster, self.text_caps, self._drows = takeover, last_roster, text_caps, None
         self.negotiated, self._tensors, self.out_cap, self.msg_cap = negotiated, tensors, out_cap, messages.msg_cap
         m = len(self.decoded.ids)
         self.outs = [tensors["out"][out_cap * k:out_cap * (k + 1)] for k in range(m)]
@@ -649,6 +651,10 @@ class GroupDeflate:
     def zroom_result(self, r):
         """xyws_room_result of room r's compressed wire."""
         return self._zrows[r]
+
+    def room_result(self, r):
+        """xyws_deflate_room_result of room r (deflate(takeover=...) only)."""
+        return self._drows[r]
 
     def zwire(self, r):
         """Room r's compressed wire of this sweep (a device tensor: the first min(wire_len, wire_cap) bytes)."""
@@ -947,6 +953,7 @@ class connection_group:
         # inflate(): the inflate carries (its tables, out ranges and rows belong to the GroupInflate it returns)
         self.icarry_t = _lib.alloc_rows(_lib.InflateCarry, n, dev)
         self._iwindows = {}  # inflate(takeover=...): connection id -> its 32 KiB window, made when first named, kept
+        self._dtexts, self._dcarries = {}, {}  # deflate(takeover=...): room -> its text area and its carry, kept
         # backlog(): per room a log and a carry, made when the room is first seen and kept across sweeps
         self._blogs, self._bcarries = [], []
         # inbox(): the receive slab, the inbox carries and the resident tables, made by the first inbox() call
@@ -1044,7 +1051,11 @@ class connection_group:
         the caller), out_items[k] the device uint8 tensor that receives its
         response (129 bytes always suffice; 231 with ACC_DEFLATE in policy,
         which agrees to an offer of permessage-deflate: result(k).status then
-        has ACC_DEFLATED and inflate() takes the connection as negotiated). A whole request is checked by
+        has ACC_DEFLATED and inflate() takes the connection as negotiated;
+        ACC_DEFLATE_TAKEOVER and ACC_DEFLATE_SERVER_TAKEOVER beside it let the
+        client and the server keep their context where the offer allows, which
+        only shortens the 101: status then has ACC_TAKEOVER for inflate(takeover=...)
+        and ACC_SERVER_TAKEOVER for deflate(takeover=...)). A whole request is checked by
         RFC 6455 4.2.1 (policy 0) or as the reference's handler does
         (ACC_REFERENCE) and answered; an incomplete one is reported as such:
         call again with more bytes. The call keeps no state: on ACCEPTED the
@@ -1317,7 +1328,16 @@ class connection_group:
                    slot=dec.slot)
         return GroupInflate(self, src, tensors, out_cap, [i not in agreed for i in dec.ids])
 
-    def deflate(self, messages_or_hold_or_inflate, negotiated, out_cap, dynamic=False):
+    def deflate_carry(self, room):
+        """Host copy of a room's xyws_deflate_room_carry (synchronizes)."""
+        return _lib.read_rows(_lib.DeflateRoomCarry, self._dcarries[int(room)], 1)[0]
+
+    def deflate_history(self, room):
+        """The history deflate(takeover=...) keeps for a room: a device tensor of carry.hist_len bytes (synchronizes)."""
+        return self._dtexts[int(room)][:self.deflate_carry(room).hist_len]
+
+    def deflate(self, messages_or_hold_or_inflate, negotiated, out_cap, dynamic=False, takeover=(), last_roster=None,
+                text_caps=None):
         """Compress the sweep's outbound messages once per message
         (xyws_deflate_streams, one launch) for the members that negotiated
         permessage-deflate: `messages_or_hold_or_inflate` is what broadcast()
@@ -1326,7 +1346,21 @@ class connection_group:
         (a message of L bytes with its head needs at most
         L + 5 * ceil(L / 65535) + 1). dynamic: a piece of a message may go out
         as a dynamic-Huffman block where that is shorter (XYWS_DFO_DYNAMIC;
-        result(k).n_dynamic counts the messages with one). Returns a GroupDeflate for
+        result(k).n_dynamic counts the messages with one). takeover: the rooms
+        (indices of broadcast()'s `rooms`, or the RoomSet for all of its rooms)
+        whose compressed wire keeps the server's context from message to
+        message and from sweep to sweep: the call is then
+        xyws_deflate_windows_streams (three launches), the group makes and keeps
+        each such room's text area (32 KiB of history and the sweep's text) and
+        carry, room_result(r) of the result says how many records reached into
+        the history (n_history) and whether the room's negotiated members must
+        be closed (DFR_DESYNC). Name as negotiated only connections whose
+        accept() ran with ACC_DEFLATE | ACC_DEFLATE_SERVER_TAKEOVER and whose
+        result(k).status has ACC_SERVER_TAKEOVER. last_roster: the GroupRoster
+        of the previous sweep: a room it admitted a joiner to starts this sweep
+        with an empty history, so the joiner's empty inflater is right.
+        text_caps: {room: text_cap} in place of the bound that always suffices.
+        takeover does not combine with dynamic. Returns a GroupDeflate for
         broadcast(..., deflated=...), which issues the launch: the call reads
         the heads, reply rows and rooms that broadcast() lays out."""
         src = messages_or_hold_or_inflate
@@ -1335,6 +1369,13 @@ class connection_group:
         dec, out_cap, agreed = src.decoded, int(out_cap), {int(i) for i in negotiated}
         if out_cap < 0:
             raise ValueError("out_cap must not be negative")
+        keeps = takeover if isinstance(takeover, RoomSet) else sorted({int(r) for r in takeover})
+        if isinstance(keeps, RoomSet):
+            keeps = list(range(keeps.nr))
+        if keeps and dynamic:
+            raise ValueError("takeover does not combine with dynamic")
+        if last_roster is not None and not (isinstance(last_roster, GroupRoster) and last_roster.group is self):
+            raise XywsError(-1, "last_roster is the roster() result of this group's previous sweep")
         import torch
         m, dev = len(dec.ids), self.device
         dtab = _lib.Table(_lib.DeflateConn, m)
@@ -1348,7 +1389,28 @@ class connection_group:
             row.vmsg_cap = src.msg_cap
             row.flags = _lib.DFC_NEGOTIATED if i in agreed else 0
         tensors["dconns"] = dtab.upload(dev)
-        return GroupDeflate(self, src, agreed, tensors, out_cap, dynamic)
+        return GroupDeflate(self, src, agreed, tensors, out_cap, dynamic, keeps, last_roster, dict(text_caps or {}))
+
+    def _deflate_rooms(self, deflated, wires, nr):
+        """The xyws_deflate_room table of a deflate(takeover=...) call: every
+        named room's text area (kept, grown when the sweep needs more) and
+        carry; the other rooms' rows stay null."""
+        import torch
+        dev = self.device
+        tab = _lib.Table(_lib.DeflateRoom, nr)
+        for r in deflated.takeover:
+            if not 0 <= r < nr:
+                raise XywsError(-1, "takeover names a room the broadcast does not have")
+            cap = int(deflated.text_caps.get(r, _lib.DFL_WINDOW + wires[r].numel()))  # (the wire bounds the sweep's text)
+            old = self._dtexts.get(r)
+            if old is None or old.numel() < cap:
+                self._dtexts[r] = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+                if old is not None:
+                    self._dtexts[r][:old.numel()].copy_(old)
+            if r not in self._dcarries:
+                self._dcarries[r] = _lib.alloc_rows(_lib.DeflateRoomCarry, 1, dev)
+            tab[r].text, tab[r].text_cap, tab[r].carry = self._dtexts[r].data_ptr(), cap, self._dcarries[r].data_ptr()
+        return tab.upload(dev)
 
     def _broadcast_deflated(self, messages, deflated, tensors, wires, m, nr, flags, enc_opts, slot):
         """broadcast(..., deflated=...): xyws_deflate_streams, then
@@ -1369,9 +1431,20 @@ class connection_group:
             cols[:, _lib.Room.wire_cap.offset // 8] = torch.tensor([w.numel() for w in zwires], dtype=torch.int64).to(dev)
         d.update(zrooms=zrooms, zroom_results=_lib.alloc_rows(_lib.RoomResult, nr, dev), bcast=tensors)
         deflated._zwires, deflated._zrows = zwires, _Rows(_lib.RoomResult, d["zroom_results"], nr)
-        self._call("xyws_deflate_streams", *messages.tables(), tensors["bconns"], d["dconns"], m,
-                   _lib.DFO_DYNAMIC if deflated.dynamic else 0, d["view"],
-                   d["view_results"], d["view_bconns"], d["results"], slot=slot)
+        if deflated.takeover:
+            ro = deflated.last_roster
+            if ro is not None and ro.room_set.nr != nr:
+                raise XywsError(-1, "last_roster has other rooms than this broadcast")
+            d.update(drooms=self._deflate_rooms(deflated, wires, nr),
+                     droom_results=_lib.alloc_rows(_lib.DeflateRoomResult, nr, dev))
+            deflated._drows = _Rows(_lib.DeflateRoomResult, d["droom_results"], nr)
+            self._call("xyws_deflate_windows_streams", *messages.tables(), tensors["bconns"], d["dconns"], m, tensors["rooms"],
+                       d["drooms"], ro._tensors["room_results"] if ro is not None else 0, nr, 0, d["view"], d["view_results"],
+                       d["view_bconns"], d["results"], d["droom_results"], slot=slot)
+        else:
+            self._call("xyws_deflate_streams", *messages.tables(), tensors["bconns"], d["dconns"], m,
+                       _lib.DFO_DYNAMIC if deflated.dynamic else 0, d["view"],
+                       d["view_results"], d["view_bconns"], d["results"], slot=slot)
         self._call("xyws_broadcast_deflated_streams", *messages.tables(), tensors["bconns"], m, tensors["rooms"],
                    tensors["room_results"], nr, flags, enc_opts, tensors["results"], d["view"], d["view_results"],
                    d["view_bconns"], d["dconns"], d["zrooms"], d["zroom_results"], slot=slot)
