@@ -1342,7 +1342,7 @@ typedef struct xyws_deflate_result { /* 32 bytes */
   uint32_t n_deflated; /* records sent as Huffman blocks, fixed or dynamic */
   uint32_t n_stored;   /* records sent as stored blocks */
   uint32_t status;     /* XYWS_DFL_* */
-  uint32_t reserved0;  /* with XYWS_DFO_DYNAMIC: the records among n_deflated with at least one dynamic block; else 0 */
+  uint32_t reserved0;  /* with XYWS_DFO_DYNAMIC or XYWS_DFO_WINDOW_DYNAMIC: the records among n_deflated with at least one dynamic block; else 0 */
 } xyws_deflate_result;
 #define XYWS_DFL_TOO_LONG 0x1u /* a record did not fit in out_cap */
 #define XYWS_DFL_MSG_CAP  0x2u /* a deliverable record beyond vmsg_cap */
@@ -1374,7 +1374,9 @@ int xyws_deflate_streams(xyws_ctx* ctx,
  *     compressed exactly as xyws_deflate_streams (opts 0) compresses it, byte
  *     for byte; so is one that dev_rooms[room].members does not list (every
  *     connection of a takeover room is listed there once, and its bconns row
- *     names that room: the fan-out assumes the same).
+ *     names that room: the fan-out assumes the same). With
+ *     XYWS_DFO_WINDOW_DYNAMIC in opts such a connection is compressed byte for
+ *     byte as xyws_deflate_streams with XYWS_DFO_DYNAMIC compresses it.
  *  3. Room text. The text of a room is its members' deliverable records in the
  *     wire order of xyws_broadcast_streams 3. (members[] order, each member's
  *     records in record order; the same code computes it), each record
@@ -1390,6 +1392,22 @@ int xyws_deflate_streams(xyws_ctx* ctx,
  *     without the window (a tie goes to without), per record the stored form
  *     is the fallback as in 8. of xyws_deflate_streams: a record is never
  *     longer than xyws_deflate_streams makes it.
+ *     With XYWS_DFO_WINDOW_DYNAMIC in opts a piece has four candidates: the
+ *     search without the window and the search with it, each as a fixed and
+ *     as a dynamic-Huffman block over its own tokens (the code is built from
+ *     the counts of that search). The piece takes the shortest; ties go to
+ *     without the window before with it, then to fixed before dynamic. A piece
+ *     that has no window (nothing in front of it, or a piece of a record
+ *     beyond the kernel's 64th) chooses between fixed and dynamic as under
+ *     XYWS_DFO_DYNAMIC. Blocks stay non-final, the record ends as above and
+ *     the stored form stays the fallback per record, a tie going to stored.
+ *     So a record is never longer than this call makes it with opts == 0, and
+ *     never longer than xyws_deflate_streams makes it with XYWS_DFO_DYNAMIC.
+ *     dev_results[i].reserved0 then counts the records with at least one
+ *     dynamic block, as under XYWS_DFO_DYNAMIC; n_history keeps its meaning
+ *     and the room row's reserved words are zero after the call. The text
+ *     build and the slide are the same; 1., 3. and 5. to 9. hold unchanged,
+ *     and with opts == 0 the call is byte for byte what it was.
  *  5. Reset. The room starts the call with an empty history when
  *     dev_last_roster is given and dev_last_roster[r].joined != 0 (the previous
  *     sweep's xyws_roster_streams rows), or when the carry is all zero. In the
@@ -1434,10 +1452,12 @@ int xyws_deflate_streams(xyws_ctx* ctx,
  *     words of dev_droom_results[r] are the call's scratch. No host read of
  *     device state, no reserve; capturable into a hipGraph at once.
  *     XYWS_ERR_INVALID, on the arguments alone: what xyws_deflate_streams
- *     refuses; any bit of opts (XYWS_DFO_DYNAMIC included); a null dev_rooms,
+ *     refuses; any bit of opts other than XYWS_DFO_WINDOW_DYNAMIC
+ *     (XYWS_DFO_DYNAMIC included, alone or beside it); a null dev_rooms,
  *     dev_drooms or dev_droom_results with n_rooms > 0; n_rooms >= UINT32_MAX.
+ *     xyws_deflate_streams refuses XYWS_DFO_WINDOW_DYNAMIC.
  *
- * Not built: dynamic blocks over a history; a second z wire for the members
+ * Not built: a second z wire for the members
  * of a takeover room that refuse server takeover; server_max_window_bits. */
 typedef struct xyws_deflate_room_carry { /* 32 bytes; all zero = no history */
   uint64_t hist_len;   /* bytes of history in front of the text: text[0, hist_len), <= 32768 */
@@ -1466,6 +1486,7 @@ typedef struct xyws_deflate_room_result { /* 32 bytes */
 #define XYWS_DFR_TEXT_CAP 0x2u /* the sweep's text did not fit in text_cap */
 #define XYWS_DFR_DESYNC   0x4u /* a record of the text was left out of the z wire: close the negotiated members */
 #define XYWS_DFL_WINDOW 32768u /* bytes of history a room keeps */
+#define XYWS_DFO_WINDOW_DYNAMIC 0x4u /* opts of xyws_deflate_windows_streams only: dynamic-Huffman blocks too, over the window or not */
 
 struct xyws_roster_room_result;
 int xyws_deflate_windows_streams(xyws_ctx* ctx,
@@ -1474,7 +1495,7 @@ int xyws_deflate_windows_streams(xyws_ctx* ctx,
                                  const xyws_deflate_conn* dev_dconns, uint64_t n,
                                  const xyws_room* dev_rooms, const xyws_deflate_room* dev_drooms,
                                  const struct xyws_roster_room_result* dev_last_roster /* n_rooms, nullable */,
-                                 uint64_t n_rooms, uint32_t opts /* 0 */,
+                                 uint64_t n_rooms, uint32_t opts /* 0 or XYWS_DFO_WINDOW_DYNAMIC */,
                                  xyws_reasm_conn* dev_view, xyws_reasm_result* dev_view_results,
                                  xyws_bcast_conn* dev_view_bconns,
                                  xyws_deflate_result* dev_results /* n, nullable */,

@@ -407,7 +407,10 @@ inline void deflate_streams(context& ctx, const xyws_reasm_conn* dev_reasm, cons
 // the previous sweep's roster rows; a room that admitted a joiner starts from
 // an empty history. dev_droom_results (n_rooms entries) is required with
 // n_rooms > 0: XYWS_DFR_DESYNC there means the room's negotiated members are
-// to be closed.
+// to be closed. opts is 0 or XYWS_DFO_WINDOW_DYNAMIC: every piece of a message
+// is then also tried as a dynamic-Huffman block, with and without the room's
+// history, and goes out as the shortest of the four; dev_results[i].reserved0
+// counts the records with such a block. XYWS_DFO_DYNAMIC is refused here.
 inline void deflate_windows_streams(context& ctx, const xyws_reasm_conn* dev_reasm,
                                     const xyws_reasm_result* dev_reasm_results, const xyws_bcast_conn* dev_bconns,
                                     const xyws_deflate_conn* dev_dconns, std::uint64_t n, const xyws_room* dev_rooms,
@@ -415,9 +418,10 @@ inline void deflate_windows_streams(context& ctx, const xyws_reasm_conn* dev_rea
                                     std::uint64_t n_rooms, xyws_reasm_conn* dev_view,
                                     xyws_reasm_result* dev_view_results, xyws_bcast_conn* dev_view_bconns,
                                     xyws_deflate_room_result* dev_droom_results,
-                                    xyws_deflate_result* dev_results = nullptr, void* stream = nullptr) {
+                                    xyws_deflate_result* dev_results = nullptr, void* stream = nullptr,
+                                    std::uint32_t opts = 0 /* or XYWS_DFO_WINDOW_DYNAMIC */) {
   check(xyws_deflate_windows_streams(ctx.native(), dev_reasm, dev_reasm_results, dev_bconns, dev_dconns, n, dev_rooms,
-                                     dev_drooms, dev_last_roster, n_rooms, 0, dev_view, dev_view_results,
+                                     dev_drooms, dev_last_roster, n_rooms, opts, dev_view, dev_view_results,
                                      dev_view_bconns, dev_results, dev_droom_results, stream),
         "xyws_deflate_windows_streams");
 }

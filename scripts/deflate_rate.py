@@ -44,7 +44,14 @@ part of the takeover call's median that this leaves out: the priming steps
 and what the search then does with the window's positions (longer chains of
 candidates, matches extended into the window).
 
-usage: deflate_rate.py [--out FILE] [--repeats R] [--dynamic | --takeover [--noprime-lib FILE]]
+With --takeover-dynamic the takeover cells are measured for
+XYWS_DFO_WINDOW_DYNAMIC and one row per cell ("option": "takeover_dynamic") is
+appended: the windows call with the bit next to the same call with opts = 0
+and next to xyws_deflate_streams with XYWS_DFO_DYNAMIC (no history), on the
+same build, alternated; the bytes of all three; the records with a dynamic
+block and the records that reached into the history.
+
+usage: deflate_rate.py [--out FILE] [--repeats R] [--dynamic | --takeover [--noprime-lib FILE] | --takeover-dynamic]
 """
 import argparse
 import ctypes as C
@@ -67,8 +74,11 @@ ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deflate_rate.js
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--dynamic", action="store_true")
 ap.add_argument("--takeover", action="store_true")
+ap.add_argument("--takeover-dynamic", action="store_true")
 ap.add_argument("--noprime-lib")
 args = ap.parse_args()
+TAKE = args.takeover or args.takeover_dynamic  # the windows call is measured, with WOPT
+WOPT = _lib.DFO_WINDOW_DYNAMIC if args.takeover_dynamic else 0
 assert args.repeats >= 5, "the spread needs at least 5 repeats"
 assert torch.cuda.is_available(), "deflate_rate.py measures on the GPU: no device, no number"
 
@@ -177,12 +187,15 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
     joined[:, 4] = 1
     drtab_t, nulltab_t, joined_t = dev(drtab), dev(nulltab), dev(joined)
 
-    def windows_call(drooms, lib=L):
+    def windows_call(drooms, lib=L, opts=0):
         _lib.check(lib.xyws_deflate_windows_streams(ctx.h, vp(mtab_t), vp(mres_t), vp(btab_t), vp(dtab_t), n, vp(rtab_t), vp(drooms),
-                                                  vp(joined_t), nr, 0, vp(view), vp(vres), vp(vbc), vp(dres), vp(drres), sp))
+                                                  vp(joined_t), nr, opts, vp(view), vp(vres), vp(vbc), vp(dres), vp(drres), sp))
 
     def deflate_call_takeover():
         windows_call(drtab_t)
+
+    def deflate_call_takeover_dynamic():
+        windows_call(drtab_t, opts=_lib.DFO_WINDOW_DYNAMIC)
 
     def deflate_call_windows_plain():
         windows_call(nulltab_t)
@@ -211,8 +224,13 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
     plain_len = rres.cpu().numpy().view(np.uint64).reshape(n, 4)[:nr, 0]
     z_len = zres.cpu().numpy().view(np.uint64).reshape(n, 4)[:nr, 0]
     assert (bres.cpu().numpy().view(np.uint64).reshape(n, 4)[:, 1] == np.repeat(z_len, ROOM)).all()
-    if args.takeover:  # every message inflates against what its room said in front of it; the bytes are the takeover's
-        deflate_call_takeover()
+    parents = {}
+    for name, fn in (("takeover", deflate_call_takeover), ("dynamic", deflate_call_dynamic)) if args.takeover_dynamic else ():
+        fn()
+        torch.cuda.synchronize()
+        parents["compressed_bytes_" + name] = int(dres.cpu().numpy().view(np.uint64).reshape(n, 4)[:, 0].sum())
+    if TAKE:  # every message inflates against what its room said in front of it; the bytes are the takeover's
+        windows_call(drtab_t, opts=WOPT)
         torch.cuda.synchronize()
         res = dres.cpu().numpy().view(np.uint64).reshape(n, 4)
         got, kinds = zout.cpu().numpy().reshape(n, ocap), dres.cpu().numpy().view(np.uint32).reshape(n, 8)
@@ -232,6 +250,9 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
             modes["deflate_call_takeover_noprime"] = deflate_call_takeover_noprime
     if args.dynamic:
         modes = {"deflate_call": deflate_call, "deflate_call_dynamic": deflate_call_dynamic}
+    if args.takeover_dynamic:
+        modes = {"deflate_call": deflate_call, "deflate_call_dynamic": deflate_call_dynamic,
+                 "deflate_call_takeover": deflate_call_takeover, "deflate_call_takeover_dynamic": deflate_call_takeover_dynamic}
     for fn in modes.values():
         fn()
         fn()
@@ -257,7 +278,7 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
         row["n_deflated"] = row.pop("n_fixed")
         row.update(option="dynamic", n_dynamic=int(kinds[:, 7].sum()), dynamic_share=round(int(kinds[:, 7].sum()) / n, 3),
                    deflate_dynamic_MBps_in=round(total / row["deflate_call_dynamic"]["median_us"], 1))
-    if args.takeover:  # (compressed_bytes and ratio are the takeover's; the send bytes are left out: no wire was built)
+    if TAKE:  # (compressed_bytes and ratio are the takeover's; the send bytes are left out: no wire was built)
         one = zlib.compressobj(6, zlib.DEFLATED, -15)
         chained = 0
         for i, m in enumerate(msgs):  # zlib level 6 with its context kept through a room's sweep
@@ -269,6 +290,14 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
             row.pop(k)
         row.update(option="takeover", n_history=int(room_rows[:, 3].sum()), ratio_zlib6_chained=round(chained / total, 3),
                    takeover_MBps_in=round(total / row["deflate_call_takeover"]["median_us"], 1))
+        if args.takeover_dynamic:  # (compressed_bytes and ratio are the bit's; the two calls it combines beside them)
+            took = row["deflate_call_takeover_dynamic"]["median_us"]
+            row.update(parents, option="takeover_dynamic", n_dynamic=int(kinds[:, 7].sum()),
+                       ratio_takeover=round(parents["compressed_bytes_takeover"] / total, 3),
+                       ratio_dynamic=round(parents["compressed_bytes_dynamic"] / total, 3),
+                       time_vs_takeover=round(took / row["deflate_call_takeover"]["median_us"], 2),
+                       time_vs_dynamic=round(took / row["deflate_call_dynamic"]["median_us"], 2),
+                       takeover_dynamic_MBps_in=round(total / took, 1))
         if NOPRIME:
             took = row["deflate_call_takeover"]["median_us"]
             row["priming_net_share"] = round((took - row["deflate_call_takeover_noprime"]["median_us"]) / took, 3)
@@ -277,6 +306,6 @@ for corpus, n, lo, hi in (("chat", 1024, 200, 1000), ("chat", 16384, 200, 1000),
 
 assert ctx.last_device_error() == 0
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "a" if args.dynamic or args.takeover else "w") as f:
+with open(args.out, "a" if args.dynamic or TAKE else "w") as f:
     for row in rows:
         f.write(json.dumps(row) + "\n")

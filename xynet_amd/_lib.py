@@ -276,7 +276,7 @@ class DeflateResult(C.Structure):
     """xyws_deflate_result (include/xyws.h), 32 bytes."""
     _fields_ = [("out_len", C.c_uint64), ("in_len", C.c_uint64), ("n_deflated", C.c_uint32), ("n_stored", C.c_uint32),
                 ("status", C.c_uint32), ("reserved0", C.c_uint32)]
-    n_dynamic = property(lambda self: self.reserved0, doc="With DFO_DYNAMIC: the records with at least one dynamic block.")
+    n_dynamic = property(lambda self: self.reserved0, doc="With DFO_DYNAMIC or DFO_WINDOW_DYNAMIC: the records with at least one dynamic block.")
 
 
 assert C.sizeof(DeflateConn) == 64 and C.sizeof(DeflateResult) == 32
@@ -306,6 +306,7 @@ class DeflateRoomResult(C.Structure):
 assert C.sizeof(DeflateRoomCarry) == 32 and C.sizeof(DeflateRoom) == 32 and C.sizeof(DeflateRoomResult) == 32
 DFR_RESET, DFR_TEXT_CAP, DFR_DESYNC = 0x1, 0x2, 0x4  # xyws_deflate_room_result.status
 DFL_WINDOW = 32768  # bytes of history a room keeps
+DFO_WINDOW_DYNAMIC = 0x4  # xyws_deflate_windows_streams' opts (xyws_deflate_streams refuses it)
 
 
 BACKLOG_MAX = 16

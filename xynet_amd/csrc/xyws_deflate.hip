@@ -60,6 +60,15 @@
 // searched without and with the window; k_room_slide moves the last 32 KiB to
 // the front for the next sweep. LDS: 16 KiB window and piece + 8 KiB table +
 // 9 KiB output stage: four waves per CU.
+//
+// With XYWS_DFO_WINDOW_DYNAMIC (k_deflate_streams<true, true>) both hold: the
+// window layout and the 316 words of histograms and codes, 35 KiB, still four
+// waves per CU. A piece with a window is searched without it and with it, each
+// search counted into its own histograms and planned (plan_piece) before the
+// next one overwrites them; the shortest of the four blocks is kept in two
+// mask bits a piece (wmask: with the window, dmask: dynamic). The emitting pass
+// stages the piece again, repeats the chosen search and, where the block is
+// dynamic, its count and plan: the codes do not survive the next piece.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
@@ -141,6 +150,12 @@ template <>
 struct lds_of<true, false> { typedef deflate_lds_dynamic type; };
 template <>
 struct lds_of<false, true> { typedef deflate_lds_window type; };
+// With both (XYWS_DFO_WINDOW_DYNAMIC): the window layout and the dynamic layout's histograms and codes.
+struct deflate_lds_window_dynamic : deflate_lds_window {
+  uint32_t code[DFL_LITLEN + DFL_DIST];
+};
+template <>
+struct lds_of<true, true> { typedef deflate_lds_window_dynamic type; };
 
 XYWS_DEV uint64_t below(uint32_t p) { return (1ull << p) - 1ull; }  // (p < 64)
 XYWS_DEV uint32_t lane_value(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
@@ -381,7 +396,8 @@ XYWS_DEV uint32_t clen_order(uint32_t i) {
 // the dynamic block can be shorter than the fbits of the fixed one, its header
 // bits in the workspace. Returns the header's bits with the dynamic block's
 // bits in dbits, or 0 when the fixed block is no longer (a tie goes to it).
-XYWS_DEV uint32_t plan_piece(deflate_lds_dynamic& S, uint32_t fbits, uint32_t& dbits, uint32_t lane) {
+template <class LDS>  // deflate_lds_dynamic or deflate_lds_window_dynamic
+XYWS_DEV uint32_t plan_piece(LDS& S, uint32_t fbits, uint32_t& dbits, uint32_t lane) {
   uint32_t* const ws = S.tab;
   __syncthreads();
   // HLIT and HDIST end at the last used symbol; the extra bits depend on the symbol alone
@@ -650,6 +666,8 @@ XYWS_DEV uint32_t huff_block(typename lds_of<DYN, WIN>::type& S, uint32_t n, boo
 // choices of a record's first DFL_WIN_PIECES pieces are kept in a mask for the
 // emitting pass; later pieces go without). Every other record takes the path
 // of k_deflate_streams<false>, the piece at byte DFL_HIST of the stage.
+// DYN and WIN: each of the two searches is also planned as a dynamic block, and
+// every other record takes the path of k_deflate_streams<true>.
 template <bool DYN, bool WIN = false>  // XYWS_DFO_DYNAMIC; xyws_deflate_windows_streams
 __global__ void __launch_bounds__(DFL_LANES)
     k_deflate_streams(const xyws_reasm_conn* __restrict__ reasm, const xyws_reasm_result* __restrict__ rres,
@@ -658,7 +676,6 @@ __global__ void __launch_bounds__(DFL_LANES)
                       xyws_bcast_conn* __restrict__ vbconns, xyws_deflate_result* __restrict__ results,
                       const xyws_deflate_room* __restrict__ drooms = nullptr, xyws_deflate_room_result* droom_results = nullptr,
                       uint64_t n_rooms = 0) {
-  static_assert(!(DYN && WIN), "dynamic blocks over a history are not built");
   __shared__ typename lds_of<DYN, WIN>::type S;
   uint32_t* const s_piece = S.in + (WIN ? DFL_HIST / 4u : 0u);
   const uint32_t lane = threadIdx.x;
@@ -719,11 +736,41 @@ __global__ void __launch_bounds__(DFL_LANES)
       uint64_t fbits = 0;
       uint32_t hbits = 0, dynamic = 0;  // the last piece's dynamic header, 0: fixed; pieces that chose the dynamic block
       uint64_t wmask = 0;               // WIN: bit k: piece k goes out as the block searched with the window
+      uint64_t dmask = 0;               // DYN and WIN: bit k: piece k goes out as a dynamic block
       uint32_t hist = 0;                // WIN: such a block has a match whose source lies in front of the record
       bool staged = single;             // the stage holds the record's one block when the counting is done
+      bool planned = true;              // DYN and WIN: the plan in LDS (codes, header, hbits) is the chosen block's
       for (uint64_t q0 = 0; q0 < L; q0 += DFL_STAGE) {
         const uint32_t pn = L - q0 < DFL_STAGE ? (uint32_t)(L - q0) : DFL_STAGE;
-        if constexpr (WIN) {
+        if constexpr (DYN && WIN) {
+          // four candidates: the search without the window and the one with it, each counted into its
+          // own histograms and planned; without before with, fixed before dynamic (plan_piece's tie)
+          const uint64_t k = q0 / DFL_STAGE;
+          uint32_t H = 0;
+          if (inwin) {
+            const uint64_t T = P + q0;
+            H = T < DFL_HIST ? (uint32_t)T : DFL_HIST;
+            stage_text(S.in, text, T, H, pn, lane);
+          } else {
+            stage_piece(s_piece, head, hl, msg, q0, pn, lane);
+          }
+          uint32_t db;
+          const uint32_t pf = huff_block<true, true>(S, pn, false, 0, 0, 0, lane);
+          hbits = plan_piece(S, pf, db, lane);
+          uint32_t best = hbits ? db : pf;
+          if (H && k < DFL_WIN_PIECES) {
+            const uint32_t front = q0 < DFL_HIST ? DFL_HIST - (uint32_t)q0 : 0u;
+            uint32_t h = 0;
+            const uint32_t wf = huff_block<true, true>(S, pn, false, 0, 0, 0, lane, H, true, front, &h);
+            const uint32_t wh = plan_piece(S, wf, db, lane), wbest = wh ? db : wf;
+            planned = wbest < best;  // (the codes and the header in LDS are the window's now)
+            if (planned) wmask |= 1ull << k, hist |= h, best = wbest, hbits = wh;
+          }
+          if (hbits && k < DFL_WIN_PIECES) dmask |= 1ull << k;
+          fbits += best;
+          dynamic += hbits != 0u;
+          continue;
+        } else if constexpr (WIN) {
           if (inwin) {
             const uint64_t T = P + q0, k = q0 / DFL_STAGE;
             const uint32_t H = T < DFL_HIST ? (uint32_t)T : DFL_HIST;
@@ -742,8 +789,8 @@ __global__ void __launch_bounds__(DFL_LANES)
           }
         }
         stage_piece(s_piece, head, hl, msg, q0, pn, lane);
-        if constexpr (DYN) {
-          const uint32_t fb = huff_block<true>(S, pn, false, 0, 0, 0, lane);
+        if constexpr (DYN) {  // (without WIN: with it every piece took the branch at the top)
+          const uint32_t fb = huff_block<true, WIN>(S, pn, false, 0, 0, 0, lane);
           uint32_t db;
           hbits = plan_piece(S, fb, db, lane);
           fbits += hbits ? db : fb;
@@ -769,7 +816,26 @@ __global__ void __launch_bounds__(DFL_LANES)
           const uint32_t pn = L - q0 < DFL_STAGE ? (uint32_t)(L - q0) : DFL_STAGE;
           bool win = false;  // WIN: this piece's block is the one searched with its window of wh bytes
           uint32_t wh = 0;
-          if constexpr (DYN) {
+          if constexpr (DYN && WIN) {
+            // the chosen search again, and its plan where the block is dynamic; a record of one
+            // piece is staged still and keeps the plan if the last one made is the chosen block's
+            const uint64_t k = q0 / DFL_STAGE;
+            if (inwin) {
+              const uint64_t T = P + q0;
+              wh = T < DFL_HIST ? (uint32_t)T : DFL_HIST;
+              if (!single) stage_text(S.in, text, T, wh, pn, lane);
+              win = k < DFL_WIN_PIECES && ((wmask >> k) & 1u);
+            } else if (!single) {
+              stage_piece(s_piece, head, hl, msg, q0, pn, lane);
+            }
+            if (!single || !planned) {
+              hbits = 0;
+              if (k >= DFL_WIN_PIECES || ((dmask >> k) & 1u)) {  // (behind the masks: planned again, as without WIN)
+                uint32_t db;
+                hbits = plan_piece(S, huff_block<true, true>(S, pn, false, 0, 0, 0, lane, wh, win), db, lane);
+              }
+            }
+          } else if constexpr (DYN) {
             if (!single) {  // the piece's plan again: the codes of the one before it are gone
               stage_piece(S.in, head, hl, msg, q0, pn, lane);
               uint32_t db;
@@ -1088,16 +1154,17 @@ int xyws_deflate_windows_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm
                      !dev_view_bconns)))
     return XYWS_ERR_INVALID;
   if (n_rooms && (!dev_rooms || !dev_drooms || !dev_droom_results)) return XYWS_ERR_INVALID;
-  if (opts || n >= UINT32_MAX || n_rooms >= UINT32_MAX) return XYWS_ERR_INVALID;
+  if ((opts & ~XYWS_DFO_WINDOW_DYNAMIC) || n >= UINT32_MAX || n_rooms >= UINT32_MAX) return XYWS_ERR_INVALID;
   if (!n) return XYWS_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
   device_guard g(ctx->device);
   if (!g.ok) return XYWS_ERR_HIP;
   const hipStream_t s = (hipStream_t)stream;
+  const auto sibling = opts ? k_deflate_streams<true> : k_deflate_streams<false>;
+  const auto windows = opts ? k_deflate_streams<true, true> : k_deflate_streams<false, true>;
   if (!n_rooms) {  // nobody takes over: the sibling's launch
-    hipLaunchKernelGGL(k_deflate_streams<false>, dim3(grid_for(n, 1, DFL_GRID_CAP)), dim3(DFL_LANES), 0, s, dev_reasm,
-                       dev_reasm_results, dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results,
-                       nullptr, nullptr, 0);
+    hipLaunchKernelGGL(sibling, dim3(grid_for(n, 1, DFL_GRID_CAP)), dim3(DFL_LANES), 0, s, dev_reasm, dev_reasm_results,
+                       dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results, nullptr, nullptr, 0);
     return hip_err(hipGetLastError());
   }
   const uint32_t rgrid = grid_for(n_rooms, 1, BC_GRID_CAP);
@@ -1105,9 +1172,9 @@ int xyws_deflate_windows_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm
                      dev_rooms, dev_drooms, dev_last_roster, n_rooms, dev_view_results, dev_droom_results);
   int rc = hip_err(hipGetLastError());
   if (rc != XYWS_OK) return rc;
-  hipLaunchKernelGGL((k_deflate_streams<false, true>), dim3(grid_for(n, 1, DFL_WIN_GRID_CAP)), dim3(DFL_LANES), 0, s, dev_reasm,
-                     dev_reasm_results, dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results,
-                     dev_drooms, dev_droom_results, n_rooms);
+  hipLaunchKernelGGL(windows, dim3(grid_for(n, 1, DFL_WIN_GRID_CAP)), dim3(DFL_LANES), 0, s, dev_reasm, dev_reasm_results,
+                     dev_bconns, dev_dconns, n, dev_view, dev_view_results, dev_view_bconns, dev_results, dev_drooms,
+                     dev_droom_results, n_rooms);
   rc = hip_err(hipGetLastError());
   if (rc != XYWS_OK) return rc;
   hipLaunchKernelGGL(k_room_slide, dim3(rgrid), dim3(DFL_SLIDE_THREADS), 0, s, dev_drooms, n_rooms, dev_droom_results);
@@ -1115,7 +1182,7 @@ int xyws_deflate_windows_streams(xyws_ctx* ctx, const xyws_reasm_conn* dev_reasm
 }
 
 // Internal (tests and measurements, no HIP call): the geometry of
-// k_deflate_streams<false, true>. out: {stage bytes W, window bytes in front of
+// k_deflate_streams<false, true> and <true, true>. out: {stage bytes W, window bytes in front of
 // a piece, hash slots, grid cap, wave size, the room's history in bytes}.
 int xyws_debug_deflate_windows_geometry(uint64_t out[6]) {
   if (!out) return XYWS_ERR_INVALID;
@@ -1126,6 +1193,8 @@ int xyws_debug_deflate_windows_geometry(uint64_t out[6]) {
   out[4] = DFL_LANES;
   out[5] = XYWS_DFL_WINDOW;
   static_assert(sizeof(deflate_lds_window) * (DFL_WIN_GRID_CAP / 256u) <= 160u * 1024u, "four waves' LDS per CU");
+  static_assert(sizeof(deflate_lds_window_dynamic) * (DFL_WIN_GRID_CAP / 256u) <= 160u * 1024u,
+                "and with XYWS_DFO_WINDOW_DYNAMIC: the same grid cap");
   return XYWS_OK;
 }
 

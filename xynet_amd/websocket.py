@@ -1360,7 +1360,9 @@ class connection_group:
         of the previous sweep: a room it admitted a joiner to starts this sweep
         with an empty history, so the joiner's empty inflater is right.
         text_caps: {room: text_cap} in place of the bound that always suffices.
-        takeover does not combine with dynamic. Returns a GroupDeflate for
+        With both dynamic and takeover the call has XYWS_DFO_WINDOW_DYNAMIC:
+        a piece takes the shortest of the fixed and the dynamic block, each
+        searched without and with the room's history. Returns a GroupDeflate for
         broadcast(..., deflated=...), which issues the launch: the call reads
         the heads, reply rows and rooms that broadcast() lays out."""
         src = messages_or_hold_or_inflate
@@ -1372,8 +1374,6 @@ class connection_group:
         keeps = takeover if isinstance(takeover, RoomSet) else sorted({int(r) for r in takeover})
         if isinstance(keeps, RoomSet):
             keeps = list(range(keeps.nr))
-        if keeps and dynamic:
-            raise ValueError("takeover does not combine with dynamic")
         if last_roster is not None and not (isinstance(last_roster, GroupRoster) and last_roster.group is self):
             raise XywsError(-1, "last_roster is the roster() result of this group's previous sweep")
         import torch
@@ -1439,7 +1439,8 @@ class connection_group:
                      droom_results=_lib.alloc_rows(_lib.DeflateRoomResult, nr, dev))
             deflated._drows = _Rows(_lib.DeflateRoomResult, d["droom_results"], nr)
             self._call("xyws_deflate_windows_streams", *messages.tables(), tensors["bconns"], d["dconns"], m, tensors["rooms"],
-                       d["drooms"], ro._tensors["room_results"] if ro is not None else 0, nr, 0, d["view"], d["view_results"],
+                       d["drooms"], ro._tensors["room_results"] if ro is not None else 0, nr,
+                       _lib.DFO_WINDOW_DYNAMIC if deflated.dynamic else 0, d["view"], d["view_results"],
                        d["view_bconns"], d["results"], d["droom_results"], slot=slot)
         else:
             self._call("xyws_deflate_streams", *messages.tables(), tensors["bconns"], d["dconns"], m,
