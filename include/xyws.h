@@ -2587,6 +2587,113 @@ int xyws_inbox_streams(xyws_ctx* ctx, const xyws_inbox_conn* dev_iconns, uint64_
                        xyws_inbox_result* dev_results /* n, nullable */, xyws_inbox_summary* summary,
                        void* dev_scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- send bytes a socket did not take -----------------------------------------------
+ * The reference keeps m_write_msgs per session and drains it as the socket
+ * allows (chat_session::writer). xyws_outbox_streams hands the host `len` bytes
+ * per connection; when send() takes fewer, the two calls here keep the rest on
+ * the device, directly in front of the connection's send range, the way the
+ * hold keeps its bytes: the next sweep's producers write behind it from `out`
+ * on as ever, and the next outbox lists `tail | new bytes` as one range.
+ *
+ *  1. Memory contract. The caller lays every connection's send buffer out as
+ *     [pend_cap bytes | out .. out + out_cap): the pend_cap bytes below `out`
+ *     are the connection's own. The pending tail lies right-aligned in them, in
+ *     [out - pend_len, out). pend_cap is per connection and may be 0: such a
+ *     connection behaves as without these calls, and any short send overflows.
+ *     Buffers have any alignment; neighbours share 16-byte lines.
+ *  2. The report stamp. After its sends the host writes one xyws_unsent_report
+ *     {sent, sweep} into row i of `reports` for every socket that took fewer
+ *     bytes than its entry's len, `sweep` being the number it gives the coming
+ *     xyws_unsent_streams call in the head. A row counts only when its sweep
+ *     equals head->sweep; a connection without such a row took everything. Rows
+ *     are never reset, and no connection can be named twice. reports (n rows;
+ *     null: no row counts) and the 16-byte head are device memory or pinned
+ *     host memory by its device pointer (xyws_outbox_map), read by the kernel:
+ *     one captured graph serves every sweep.
+ *  3. xyws_unsent_streams, at sweep start, behind the inbox and before any
+ *     producer. What the previous sweep offered connection i was
+ *     S = out - carry.pend_len, carry.last_len bytes. sent > last_len is taken
+ *     as last_len (XYWS_US_BAD_REPORT). The new tail is S[sent .. last_len), t
+ *     bytes. t == 0: pend_len = 0, no payload byte is read or written.
+ *     0 < t <= pend_cap: the tail moves to [out - t, out), pend_len = t
+ *     (XYWS_US_KEPT); source and destination may overlap either way. The
+ *     overflow rule: t > pend_cap: no byte is written, pend_len = 0,
+ *     XYWS_US_OVERFLOW: bytes of the stream are lost, and the caller closes the
+ *     connection (dropping whole frames instead is not done here). The carry gets pend_len,
+ *     last_len = pend_len, the head's sweep and the status as flags; the result
+ *     row (dev_results, nullable) pend_len, the bytes moved and the status. A
+ *     row with a null carry is skipped, its result row zero. Only whole 16-byte
+ *     lines that hold a tail byte are loaded, only bytes of [out - t, out) are
+ *     stored.
+ *  4. xyws_unsent_view_streams, at sweep end, directly before
+ *     xyws_outbox_streams, which is then called on dev_view in place of
+ *     dev_conns. Row i of dev_uconns and of dev_conns are the same connection
+ *     (the same `out`). View row i: out - pend_len, out_cap + pend_len, the
+ *     bcast, reply and accept pointers as they are (so the outbox's flags are
+ *     what they were, XYWS_OB_TRUNCATED included), backlog = dev_view_rows + i,
+ *     a synthesized row whose send_len is pend_len + full_len, full_len by rule
+ *     1 of xyws_outbox_streams. carry.last_len = pend_len + min(full_len,
+ *     out_cap): the len the outbox lists. A null `out` or carry counts as
+ *     pend_len 0. No payload byte is copied.
+ *  5. Properties. One launch each on `stream`. No atomics, nothing spins, no
+ *     workgroup waits for another; the device error word is untouched, no device
+ *     state is read on the host, no reserve is needed: both can be captured
+ *     into a hipGraph at once. dev_scratch (8-byte aligned,
+ *     xyws_unsent_scratch_bytes(n) bytes, the call's alone until the stream has
+ *     passed it) holds the list of the connections with a tail to move. The
+ *     ranges, carries and rows of two rows of dev_uconns must not overlap.
+ *     n == 0 returns XYWS_OK and launches nothing. XYWS_ERR_INVALID, decided on
+ *     the arguments alone, before the context is used: a null ctx; with n > 0 a
+ *     null table (dev_uconns, head, dev_scratch; dev_conns, dev_view,
+ *     dev_view_rows); n >= UINT32_MAX; scratch_bytes below
+ *     xyws_unsent_scratch_bytes(n). */
+typedef struct xyws_unsent_carry {    /* 32 bytes; all zero: nothing pending */
+  uint64_t pend_len;   /* bytes of [out - pend_len, out) that wait to be sent */
+  uint64_t last_len;   /* what the previous outbox listed for this connection */
+  uint32_t sweep;      /* head->sweep of the last xyws_unsent_streams call */
+  uint32_t flags;      /* XYWS_US_* of that call */
+  uint64_t reserved;
+} xyws_unsent_carry;
+
+typedef struct xyws_unsent_conn {     /* 32 bytes; entry i is connection i of the sweep's slot-stable tables */
+  void*              out;        /* device: the send range; the pend_cap bytes below it are the connection's */
+  uint64_t           pend_cap;
+  xyws_unsent_carry* carry;      /* device, nullable; read, then written */
+  uint64_t           reserved;
+} xyws_unsent_conn;
+
+typedef struct xyws_unsent_report {   /* 8 bytes, written by the host */
+  uint32_t sent;       /* bytes of the entry's len the socket took */
+  uint32_t sweep;      /* the stamp: counts when it equals head->sweep */
+} xyws_unsent_report;
+
+typedef struct xyws_unsent_head {     /* 16 bytes */
+  uint32_t sweep;
+  uint32_t reserved0;
+  uint64_t reserved;
+} xyws_unsent_head;
+
+typedef struct xyws_unsent_result {   /* 32 bytes */
+  uint64_t pend_len;
+  uint64_t moved;      /* bytes this call copied (0 when the tail already lay in place) */
+  uint32_t status;     /* XYWS_US_* */
+  uint32_t reserved0;
+  uint64_t reserved;
+} xyws_unsent_result;
+#define XYWS_US_KEPT       0x1u /* a tail is pending */
+#define XYWS_US_OVERFLOW   0x2u /* the tail did not fit pend_cap: bytes were lost, the caller closes the connection */
+#define XYWS_US_BAD_REPORT 0x4u /* sent > last_len: taken as last_len */
+
+uint64_t xyws_unsent_scratch_bytes(uint64_t n);   /* host */
+int xyws_unsent_streams(xyws_ctx* ctx, const xyws_unsent_conn* dev_uconns, uint64_t n,
+                        const xyws_unsent_report* reports /* n, nullable */, const xyws_unsent_head* head,
+                        xyws_unsent_result* dev_results /* n, nullable */,
+                        void* dev_scratch, uint64_t scratch_bytes, void* stream);
+int xyws_unsent_view_streams(xyws_ctx* ctx, const xyws_unsent_conn* dev_uconns,
+                             const xyws_outbox_conn* dev_conns, uint64_t n,
+                             xyws_outbox_conn* dev_view /* n */, xyws_backlog_result* dev_view_rows /* n */,
+                             void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -577,6 +577,30 @@ inline void* outbox_map(void* pinned_host) {
   return dev;
 }
 
+// The send bytes the sockets did not take, kept on the device in front of each
+// connection's send range ([pend_cap bytes | out ..), include/xyws.h).
+// unsent_streams (one launch) runs at sweep start, before any producer:
+// `reports` (n rows, nullable) holds {sent, sweep} for the sockets that were
+// short, counted when the stamp equals head->sweep; both may be pinned memory
+// by its device pointer (outbox_map). unsent_view_streams (one launch, no
+// payload byte copied) runs at sweep end and writes the table dev_view that
+// outbox_streams is then called on: every entry is `tail | new bytes`. A
+// connection whose result row has XYWS_US_OVERFLOW lost bytes: close it.
+inline std::uint64_t unsent_scratch_bytes(std::uint64_t n) { return xyws_unsent_scratch_bytes(n); }
+inline void unsent_streams(context& ctx, const xyws_unsent_conn* dev_uconns, std::uint64_t n,
+                           const xyws_unsent_report* reports, const xyws_unsent_head* head,
+                           xyws_unsent_result* dev_results, void* dev_scratch, std::uint64_t scratch_bytes,
+                           void* stream = nullptr) {
+  check(xyws_unsent_streams(ctx.native(), dev_uconns, n, reports, head, dev_results, dev_scratch, scratch_bytes, stream),
+        "xyws_unsent_streams");
+}
+inline void unsent_view_streams(context& ctx, const xyws_unsent_conn* dev_uconns, const xyws_outbox_conn* dev_conns,
+                                std::uint64_t n, xyws_outbox_conn* dev_view, xyws_backlog_result* dev_view_rows,
+                                void* stream = nullptr) {
+  check(xyws_unsent_view_streams(ctx.native(), dev_uconns, dev_conns, n, dev_view, dev_view_rows, stream),
+        "xyws_unsent_view_streams");
+}
+
 // A sweep's received bytes scattered to the connections by its first call
 // (xyws_inbox_streams, five launches): dev_iconns[i] names connection i's
 // receive range, its inbox carry and the resident xyws_conn and

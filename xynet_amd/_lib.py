@@ -534,6 +534,38 @@ IB_HTTP, IB_OPEN, IB_DEAD = 0, 1, 2  # xyws_inbox_carry.state
 IBM_BAD_ENTRIES, IBM_BROKEN, IBM_CLIPPED = 0x1, 0x2, 0x4  # xyws_inbox_summary.status
 
 
+class UnsentCarry(C.Structure):
+    """xyws_unsent_carry (include/xyws.h), 32 bytes; all zero: nothing pending."""
+    _fields_ = [("pend_len", C.c_uint64), ("last_len", C.c_uint64), ("sweep", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+class UnsentConn(C.Structure):
+    """xyws_unsent_conn (include/xyws.h), 32 bytes: entry i is connection i of the sweep's tables."""
+    _fields_ = [("out", C.c_void_p), ("pend_cap", C.c_uint64), ("carry", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+class UnsentReport(C.Structure):
+    """xyws_unsent_report (include/xyws.h), 8 bytes: what a short socket took, stamped with the sweep."""
+    _fields_ = [("sent", C.c_uint32), ("sweep", C.c_uint32)]
+
+
+class UnsentHead(C.Structure):
+    """xyws_unsent_head (include/xyws.h), 16 bytes: the sweep whose reports count."""
+    _fields_ = [("sweep", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class UnsentResult(C.Structure):
+    """xyws_unsent_result (include/xyws.h), 32 bytes."""
+    _fields_ = [("pend_len", C.c_uint64), ("moved", C.c_uint64), ("status", C.c_uint32), ("reserved0", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+assert (C.sizeof(UnsentCarry), C.sizeof(UnsentConn), C.sizeof(UnsentReport), C.sizeof(UnsentHead),
+        C.sizeof(UnsentResult)) == (32, 32, 8, 16, 32)
+US_KEPT, US_OVERFLOW, US_BAD_REPORT = 0x1, 0x2, 0x4  # xyws_unsent_result.status
+
+
 class Table:
     """n rows of the ctypes structure `struct` (one of the row types above),
     filled by field name (`t[k].out_cap = ...`) and uploaded as they are: over
@@ -770,6 +802,15 @@ def load():
     # (measurements: one host-to-device copy per entry, issued from C by the calling thread)
     L.xyws_debug_inbox_host_scatter.restype = i32
     L.xyws_debug_inbox_host_scatter.argtypes = [vp, vp, vp, u64, vp, vp]
+    L.xyws_unsent_scratch_bytes.restype = u64
+    L.xyws_unsent_scratch_bytes.argtypes = [u64]
+    L.xyws_unsent_streams.restype = i32
+    L.xyws_unsent_streams.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, vp]
+    L.xyws_unsent_view_streams.restype = i32
+    L.xyws_unsent_view_streams.argtypes = [vp, vp, vp, u64, vp, vp, vp]
+    # (no HIP call: connections per tile, bytes a wave moves per step, waves per tile, bytes of a move record)
+    L.xyws_debug_unsent_geometry.restype = i32
+    L.xyws_debug_unsent_geometry.argtypes = [C.POINTER(u64)]
     # (no HIP call: k_unmask_range's tile bytes, threads per workgroup, workgroups per CU; a context's scratch slots)
     L.xyws_debug_unmask_geometry.restype = i32
     L.xyws_debug_unmask_geometry.argtypes = [C.POINTER(u64)]

@@ -37,6 +37,7 @@
 #include "xyws_device.h"
 #include "xyws_ctx.h"
 #include "xyws_lines.h"
+#include "xyws_outbox.h"
 #include "xyws_room.h"
 #include "xyws_rows.h"
 
@@ -90,29 +91,10 @@ __global__ void __launch_bounds__(OB_TILE)
   uint64_t len = 0, full = 0;
   uint32_t flags = 0;
   if (i < n) {
-    const rows::outbox_conn_row c = rows::load_outbox_conn<false>(conns + i);
-    uint32_t rst = 0, ast = 0, resp_len = 0;
-    uint64_t reply_len = 0;
-    if (c.reply) {
-      const rows::reply_result_row r = rows::load_reply_result<false>((const xyws_reply_result*)c.reply);
-      reply_len = r.reply_len;
-      rst = r.status;
-    }
-    if (c.accept) {
-      const rows::accept_brief a = rows::load_accept_brief<false>((const xyws_accept_result*)c.accept);
-      ast = a.status;
-      resp_len = a.resp_len;
-    }
-    // rule 1: the last call of the sweep that wrote a row for it says what there is to send
-    if (c.backlog) full = rows::load_backlog_send_len((const xyws_backlog_result*)c.backlog);
-    else if (c.bcast) full = rows::load_bcast_result_own((const xyws_bcast_result*)c.bcast).send_len;
-    else if (c.reply) full = reply_len;
-    else if (ast & (XYWS_ACC_ACCEPTED | XYWS_ACC_REJECTED)) full = resp_len;
-    len = full < c.out_cap ? full : c.out_cap;
-    // rule 2
-    if ((rst & XYWS_RPL_CLOSED) || (ast & XYWS_ACC_REJECTED)) flags |= XYWS_OB_CLOSE;
-    if (rst & XYWS_RPL_OVERFLOW) flags |= XYWS_OB_OVERFLOW;
-    if (full > c.out_cap) flags |= XYWS_OB_TRUNCATED;
+    const outbox_lengths r = outbox_rules(rows::load_outbox_conn<false>(conns + i));  // rules 1 and 2
+    len = r.len;
+    full = r.full;
+    flags = r.flags;
   }
   const bool listed = len || flags;
   const uint64_t slot = align16(len);

@@ -563,6 +563,31 @@ XYWS_HD deflate_room_state unpack_deflate_room_state(uint64_t w) {
   return {XYWS_GET(xyws_deflate_room_result, status, w), XYWS_GET(xyws_deflate_room_result, reserved0, w)};
 }
 
+// ---------------------------------------------------------------- the unsent tail's rows
+// Conn, carry and result are four words each; a report is one word of two
+// fields, and so is the first word of the head.
+struct unsent_report { uint32_t sent, sweep; };  // xyws_unsent_report
+struct unsent_stamp { uint32_t sweep, flags; };  // xyws_unsent_carry
+XYWS_ONE_WORD(xyws_unsent_report, sent, sweep);
+XYWS_ONE_WORD(xyws_unsent_carry, sweep, flags);
+XYWS_ONE_WORD(xyws_unsent_head, sweep, reserved0);
+XYWS_ONE_WORD(xyws_unsent_result, status, reserved0);
+static_assert(sizeof(xyws_unsent_conn) == 4 * 8 && sizeof(xyws_unsent_carry) == 4 * 8 && sizeof(xyws_unsent_result) == 4 * 8 &&
+                  sizeof(xyws_unsent_report) == 8 && sizeof(xyws_unsent_head) == 2 * 8,
+              "the unsent tail's rows: whole words");
+XYWS_HD unsent_report unpack_unsent_report(uint64_t w) {
+  return {XYWS_GET(xyws_unsent_report, sent, w), XYWS_GET(xyws_unsent_report, sweep, w)};
+}
+XYWS_HD uint64_t pack_unsent_report(unsent_report r) {
+  return XYWS_PUT(xyws_unsent_report, sent, r.sent) | XYWS_PUT(xyws_unsent_report, sweep, r.sweep);
+}
+XYWS_HD uint64_t pack_unsent_stamp(unsent_stamp s) {
+  return XYWS_PUT(xyws_unsent_carry, sweep, s.sweep) | XYWS_PUT(xyws_unsent_carry, flags, s.flags);
+}
+XYWS_HD unsent_stamp unpack_unsent_stamp(uint64_t w) {
+  return {XYWS_GET(xyws_unsent_carry, sweep, w), XYWS_GET(xyws_unsent_carry, flags, w)};
+}
+
 }  // namespace xyws_rows
 
 // ================================================================ the device part
@@ -1209,6 +1234,53 @@ XYWS_DEV void raise_deflate_room_status(xyws_deflate_room_result* p, uint32_t bi
 // The joiners a roster row admitted.
 XYWS_DEV uint32_t load_roster_joined(const xyws_roster_room_result* p) {
   return unpack_roster_counts(XYWS_LD(true, xyws_roster_room_result, p, joined)).joined;
+}
+
+// ---- the unsent tail's rows (each thread's own), and the outbox and backlog rows its view writes
+struct unsent_conn_row { uint64_t out, pend_cap, carry; };
+XYWS_DEV unsent_conn_row load_unsent_conn(const xyws_unsent_conn* p) {
+  return {XYWS_LD(false, xyws_unsent_conn, p, out), XYWS_LD(false, xyws_unsent_conn, p, pend_cap),
+          XYWS_LD(false, xyws_unsent_conn, p, carry)};
+}
+struct unsent_carry_row { uint64_t pend_len, last_len; };
+XYWS_DEV unsent_carry_row load_unsent_carry(const xyws_unsent_carry* p) {
+  return {XYWS_LD(false, xyws_unsent_carry, p, pend_len), XYWS_LD(false, xyws_unsent_carry, p, last_len)};
+}
+XYWS_DEV uint64_t load_unsent_pend_len(const xyws_unsent_carry* p) { return XYWS_LD(false, xyws_unsent_carry, p, pend_len); }
+// (the carry's reserved word stays the caller's)
+XYWS_DEV void store_unsent_carry(xyws_unsent_carry* p, uint64_t pend_len, uint64_t last_len, unsent_stamp s) {
+  XYWS_ST(xyws_unsent_carry, p, pend_len, pend_len);
+  XYWS_ST(xyws_unsent_carry, p, last_len, last_len);
+  XYWS_ST(xyws_unsent_carry, p, sweep, pack_unsent_stamp(s));
+}
+XYWS_DEV void store_unsent_last_len(xyws_unsent_carry* p, uint64_t last_len) { XYWS_ST(xyws_unsent_carry, p, last_len, last_len); }
+XYWS_DEV unsent_report load_unsent_report(const xyws_unsent_report* p) {
+  return unpack_unsent_report(XYWS_LD(false, xyws_unsent_report, p, sent));
+}
+XYWS_DEV uint32_t load_unsent_sweep(const xyws_unsent_head* p) {
+  return XYWS_GET(xyws_unsent_head, sweep, XYWS_LD(false, xyws_unsent_head, p, sweep));
+}
+XYWS_DEV void store_unsent_result(xyws_unsent_result* p, uint64_t pend_len, uint64_t moved, uint32_t status) {
+  XYWS_ST(xyws_unsent_result, p, pend_len, pend_len);
+  XYWS_ST(xyws_unsent_result, p, moved, moved);
+  XYWS_ST(xyws_unsent_result, p, status, XYWS_PUT(xyws_unsent_result, status, status));
+  XYWS_ST(xyws_unsent_result, p, reserved, 0);
+}
+XYWS_DEV void store_outbox_conn(xyws_outbox_conn* p, const outbox_conn_row& r) {
+  XYWS_ST(xyws_outbox_conn, p, out, r.out);
+  XYWS_ST(xyws_outbox_conn, p, out_cap, r.out_cap);
+  XYWS_ST(xyws_outbox_conn, p, backlog, r.backlog);
+  XYWS_ST(xyws_outbox_conn, p, bcast, r.bcast);
+  XYWS_ST(xyws_outbox_conn, p, reply, r.reply);
+  XYWS_ST(xyws_outbox_conn, p, accept, r.accept);
+  for (size_t w = XYWS_WORD(xyws_outbox_conn, reserved); w < sizeof(xyws_outbox_conn) / 8; w++) ((g_u64*)p)[w] = 0;
+}
+// A backlog row that says send_len and nothing else.
+XYWS_DEV void store_backlog_send_len(xyws_backlog_result* p, uint64_t send_len) {
+  XYWS_ST(xyws_backlog_result, p, send_len, send_len);
+  XYWS_ST(xyws_backlog_result, p, backlog_len, 0);
+  XYWS_ST(xyws_backlog_result, p, status, 0);
+  XYWS_ST(xyws_backlog_result, p, reserved, 0);
 }
 
 // The broadcast row at src without its head, one word per lane.

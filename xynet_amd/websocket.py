@@ -817,9 +817,9 @@ class GroupOutbox:
     items that are no item of the sweep. conn_ids[i] is row i's connection id.
     It owns the call's table, outputs and scratch."""
 
-    def __init__(self, group, conn_ids, outs, tensors, pack_cap, host, last, accept, done):
+    def __init__(self, group, conn_ids, outs, tensors, pack_cap, host, last, accept, done, unsent=None):
         self.group, self.conn_ids, self.outs, self._tensors = group, conn_ids, outs, tensors
-        self.pack_cap, self.host = pack_cap, host
+        self.pack_cap, self.host, self.unsent = pack_cap, host, unsent
         self.last, self.accept, self._done = last, accept, done  # (the sweep's results, whose rows the table names)
         self._summary = self._entries = self._pack = None
 
@@ -845,11 +845,39 @@ class GroupOutbox:
 
     def bytes(self, k):
         """The bytes entry k sends: its slot of the pack, or for a deferred
-        entry the first len bytes of its send tensor."""
+        entry the first len bytes of its send tensor (under unsent=: of the
+        range that begins at its pending tail)."""
         e = self.entries()[k]
         if e.flags & _lib.OB_DEFERRED:
+            if self.unsent is not None:
+                first = self.unsent.pend_caps[e.conn] - self.unsent.result(e.conn).pend_len
+                return self.unsent.buffers[e.conn][first:first + e.len].cpu().numpy().tobytes()
             return self.outs[e.conn][:e.len].cpu().numpy().tobytes()
         return self.pack()[e.off:e.off + e.len]
+
+
+class GroupUnsent:
+    """Result of one connection_group.unsent call (host copies on demand; every
+    accessor waits for the call). Row i is connection i of the group.
+    buffers[i]: connection i's whole send buffer, [pend_cap | out ..), or None;
+    pend_caps[i]: its pend_cap. outbox(unsent=) takes it at the sweep's end."""
+
+    def __init__(self, group, sweep, state, results_t, done):
+        self.group, self.sweep, self._state, self._results_t, self._done = group, sweep, state, results_t, done
+        self.buffers, self.pend_caps = state["buffers"], state["pend_caps"]
+        self._rows = None
+
+    def result(self, k):
+        """xyws_unsent_result of connection k."""
+        if self._rows is None:
+            self._done.wait()
+            self._rows = _lib.read_rows(_lib.UnsentResult, self._results_t, self.group.n)
+        return self._rows[k]
+
+    def pending(self, k):
+        """The bytes of connection k that wait in front of its send range (synchronizes)."""
+        p, cap = self.result(k).pend_len, self.pend_caps[k]
+        return self.buffers[k][cap - p:cap].cpu().numpy().tobytes() if p else b""
 
 
 class GroupInbox:
@@ -958,6 +986,8 @@ class connection_group:
         self._blogs, self._bcarries = [], []
         # inbox(): the receive slab, the inbox carries and the resident tables, made by the first inbox() call
         self._ib = None
+        # unsent(): every connection's send buffer and pend_cap, the unsent carries, the report rows and the table (first call)
+        self._us = None
 
     def _call(self, name, *args, slot=None, done=None):
         """One call of the library on the group's device and its current
@@ -980,6 +1010,8 @@ class connection_group:
                  (self.hcarry_t, _lib.HoldCarry), (self.icarry_t, _lib.InflateCarry)]
         if self._ib is not None:
             pairs += [(self._ib["carries"], _lib.InboxCarry), (self._ib["aresults"], _lib.AcceptResult)]
+        if self._us is not None:
+            pairs += [(self._us["carries"], _lib.UnsentCarry)]
         return pairs
 
     def reset(self, ids=None):
@@ -1735,7 +1767,60 @@ class connection_group:
                    slot=dec.slot)
         return GroupBacklog(self, bcast, roster, tensors, nr)
 
-    def outbox(self, last, accept=None, pack_cap=None, host=False):
+    def unsent(self, reports, sweep, pend_cap, buffers=None):
+        """Keep what the sockets did not take (xyws_unsent_streams, one launch,
+        at sweep start before any producer). buffers, in the group's first
+        call: connection i's whole send buffer (a uint8 tensor on the group's
+        device, or None), laid out [pend_cap bytes | send range]: the sweep's
+        producers are given buffers[i][pend_cap:]. pend_cap: one number, or one
+        per connection. reports: a (conn_id, sent[, stamp]) tuple for every
+        socket that took fewer bytes than the previous outbox(unsent=) listed
+        for it; the row is stamped with `sweep` (or stamp), and rows of earlier
+        sweeps stay where they are and do not count. Returns a GroupUnsent,
+        which the sweep's outbox() takes as unsent=."""
+        import torch
+        n, dev, L = self.n, self.device, self.ctx.L
+        us = self._us
+        if us is None:
+            if buffers is None or len(buffers) != n:
+                raise XywsError(-1, "the group's first unsent() call takes every connection's send buffer")
+            caps = [int(pend_cap)] * n if isinstance(pend_cap, int) else [int(c) for c in pend_cap]
+            if len(caps) != n or min(caps, default=0) < 0:
+                raise XywsError(-1, "pend_cap is one number or one per connection, none negative")
+            us = dict(buffers=list(buffers), pend_caps=caps, carries=_lib.alloc_rows(_lib.UnsentCarry, n, dev),
+                      reports=_lib.Table(_lib.UnsentReport, n))
+            tab = _lib.Table(_lib.UnsentConn, n)
+            for i, (t, cap) in enumerate(zip(buffers, caps)):
+                if t is not None:
+                    if t.device != dev or t.numel() < cap:
+                        raise XywsError(-1, "a send buffer on another device, or shorter than its pend_cap")
+                    tab[i].out, tab[i].pend_cap = _dev_u8(t).data_ptr() + cap, cap
+                tab[i].carry = _lib.row_ptr(us["carries"], _lib.UnsentCarry, i)
+            us["uconns"] = tab.upload(dev)
+            self._us = us
+        sweep = int(sweep) & 0xFFFFFFFF
+        for r in reports:
+            row = us["reports"][int(r[0])]
+            row.sent, row.sweep = int(r[1]), (int(r[2]) & 0xFFFFFFFF) if len(r) > 2 else sweep
+        head = _lib.Table(_lib.UnsentHead, 1)
+        head[0].sweep = sweep
+        keep = dict(reports=us["reports"].upload(dev), head=head.upload(dev),
+                    results=_lib.alloc_rows(_lib.UnsentResult, n, dev),
+                    scratch=torch.empty(max(L.xyws_unsent_scratch_bytes(n), 8), dtype=torch.uint8, device=dev))
+        done = _Done()
+        self._call("xyws_unsent_streams", us["uconns"], n, keep["reports"], keep["head"], keep["results"], keep["scratch"],
+                   keep["scratch"].numel(), done=done)
+        res = GroupUnsent(self, sweep, us, keep["results"], done)
+        res._keep = keep
+        return res
+
+    def unsent_carry(self, conn_id):
+        """Host copy of a connection's unsent carry (synchronizes)."""
+        if self._us is None:
+            raise XywsError(-1, "no unsent() call yet")
+        return self._carry_of(self._us["carries"], _lib.UnsentCarry, conn_id)
+
+    def outbox(self, last, accept=None, pack_cap=None, host=False, unsent=None):
         """Pack what a sweep left to send (xyws_outbox_streams, three
         launches, the sweep's last call): `last` is the sweep's last result
         object, a GroupBacklog, GroupRoster, GroupBroadcast or GroupReply (None
@@ -1746,7 +1831,14 @@ class connection_group:
         row, any other gets a row of its own behind them. pack_cap: the pack's
         capacity (default: what always suffices). host=True puts the pack, the
         list and the summary into pinned host memory, which the kernels write
-        through its device pointer (xyws_outbox_map). Returns a GroupOutbox."""
+        through its device pointer (xyws_outbox_map). Returns a GroupOutbox.
+
+        unsent: the GroupUnsent of this sweep's unsent() call. The table then
+        has one row per connection of the group, row i connection i (one that
+        is no item of the sweep still sends its pending tail), and
+        xyws_unsent_view_streams lays the view over it that the outbox call is
+        made on: every entry is `tail | new bytes`. An item's send tensor must
+        be buffers[i][pend_cap:] of that unsent() call."""
         import torch
         roster = bcast = reply = None
         backlog = last if isinstance(last, GroupBacklog) else None
@@ -1758,7 +1850,7 @@ class connection_group:
             bcast = last
         elif isinstance(last, GroupReply):
             reply = last
-        elif last is not None or accept is None:
+        elif last is not None or (accept is None and unsent is None):
             raise XywsError(-1, "outbox() takes the result of this group's backlog(), roster(), broadcast() or reply()")
         if (last is not None and last.group is not self) or (accept is not None and accept.group is not self):
             raise XywsError(-1, "outbox() takes results of this group")
@@ -1790,6 +1882,23 @@ class connection_group:
                 # (as roster(): a connection still in HTTP state has no reply row of this sweep)
                 row.reply = self._reply_row(k) if replied and k not in acc_of else 0
             row.accept = _lib.row_ptr(accept.results_t, _lib.AcceptResult, acc_of[k]) if k in acc_of else 0
+        if unsent is not None:
+            if unsent.group is not self:
+                raise XywsError(-1, "outbox() takes results of this group")
+            items, n = tab, self.n
+            tab = _lib.Table(_lib.OutboxConn, n)
+            for i, (t, pc) in enumerate(zip(unsent.buffers, unsent.pend_caps)):
+                if t is not None and t.numel() > pc:
+                    tab[i].out, tab[i].out_cap = t.data_ptr() + pc, t.numel() - pc
+            for k, i in enumerate(ids):
+                if items[k].out and items[k].out != tab[i].out:
+                    raise XywsError(-1, "under unsent=, an item's send tensor is buffers[i][pend_cap:] of the unsent() call")
+                if items[k].out:
+                    tab[i].out_cap = items[k].out_cap
+                for name in ("backlog", "bcast", "reply", "accept"):
+                    setattr(tab[i], name, getattr(items[k], name))
+            ids = list(range(n))
+            outs = [t if t is not None else torch.zeros(0, dtype=torch.uint8, device=self.device) for t in unsent.buffers]
         cap = sum((t.numel() + 15) & ~15 for t in outs) if pack_cap is None else int(pack_cap)
         L = self.ctx.L
         where = "cpu" if host else self.device
@@ -1809,9 +1918,14 @@ class connection_group:
         tensors = dict(keep, conns=tab.upload(self.device),
                        scratch=torch.empty(max(L.xyws_outbox_scratch_bytes(n), 8), dtype=torch.uint8, device=self.device))
         done = _Done()
-        self._call("xyws_outbox_streams", tensors["conns"], n, ptr["pack"] if cap else None, cap, ptr["entries"],
+        table = tensors["conns"]
+        if unsent is not None:
+            tensors["view"] = table = _lib.alloc_rows(_lib.OutboxConn, n, self.device)
+            tensors["view_rows"] = _lib.alloc_rows(_lib.BacklogResult, n, self.device)
+            self._call("xyws_unsent_view_streams", self._us["uconns"], tensors["conns"], n, table, tensors["view_rows"])
+        self._call("xyws_outbox_streams", table, n, ptr["pack"] if cap else None, cap, ptr["entries"],
                    ptr["summary"], tensors["scratch"], tensors["scratch"].numel(), done=done)
-        return GroupOutbox(self, ids, outs, tensors, cap, host, last, accept, done)
+        return GroupOutbox(self, ids, outs, tensors, cap, host, last, accept, done, unsent)
 
     def _inbox_state(self, recv_cap, resp_cap):
         """The receive slab, the inbox carries and the resident tables (made once)."""
